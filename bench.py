@@ -10,9 +10,17 @@ The batch axis shards across ranks with no data-path collective (weak scaling: 2
 the only collective is the all-reduce of the scalar sum of losses (RCCL), issued every step.
 
 Rank 0 prints ONE JSON line with the fields the driver reads plus
-  "roofline":     HBM roofline of the loss+grad pipeline (algorithmic bytes 2*T*V*4 per utterance)
-  "cpu_baseline": the oracle (NumPy restatement of the reference, oracle/ctc_oracle.py) timed on this
-                  box's host cores on a bounded sample of the same workload.
+  "roofline":     HBM roofline of the loss+grad pipeline (algorithmic bytes 2*T*V*4 per utterance), from the event pairs
+                  of the timed region itself.
+A plain run does only what that line needs: set-up, warm-up, the --steps timed steps, the line.  `--full` adds what takes
+runs of its own, after the timed region:
+  "kernel_us_after_timed_region": 100 more launches, an event pair around each;
+  "box":          a 1 GiB device copy (tells a slow box from a slow kernel);
+  "cpu_baseline": the C restatement of the reference (oracle/ctc_oracle.c) timed on the host cores on a bounded sample of
+                  the same workload (--no-cpu-baseline leaves it out);
+  "secondary":    the other configurations and callers of the path (--no-secondary leaves it out);
+and the check that the in-kernel [sum(loss), count] pair of the last step equals a reduction of its losses.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -49,6 +57,30 @@ def make_inputs(B, T, U, V, seed, ragged, device, scale=1.0):
     host = dict(logits=logits, labels=labels, label_length=label_length, logit_length=logit_length)
     dev = {k: torch.from_numpy(v).to(device) for k, v in host.items()}
     return host, dev
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of an output larger than this by --dump-outputs (16 MB of float32)
+DUMP_LIMIT = 64 << 20  # bytes written by --dump-outputs in all
+
+
+def output_sample(t, n=DUMP_SAMPLE, seed=0):
+    """Tensor t as a float32 array: all of it if it has at most n elements, else the elements at n seeded-random flat
+    indices (row-major order of t's shape, sorted, repeats dropped) -- the same positions in every run with the same shape."""
+    t = t.detach()
+    if t.numel() <= n:
+        return t.float().cpu().numpy()
+    idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), n, dtype=np.int64))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: writes {name: float32 / float64 array} as path/<name>.npy (at most DUMP_LIMIT bytes in all)."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(kind, host, budget_s=15.0):
@@ -501,8 +533,15 @@ def parse_args(argv=None):
     ap.add_argument("--V", type=int, default=256)
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--hessian", action="store_true", help="time the dense Hessian at B=32 T=200 U=32 V=64 (configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (simplified, ragged, drop-in autograd, HVP, Hessian)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the per-launch distribution, the box probe, the CPU baseline, the secondary "
+                         "configurations and the check of the in-kernel loss sum (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: loss, the [sum(loss), count] "
+                         "pair, and a fixed seeded sample of 2^22 elements of the gradient (--hessian: of the Hessian)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without the secondary configurations (simplified, ragged, drop-in autograd, HVP, Hessian)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="element type of logits and gradient (producer format)")
     ap.add_argument("--time-major", action="store_true", help="logits stored [T,B,V] (producer format), passed as a strided view")
     ap.add_argument("--reduce-every", type=int, default=8,
@@ -687,10 +726,10 @@ def main():
     # all-reduce of the pair; the Hessian workload keeps the separate ctc_amd_reduce_loss launch
     seen = []
     grouped = in_kernel_sum and args.reduce_every > 1
-    cdist.pipelined_steps(timed_step, args.steps, reduced=in_kernel_sum, depth=args.pipeline_depth, all_reduce=emu,
-                          consume=(lambda i, pair: seen.append(pair.reshape(-1, 2)[-1]) if i == args.steps - 1 else None) if in_kernel_sum else None,
-                          **(dict(every=args.reduce_every, group_view=lambda first, n: (group_views[(first % NBUF) // args.reduce_every] if n == args.reduce_every
-                                                                                            else group_views[(first % NBUF) // args.reduce_every][:n])) if grouped else {}))
+    pairs = cdist.pipelined_steps(timed_step, args.steps, reduced=in_kernel_sum, depth=args.pipeline_depth, all_reduce=emu,
+                                  consume=(lambda i, pair: seen.append(pair.reshape(-1, 2)[-1]) if i == args.steps - 1 else None) if in_kernel_sum else None,
+                                  **(dict(every=args.reduce_every, group_view=lambda first, n: (group_views[(first % NBUF) // args.reduce_every] if n == args.reduce_every
+                                                                                                    else group_views[(first % NBUF) // args.reduce_every][:n])) if grouped else {}))
     ev1.record()
     torch.cuda.synchronize()
     if world > 1:
@@ -698,13 +737,23 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
-    if in_kernel_sum and world == 1 and seen:  # (outside the timed region) the pair the kernel accumulated is the sum of its losses
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the losses, the [sum(loss), count] pair (all-reduced when N > 1; the
+        # kernel's fixed-point sum taken back to float, or the pair of ctc_amd_reduce_loss for the Hessian) and a fixed sample
+        # of the gradient / Hessian (positions in [B,T,V] / [B,T,V,T,V] order, a time-major gradient included)
+        if in_kernel_sum:
+            pair = seen[0].double().cpu().numpy() / np.array([1048576.0, 1.0])
+        else:
+            pair = pairs[-1].double().cpu().numpy()
+        dump_outputs(args.dump_outputs, {"loss": output_sample(loss), "loss_sum_count": pair,
+                                         ("hessian_sample" if args.hessian else "grad_sample"): output_sample(hess if args.hessian else grad)})
+    if args.full and in_kernel_sum and world == 1 and seen:  # (outside the timed region) the pair the kernel accumulated is the sum of its losses
         fin = torch.isfinite(loss)
         want = float(loss[fin].double().sum())
         got, cnt = float(seen[0][0]) / 1048576.0, int(seen[0][1])
         assert cnt == int(fin.sum()) and abs(got - want) <= 1e-6 * max(1.0, abs(want)) + B * 1e-6, (got, want, cnt)
     reduced_check = None
-    if in_kernel_sum and world > 1 and seen:
+    if args.full and in_kernel_sum and world > 1 and seen:
         # (outside the timed region) the pair of the last step as the collective left it on this rank against an independent
         # reduction of the ranks' own losses: the same count, the same sum in fixed point -- on every rank
         fin = torch.isfinite(loss)
@@ -720,9 +769,9 @@ def main():
     wall = float(tmax.item())
     kernel_ts = [a.elapsed_time(b) / min(KEV, args.steps - KEV * g) for g, (a, b) in enumerate(kev)]  # per launch, by group
     kernel_ms = sum(a.elapsed_time(b) for a, b in kev) / args.steps
-    # after the timed region: the same launch 100 more times with an event pair around each, for the per-launch distribution
+    # (--full) after the timed region: the same launch 100 more times with an event pair around each, for the per-launch distribution
     post = []
-    if not args.hessian:
+    if args.full and not args.hessian:
         for _ in range(100):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
@@ -780,14 +829,14 @@ def main():
                                                            what=f"per launch, event pairs around runs of {KEV} launches"),
                          "kernel_us_after_timed_region": dict(_dist(post), what="100 more launches, an event pair around EACH (adds the event packets' own time)") if post else None},
             "warmup_effective": args.warmup + extra_warm,
-            "box": box_probe(lib, device) if world == 1 else None,
+            "box": box_probe(lib, device) if world == 1 and args.full else None,
             "reduced_check": reduced_check,
         }
-        if not args.no_cpu_baseline and not args.hessian and world == 1:  # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and not args.hessian and world == 1:  # reported at N = 1 only (rank 0's host cores)
             out["cpu_baseline"] = cpu_baseline(args.kind, host)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary and not args.hessian and (B, T, U, V) == (256, 1000, 128, 256):
+        if args.full and world == 1 and not args.no_secondary and not args.hessian and (B, T, U, V) == (256, 1000, 128, 256):
             out["secondary"] = secondary(device, rank)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 bash scripts/r02_profile_head.sh r02_final > $OUT/profile.log 2>&1
 echo "profile done"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench done"
 python3 scripts/autograd_time.py > $OUT/autograd_time.txt 2>&1
 python3 scripts/ab_time.py tree > $OUT/ab_time.txt 2>/dev/null

@@ -8,8 +8,8 @@ mkdir -p $OUT
 PART=${1:-1}
 COMMIT=$(cat .commit_id 2>/dev/null || echo unknown)
 if [ "$PART" = 1 ]; then
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_settings.json 2> $OUT/bench_driver_settings.err; echo "bench 20/5 rc=$?"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_settings.json 2> $OUT/bench_driver_settings.err; echo "bench 20/5 rc=$?"
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
 rm -rf $OUT/trace && rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 bench.py --steps 200 --warmup 20 --no-secondary --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err; echo "rocprof rc=$?"
 python3 - <<'PY'
 import csv, glob, statistics as st

@@ -8,8 +8,8 @@ mkdir -p $OUT
 PART=${1:-1}
 COMMIT=$(cat .commit_id 2>/dev/null || echo unknown)
 if [ "$PART" = 1 ]; then
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_settings.json 2> $OUT/bench_driver_settings.err; echo "bench 20/5 rc=$?"
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_settings.json 2> $OUT/bench_driver_settings.err; echo "bench 20/5 rc=$?"
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench default rc=$?"
 rm -rf $OUT/trace && rocprofv3 --kernel-trace --stats -d $OUT/trace --output-format csv -- python3 bench.py --steps 200 --warmup 20 --no-secondary --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err; echo "rocprof rc=$?"
 python3 - <<'PY'
 import csv, glob, statistics as st
@@ -39,5 +39,5 @@ else
 python3 benchmarks/reference_table.py --steps 100 --warmup 20 --json $OUT/ref_table.json > $OUT/ref_table.md 2> $OUT/ref_table.err; echo "ref table rc=$?"
 python3 benchmarks/reference_table.py --tsweep --steps 5 --warmup 2 --json $OUT/tsweep.json > $OUT/tsweep.md 2> $OUT/tsweep.err; echo "sweep rc=$?"
 python3 scripts/shape_table.py > $OUT/shape_table.md 2> $OUT/shape_table.err; echo "shape table rc=$?"
-python3 bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"
+python3 bench.py --full --gpus 2 --backend gloo --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err; echo "2-rank gloo rc=$?"
 fi

@@ -1,10 +1,60 @@
-"""Shared helpers for tests: loads the golden known-answer table and turns records into arrays."""
+"""Shared helpers for tests: loads the golden known-answer table and turns records into arrays; the array fixtures that are
+stored in parts."""
+import glob
+import io
 import json
 import os
 
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PART_BYTES = 1000000  # a committed fixture file stays below 1 MiB: larger sets of arrays go into numbered parts
+
+
+class GoldenArrays(dict):
+    """{name: array} of a fixture kept in parts; `.files` lists the names like the NpzFile of np.load."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden_parts(stem):
+    """All arrays of tests/golden/<stem>.<i>.npz, i = 0, 1, ... (written by save_golden_parts)."""
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(stem) + ".[0-9]*.npz")),
+                   key=lambda p: int(p[:-len(".npz")].rsplit(".", 1)[1]))
+    assert parts, f"no parts of tests/golden/{stem}"
+    out = GoldenArrays()
+    for p in parts:
+        with np.load(p) as z:
+            for k in z.files:
+                out[k] = z[k]
+    return out
+
+
+def save_golden_parts(stem, arrays, directory=GOLDEN):
+    """Writes {name: array} as directory/<stem>.<i>.npz (compressed), arrays in the given order, a new part whenever the next
+    array would take the current one past PART_BYTES; one array compressed on its own must fit.  Returns the paths."""
+    def packed(group):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **group)
+        return buf.getvalue()
+
+    groups, cur = [], {}
+    for k, a in arrays.items():
+        if cur and len(packed({**cur, k: a})) > PART_BYTES:
+            groups.append(cur)
+            cur = {}
+        cur[k] = a
+    groups.append(cur)
+    paths = []
+    for i, g in enumerate(groups):
+        data = packed(g)
+        assert len(data) <= PART_BYTES, (k, len(data))
+        paths.append(os.path.join(directory, f"{stem}.{i}.npz"))
+        with open(paths[-1], "wb") as f:
+            f.write(data)
+    return paths
 
 
 def _num(x):

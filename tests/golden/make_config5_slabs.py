@@ -1,4 +1,4 @@
-"""Writes tests/golden/config5_hessian_slabs.npz: entries of the float64 oracle Hessian at the FULL size of BASELINE.json
+"""Writes tests/golden/config5_hessian_slabs.<i>.npz (parts below 1 MiB): entries of the float64 oracle Hessian at the FULL size of BASELINE.json
 configs[4] (classic / simplified, T=200 U=32 V=64), for utterances 0 and 13 of the config-5 tensor.
 
 SELF-GENERATED, NOT REFERENCE-GENERATED (TensorFlow is not available here): the vectors come from oracle/ctc_oracle.py --
@@ -9,7 +9,7 @@ in float64; ~10 GB peak, a few minutes on the build container.  Stored: for each
 H[t1,k1,:,:] ([T,V] each) in logits space and in log-probability space, float32 (the comparison tolerance is 1e-4), with the
 (t1,k1) list.  Inputs are regenerated from the seed in the test (tests/test_gpu_configs.py::_inputs), not stored.
 
-Run:  python tests/golden/make_config5_slabs.py        (writes ~1.6 MB)
+Run:  python tests/golden/make_config5_slabs.py        (writes ~4.8 MB in parts below 1 MiB)
 """
 import os
 import sys
@@ -19,6 +19,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from oracle import ctc_oracle as O  # noqa: E402
+from tests._cases import save_golden_parts  # noqa: E402
 
 B, T, U, V = 32, 200, 32, 64
 UTTERANCES = (0, 13)
@@ -63,6 +64,5 @@ if __name__ == "__main__":
             out[f"u{b}/{kind}/loss"] = d.loss.astype(np.float64)
             print(f"utterance {b} {kind}: {time.time() - t0:.0f} s, loss {d.loss[0]:.4f}, max|H_logits| {np.abs(h_x).max():.3f}", flush=True)
             del d, h_lp, h_x
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config5_hessian_slabs.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    for path in save_golden_parts("config5_hessian_slabs", out):
+        print("wrote", path, os.path.getsize(path), "bytes")

@@ -1,4 +1,4 @@
-"""Writes tests/golden/oracle_vectors.npz: seeded random inputs with fp64 oracle outputs.
+"""Writes tests/golden/oracle_vectors.<i>.npz (parts below 1 MiB): seeded random inputs with fp64 oracle outputs.
 
 SELF-GENERATED, NOT REFERENCE-GENERATED: the TensorFlow reference cannot run here, so these vectors come from
 oracle/ctc_oracle.py after it passed the reference's known-answer table, brute force, torch and finite-difference
@@ -13,6 +13,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from oracle import ctc_oracle as O  # noqa: E402
+from tests._cases import save_golden_parts  # noqa: E402
 
 CASES = [  # (name, B, T, V, seed, max_label_length or None)
     ("ref_sizes_a", 8, 20, 8, 0, None),
@@ -34,6 +35,5 @@ if __name__ == "__main__":
             if T <= 20:
                 out[f"{name}/{kind}/hessian_logits"] = O.logits_hessian(d, inp["logits"]).astype(np.float32)  # 1e-4 tolerance: float32 storage
                 out[f"{name}/{kind}/hessian_logprobs"] = d.hessian.astype(np.float32)
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "oracle_vectors.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    for path in save_golden_parts("oracle_vectors", out):
+        print("wrote", path, os.path.getsize(path), "bytes")

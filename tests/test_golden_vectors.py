@@ -1,13 +1,12 @@
-"""Golden fixtures (tests/golden/oracle_vectors.npz, self-generated -- see make_oracle_vectors.py).
+"""Golden fixtures (tests/golden/oracle_vectors.<i>.npz, self-generated -- see make_oracle_vectors.py).
 CPU: the oracle still reproduces them.  GPU: the HIP path matches them within the north-star tolerance."""
-import os
-
 import numpy as np
 import pytest
 
 from oracle import ctc_oracle as O
+from tests._cases import load_golden_parts
 
-G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vectors.npz"))
+G = load_golden_parts("oracle_vectors")
 NAMES = sorted({k.split("/")[0] for k in G.files})
 TOL = 1e-4
 

@@ -47,8 +47,8 @@ def test_config5_full_batch_hessian(kind, kernel):
 
 
 def _golden_slabs():
-    import os
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config5_hessian_slabs.npz"))
+    from tests._cases import load_golden_parts
+    return load_golden_parts("config5_hessian_slabs")
 
 
 @pytest.mark.parametrize("kind", ["classic", "simplified"])
@@ -99,7 +99,7 @@ def _config5_body(kind):
         if n < T:
             assert h[b, n:].abs().max().item() == 0 and h[b, :, :, n:].abs().max().item() == 0
     # entry by entry against the float64 gamma-oracle at FULL size: 20 slabs H[b, t1, k1, :, :] of utterances 0 and 13
-    # (tests/golden/config5_hessian_slabs.npz, written by tests/golden/make_config5_slabs.py from oracle/ctc_oracle.py)
+    # (tests/golden/config5_hessian_slabs.<i>.npz, written by tests/golden/make_config5_slabs.py from oracle/ctc_oracle.py)
     gold = _golden_slabs()
     for b in (0, 13):
         idx = gold[f"u{b}/index"]
