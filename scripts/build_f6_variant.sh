@@ -1,7 +1,7 @@
 #!/bin/bash
 # builds scratch/libctc_f6v.so: the library with ctc_fused6.hip (classic, NL=2) recompiled with extra flags, e.g.
-#   scripts/build_f6_variant.sh -DCTC_F6_DEBUG      then CTC_AMD_LIB=scratch/libctc_f6v.so python scripts/...
-# Variant builds define CTC_DIAG (the experiment switches of the sources exist only then); ctc_capi.hip is rebuilt with it
+#   scripts/build_f6_variant.sh -DCTC_F6_NS_ONLY -DCTC_F6_STAMPS      then CTC_AMD_LIB=scratch/libctc_f6v.so python scripts/...
+# Variant builds define CTC_DIAG (the stamps and the one-instantiation build exist only then); ctc_capi.hip is rebuilt with it
 # too, because the diagnostic workspace regions are part of the layout it computes.
 set -e
 cd "$(dirname "$0")/.."

@@ -12,37 +12,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Product builds carry no experiment / diagnostic switch: every one of them is cleared here unless the build sets CTC_DIAG
-// (scripts/build_*variant.sh do).  (ctc_fused6.hip clears its own parameter macros the same way.)
+// Product builds carry no instrument switch (cycle stamps, the one-instantiation build): every one of them is cleared here unless
+// the build sets CTC_DIAG (scripts/build_f6_variant.sh does).
 #ifndef CTC_DIAG
 #undef CTC_FUSED_STAMPS
-#undef CTC_F5_X
-#undef CTC_F5_Y
-#undef CTC_DBG_NO_E2
-#undef CTC_DBG_NO_G
 #undef CTC_HESS_STAMPS
-#undef CTC_HESS_DBG_NOSWEEP
-#undef CTC_HESS_DBG_NOFILL
-#undef CTC_HESS_DBG_NOSTORE
-#undef CTC_EXPERIMENT_NO_STORE
 #undef CTC_F6_STAMPS
-#undef CTC_F6_DEBUG
-#undef CTC_F6_DEBUG2
-#undef CTC_F6_SYNC
-#undef CTC_F6_ONLY
-#undef CTC_F6_X
-#undef CTC_F6_Y
-#undef CTC_F6_PFD
-#undef CTC_F6_RN12
-#undef CTC_F6_PRIO1
-#undef CTC_F6_NH12
-#undef CTC_F6_LA
-#undef CTC_F6_HPRIO_B
 #undef CTC_F6_NS_ONLY
-#undef CTC_F6_NO_D7
-#undef CTC_F6_GAP_LIVE
-#undef CTC_F6_PACKED
-#undef CTC_F6_P1SYNC
 #endif
 
 namespace ctc {

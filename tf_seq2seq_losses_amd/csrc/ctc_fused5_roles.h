@@ -215,18 +215,12 @@ __device__ __forceinline__ void init_labels(S_t &S, const Problem &p, int b, int
 // other side's pass over them in phase 2.  One barrier per block, like every other role.
 // ------------------------------------------------------------------------------------------------
 // (measured: 1/3/4 for two label positions per lane, 2/3/2 for one -- the chain is half as long there)
-#ifndef CTC_F5_X
-#define CTC_F5_X (NL == 1 ? 2 : 1)
-#endif
-#ifndef CTC_F5_Y
-#define CTC_F5_Y 3
-#endif
 template <int BLK, int NH, int NL>
 struct P1Split {
   // NH = 4 (12-frame blocks): X / X / Y / Y / R as above.  NH = 2 (6-frame blocks of the 4-positions-per-lane variant):
   // the two helpers and the recompute wavefront take a third each.
   // NH = 1 (3-frame blocks of the 8-positions-per-lane variant): two frames for the helper, one for the recompute wavefront.
-  static constexpr int X = NH == 4 ? CTC_F5_X : NH == 2 ? BLK / 3 : 2, Y = NH == 4 ? CTC_F5_Y : NH == 2 ? BLK / 3 : 0;
+  static constexpr int X = NH == 4 ? (NL == 1 ? 2 : 1) : NH == 2 ? BLK / 3 : 2, Y = NH == 4 ? 3 : NH == 2 ? BLK / 3 : 0;
   static constexpr int R = NH == 4 ? BLK - 2 * X - 2 * Y : NH == 2 ? BLK - X - Y : BLK - X;
   static_assert(NH == 4 || NH == 2 || NH == 1, "helpers per side");
   static_assert(X >= 0 && Y >= 0 && R >= 0 && X <= 6 && Y <= 6 && R <= 6, "phase-1 split: at most 6 frames per worker");
@@ -702,11 +696,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
       // ---- E stage (block it) ----
       const int j = it;
       SG[r] = st_cur;
-#ifdef CTC_DBG_NO_E2
-      if (false) {
-#else
       if (j < nb) {
-#endif
         const int g = geo.absblock(2, DIR, j);
         const int nv = geo.nvof(g);
         float(*E)[LD::ES] = lds.E[DIR][j % 3];
@@ -734,11 +724,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
       }
       // ---- G stage (block it-3): posterior scatter + gradient rows ----
       const int gj = it - 3;
-#ifdef CTC_DBG_NO_G
-      if (false) {
-#else
       if (feasible && gj >= 0 && gj < nb) {
-#endif
         const int g = geo.absblock(2, DIR, gj);
         const int nv = geo.nvof(g);
         const float(*SR)[LD::RS] = lds.R[DIR][gj % 3];

@@ -48,7 +48,8 @@
 #error "compile with -DCTC_FUSED_KIND=0 (classic) or 1 (simplified)"
 #endif
 
-// (the CTC_F6_* switches below exist in CTC_DIAG builds only: ctc_common.h clears them otherwise)
+// (CTC_F6_STAMPS and CTC_F6_NS_ONLY exist in CTC_DIAG builds only: ctc_common.h clears them otherwise.  The variants that were built,
+// measured and rejected -- and their numbers -- are in profiles/r04_kernel_experiments.md and DESIGN.md sections 5-7.)
 namespace ctc {
 namespace fused6 {
 
@@ -56,15 +57,12 @@ using namespace ctc::fused;
 
 using linear::DEAD; using linear::GAP; using linear::GAP_WIDE; using linear::DOWN_MAX; using linear::DECAY_MAX; using linear::KK_MAX;
 using linear::KK_MAX2; using linear::EMIS_MIN; using linear::MASS_TOL;  // (ctc_linear_flags.h: shared with ctc_hvp_fused.hip)
-#ifndef CTC_F6_GAP_LIVE
-#define CTC_F6_GAP_LIVE 16
-#endif
 // Gap to which a lane that HOLDS mass is lifted towards its upstream neighbour.  It has to be the adoption gap: r04 tried 80 (a live
 // lane's own thin values then survive 2^64 deeper -- tests/tools/linear_model.py shows the mass of tests/golden/soak_case_endloss_u128.npz
 // intact with it), but mantissas then reach 2^120 where a steep front crosses thin live lanes, the posterior PRODUCTS of phase 2
 // overflow, and between the frames D6 samples that went unnoticed: a gradient 3.0 off, unflagged (tests/tools/flag_stats.py, cell
 // sigma 5, V = 3, U = 32, slack 2).  With 16 per level and LV levels a mantissa stays below 2^55 and a product below 2^110.
-constexpr int GAP_LIVE = CTC_F6_GAP_LIVE;
+constexpr int GAP_LIVE = 16;
 // GAP_WIDE (ctc_linear_flags.h):      // ... when ONE level suffices (a lane of 4 or 8 label positions is never crossed within a period):
                                   // neighbouring lanes then differ by 2^100 and more on benign inputs, and lifting a lane to
                                   // 2^-16 of its neighbour pushed its own values towards the float32 underflow (D4)
@@ -97,11 +95,7 @@ constexpr int D10_DWELL = 2048;
 // WITHOUT tripping D1..D5 (loss off by 1e-4 .. 3e-2 relative): a call with a gradient sees it in the posterior mass (D6) and redoes the
 // utterance, a loss-only call has nothing to check against.  Every such case had a needed emission below 2^-18.9; N(0,1) logits stay
 // above 2^-13 (the 4.5-sigma tail of 129 000 draws).  So a loss-only call hands sharp utterances to the log domain.
-#ifdef CTC_F6_NO_D7  // (diagnostic builds: what do loss-only calls lose without the guard?)
-constexpr float EMIS_SOFT = 0.f;
-#else
 using linear::EMIS_SOFT;                           // 2^-16 (D7)
-#endif
 // D6: tolerated deviation of a frame's posterior mass from 1.  The gradient of an unflagged utterance is off by about as much, and the
 // bar is 1e-4: with a tolerance of 1e-4 the soak runs measured up to 9.0e-5 on unflagged utterances -- no margin (r03).
 // MASS_TOL (ctc_linear_flags.h):
@@ -131,67 +125,15 @@ __device__ Stamps *g_stamps_dummy;
 #define F6_STAMP_DUMP(wave)
 #endif
 __device__ __forceinline__ void block_barrier_raw() {
-#ifdef CTC_F6_SYNC
-  __syncthreads();
-#else
   __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed; vmcnt untouched
   __builtin_amdgcn_s_barrier();
-#endif
 }
 
-// ------------------------------------------------------------------------------------------------
-// Producer / consumer words in LDS instead of a block barrier (phase 1).  With one s_barrier per block every block lasts as long
-// as its slowest wavefront, and the slowest changes from block to block (a late HBM row here, a renormalisation there): r03's
-// stamps showed every wavefront WAITING 45 % of phase 1.  Each stage has a dependent chain of ~1 us per block (load -> reduction
-// -> exponentials -> reduction -> LDS gather; twelve dependent lattice steps), which the barrier lines up end to end instead
-// of letting them overlap.  Now every E-stage worker publishes "my rows of block j are in LDS" in a word of its own, the chain
-// publishes "block j is in my registers", and a wavefront only ever waits for what it really needs; the E rows' three slots let
-// the workers run up to two blocks ahead of the chain.
-//   * LDS operations of one wavefront execute in program order: a progress word written after the rows it announces is
-//     visible after them, and the chain's "consumed" word, written after its row reads were issued, lands after they executed.
-//   * every wait is bounded: a wavefront that gives up raises D8 (the utterance is redone by the log-domain roles, which use
-//     real barriers) and carries on -- nothing can hang.
-// ------------------------------------------------------------------------------------------------
-#ifndef CTC_F6_P1SYNC
-#define CTC_F6_P1SYNC 0
-#endif
-#ifdef CTC_F6_D9
-#define CTC_F6_D9_ON true
-#else
-#define CTC_F6_D9_ON false
-#endif
-constexpr int D9_RANGE = 512;                   // flag: a nonzero lattice value left the range a lane's exponent can hold (checked renorm)
-constexpr unsigned RANGE_MIN_BITS = 0x0D800000u - 1u;  // bits of 2^-100, minus one: (bits - 1) < this  <=>  0 < value < 2^-100
-__device__ __forceinline__ unsigned umin(unsigned a, unsigned b) { return a < b ? a : b; }
-constexpr int SYNC_LIMIT = 1 << 16;  // polls (~100 cycles each with the sleep) before a wait gives up
-constexpr int D8_SYNC = 256;         // flag: a producer / consumer wait timed out
-// (the words are addressed as LDS explicitly: through a generic pointer a volatile access becomes a flat load with `s_waitcnt vmcnt(0)`,
-// which would drain every outstanding HBM load of the polling wavefront)
-typedef __attribute__((address_space(3))) volatile int lds_vint;
-__device__ __forceinline__ lds_vint *as_lds(const int *p) { return (lds_vint *)p; }
-// waits until *p >= target (one word, same address in every lane: an LDS broadcast); false on timeout
-__device__ __forceinline__ bool wait_word_ge(const int *p, int target) {
-  lds_vint *q = as_lds(p);
-  for (int n = 0; n < SYNC_LIMIT; ++n) {
-    if (__builtin_amdgcn_readfirstlane(*q) >= target) return true;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
-// waits until p[0 .. n-1] are all >= target (lane i reads word min(i, n-1))
-__device__ __forceinline__ bool wait_words_ge(const int *p, int n, int target, int lane) {
-  lds_vint *q = as_lds(p) + (lane < n ? lane : n - 1);
-  for (int it = 0; it < SYNC_LIMIT; ++it) {
-    if (__builtin_amdgcn_ballot_w64(*q < target) == 0) return true;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return false;
-}
-// lane 0 stores v at p, the other lanes into a sink of their own (no exec-mask branch around the store)
-__device__ __forceinline__ void publish_word(int *p, float *dump, int lane, int v) {
-  const int *q = (lane == 0) ? p : reinterpret_cast<const int *>(dump) + lane;
-  *as_lds(q) = v;
-}
+// One block barrier per block in phase 1.  Producer / consumer words in LDS in its place were built and measured in r04: no gain
+// (134.7-137.6 against 135.3-136.0 us), and racy as written; profiles/r04_kernel_experiments.md, profiles/r04_p1sync_stamps.txt.
+// Flag bits 256 (D8: such a wait timed out) and 512 (D9: a checked renormalisation saw a value leave its lane's range -- flagged 60 %
+// of benign utterances and still missed a harmful one, tests/tools/flag_stats.py) are retired, never set, and stay reserved.
+constexpr int D8_RETIRED = 256, D9_RETIRED = 512;  // still in the masks of the meeting point and in flag_or(): the same device code
 
 __device__ __forceinline__ int from_prev_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ int from_next_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x130, 0xf, 0xf, false); }
@@ -204,9 +146,6 @@ __device__ __forceinline__ int readlane_i(int v, int l) { return __builtin_amdgc
 // way (r04: 263 -> 238 instructions per block) made phase 1 two microseconds SLOWER and phase 2 no faster -- a packed operation
 // occupies the SIMD for two passes, and the helpers share their SIMDs' pipes with the chains (profiles/r04_kernel_experiments.md).
 typedef float f2v __attribute__((ext_vector_type(2)));
-#ifndef CTC_F6_PACKED
-#define CTC_F6_PACKED 1
-#endif
 // acc += (x of the upstream neighbour lane) * sc in ONE instruction (v_fmac_f32 with a DPP source; was v_mov_b32_dpp + v_ldexp_f32 +
 // v_add_f32).  The lane without an upstream neighbour (0 for wave_shr, 63 for wave_shl) is left unchanged (bound_ctrl off: the
 // lane is disabled).  `s_nop 1`: a DPP source written by the preceding VALU instruction needs two wait states, and the compiler
@@ -222,12 +161,10 @@ __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 // renormalisation period inside a block and the number of lanes the lattice front can cross in one period
 template <int BLK, int NL>
 struct Cad {
-#ifndef CTC_F6_RN12
-#define CTC_F6_RN12 6
-#endif
   // 12-frame blocks: two label positions per lane renormalise every 6 frames (r03: with the posterior scale in two factors the
   // longer period no longer raises D5 on long utterances; -4 us at the north-star shape), one position per lane every 4
-  static constexpr int RN = (BLK % 4 == 0) ? (NL == 2 ? CTC_F6_RN12 : 4) : 3;
+  static constexpr int RN12 = 6;  // other periods were measured as build variants, profiles/r04_kernel_experiments.md
+  static constexpr int RN = (BLK % 4 == 0) ? (NL == 2 ? RN12 : 4) : 3;
   static constexpr int NG = BLK / RN;            // exponent groups of the rows of one block
   static constexpr int LV = (RN + NL - 1) / NL;  // adoption levels: lanes the lattice front can cross in one period
   static constexpr int NSEG = 2 * NG + 1;        // posterior-scale segments of one block (kl_segment)
@@ -274,8 +211,8 @@ struct Lds {
   float bins[2 * NH][V + 4];
   float dump[NW][64];
   double l2s[NW];           // per worker: sum over its phase-1 frames of log2 sum_k exp(x_k - rowmax)
-  int p1_prog[2][8];        // phase 1: blocks of side s whose E rows worker w has written (its own word)
-  int p1_cons[2];           // phase 1: blocks of side s whose E rows the main chain has read into registers
+  int p1_unused[18];        // zeroed at kernel start, never read (words of the retired phase-1 hand-off): dropping them and their
+                            // zeroing stores would change the product's device code, which this layout is measured with
   int flag;                 // OR of D1..D5 over the wavefronts
   int feasible;             // 1: phase 2 runs
   int lp_int;               // posterior scale: 2^-lp_int * cf = 1 / (P in mantissa units)
@@ -373,7 +310,7 @@ struct RRow {
 };
 template <int KIND, int NL, class LDt>
 __device__ __forceinline__ void read_R(const float *row, int lane, RRow<KIND, NL> &r) {
-  if constexpr (KIND == 0 && NL == 2 && CTC_F6_PACKED != 0) {  // (c0, c1, o0, o1): both halves are register pairs for the packed products
+  if constexpr (KIND == 0 && NL == 2) {  // (c0, c1, o0, o1): both halves are register pairs for the packed products
     const float4 t = *reinterpret_cast<const float4 *>(row + 4 * lane);
     r.c[0] = t.x; r.c[1] = t.y; r.o[0] = t.z; r.o[1] = t.w;
   } else ld_pairs<NL>(row + 2 * lane * NL, r.c, r.o);
@@ -382,7 +319,7 @@ __device__ __forceinline__ void read_R(const float *row, int lane, RRow<KIND, NL
 }
 template <int KIND, int NL, class LDt>
 __device__ __forceinline__ void write_R(float *row, float *dump, int lane, const float (&c)[NL], const float (&o)[NL], float cx, int kx) {
-  if constexpr (KIND == 0 && NL == 2 && CTC_F6_PACKED != 0) *reinterpret_cast<float4 *>(row + 4 * lane) = make_float4(c[0], c[1], o[0], o[1]);
+  if constexpr (KIND == 0 && NL == 2) *reinterpret_cast<float4 *>(row + 4 * lane) = make_float4(c[0], c[1], o[0], o[1]);
   else st_pairs<NL>(row + 2 * lane * NL, c, o);
   float *tq = (lane == 0) ? row + 2 * LDt::UP : dump + (lane & 31) * 2;  // lanes > 0 write a sink
   *reinterpret_cast<float2 *>(tq) = make_float2(cx, __int_as_float(kx));
@@ -402,7 +339,7 @@ struct Chain {
   int k, kx, dk;
   bool norep[NL], norep_next[NL];
   int flag;
-  static constexpr bool PACKED = (CTC_F6_PACKED != 0) && KIND == 0 && NL == 2;
+  static constexpr bool PACKED = KIND == 0 && NL == 2;
   float nrf[NL];  // PACKED: 1.0 where the repeat rule lets the diagonal pass (norep_next for A, norep for B), else 0.0
   float sc, scb;  // PACKED: 2^dk as a float (0 below 2^-126: what v_ldexp_f32 would flush), and the same on the boundary lane only
 
@@ -522,15 +459,8 @@ struct Chain {
 
   // per-lane renormalisation: k <- exponent of the lane maximum (lanes without mass adopt the upstream exponent - GAP so
   // that what flows in during the next period is representable), cx to its own exponent, dk refreshed
-  // `checked` (wave-uniform; loss-only calls, which have no posterior mass to check -- D6 -- against): D9, the exact form of "the format
-  // lost something".  With needed emissions > 0 (D2) a lattice value that is nonzero stays nonzero, so (a) a mantissa that WAS
-  // nonzero at the previous renormalisation and is zero now has been flushed, and (b) a nonzero mantissa below 2^-RANGE_MIN of its
-  // lane's exponent -- before or after this renormalisation's shift -- is about to lose bits to gradual underflow, or cannot take a
-  // small inflow any more.  Values only decay between two renormalisations unless something larger flows in, so looking here,
-  // every RN frames, misses nothing.  (Until r04 loss-only calls relied on D3 / D4 -- lane maxima only -- and on D7, a sharpness
-  // heuristic that sent every utterance of a trained model to the log domain.)
   template <int LV>
-  __device__ __forceinline__ void renorm(bool checked = false) {
+  __device__ __forceinline__ void renorm() {
     float m = c[0];
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
@@ -543,8 +473,8 @@ struct Chain {
     const bool xlive = cx > 0.f;
     const int ex = xlive ? frexp_e(cx) + kx : DEAD;
     int kn = e_own;
-    // one level always (a lane far below its upstream neighbour is lifted to its exponent - GAP); the further levels only
-    // serve lanes without mass, which need an exponent before the front reaches them (wave-uniform branch)
+    // the first level: a lane far below its upstream neighbour is lifted to that neighbour's exponent - GAP (a lane that holds mass:
+    // - GAP_LIVE at least); lanes without mass get an exponent this way before the front reaches them
     {
       const int nb = (DIR == 0) ? from_prev_lane_i(kn, ex) : from_next_lane_i(kn, ex);
       kn = imax(kn, nb - (live ? imax(GAP_LIVE, LV == 1 ? GAP_WIDE : GAP) : (LV == 1 ? GAP_WIDE : GAP)));
@@ -569,28 +499,6 @@ struct Chain {
     // legitimately swamped when the bulk arrives, ~1 in 256 benign utterances)
     age = (live && alive) ? age + 1 : 0;
     flag |= (live && age >= 3 && d < -DOWN_MAX ? 4 : 0) | (live && fe < -DECAY_MAX ? 8 : 0) | (!live && alive ? 16 : 0);
-#ifdef CTC_F6_DEBUG
-    ++cnt;
-    if (live && d < -DOWN_MAX && dbg0 == 0) { dbg0 = cnt; dbg1 = d; dbg2 = fe; }
-    mlast = m;
-#endif
-    if (checked) {
-      // min over the lane's NONZERO mantissas, before and after the shift ((bits - 1) as unsigned: zero becomes the largest value),
-      // and the pattern of zeros against the previous renormalisation's
-      unsigned mn = 0xFFFFFFFFu, zeros = 0u;
-      const int dneg = imin(d, 0);
-#pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        mn = umin(mn, __float_as_uint(ldexp_f(c[j], dneg)) - 1u);
-        zeros |= (c[j] == 0.f ? 1u : 0u) << (2 * j);
-        if constexpr (KIND == 0) {
-          mn = umin(mn, __float_as_uint(ldexp_f(o[j], dneg)) - 1u);
-          zeros |= (o[j] == 0.f ? 2u : 0u) << (2 * j);
-        }
-      }
-      flag |= ((mn < RANGE_MIN_BITS) || (zeros & ~zprev) != 0u) ? D9_RANGE : 0;
-      zprev = zeros;
-    }
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       c[j] = ldexp_f(c[j], d);
@@ -603,7 +511,6 @@ struct Chain {
     set_scale();
     alive = live;
   }
-  unsigned zprev = 0xFFFFFFFFu;  // D9: which of the lane's mantissas were zero at the previous renormalisation (everything, at the start)
   bool boundary = false;
   // dk as the factor the packed step multiplies by (after every change of dk)
   __device__ __forceinline__ void set_scale() {
@@ -615,10 +522,6 @@ struct Chain {
   bool alive = false;  // the lane had mass at its last renormalisation
   int age = 0;         // consecutive renormalisations with mass
   bool relevant = true;
-#ifdef CTC_F6_DEBUG
-  int cnt = 0, dbg0 = 0, dbg1 = 0, dbg2 = 0;
-  float mlast = 0.f;
-#endif
   // number of label positions 1 .. ll-1 that repeat their predecessor (classic: each costs one more frame); wave-uniform
   __device__ __forceinline__ int repeats(int ll, int lane) const {
     int n = 0;
@@ -631,10 +534,9 @@ struct Chain {
     int f = 0;
 #pragma unroll
     for (int bit = 4; bit <= 16; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
-    f |= (__builtin_amdgcn_ballot_w64((flag & D9_RANGE) != 0) != 0) ? D9_RANGE : 0;
+    f |= (__builtin_amdgcn_ballot_w64((flag & D9_RETIRED) != 0) != 0) ? D9_RETIRED : 0;  // (never set; the compiler cannot always tell)
     return f;
   }
-
 };
 
 // checkpoint row in HBM: the chain's NATIVE state.  rows: [slot][SRS] floats (pairs (c, o) for classic, c for simplified,
@@ -847,40 +749,20 @@ struct Rows {
 // point): positions P0 .. P0+NQ-1 of every block of side SIDE.  Records (mxl, inv) per frame for phase 2, accumulates
 // log2 sum exp of its frames in double and tracks the smallest needed emission (D2).
 // ------------------------------------------------------------------------------------------------
-#ifndef CTC_F6_PFD
-#define CTC_F6_PFD 2
-#endif
-#ifndef CTC_F6_ONLY  // experiment: which roles work in phase 2 (1 main, 2 recompute, 4 helper E stage, 8 helper G stage) and in phase 1 (16 main, 32 E stage); others only keep the barriers
-#define CTC_F6_ONLY 63
-#endif
-#ifndef CTC_F6_NH12   // helpers per side of the 12-frame-block instantiations (V <= 256, U <= 128).  6 = sixteen wavefronts, two frames per
-#define CTC_F6_NH12 4 // helper and block, was built and measured in r03: 134 against 127 us at B = 64, 161 against 151 at B = 256 (same box) --
-#endif                // the main chains lose more to two extra wavefronts on their SIMDs than the helpers gain.  Diagnostic builds only.
-#ifndef CTC_F6_PRIO1  // experiment: issue priority of the main chains before the meeting point / of the helpers of side B
-#define CTC_F6_PRIO1 3
-#endif
-#ifndef CTC_F6_HPRIO_B
-#define CTC_F6_HPRIO_B 0
-#endif
-#ifndef CTC_F6_X
-#define CTC_F6_X 2
-#endif
-#ifndef CTC_F6_Y
-#define CTC_F6_Y 2
-#endif
+// Frames of a block per E-stage worker of a side: NH = 4 (12-frame blocks) X / X / Y / Y for the helpers and R for the recompute wavefront.
 template <int BLK, int NH, int NL>
 struct P1Split {
-  // (NH = 1, the 3-frame blocks of the 8-positions-per-lane variant: two frames for the helper, one for the recompute wavefront;
-  // NH = 6, sixteen wavefronts: two frames for every helper, none for the recompute wavefronts)
+  // (NH = 1, the 3-frame blocks of the 8-positions-per-lane variant: two frames for the helper, one for the recompute wavefront)
   // (NH = 3 for the six-frame blocks of the four-positions-per-lane variant -- 2, 2, 1 frames for the helpers, 1 for the recompute
   // wavefront -- was built and measured in r04: 227 us against 211 at U = 256: those shapes are bound by their chains, and more
-  // helpers only take issue slots from them)
-  static constexpr int X = NH == 6 ? BLK / 6 : NH == 4 ? CTC_F6_X : NH == 2 ? BLK / 3 : 2, Y = NH == 6 ? BLK / 6 : NH == 4 ? CTC_F6_Y : NH == 2 ? BLK / 3 : 0;
-  static constexpr int R = NH == 6 ? 0 : NH == 4 ? BLK - 2 * X - 2 * Y : NH == 2 ? BLK - X - Y : BLK - X;
-  static_assert(NH == 6 || NH == 4 || NH == 2 || NH == 1, "helpers per side");
+  // helpers only take issue slots from them.  NH = 6 for the 12-frame blocks, sixteen wavefronts, two frames per helper: r03, 134
+  // against 127 us at B = 64, 161 against 151 at B = 256 -- the main chains lose more to two extra wavefronts on their SIMDs than
+  // the helpers gain.  Other splits for NH = 4: profiles/r04_kernel_experiments.md.)
+  static constexpr int X = NH == 4 ? 2 : NH == 2 ? BLK / 3 : 2, Y = NH == 4 ? 2 : NH == 2 ? BLK / 3 : 0;
+  static constexpr int R = NH == 4 ? BLK - 2 * X - 2 * Y : NH == 2 ? BLK - X - Y : BLK - X;
+  static_assert(NH == 4 || NH == 2 || NH == 1, "helpers per side");
   static_assert(X >= 0 && Y >= 0 && R >= 0 && X <= 6 && Y <= 6 && R <= 6, "phase-1 split: at most 6 frames per worker");
   static constexpr int count(int worker) {
-    if (NH == 6) return worker < 6 ? X : R;
     if (NH == 4) return worker < 2 ? X : worker < 4 ? Y : R;
     if (NH == 1) return worker == 0 ? X : R;
     return worker == 0 ? X : worker == 1 ? Y : R;
@@ -921,7 +803,7 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KI
   // logits rows are loaded PFD blocks ahead of their use (a block lasts ~2 us, an HBM load under load about as long: one
   // block of look-ahead left the E stage waiting on memory for half of phase 1), in a ring of register sets addressed by
   // (block mod PFD) at COMPILE time -- the loop is unrolled by PFD
-  constexpr int PFD = CTC_F6_PFD;
+  constexpr int PFD = 2;  // other depths were build variants, profiles/r04_kernel_experiments.md
   float4 xb[PFD][NQA][VPL];
   static_for<0, PFD>([&](auto R) {
     static_for<0, NQA>([&](auto Q) {
@@ -944,19 +826,14 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KI
   // conditional store or load in the loop that is zero, every use of the ring drained ALL outstanding loads and the
   // look-ahead bought nothing (phase 1 ran at the latency of one HBM round trip per block).
   float2 *sink = stats_sink + (wave & 7) * 32 + (lane & 31);  // statistics of lanes that hold no frame go here
-  const int widx = (wave < 4) ? NH : (wave - 4) % NH;         // this worker's progress word (helpers 0 .. NH-1, the recompute wavefront NH)
-  bool sync_bad = false;
   auto body = [&](auto R, auto FASTt, int it) __attribute__((always_inline)) {
     constexpr int r = decltype(R)::value;  // = it mod PFD
     constexpr bool FAST = decltype(FASTt)::value;
     const int j = it;
-    if ((CTC_F6_ONLY & 32) && (FAST || (NQ > 0 && j < nb))) {
+    if (FAST || (NQ > 0 && j < nb)) {
       const int g = geo.absblock(1, SIDE, j);
       const int nv = FAST ? BLK : geo.nvof(g);
       float(*E)[LD::ES] = lds.E[SIDE][j % 3];
-      if constexpr (CTC_F6_P1SYNC != 0) {  // slot j % 3 is free once the chain has block j - 3 in its registers
-        F6_WAIT(if (j >= 3 && !wait_word_ge(&lds.p1_cons[SIDE], j - 2)) sync_bad = true);
-      }
       float smx = 0.f, ssum = 1.f;  // lane d keeps the statistics of position d of the block (its sum; ONE reciprocal below)
       if (FAST || nv == BLK) {
         if constexpr (NQ > 0) {
@@ -1004,9 +881,8 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KI
       const bool mine = lane >= P0 && lane < P0 + NQ && lane < nv;
       float2 *dst = mine ? stats + geo.frame(SIDE, g, mine ? lane : 0) : sink;  // unconditional store: no branch
       *dst = make_float2(smx, __builtin_amdgcn_rcpf(ssum));  // 1 / sum exp of this lane's frame
-      if constexpr (CTC_F6_P1SYNC != 0) publish_word(&lds.p1_prog[SIDE][widx], dump, lane, j + 1);  // (after the E rows, in order)
     }
-    if constexpr (CTC_F6_P1SYNC == 0) F6_BARRIER();
+    F6_BARRIER();
   };
   // the first PFD blocks through the general body (side B starts with the utterance's last block, the only one that can
   // be partial); then the steady state; then whatever is left of the NB + 1 iterations every wavefront makes
@@ -1041,7 +917,6 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KI
   for (int j = 0; j < NL; ++j) sharp = sharp || (S.valid[j] && !(zmin[j] >= EMIS_SOFT));
   if (NQ > 0 && nb > 0 && __builtin_amdgcn_ballot_w64(sharp) != 0 && lane == 0) atomicOr(&lds.flag, 128);
   if (lane == 0) lds.l2s[wave] = acc;
-  if (sync_bad && lane == 0) atomicOr(&lds.flag, D8_SYNC);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1069,8 +944,6 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
   const int *oth_k = kexp_ws + ((long)b * 2 + (1 - DIR)) * nslot * 64;
   S.init_labels(p, b, lane, ll);
   S.template start<LV>(lane, ll, UP);
-  float *dump = lds.dump[DIR];
-  (void)dump;
   int *flag_ws_dbg = flag_ws;
   (void)flag_ws_dbg;
   F6_STAMP_DECL
@@ -1084,51 +957,39 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
   // ================= phase 1: lattice steps, one checkpoint row per block =================
   {
     const int nb = geo.nblocks(1, DIR);
-    using SPm = P1Split<BLK, NH, NL>;
-    constexpr int NWK = NH + (SPm::count(NH) > 0 ? 1 : 0);  // E-stage workers of a side that hold frames
-    bool sync_bad = false;
-    for (int it = (CTC_F6_P1SYNC != 0 ? 1 : 0); it <= (CTC_F6_P1SYNC != 0 ? nb : geo.NB); ++it) {
+    bool p1_timeout = false;  // never set (retired D8); with it and the statement behind the loop gone the loop's exit branch compiles the
+                              // other way round: kept until a change that may alter the device code
+    for (int it = 0; it <= geo.NB; ++it) {
       const int j = it - 1;
-      if ((CTC_F6_ONLY & 16) && j >= 0 && j < nb) {
+      if (j >= 0 && j < nb) {
         const int g = geo.absblock(1, DIR, j);
         const int nv = geo.nvof(g);
         const float(*E)[LD::ES] = lds.E[DIR][j % 3];
         spill<KIND, NL, DIR>(S, own_rows, own_k, geo.slot(DIR == 0 ? BLK * g : BLK * g + nv), SRS, UP, lane);
-        if constexpr (CTC_F6_P1SYNC != 0) {  // every worker of this side has written its rows of block j
-          F6_WAIT(if (!wait_words_ge(lds.p1_prog[DIR], NWK, j + 1, lane)) sync_bad = true);
-        }
         if (nv == BLK) {
           // the emission rows of the whole block go to registers first: the sequential chain never waits for an LDS round
           // trip (with the read next to its use every frame paid one, ~100 of its ~190 cycles)
           Emis<NL> eb[BLK];
           static_for<0, BLK>([&](auto D) { read_E<NL, LD>(E[decltype(D)::value], lane, eb[decltype(D)::value]); });
-          if constexpr (CTC_F6_P1SYNC != 0) publish_word(&lds.p1_cons[DIR], dump, lane, j + 1);  // (behind the reads, in order)
           static_for<0, BLK>([&](auto D) {
             constexpr int d = decltype(D)::value;
             S.step(eb[d]);
-            if ((d + 1) % RN == 0) S.template renorm<LV>(CTC_F6_D9_ON && !want_grad);
+            if ((d + 1) % RN == 0) S.template renorm<LV>();
           });
         } else {
           for (int d = 0; d < nv; ++d) {
             Emis<NL> e;
             read_E<NL, LD>(E[d], lane, e);
             S.step(e);
-            if ((d + 1) % RN == 0 || d == nv - 1) S.template renorm<LV>(CTC_F6_D9_ON && !want_grad);
+            if ((d + 1) % RN == 0 || d == nv - 1) S.template renorm<LV>();
           }
-          if constexpr (CTC_F6_P1SYNC != 0) publish_word(&lds.p1_cons[DIR], dump, lane, j + 1);
         }
       }
-      if constexpr (CTC_F6_P1SYNC == 0) F6_BARRIER();
+      F6_BARRIER();
     }
-    if (sync_bad && lane == 0) atomicOr(&lds.flag, D8_SYNC);
+    if (p1_timeout && lane == 0) atomicOr(&lds.flag, D8_RETIRED);
   }
   spill<KIND, NL, DIR>(S, own_rows, own_k, geo.slot(geo.tm), SRS, UP, lane);  // alpha[tm] / beta[tm]: the meeting row
-#ifdef CTC_F6_DEBUG
-  {
-    int *dbg = flag_ws + p.B + ((long)b * 2 + DIR) * 256 + 0;  // diagnostic builds: per lane (renorm count at death, k, last max)
-    dbg[lane] = S.dbg0; dbg[64 + lane] = S.dbg1; dbg[128 + lane] = S.dbg2; dbg[192 + lane] = S.k;
-  }
-#endif
   {
     const int f = S.flag_or();  // D3 / D4 of phase 1
     if (f != 0 && lane == 0) atomicOr(&lds.flag, f);
@@ -1183,9 +1044,9 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
     double sl2 = 0.0;
     for (int w = 2; w < LD::NW; ++w) sl2 += lds.l2s[w];
     // D3 / D4 (bits 4, 8, 16) and D7 (128) send a loss-only call to the log-domain kernel; with a gradient the mass check D6 decides.
-    // (D9, the exact "a nonzero value left its lane's range" of checked renormalisations, is recorded in CTC_F6_D9 diagnostic builds
-    // only: benign utterances flush irrelevant values all the time -- the thin front ahead of the bulk, the tail behind it -- so it
-    // flags 60 % of the N(0,1) utterances at T = 1000 and still missed one harmful case in 30 000; tests/tools/flag_stats.py)
+    // (D9, the exact "a nonzero value left its lane's range" at every renormalisation, was tried and retired: benign utterances flush
+    // irrelevant values all the time -- the thin front ahead of the bulk, the tail behind it -- so it flagged 60 % of the N(0,1)
+    // utterances at T = 1000 and still missed one harmful case in 30 000; tests/tools/flag_stats.py)
     // r04: ... in the FIRST HALF OF A FORWARD / BACKWARD PAIR (ctc_amd_loss_forward: the resume call will check every utterance's
     // posterior mass and redo what fails) only where the sound detector, the mass check D6 of calls with a gradient, finds
     // something to redo -- measured over ~100 000 utterances (tests/tools/flag_stats.py, flag_stats_short_labels.py; U <= 128,
@@ -1210,7 +1071,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
     // calls returned a loss more than 1e-4 off (r04, tests/tools/flag_stats_short_labels.py; r03's rules had the same hole).
     // Nothing is redone at 30 frames per label position, 0-1.6 % at 57.
     const int hard = (!want_grad && NL >= 2 && okP && len > DWELL_HARD * (ll + 1)) ? D10_DWELL : 0;
-    const int fl = (lds.flag & (want_grad ? (3 | D8_SYNC) : (3 | soft | D8_SYNC))) | (okP ? 0 : 1) | hard;
+    const int fl = (lds.flag & (want_grad ? (3 | D8_RETIRED) : (3 | soft | D8_RETIRED))) | (okP ? 0 : 1) | hard;
     if (lane == 0) {
       const double dlogp = (double)flog2(s) + (double)EX - sl2;
       logp_ws[b] = okP ? dlogp : -INFINITY;
@@ -1239,7 +1100,6 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
   const float cf30 = ldexp_f(lds.cf, 30);
   const bool carrier = lane == (DIR == 0 ? 0 : 63);
   F6_STAMP_PHASE2
-  if (CTC_F6_PRIO1 != 3) __builtin_amdgcn_s_setprio(3);
 
   // ================= phase 2: everything from LDS =================
   {
@@ -1247,7 +1107,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
     int kflag = 0;
     for (int it = 0; it <= geo.NB + 2; ++it) {
       const int j = it - 2;
-      if ((CTC_F6_ONLY & 1) && j >= 0 && j < nb) {
+      if (j >= 0 && j < nb) {
         const int g = geo.absblock(2, DIR, j);
         const int nv = geo.nvof(g);
         const float(*E)[LD::ES] = lds.E[DIR][j % 3];
@@ -1538,7 +1398,7 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const Layout &L,
   load_ck<KIND, NL>(ck_next, ck_rows, ck_k, ck_slot(0), SRS, UP, lane);
   for (int it = 0; it <= geo.NB + 2; ++it) {
     const int j = it - 1;
-    if ((CTC_F6_ONLY & 2) && j >= 0 && j < nb) {
+    if (j >= 0 && j < nb) {
       const int g = geo.absblock(2, SIDE, j);
       const int nv = geo.nvof(g);
       const float(*E)[LD::ES] = lds.E[SIDE][j % 3];
@@ -1652,16 +1512,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
   // ================= phase 1: E stage with statistics =================
   if (p.resume != 1) {
     using SP = P1Split<BLK, NH, NL>;
-    if constexpr (NH == 6) {
-      switch (h) {
-        case 0: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(0), SP::count(0)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-        case 1: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(1), SP::count(1)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-        case 2: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(2), SP::count(2)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-        case 3: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(3), SP::count(3)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-        case 4: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(4), SP::count(4)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-        default: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(5), SP::count(5)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
-      }
-    } else if constexpr (NH == 4) {
+    if constexpr (NH == 4) {
       switch (h) {
         case 0: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(0), SP::count(0)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
         case 1: estage1<KIND, NL, NH, BLK, VPL, XT, DIR, SP::first(1), SP::count(1)>(S, lds, geo, stats, sinkp, dump, lane, wave F6_ST_ARG); break;
@@ -1692,14 +1543,9 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
     // stage three blocks later: a ring of five register sets addressed by (block mod 5) at COMPILE time.  Wide vocabularies
     // (four row segments per lane) hold two sets; their G stage re-reads and re-exponentiates its rows.
     constexpr bool RELOAD = VPL >= 4;
-    // LA = 1: rows of block it+1 requested at the top of iteration it.  LA = 2: the register set the G stage has just consumed
-    // (block it-3) takes the rows of block it+2 at once, at the END of iteration it -- nearly two blocks of look-ahead with the same
-    // five sets.  Measured in r03 (one process, same box): LA = 2 153 us against 139 at B = 256, 131 against 125 at B = 64; a six-set
-    // ring spills (193 against 149).  More look-ahead does not help this kernel; LA = 2 stays a diagnostic switch.
-#ifndef CTC_F6_LA
-#define CTC_F6_LA 1
-#endif
-    constexpr int LA = RELOAD ? 1 : CTC_F6_LA;
+    // Rows of block it+1 are requested at the top of iteration it.  Two blocks of look-ahead with the same five sets (the set the G
+    // stage has just consumed taking block it+2 at the end of iteration it) were measured in r03 (one process, same box): 153 us
+    // against 139 at B = 256, 131 against 125 at B = 64; a six-set ring spills (193 against 149).  More look-ahead does not help.
     constexpr int RING = RELOAD ? 2 : 5;
     float4 X[RING][FPH][VPL];
     float4 XG[RELOAD ? FPH : 1][VPL];
@@ -1711,14 +1557,11 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
         static_for<0, VPL>([&](auto W) { X[decltype(R)::value][decltype(Q)::value][decltype(W)::value] = make_float4(0.f, 0.f, 0.f, 0.f); });
       });
     });
-    float2 st_cur = make_float2(0.f, 0.f), st_n1 = make_float2(0.f, 0.f), st_next = make_float2(0.f, 0.f);
+    float2 st_cur = make_float2(0.f, 0.f), st_next = make_float2(0.f, 0.f);
     bool massbad = false;
     if (nb > 0) {
-      static_for<0, LA>([&](auto A) {
-        static_for<0, FPH>([&](auto Q) { S.io.load_x(X[decltype(A)::value][decltype(Q)::value], fr(2, decltype(A)::value, h + NH * decltype(Q)::value)); });
-      });
+      static_for<0, FPH>([&](auto Q) { S.io.load_x(X[0][decltype(Q)::value], fr(2, 0, h + NH * decltype(Q)::value)); });
       st_cur = stats[fr(2, 0, lane)];
-      if constexpr (LA == 2) st_n1 = stats[fr(2, 1, lane)];
     }
     // FAST: steady state (E stage on a full block, G stage on a full block): no branch around a memory operation, so the
     // `s_waitcnt vmcnt(N)` hipcc derives for the ring leave the look-ahead loads AND the gradient stores of the last
@@ -1726,8 +1569,8 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
     auto body = [&](auto R, auto FASTt, int it) __attribute__((always_inline)) {
       constexpr bool FAST = decltype(FASTt)::value;
       constexpr int r = decltype(R)::value;         // = it mod RING
-      constexpr int rn = (r + 1) % RING;            // block it+1 (LA = 1: being loaded)
-      constexpr int rg = (r + 2) % RING;            // block it-3 (G stage; not with RELOAD), then block it+2 (LA = 2)
+      constexpr int rn = (r + 1) % RING;            // block it+1 (being loaded)
+      constexpr int rg = (r + 2) % RING;            // block it-3 (G stage; not with RELOAD)
       if constexpr (RELOAD) {
         static_for<0, FPH>([&](auto Q) { S.io.load_x(XG[decltype(Q)::value], fr(2, it - 3, h + NH * decltype(Q)::value)); });
         sgl = stats[fr(2, it - 3, lane)];
@@ -1735,16 +1578,14 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
       // ---- E stage (block it) ----
       const int j = it;
       SG[r] = st_cur;
-      if ((CTC_F6_ONLY & 4) && (FAST || j < nb)) {
+      if (FAST || j < nb) {
         const int g = geo.absblock(2, DIR, j);
         const int nv = FAST ? BLK : geo.nvof(g);
         float(*E)[LD::ES] = lds.E[DIR][j % 3];
-        if constexpr (LA == 1) {
-          st_next = stats[fr(2, j + 1, lane)];
-          // rows of the next block: their register set was freed by the G stage of the previous iteration, so the loads go out
-          // first and have the whole iteration (not the part after this block's E stage) to arrive
-          static_for<0, FPH>([&](auto Q) { S.io.load_x(X[rn][decltype(Q)::value], fr(2, j + 1, h + NH * decltype(Q)::value)); });
-        }
+        st_next = stats[fr(2, j + 1, lane)];
+        // rows of the next block: their register set was freed by the G stage of the previous iteration, so the loads go out
+        // first and have the whole iteration (not the part after this block's E stage) to arrive
+        static_for<0, FPH>([&](auto Q) { S.io.load_x(X[rn][decltype(Q)::value], fr(2, j + 1, h + NH * decltype(Q)::value)); });
         if (FAST || __builtin_expect(nv == BLK, 1)) {
           // (three passes over the frames: the gathers of all of them go through the one LDS copy back to back -- in order --
           // and their round trips overlap instead of adding up)
@@ -1771,11 +1612,11 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
             write_E(E[d], e);
           }
         }
-        if constexpr (LA == 1) st_cur = st_next;
+        st_cur = st_next;
       }
       // ---- G stage (block it-3): posterior scatter + gradient rows ----
       const int gj = it - 3;
-      if ((CTC_F6_ONLY & 8) && (FAST || (gj >= 0 && gj < nb))) {
+      if (FAST || (gj >= 0 && gj < nb)) {
         const int g = geo.absblock(2, DIR, gj);
         const int nv = FAST ? BLK : geo.nvof(g);
         const float(*SR)[LD::RS] = lds.R[DIR][gj % 3];
@@ -1822,12 +1663,6 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
           for (int jj = 0; jj < NL; ++jj) qb[FPH] += qt[FPH - 1][jj];
 #pragma unroll
           for (int f = FPH + 1; f < 4; ++f) qb[f] = 0.f;
-#ifdef CTC_F6_DEBUG2
-          if (DIR == 0 && gj == 0 && h == 1 && NL == 2) {  // what helper 1 of side A reads for position d = 1 of the first block
-            int *dbg = flag_ws_dbg + p.B + (long)b * 2048 + 1024;
-            dbg[lane] = __float_as_int(qb[0]); dbg[64 + lane] = __float_as_int(qt[0][0]); dbg[128 + lane] = __float_as_int(qt[0][NL - 1]);
-          }
-#endif
           static_assert(FPH == 3 || FPH == 2, "one four-value reduction");
           const float qall = swap_reduce<4, false>(qb);  // blank posteriors of the FPH frames and one total mass
           massbad |= !(fabsf(readlane_f(qall, SwapLanes<4>::lane(FPH)) - 1073741824.0f) < 1073741824.0f * MASS_TOL);
@@ -1864,11 +1699,6 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
             S.grad_row(geo.frame(DIR, g, d), qb, qt, ev, sd.y);
           }
         }
-      }
-      if constexpr (LA == 2) {  // (unconditional, clamped frame indices: no branch around a memory operation)
-        st_next = stats[fr(2, it + 2, lane)];
-        static_for<0, FPH>([&](auto Q) { S.io.load_x(X[rg][decltype(Q)::value], fr(2, it + 2, h + NH * decltype(Q)::value)); });
-        st_cur = st_n1; st_n1 = st_next;
       }
       F6_BARRIER();
     };
@@ -1915,9 +1745,8 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   // (the log-domain roles reuse the LDS once the linear-domain ones are done with it)
   __shared__ __attribute__((aligned(16))) union LdsBoth {
     Lds<KIND, NL, NH, BLK, VPL> lin;
-    fused5::Lds<KIND, NL, (NH == 6 ? 4 : NH), BLK, VPL> log;  // (the log-domain roles know up to four helpers per side)
+    fused5::Lds<KIND, NL, NH, BLK, VPL> log;
   } both;
-  constexpr int NH5 = NH == 6 ? 4 : NH;
   Lds<KIND, NL, NH, BLK, VPL> &lds = both.lin;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = perm ? perm[blockIdx.x] : (int)blockIdx.x;
@@ -1925,9 +1754,9 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   geo.init(clampi(p.logit_length[b], 0, p.T));
   if (threadIdx.x == 0) {
     lds.flag = 0; lds.feasible = 0; lds.lossval = INFINITY; lds.added = 0;
-    lds.p1_cons[0] = 0; lds.p1_cons[1] = 0;
+    lds.p1_unused[16] = 0; lds.p1_unused[17] = 0;  // (this order of the stores: the one the measured code has)
 #pragma unroll
-    for (int w_ = 0; w_ < 8; ++w_) { lds.p1_prog[0][w_] = 0; lds.p1_prog[1][w_] = 0; }
+    for (int i = 0; i < 8; ++i) { lds.p1_unused[i] = 0; lds.p1_unused[8 + i] = 0; }
     if (p.resume == 1) {  // the loss-only call left the outcome of the meeting point in the workspace
       const int f = flag_ws[b];
       const int2 m = meet_ws[b];
@@ -1936,11 +1765,12 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   }
   if (threadIdx.x < Lds<KIND, NL, NH, BLK, VPL>::NW) lds.l2s[threadIdx.x] = 0.0;
   __syncthreads();
+  // issue priorities: main chains 3, recompute chains 2, helpers the default 0
   if (w == 0) {
-    __builtin_amdgcn_s_setprio(CTC_F6_PRIO1);
+    __builtin_amdgcn_s_setprio(3);
     run_main<KIND, NL, NH, BLK, VPL, 0>(p, L, alpha_ws, beta_ws, kexp_ws, logp_ws, loss, flag_ws, meet_ws, lds, geo, grad != nullptr, b);
   } else if (w == 1) {
-    __builtin_amdgcn_s_setprio(CTC_F6_PRIO1);
+    __builtin_amdgcn_s_setprio(3);
     run_main<KIND, NL, NH, BLK, VPL, 1>(p, L, alpha_ws, beta_ws, kexp_ws, logp_ws, loss, flag_ws, meet_ws, lds, geo, grad != nullptr, b);
   } else if (w == 2) {
     __builtin_amdgcn_s_setprio(2);
@@ -1951,23 +1781,13 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   } else {
     // which helper a wavefront is.  Wavefronts go to the SIMDs in the order 0, 2, 1, 3, 0, ... and a SIMD prefers its OLDER wavefronts:
     // with the plain order (side A = wavefronts 4 .. 3+NH, side B after them) the side-B helpers are the youngest wavefront of every
-    // SIMD (r04 stamps: 82-85 us of work in phase 2 against 66-70 for side A).  CTC_F6_ROLEMAP (experiment builds): other orders.
-#ifndef CTC_F6_ROLEMAP
-#define CTC_F6_ROLEMAP 0
-#endif
+    // SIMD (r04 stamps: 82-85 us of work in phase 2 against 66-70 for side A).  Three other orders were measured and kept out:
+    // profiles/r04_kernel_experiments.md.
     int hs = (w - 4) / NH, hh = (w - 4) % NH;  // (side, index): the plain order
-    if constexpr (CTC_F6_ROLEMAP == 1 && NH == 4) {        // A0 A1 B0 B1 A2 A3 B2 B3: side A beside the main chains, side B beside the recompute chains
-      const int q = w - 4; hs = (q >> 1) & 1; hh = (q & 1) + 2 * (q >> 2);
-    } else if constexpr (CTC_F6_ROLEMAP == 2) {             // side B first (older)
-      hs = 1 - hs;
-    } else if constexpr (CTC_F6_ROLEMAP == 3 && NH == 4) {  // A0 B0 A1 B1 A2 B2 A3 B3
-      const int q = w - 4; hs = q & 1; hh = q >> 1;
-    }
     hs = __builtin_amdgcn_readfirstlane(hs); hh = __builtin_amdgcn_readfirstlane(hh);
     if (hs == 0) {
       run_helper<KIND, NL, NH, BLK, VPL, 0, XT>(p, L, stats_ws, sink_ws, d_loss, grad, lds, geo, hh, b, flag_ws);
     } else {
-      if (CTC_F6_HPRIO_B != 0) __builtin_amdgcn_s_setprio(CTC_F6_HPRIO_B);
       run_helper<KIND, NL, NH, BLK, VPL, 1, XT>(p, L, stats_ws, sink_ws, d_loss, grad, lds, geo, hh, b, flag_ws);
     }
   }
@@ -1981,8 +1801,8 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   __syncthreads();
   if (fl != 0) {
     __builtin_amdgcn_s_setprio(0);
-    if (w < 4 + 2 * NH5) fused5::run_roles<KIND, NL, NH5, BLK, VPL, XT>(p, L, alpha_ws, beta_ws, logp_ws, stats_ws, loss, d_loss, grad, sink_ws, both.log, w, b);
-    else fused5::run_idle<BLK>(p, grad != nullptr, b);  // wavefronts the log-domain roles have no work for keep their barriers
+    if (w < 4 + 2 * NH) fused5::run_roles<KIND, NL, NH, BLK, VPL, XT>(p, L, alpha_ws, beta_ws, logp_ws, stats_ws, loss, d_loss, grad, sink_ws, both.log, w, b);
+    else fused5::run_idle<BLK>(p, grad != nullptr, b);  // (never taken: the workgroup has 4 + 2 NH wavefronts)
   }
   // sum(loss) for the training loop, without a launch of its own (ctc_amd_loss_grad_sum): the thread that wrote loss[b] --
   // lane 0 of main chain A in either domain -- adds it in fixed point; the second call of a loss / gradient pair adds nothing
@@ -2058,11 +1878,7 @@ hipError_t CTC_F6_ENTRY(const Problem &p, const Layout &L, char *ws, float *loss
   }
 #if defined(CTC_F6_NS_ONLY)
   if (p.V > 256) return hipErrorInvalidValue;
-#ifndef CTC_F6_NS_NH
-#define CTC_F6_NS_NH CTC_F6_NH12
-#define CTC_F6_NS_BLK 12
-#endif
-  return launch6<CTC_FUSED6_NL, CTC_F6_NS_NH, CTC_F6_NS_BLK, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st);
+  return launch6<CTC_FUSED6_NL, 4, 12, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st);
 #elif CTC_FUSED6_NL == 8
   return p.V <= 256 ? launch6<8, 1, 3, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st)
                     : launch6<8, 1, 3, 2>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st);
@@ -2070,7 +1886,7 @@ hipError_t CTC_F6_ENTRY(const Problem &p, const Layout &L, char *ws, float *loss
   return p.V <= 256 ? launch6<4, 2, 6, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st)
                     : launch6<4, 2, 6, 2>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st);
 #else
-  return p.V <= 256   ? launch6<CTC_FUSED6_NL, CTC_F6_NH12, 12, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st)
+  return p.V <= 256   ? launch6<CTC_FUSED6_NL, 4, 12, 1>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st)
          : p.V <= 512 ? launch6<CTC_FUSED6_NL, 2, 6, 2>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st)
                       : launch6<CTC_FUSED6_NL, 2, 6, 4>(p, L, alpha, beta, kexp, logp, stats, sink, loss, d_loss, grad, flags, meet, perm, st);
 #endif

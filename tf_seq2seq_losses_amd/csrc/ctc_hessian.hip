@@ -397,9 +397,7 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
   // their own: the nh wavefronts of this (b, t1) that sweep share them and write them a little per sweep step (the
   // sweeps are VALU-bound, the fills HBM-bound; run back to back they did not overlap: 5.4 ms = 3.5 + 1.9).
   const int nh = (npres[b] + 1) / 2;   // pairs with at least one present token (the blank is always present)
-#ifndef CTC_HESS_DBG_NOSWEEP
   if (pair >= nh) return;
-#endif
   const int32_t *lab = p.labels + (long)b * p.label_stride;
   auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
   const int tk = tok(hl);
@@ -438,13 +436,6 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
     }
   }
   zero_rows(len, T);  // columns beyond logit_length (base_loss.py:254-258)
-#ifdef CTC_HESS_DBG_NOSWEEP
-  if (true) {
-    zero_rows(0, t1);
-    zero_rows(t1 + 1, len);
-    return;
-  }
-#endif
   // ---- this wavefront's share of the absent tokens' slabs: order positions [a_lo, a_hi) ----
   const int na = V - 2 * nh;
   const int a_lo = 2 * nh + (int)(((long)pair * na) / nh), a_hi = 2 * nh + (int)(((long)(pair + 1) * na) / nh);
@@ -503,9 +494,6 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
     const int rows = len - 1 > 0 ? len - 1 : 1;
     f_per_row = (int)((units + rows - 1) / rows);
   }
-#ifdef CTC_HESS_DBG_NOFILL
-  f_done = true;
-#endif
 
   // LDS per wavefront: two token rows (V + 4 each), then two staging buffers of SR output rows (burst writes, below)
   constexpr int SR = 8;
@@ -597,11 +585,7 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
   // row and ~10^4 slabs in flight the HBM write stream had no page locality (2.5 TB/s where a plain fill reaches 6.8).
   auto flush = [&](int lo, int hi) {  // rows lo..hi of this half's slab, lo and hi in the same aligned group of SR rows
     wave_lds_fence();
-#ifdef CTC_HESS_DBG_NOSTORE
-    if (have && lp == 12345.0) {
-#else
     if (have) {
-#endif
       const float *src = stage + (lo & (SR - 1)) * V;
       float *dst = out + (long)lo * V;
       const int n = (hi - lo + 1) * V;

@@ -41,19 +41,13 @@ namespace hvpf {
 
 using namespace ctc::fused;
 
-#ifndef CTC_HVPF_RN
-#define CTC_HVPF_RN 3   // frames between renormalisations of a chain (experiment builds: scripts/build_hvp_variant.sh -DCTC_HVPF_RN=6)
-#endif
-constexpr int BLK = HVPF_BLK, NH = 3, RN = CTC_HVPF_RN, NG = BLK / RN, NW = 4 + 2 * NH;  // 10 wavefronts: 4 chains + 3 helpers a side
+constexpr int BLK = HVPF_BLK, NH = 3, RN = 3, NG = BLK / RN, NW = 4 + 2 * NH;  // 10 wavefronts: 4 chains + 3 helpers a side
 constexpr int V = 256;
 using linear::DEAD; using linear::GAP; using linear::GAP_WIDE; using linear::DOWN_MAX; using linear::DECAY_MAX; using linear::KK_MAX;
 using linear::EMIS_MIN; using linear::MASS_TOL;  // (ctc_linear_flags.h: one copy for this kernel and ctc_fused6.hip)
 
 // packed float32 pairs and the one-instruction inflow for the classic two-positions-per-lane chains (as ctc_fused6.hip, r04)
 typedef float f2v __attribute__((ext_vector_type(2)));
-#ifndef CTC_HVPF_PACKED
-#define CTC_HVPF_PACKED 1
-#endif
 template <int DIR>
 __device__ __forceinline__ void fmac_from_upstream(float &acc, float x, float sc) {
   if constexpr (DIR == 0) asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
@@ -181,7 +175,7 @@ struct Chain {
   int k, kx, dk;
   bool norep[NL], norep_next[NL];
   int flag;
-  static constexpr bool PACKED = (CTC_HVPF_PACKED != 0) && KIND == 0 && NL == 2;
+  static constexpr bool PACKED = KIND == 0 && NL == 2;
   float nrf[NL];  // PACKED: 1.0 where the repeat rule lets the diagonal pass (norep_next for A, norep for B)
   float sc = 1.f, scb = 0.f;  // PACKED: 2^dk as a float (0 below 2^-126), and the same on the boundary lane only
   bool boundary = false;
@@ -551,10 +545,7 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL> &S, Lds<KIND, NL> &
   // rows are loaded PFD blocks ahead of their use, in a ring of register sets addressed by (block mod PFD) at COMPILE time (the
   // loop is unrolled by PFD): a 6-frame block lasts ~0.7 us, an HBM load under load ~2 us -- with one block of look-ahead every
   // iteration waited for memory (phase 1: 165 us instead of ~70)
-#ifndef CTC_HVPF_PFD
-#define CTC_HVPF_PFD 4
-#endif
-  constexpr int PFD = CTC_HVPF_PFD;
+  constexpr int PFD = 4;
   float4 xb[PFD][NQ], vb[PFD][NQ];
   static_for<0, PFD>([&](auto R) {
     constexpr int r = decltype(R)::value;
@@ -605,9 +596,6 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL> &S, Lds<KIND, NL> &
     // s_waitcnt in front of a slot's use is a COUNT of younger loads that may stay in flight, fixed at compile time -- with a
     // path on which the younger refills are skipped (the tail: j >= nb) that count is 0, on every iteration.  r03 had both:
     // s_waitcnt vmcnt(0) behind each load, nothing ever in flight across an iteration, 136 us for a phase 1 whose loads take 89.
-#ifdef CTC_HVPF_DIAG_NOLOAD
-    if (!(lds.mode & 16))
-#endif
 #pragma unroll
     for (int q = 0; q < NQ; ++q) S.load_xv(xb[r][q], vb[r][q], fr(j + PFD, P0 + q));
     block_barrier_raw();
@@ -1177,12 +1165,7 @@ __global__ __launch_bounds__(64 * NW) void hvp_fused_kernel(Problem p, Layout L,
   __syncthreads();
   // Wavefronts w, w + 4, w + 8 share a SIMD (0 and 1 hold three, 2 and 3 two): the main chains -- the busiest wavefronts -- sit on
   // the two-wavefront SIMDs with one helper each, the recompute chains with two helpers each.
-  // (CTC_HVPF_PROBE_ROLE, diagnostic builds: compile ONE role only, to read its register need off -Rpass-analysis=kernel-resource-usage)
-#ifndef CTC_HVPF_PROBE_ROLE
-#define CTC_HVPF_PROBE_ROLE -1
-#endif
-  constexpr int PR = CTC_HVPF_PROBE_ROLE;
-  auto is = [&](int role) { return (PR < 0 || PR == role) && w == role; };
+  auto is = [&](int role) { return w == role; };  // (a lambda: with plain comparisons the compiler schedules the prologue differently)
   if (is(2)) {
     __builtin_amdgcn_s_setprio(3);
     run_main<KIND, NL, 0>(p, rows_ws, kexp_ws, nslot, loss, flag_ws, lds, geo, b);
@@ -1212,9 +1195,7 @@ __global__ __launch_bounds__(64 * NW) void hvp_fused_kernel(Problem p, Layout L,
   __syncthreads();
   const int fl = lds.mode ? 0 : lds.flag;
   __syncthreads();  // (the LDS is reused from here on)
-#ifndef CTC_HVPF_NO_REDO
-  if (PR < 0 && fl != 0) redo_log_domain<KIND, NL>(p, L, ws_v1, vec, loss, out, reinterpret_cast<float *>(&lds), w, b);
-#endif
+  if (fl != 0) redo_log_domain<KIND, NL>(p, L, ws_v1, vec, loss, out, reinterpret_cast<float *>(&lds), w, b);
 }
 
 }  // namespace hvpf

@@ -393,9 +393,7 @@ __device__ __forceinline__ void scan_body(const Problem &p, const Layout &L, con
         load_erow<NL>(buf[d], erow_ptr(k0 + d + PF), lane, UP, vz);  // clamped: re-reads the last row near the end
         if (d == RENORM - 1) S.renorm();
         else if constexpr (FINE) S.renorm_lagged();
-#ifndef CTC_EXPERIMENT_NO_STORE
         S.store_row(out_row(k0 + d), lane, UP);
-#endif
       }
     }
     // tail: fewer than PF steps left, their rows are already in buf[0 .. len-k0)
