@@ -19,12 +19,18 @@ WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
 
-_c_int, _c_void_p, _c_size_t = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
+_c_int, _c_int64, _c_void_p, _c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 
 _COMMON = [_c_int, _c_int,            # kind, wrt
            _c_void_p, _c_void_p, _c_int,  # logits, labels, label_stride
            _c_void_p, _c_void_p, _c_int,  # label_length, logit_length, blank_index
            _c_int, _c_int, _c_int, _c_int]  # B, T, V, U
+# the same for the producer-format entry points: element type and strides behind the logits pointer
+_COMMON_EX = [_c_int, _c_int,                               # kind, wrt
+              _c_void_p, _c_int, _c_int64, _c_int64,        # logits, dtype, stride_b, stride_t
+              _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,  # labels, label_stride, label_length, logit_length, blank_index
+              _c_int, _c_int, _c_int, _c_int]               # B, T, V, U
+_OUT_EX = [_c_void_p, _c_void_p, _c_int, _c_int64, _c_int64]  # loss, grad, dtype, stride_b, stride_t
 
 # every symbol include/ctc_amd.h declares, with its argument types
 SIGNATURES = {
@@ -40,30 +46,15 @@ SIGNATURES = {
     "ctc_amd_check_labels": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p]),
     "ctc_amd_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),
     "ctc_amd_loss_grad": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
-    "ctc_amd_loss_grad_ex": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,  # kind, wrt, logits, dtype, strides
-                                      _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,                 # labels .. blank_index
-                                      _c_int, _c_int, _c_int, _c_int,                                   # B, T, V, U
-                                      _c_void_p, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,    # loss, grad, dtype, strides
-                                      _c_void_p, _c_void_p, _c_size_t, _c_void_p]),                     # d_loss, ws, bytes, stream
-    "ctc_amd_loss_grad_packed": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, _c_void_p, ctypes.c_int64,        # kind, wrt, logits, dtype, row_offsets, row_stride
-                                          _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,                  # labels .. blank_index
-                                          _c_int, _c_int, _c_int, _c_int,                                    # B, T, V, U
-                                          _c_void_p, _c_void_p, _c_int, ctypes.c_int64,                      # loss, grad, dtype, grad row stride
-                                          _c_void_p, _c_void_p, _c_size_t, _c_void_p]),                      # d_loss, ws, bytes, stream
-    "ctc_amd_loss_grad_sum": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,
-                                       _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,
-                                       _c_int, _c_int, _c_int, _c_int,
-                                       _c_void_p, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,
-                                       _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # d_loss, sum2, zero_next, ws, bytes, stream
-    "ctc_amd_loss_forward": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,
-                                      _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,
-                                      _c_int, _c_int, _c_int, _c_int,
-                                      _c_void_p, _c_void_p, _c_size_t, _c_void_p]),                     # loss, ws, bytes, stream
-    "ctc_amd_grad_resume": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,
-                                     _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,
-                                     _c_int, _c_int, _c_int, _c_int,
-                                     _c_void_p, _c_void_p, _c_int, ctypes.c_int64, ctypes.c_int64,
-                                     _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_loss_grad_ex": (_c_int, _COMMON_EX + _OUT_EX + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # d_loss, ws, bytes, stream
+    "ctc_amd_loss_grad_packed": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int64,          # kind, wrt, logits, dtype, row_offsets, row_stride
+                                          *_COMMON_EX[6:],                                                 # labels .. U
+                                          _c_void_p, _c_void_p, _c_int, _c_int64,                          # loss, grad, dtype, grad row stride
+                                          _c_void_p, _c_void_p, _c_size_t, _c_void_p]),                    # d_loss, ws, bytes, stream
+    "ctc_amd_loss_grad_sum": (_c_int, _COMMON_EX + _OUT_EX + [_c_void_p, _c_void_p, _c_void_p,             # d_loss, sum2, zero_next
+                                                             _c_void_p, _c_size_t, _c_void_p]),          # ws, bytes, stream
+    "ctc_amd_loss_forward": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),           # loss, ws, bytes, stream
+    "ctc_amd_grad_resume": (_c_int, _COMMON_EX + _OUT_EX + [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # d_loss, ws, bytes, stream
     "ctc_amd_alpha_beta": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_hessian": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_log_posterior": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),

@@ -23,12 +23,13 @@
 //   8 bytes of softmax statistics per frame: ~1.55x the algorithmic 2*T*V*4 bytes (ctc_fused4.hip: 2.5x, v1: 4.4x).
 //
 // References: classic_ctc_loss.py:310-462,565-669, simplified_ctc_loss.py:291-438,456-534, base_loss.py:262-298,328-344,
-// 420-468, tools.py:27-40.  Eligibility (fused5_eligible in ctc_capi.hip): logits input, V <= 512 with U <= 512 or V <= 1024 with
+// 420-468, tools.py:27-40.  Eligibility (fused_eligible in ctc_capi.hip): logits input, V <= 512 with U <= 512 or V <= 1024 with
 // U <= 128 (LDS budget); otherwise ctc_fused.hip / the v1 pipeline run.  The roles live in ctc_fused5_roles.h (shared with
 // ctc_fused6.hip, which runs them inside its own launch for the utterances it flags).
 // Instantiated per input/output format XT (Side in ctc_fused_common.h): contiguous float32, strided float32, bfloat16,
 // and float32 rows that are not 16-byte aligned.  With grad == NULL every role returns at the meeting point (loss only).
 #include "ctc_fused5_roles.h"
+#include "ctc_launch.h"
 
 namespace ctc {
 namespace fused5 {
@@ -49,14 +50,13 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused5_kernel(Problem p, La
   // utterance of this workgroup: workgroups start in index order, and with more utterances than CUs the longest ones
   // go first (perm from order_kernel; ragged batch of 512: -22 %)
   const int b = perm ? perm[blockIdx.x] : (int)blockIdx.x;
-  // fallback launch behind the linear-domain kernel (ctc_fused6.hip): only the utterances it flagged
+  // (no caller passes only_if any more: it served a fallback launch behind ctc_fused6.hip, which now redoes its flagged
+  // utterances inside its own launch)
   if (only_if && only_if[b] == 0) return;
   fused5::run_roles<KIND, NL, NH, BLK, VPL, XT>(p, L, alpha_ws, beta_ws, logp_ws, stats_ws, loss, d_loss, grad, stamp_ws, lds, w, b);
 }
 
 }  // namespace fused5
-
-hipError_t run_order(const Problem &p, const Layout &L, char *ws, hipStream_t st);  // ctc_kernels.hip: longest utterances first
 
 template <int NL, int NH, int BLK, int VPL>
 static hipError_t launch5(const Problem &p, const Layout &L, float *a, float *b, double *lp, float2 *stats, float *loss,
@@ -80,10 +80,10 @@ static hipError_t launch5(const Problem &p, const Layout &L, float *a, float *b,
   return hipGetLastError();
 }
 
-// One translation unit per (lattice kind, label positions per lane): -DCTC_FUSED_KIND=0|1 -DCTC_FUSED5_NL=1|2|4 (the
+// One translation unit per (lattice kind, label positions per lane): -DCTC_FUSED_KIND=0|1 -DCTC_FUSED5_NL=1|2|4|8 (the
 // instantiations are large; split like this they compile in parallel).  Exported: run_fused5_<kind>_nl<NL>.
 #ifndef CTC_FUSED5_NL
-#error "compile with -DCTC_FUSED5_NL=1, 2 or 4"
+#error "compile with -DCTC_FUSED5_NL=1, 2, 4 or 8"
 #endif
 #define CTC_F5_CAT2(a, b, c) a##b##c
 #define CTC_F5_CAT(a, b, c) CTC_F5_CAT2(a, b, c)
@@ -93,7 +93,7 @@ static hipError_t launch5(const Problem &p, const Layout &L, float *a, float *b,
 #define CTC_F5_ENTRY CTC_F5_CAT(run_fused5_simplified, _nl, CTC_FUSED5_NL)
 #endif
 hipError_t CTC_F5_ENTRY(const Problem &p, const Layout &L, char *ws, float *loss, const float *d_loss, float *grad,
-                        bool only_flagged, hipStream_t st) {
+                        hipStream_t st) {  // (FusedEntry, ctc_launch.h)
   float *alpha = reinterpret_cast<float *>(ws + L.off_alpha);
   float *beta = reinterpret_cast<float *>(ws + L.off_beta);
   double *logp = reinterpret_cast<double *>(ws + L.off_logp);
@@ -102,10 +102,9 @@ hipError_t CTC_F5_ENTRY(const Problem &p, const Layout &L, char *ws, float *loss
   if (L.NL != CTC_FUSED5_NL) return hipErrorInvalidValue;
   // more utterances than CUs: longest first (one small kernel; skipped for batches that fit the chip in one go)
   int *perm = nullptr;
-  // behind ctc_fused6.hip: only the utterances whose flag it set (normally none: the workgroups leave at once)
-  const int *only_if = only_flagged ? reinterpret_cast<const int *>(ws + L.off_flags) : nullptr;
+  const int *only_if = nullptr;  // every utterance (the kernel parameter is unused)
 #ifndef CTC_FUSED_STAMPS
-  if (!only_flagged && p.B > 256 && p.B <= 8192) {
+  if (p.B > 256 && p.B <= 8192) {
     hipError_t e = run_order(p, L, ws, st);
     if (e != hipSuccess) return e;
     perm = reinterpret_cast<int *>(ws + L.off_perm);

@@ -42,6 +42,7 @@
 #include "ctc_fused_common.h"
 #include "ctc_swap_reduce.h"
 #include "ctc_linear_flags.h"
+#include "ctc_launch.h"
 #include "ctc_fused5_roles.h"  // the log-domain roles: run inside this kernel for the utterances it flags
 
 #ifndef CTC_FUSED_KIND
@@ -1844,10 +1845,10 @@ static hipError_t launch6(const Problem &p, const Layout &L, float *a, float *b,
 #endif
 }
 
-// One translation unit per (lattice kind, label positions per lane): -DCTC_FUSED_KIND=0|1 -DCTC_FUSED6_NL=1|2|4.
-// Exported: run_fused6_<kind>_nl<NL>.  Writes flags[b] != 0 for every utterance the caller has to redo in the log domain.
+// One translation unit per (lattice kind, label positions per lane): -DCTC_FUSED_KIND=0|1 -DCTC_FUSED6_NL=1|2|4|8.
+// Exported: run_fused6_<kind>_nl<NL>.  flags[b] != 0 marks an utterance that the same launch redid in the log domain.
 #ifndef CTC_FUSED6_NL
-#error "compile with -DCTC_FUSED6_NL=1, 2 or 4"
+#error "compile with -DCTC_FUSED6_NL=1, 2, 4 or 8"
 #endif
 #define CTC_F6_CAT2(a, b, c) a##b##c
 #define CTC_F6_CAT(a, b, c) CTC_F6_CAT2(a, b, c)
@@ -1856,10 +1857,8 @@ static hipError_t launch6(const Problem &p, const Layout &L, float *a, float *b,
 #else
 #define CTC_F6_ENTRY CTC_F6_CAT(run_fused6_simplified, _nl, CTC_FUSED6_NL)
 #endif
-hipError_t run_order(const Problem &p, const Layout &L, char *ws, hipStream_t st);  // ctc_kernels.hip
-
 hipError_t CTC_F6_ENTRY(const Problem &p, const Layout &L, char *ws, float *loss, const float *d_loss, float *grad,
-                        hipStream_t st) {
+                        hipStream_t st) {  // (FusedEntry, ctc_launch.h)
   float *alpha = reinterpret_cast<float *>(ws + L.off_alpha);
   float *beta = reinterpret_cast<float *>(ws + L.off_beta);
   double *logp = reinterpret_cast<double *>(ws + L.off_logp);

@@ -18,9 +18,9 @@
 #include <stdlib.h>
 
 #include "ctc_fused_common.h"
+#include "ctc_launch.h"
 
 namespace ctc {
-extern int g_force_hessian_slab;  // ctc_capi.hip
 
 using namespace ctc::fused;
 

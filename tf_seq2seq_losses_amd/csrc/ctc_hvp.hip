@@ -19,6 +19,7 @@
 #include "ctc_fused_common.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_hvp_device.h"
+#include "ctc_launch.h"
 
 namespace ctc {
 

@@ -29,6 +29,7 @@
 #include "ctc_swap_reduce.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_linear_flags.h"
+#include "ctc_launch.h"
 #include "ctc_v1_device.h"   // emit_row, scan_body: the log-domain building blocks, run in this launch for flagged utterances
 #include "ctc_hvp_device.h"  // temit_row, tscan_body, hvp_out_row
 

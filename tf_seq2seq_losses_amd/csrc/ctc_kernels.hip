@@ -16,6 +16,7 @@
 #include "ctc_swap_reduce.h"
 #include "ctc_v1_device.h"
 #include "ctc_grad_row.h"
+#include "ctc_launch.h"
 
 namespace ctc {
 

@@ -1,0 +1,47 @@
+// Host launchers that cross a translation unit: every unit that defines or calls one includes this header, so a changed
+// signature is a compile error in both places.  Host declarations only.
+#pragma once
+#include "ctc_common.h"
+
+namespace ctc {
+
+// ctc_kernels.hip: the three-kernel pipeline and the small kernels around it
+hipError_t run_emit_scan(const Problem &p, const Layout &L, char *ws, float *loss, int ndir, hipStream_t st);
+hipError_t run_grad(const Problem &p, const Layout &L, char *ws, const float *d_loss, float *grad, hipStream_t st);
+hipError_t run_order(const Problem &p, const Layout &L, char *ws, hipStream_t st);  // longest utterances first, into L.off_perm
+hipError_t run_sum_loss_fixed(const float *loss, int B, long long *acc, long long *zero_next, hipStream_t st);
+hipError_t run_reduce_loss(const float *loss, int B, float *out, hipStream_t st);
+hipError_t run_log_posterior(const Problem &p, const Layout &L, char *ws, float *out, hipStream_t st);
+hipError_t run_convert(const Problem &p, const Layout &L, char *ws, float *alpha_out, float *beta_out, hipStream_t st);
+hipError_t run_probe_copy(void *dst, const void *src, size_t bytes, hipStream_t st);
+hipError_t run_probe_spin(int threads, int lds_bytes, float us, hipStream_t st);
+hipError_t run_check_labels(const int32_t *labels, int label_stride, const int32_t *label_length, int blank, int B, int V, int U,
+                            int *bad, hipStream_t st);
+
+// ctc_fused5.hip / ctc_fused6.hip: one unit, and one entry point, per (lattice kind, label positions per lane NL)
+typedef hipError_t FusedEntry(const Problem &p, const Layout &L, char *ws, float *loss, const float *d_loss, float *grad, hipStream_t st);
+FusedEntry run_fused5_classic_nl1, run_fused5_classic_nl2, run_fused5_classic_nl4, run_fused5_classic_nl8;
+FusedEntry run_fused5_simplified_nl1, run_fused5_simplified_nl2, run_fused5_simplified_nl4, run_fused5_simplified_nl8;
+FusedEntry run_fused6_classic_nl1, run_fused6_classic_nl2, run_fused6_classic_nl4, run_fused6_classic_nl8;
+FusedEntry run_fused6_simplified_nl1, run_fused6_simplified_nl2, run_fused6_simplified_nl4, run_fused6_simplified_nl8;
+
+// ctc_hessian.hip
+extern int g_force_hessian_slab;  // ctc_capi.hip (ctc_amd_debug_override "hessian")
+size_t hessian_extra_bytes(int kind, int B, int T, int V, int U);
+hipError_t run_hessian(const Problem &p, const Layout &L, char *ws, const float *g_lp, float *hess, hipStream_t st);
+
+// ctc_hvp.hip, ctc_hvp_fused.hip (one unit per lattice kind)
+size_t hvp_extra_bytes(int kind, int B, int T, int V, int U);
+size_t hvp_fused_flags_offset(int kind, int B, int T, int U);
+hipError_t run_hvp(const Problem &p, const Layout &L, char *ws, const float *vec, float *out, hipStream_t st);
+hipError_t run_hvp_fused_classic(const Problem &p, const Layout &L, char *ws, const float *vec, float *loss, float *out, int mode, hipStream_t st);
+hipError_t run_hvp_fused_simplified(const Problem &p, const Layout &L, char *ws, const float *vec, float *loss, float *out, int mode, hipStream_t st);
+
+#ifdef CTC_WIDE_EXPERIMENT
+// experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
+extern int g_wide_diag;  // timing diagnostics (results are then meaningless)
+bool wide_eligible(const Problem &p, const Layout &L);
+hipError_t run_wide(const Problem &p, const Layout &L, char *ws, float *loss, const float *d_loss, float *grad, hipStream_t st);
+#endif
+
+}  // namespace ctc

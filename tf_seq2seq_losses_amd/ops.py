@@ -92,23 +92,29 @@ class Prepared:
         """The same inputs with contiguous float32 logits (Hessian, HVP and alpha/beta read that format only), 16-byte aligned
         (ctc_amd_hvp / ctc_amd_hessian refuse other base pointers: a batch-sliced view whose offset is not a multiple of 16 bytes is
         copied once here)."""
-        if not self.native:
-            if self.x.numel() > 0 and (self.x.data_ptr() & 15) != 0:
-                q = Prepared.__new__(Prepared)
-                q.__dict__.update(self.__dict__)
-                q.x = self.x.clone()
-                return q
-            return self
+        if self.native:
+            return self._with_plain_x(self.x.to(torch.float32).contiguous())
+        if self.x.numel() > 0 and (self.x.data_ptr() & 15) != 0:
+            return self._with_plain_x(self.x.clone())
+        return self
+
+    def _with_plain_x(self, x) -> "Prepared":
         q = Prepared.__new__(Prepared)
         q.__dict__.update(self.__dict__)
-        q.x = self.x.to(torch.float32).contiguous()
-        q.native = False
+        q.x, q.native = x, False
         return q
 
     def common(self, kind: int, wrt: int):
+        """The twelve leading arguments of the entry points that read contiguous float32 logits."""
         assert not self.native, "this entry point takes contiguous float32 logits: use Prepared.plain()"
         return (kind, wrt, _ptr(self.x), _ptr(self.labels), self.stride, _ptr(self.label_length),
                 _ptr(self.logit_length), self.blank, self.B, self.T, self.V, self.U)
+
+    def common_ex(self, kind: int, wrt: int):
+        """The fifteen leading arguments of the producer-format entry points; [3:6] is the logits' (dtype, stride_b, stride_t)."""
+        x = self.x
+        return (kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(self.labels), self.stride,
+                _ptr(self.label_length), _ptr(self.logit_length), self.blank, self.B, self.T, self.V, self.U)
 
 
 _WS_BYTES = {}   # (what, kind, B, T, V, U) -> bytes: no ctypes round trip per call
@@ -186,25 +192,33 @@ class _on_device:
             self.ctx.__exit__(*a)
 
 
+def _new_grad(p: Prepared, want_grad: bool = True) -> Optional[torch.Tensor]:
+    """Uninitialised gradient of p.x: in the producer's format (same element type, same strides) for native inputs,
+    contiguous float32 [B,T,V] otherwise."""
+    if not want_grad:
+        return None
+    if p.native:
+        return torch.empty_strided(p.x.shape, p.x.stride(), dtype=p.x.dtype, device=p.device)
+    return torch.empty((p.B, p.T, p.V), dtype=torch.float32, device=p.device)
+
+
+def _d_loss(d_loss: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
+    return None if d_loss is None else d_loss.to(device=dev, dtype=torch.float32).contiguous()
+
+
 def loss_grad(kind: int, wrt: int, p: Prepared, want_grad: bool, d_loss: Optional[torch.Tensor] = None,
               workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     lib = _lib.load()
     loss = torch.empty(p.B, dtype=torch.float32, device=p.device)
-    if p.native:  # the gradient goes back in the producer's format: same element type, same strides
-        grad = torch.empty_strided(p.x.shape, p.x.stride(), dtype=p.x.dtype, device=p.device) if want_grad else None
-    else:
-        grad = torch.empty((p.B, p.T, p.V), dtype=torch.float32, device=p.device) if want_grad else None
+    grad = _new_grad(p, want_grad)
     if p.B == 0:
         return loss, grad
     ws = workspace if workspace is not None else _workspace(_loss_grad_selector(wrt, p), kind, p)
-    if d_loss is not None:
-        d_loss = d_loss.to(device=p.device, dtype=torch.float32).contiguous()
+    d_loss = _d_loss(d_loss, p.device)
     with _on_device(p.device):
         if p.native:
-            dt = _DTYPES[p.x.dtype]
-            rc = lib.ctc_amd_loss_grad_ex(kind, wrt, _ptr(p.x), dt, p.x.stride(0), p.x.stride(1), _ptr(p.labels), p.stride,
-                                          _ptr(p.label_length), _ptr(p.logit_length), p.blank, p.B, p.T, p.V, p.U,
-                                          _ptr(loss), _ptr(grad), dt, p.x.stride(0), p.x.stride(1), _ptr(d_loss),
+            ex = p.common_ex(kind, wrt)
+            rc = lib.ctc_amd_loss_grad_ex(*ex, _ptr(loss), _ptr(grad), *ex[3:6], _ptr(d_loss),  # (the gradient has the logits' format)
                                           ws.data_ptr(), ws.numel(), _stream(p.device))
         else:
             rc = lib.ctc_amd_loss_grad(*p.common(kind, wrt), _ptr(loss), _ptr(grad), _ptr(d_loss),
@@ -233,8 +247,7 @@ def loss_grad_packed(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor,
     if B == 0:
         return loss, grad
     ws = torch.empty(max(_lib.workspace_bytes(_lib.WS_LOSS_GRAD, kind, B, T, V, U), 1), dtype=torch.uint8, device=dev)
-    if d_loss is not None:
-        d_loss = d_loss.to(device=dev, dtype=torch.float32).contiguous()
+    d_loss = _d_loss(d_loss, dev)
     dt = _DTYPES[x.dtype]
     with _on_device(dev):
         rc = lib.ctc_amd_loss_grad_packed(kind, wrt, _ptr(x), dt, _ptr(row_offsets), x.stride(0), _ptr(labels), int(labels.shape[1]),
@@ -255,20 +268,13 @@ def loss_grad_sum(kind: int, wrt: int, p: Prepared, sum2: torch.Tensor, zero_nex
     lib = _lib.load()
     assert sum2.dtype == torch.int64 and sum2.numel() == 2 and sum2.device == p.device
     loss = torch.empty(p.B, dtype=torch.float32, device=p.device)
-    if p.native:
-        grad = torch.empty_strided(p.x.shape, p.x.stride(), dtype=p.x.dtype, device=p.device) if want_grad else None
-    else:
-        grad = torch.empty((p.B, p.T, p.V), dtype=torch.float32, device=p.device) if want_grad else None
+    grad = _new_grad(p, want_grad)
     ws = _workspace(_loss_grad_selector(wrt, p), kind, p)
-    if d_loss is not None:
-        d_loss = d_loss.to(device=p.device, dtype=torch.float32).contiguous()
-    dt = _DTYPES[p.x.dtype]
+    d_loss = _d_loss(d_loss, p.device)
     gs = (grad.stride(0), grad.stride(1)) if grad is not None else (p.T * p.V, p.V)
     with _on_device(p.device):
-        rc = lib.ctc_amd_loss_grad_sum(kind, wrt, _ptr(p.x), dt, p.x.stride(0), p.x.stride(1), _ptr(p.labels), p.stride,
-                                       _ptr(p.label_length), _ptr(p.logit_length), p.blank, p.B, p.T, p.V, p.U,
-                                       _ptr(loss), _ptr(grad), dt, gs[0], gs[1], _ptr(d_loss), _ptr(sum2), _ptr(zero_next),
-                                       ws.data_ptr(), ws.numel(), _stream(p.device))
+        rc = lib.ctc_amd_loss_grad_sum(*p.common_ex(kind, wrt), _ptr(loss), _ptr(grad), _DTYPES[p.x.dtype], gs[0], gs[1],
+                                       _ptr(d_loss), _ptr(sum2), _ptr(zero_next), ws.data_ptr(), ws.numel(), _stream(p.device))
     _lib.check(rc, "ctc_amd_loss_grad_sum")
     return loss, grad
 
@@ -279,20 +285,18 @@ def loss_forward(kind: int, wrt: int, p: Prepared, keep_always: bool = False) ->
     every other pipeline would recompute everything in the second call anyway, so nothing is kept (None) unless
     keep_always (the parity tests call ctc_amd_grad_resume behind every pipeline)."""
     sel = _loss_grad_selector(wrt, p)
-    if p.B == 0 or (not keep_always and (sel != _lib.WS_LOSS_GRAD_LOGITS or pipeline_of(kind, wrt, p) != "fused6")):
+    two_call = p.B > 0 and (keep_always or sel == _lib.WS_LOSS_GRAD_LOGITS) and pipeline_of(kind, wrt, p) == "fused6"
+    if not two_call and (p.B == 0 or not keep_always):  # nothing kept
         return loss_grad(kind, wrt, p, False)[0], None
     ws = torch.empty(max(_ws_bytes(sel, kind, p), 1), dtype=torch.uint8, device=p.device)
-    if keep_always and pipeline_of(kind, wrt, p) != "fused6":
-        loss, _ = loss_grad(kind, wrt, p, False, workspace=ws)
-        return loss, ws
+    if not two_call:  # kept for the tests: an ordinary loss-only call into a workspace of its own
+        return loss_grad(kind, wrt, p, False, workspace=ws)[0], ws
     # first half of a forward / backward pair (ctc_amd_loss_forward, ABI v5): the resume call verifies every utterance's posterior
     # mass, so the linear-domain kernel keeps its conservative loss-only signs for binding alignments only
     lib = _lib.load()
     loss = torch.empty(p.B, dtype=torch.float32, device=p.device)
     with _on_device(p.device):
-        rc = lib.ctc_amd_loss_forward(kind, wrt, _ptr(p.x), _DTYPES[p.x.dtype], p.x.stride(0), p.x.stride(1), _ptr(p.labels), p.stride,
-                                      _ptr(p.label_length), _ptr(p.logit_length), p.blank, p.B, p.T, p.V, p.U,
-                                      _ptr(loss), ws.data_ptr(), ws.numel(), _stream(p.device))
+        rc = lib.ctc_amd_loss_forward(*p.common_ex(kind, wrt), _ptr(loss), ws.data_ptr(), ws.numel(), _stream(p.device))
     _lib.check(rc, "ctc_amd_loss_forward")
     return loss, ws
 
@@ -305,20 +309,13 @@ def grad_resume(kind: int, wrt: int, p: Prepared, ws: torch.Tensor, d_loss: Opti
         return loss_grad(kind, wrt, p, True, d_loss=d_loss)[1]
     lib = _lib.load()
     loss = torch.empty(p.B, dtype=torch.float32, device=p.device)
-    if p.native:
-        grad = torch.empty_strided(p.x.shape, p.x.stride(), dtype=p.x.dtype, device=p.device)
-    else:
-        grad = torch.empty((p.B, p.T, p.V), dtype=torch.float32, device=p.device)
+    grad = _new_grad(p)
     if p.B == 0 or p.T == 0:
         return grad
-    if d_loss is not None:
-        d_loss = d_loss.to(device=p.device, dtype=torch.float32).contiguous()
-    dt = _DTYPES[p.x.dtype]
+    d_loss = _d_loss(d_loss, p.device)
     with _on_device(p.device):
-        rc = lib.ctc_amd_grad_resume(kind, wrt, _ptr(p.x), dt, p.x.stride(0), p.x.stride(1), _ptr(p.labels), p.stride,
-                                     _ptr(p.label_length), _ptr(p.logit_length), p.blank, p.B, p.T, p.V, p.U,
-                                     _ptr(loss), _ptr(grad), dt, grad.stride(0), grad.stride(1), _ptr(d_loss),
-                                     ws.data_ptr(), ws.numel(), _stream(p.device))
+        rc = lib.ctc_amd_grad_resume(*p.common_ex(kind, wrt), _ptr(loss), _ptr(grad), _DTYPES[p.x.dtype], grad.stride(0), grad.stride(1),
+                                     _ptr(d_loss), ws.data_ptr(), ws.numel(), _stream(p.device))
     _lib.check(rc, "ctc_amd_grad_resume")
     return grad
 
