@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define CTC_AMD_ABI_VERSION 5
+#define CTC_AMD_ABI_VERSION 6
 
 /* lattice variant */
 #define CTC_AMD_CLASSIC 0    /* classic_ctc_loss.py:33-70   (collapse repeats, then drop blanks)   */
@@ -60,6 +60,7 @@ extern "C" {
  *   U <= CTC_AMD_MAX_U          label positions (16 per lane of one wavefront)
  *   V <= CTC_AMD_MAX_V          tokens for loss / gradient / alpha-beta (one 64 KB LDS token row per wavefront)
  *   V <= CTC_AMD_MAX_V_HESSIAN  tokens for ctc_amd_hessian / ctc_amd_hvp (V + 4 floats of LDS per wavefront)
+ * ctc_amd_best_path takes V <= CTC_AMD_MAX_V as well (it stages no row in LDS; the limit is the ABI's, kept uniform).
  * ctc_amd_loss_grad* / ctc_amd_grad_resume / ctc_amd_alpha_beta: vector (16-byte / 8-byte) row accesses are used when V, the
  * strides AND the base pointers are aligned; any other alignment runs element-wise paths with identical results.
  * ctc_amd_hessian / ctc_amd_hvp require 16-byte aligned tensor pointers (CTC_AMD_EINVAL otherwise). */
@@ -325,6 +326,34 @@ int ctc_amd_hvp(int kind, int wrt,
                 int B, int T, int V, int U,
                 const float *vec, float *loss, float *grad, float *out,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Best-path (Viterbi) forced alignment, ABI v6: which frame emits which label.  The lattice of the loss in the (max, +)
+ * semiring: over the paths pi in [0, V)^T_b (T_b = logit_length[b]) that give labels[b, :label_length[b]] -- classic: after
+ * collapsing repeats, then dropping blanks; simplified: after dropping blanks only -- the one that maximises
+ * sum_t lp[b, t, pi_t], lp = log_softmax(logits) (CTC_AMD_WRT_LOGPROBS: the input as it stands).
+ * The reference has no counterpart (it answers "how probable", base_loss.py:38-99, not "where").
+ *   score[B]            float32: the maximum; -inf when no path exists
+ *   tokens[B][T]        int32:   pi_t; -1 for t >= T_b
+ *   label_index[B][T]   int32:   index into labels[b] of the label the frame emits (classic: or continues by repeating it),
+ *                                -1 on blank frames and for t >= T_b.  May be NULL.
+ * An infeasible utterance (too few frames, label_length > U, a label equal to the blank or outside [0, V), no path of finite
+ * value) gets score = -inf and -1 in every frame.  label_length == 0: the all-blank path.  T_b == 0: score 0 for an empty
+ * label, -inf otherwise.  Among paths of equal value the choice is deterministic (the same bits every run) but unspecified.
+ * The recursion runs on the raw logits in float64, so the path is the exact optimum of the float32 inputs; the error of
+ * `score` is that of the float32 row log-sum-exps (none for CTC_AMD_WRT_LOGPROBS) plus its own rounding.
+ * Logits in the producer formats of ctc_amd_loss_grad_ex (element type, element strides >= V, token axis contiguous).
+ * Workspace: ctc_amd_best_path_workspace_bytes (back-pointers: 64 to 512 bytes per frame) -- a query of its own, the
+ * selectors of ctc_amd_workspace_bytes are unchanged.  One launch, asynchronous on `stream`, capturable.
+ */
+int ctc_amd_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_best_path(int kind, int wrt,
+                      const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                      const int32_t *labels, int label_stride,
+                      const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                      int B, int T, int V, int U,
+                      float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTC_AMD_LIB", os.path.join(_HERE, "libctc_amd.so"))  # override: kernel experiments only
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 CLASSIC, SIMPLIFIED = 0, 1
 WRT_LOGITS, WRT_LOGPROBS = 0, 1
 WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 3, 4
@@ -59,6 +59,8 @@ SIGNATURES = {
     "ctc_amd_hessian": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_log_posterior": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_hvp": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),
+    "ctc_amd_best_path": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # score, tokens, label_index, ws, bytes, stream
 }
 
 _lib = None
@@ -129,4 +131,10 @@ def hvp_flags_offset(kind: int, B: int, T: int, V: int, U: int) -> int:
 def workspace_bytes(what: int, kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_workspace_bytes(what, kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_workspace_bytes")
+    return int(out.value)
+
+
+def best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_best_path_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_best_path_workspace_bytes")
     return int(out.value)

@@ -37,6 +37,10 @@ hipError_t run_hvp(const Problem &p, const Layout &L, char *ws, const float *vec
 hipError_t run_hvp_fused_classic(const Problem &p, const Layout &L, char *ws, const float *vec, float *loss, float *out, int mode, hipStream_t st);
 hipError_t run_hvp_fused_simplified(const Problem &p, const Layout &L, char *ws, const float *vec, float *loss, float *out, int mode, hipStream_t st);
 
+// ctc_align.hip: best-path (Viterbi) alignment; the workspace holds the back-pointers alone ([B][T][64] words of 1 .. 8 bytes)
+size_t align_workspace_bytes(int B, int T, int U);
+hipError_t run_align(const Problem &p, char *ws, float *score, int *tokens, int *label_index, hipStream_t st);
+
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
 extern int g_wide_diag;  // timing diagnostics (results are then meaningless)

@@ -19,7 +19,7 @@ All arithmetic is done by the HIP kernels behind the C ABI (include/ctc_amd.h); 
 from __future__ import annotations
 
 from functools import cached_property
-from typing import Optional, Union
+from typing import NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -209,6 +209,54 @@ def ctc_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_
     """base_loss.py:71-99 : loss as a function of log-probabilities treated as independent variables."""
     return _ctc(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length,
                 blank_index)
+
+
+# --------------------------------------------------------------------------------------------------
+# best-path (Viterbi) forced alignment: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcAlignment(NamedTuple):
+    """score [batch] float32: log-probability of the best path (-inf: no path exists);
+    tokens [batch, max_length] int32: the token every frame emits on it (-1 beyond logit_length);
+    label_index [batch, max_length] int32: index into labels[b] of the label the frame emits -- on the classic lattice also
+    of the label it continues by repeating it -- and -1 on blank frames and beyond logit_length.
+    An infeasible sample (loss = +inf) has score = -inf and -1 in every frame."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    label_index: torch.Tensor
+
+
+def _align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, max_label_length=None) -> CtcAlignment:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    with torch.no_grad():  # a path is not differentiable: the result is detached
+        prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
+                            host_max_label_length=max_label_length)
+        return CtcAlignment(*ops.best_path(ops.KINDS[kind_name], wrt, prep))
+
+
+def classic_ctc_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                          blank_index: Union[int, torch.Tensor] = 0, *, max_label_length: Optional[int] = None) -> CtcAlignment:
+    """Forced alignment on the classic lattice: the most probable path among those classic_ctc_loss sums over (repeats are
+    merged, then blanks dropped).  Arguments as classic_ctc_loss (float32 / bfloat16 / float16 logits, any batch / time
+    strides); returns CtcAlignment(score, tokens, label_index), not differentiable."""
+    return _align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+
+
+def simplified_ctc_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                             blank_index: Union[int, torch.Tensor] = 0, *, max_label_length: Optional[int] = None) -> CtcAlignment:
+    """Forced alignment on the simplified lattice (blanks are dropped, repeats are not merged: every non-blank frame emits
+    exactly one label).  Same arguments and return value as classic_ctc_alignment."""
+    return _align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+
+
+def ctc_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls) -> CtcAlignment:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+    return _align(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -404,6 +404,28 @@ def hvp(kind: int, wrt: int, p: Prepared, vec: torch.Tensor, want_grad: bool = F
     return loss, grad, out
 
 
+def best_path(kind: int, wrt: int, p: Prepared) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32): the best path of the lattice and which label every frame
+    emits (ctc_amd_best_path).  Reads the logits in the format `p` holds them in (Prepared(keep_format=True): bfloat16 /
+    float16 activations and time-major views in place)."""
+    lib = _lib.load()
+    score = torch.empty(p.B, dtype=torch.float32, device=p.device)
+    tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    label_index = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    if p.B == 0:
+        return score, tokens, label_index
+    key = ("best_path", kind, p.B, p.T, p.V, p.U)
+    n = _WS_BYTES.get(key)
+    if n is None:
+        n = _WS_BYTES[key] = _lib.best_path_workspace_bytes(kind, p.B, p.T, p.V, p.U)
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    with _on_device(p.device):
+        rc = lib.ctc_amd_best_path(*p.common_ex(kind, wrt), _ptr(score), _ptr(tokens), _ptr(label_index),
+                                   ws.data_ptr(), ws.numel(), _stream(p.device))
+    _lib.check(rc, "ctc_amd_best_path")
+    return score, tokens, label_index
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
