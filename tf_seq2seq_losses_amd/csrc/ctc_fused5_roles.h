@@ -13,11 +13,6 @@ namespace fused5 {
 
 using namespace ctc::fused;
 
-__device__ __forceinline__ void block_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed; vmcnt untouched
-  __builtin_amdgcn_s_barrier();
-}
-
 #ifdef CTC_FUSED_STAMPS
 struct Stamps {
   unsigned long long work = 0, wait = 0, t0 = 0, work1 = 0, wait1 = 0;
@@ -56,70 +51,7 @@ struct Lds {
   int feasible;
 };
 
-// Block geometry shared by every wavefront of the workgroup.
-template <int BLK>
-struct Geo {
-  int len, G, tmb, tm, NB;
-  __device__ __forceinline__ void init(int len_) {
-    len = len_;
-    G = (len + BLK - 1) / BLK;
-    tmb = G / 2;
-    tm = tmb * BLK;
-    NB = G - tmb;  // >= tmb: blocks per side and phase, as iteration bound
-  }
-  __device__ __forceinline__ int nvof(int g) const { int r = len - BLK * g; return r < BLK ? r : BLK; }
-  // side-local block j of (phase, side) -> absolute block; count of blocks
-  __device__ __forceinline__ int nblocks(int phase, int side) const { return (phase == 1) == (side == 0) ? tmb : G - tmb; }
-  __device__ __forceinline__ int absblock(int phase, int side, int j) const {
-    if (phase == 1) return side == 0 ? j : G - 1 - j;
-    return side == 0 ? tmb + j : tmb - 1 - j;
-  }
-  // frame processed at position d of block g by `side` (A ascending, B descending)
-  __device__ __forceinline__ int frame(int side, int g, int d) const { return side == 0 ? BLK * g + d : BLK * g + nvof(g) - 1 - d; }
-};
-
-// NL consecutive floats (or NL consecutive (a, b) pairs) of this lane in an LDS / HBM row, NL = 1, 2, 4: widest accesses
-template <int NL>
-__device__ __forceinline__ void ld_slots(const float *p, float (&v)[NL]) {
-  if constexpr (NL == 1) v[0] = p[0];
-  else if constexpr (NL == 2) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; }
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 4; ++q) {
-      const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-  }
-}
-template <int NL>
-__device__ __forceinline__ void st_slots(float *p, const float (&v)[NL]) {
-  if constexpr (NL == 1) p[0] = v[0];
-  else if constexpr (NL == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 4; ++q) *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  }
-}
-template <int NL>
-__device__ __forceinline__ void ld_pairs(const float *p, float (&a)[NL], float (&b)[NL]) {
-  if constexpr (NL == 1) { const float2 t = *reinterpret_cast<const float2 *>(p); a[0] = t.x; b[0] = t.y; }
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 2; ++q) {
-      const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-      a[2 * q] = t.x; b[2 * q] = t.y; a[2 * q + 1] = t.z; b[2 * q + 1] = t.w;
-    }
-  }
-}
-template <int NL>
-__device__ __forceinline__ void st_pairs(float *p, const float (&a)[NL], const float (&b)[NL]) {
-  if constexpr (NL == 1) *reinterpret_cast<float2 *>(p) = make_float2(a[0], b[0]);
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 2; ++q) *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(a[2 * q], b[2 * q], a[2 * q + 1], b[2 * q + 1]);
-  }
-}
-
+// (block_barrier, Geo<BLK>, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h)
 template <int NL, class LDt>
 __device__ __forceinline__ void read_E(const float *row, int lane, Emis<NL> &e) {
   ld_slots<NL>(row + lane * NL, e.y);
@@ -214,28 +146,9 @@ __device__ __forceinline__ void init_labels(S_t &S, const Problem &p, int b, int
 // cycles per block, SIMD 2/3 nothing else in this phase).  The worker also records the statistics of its frames for the
 // other side's pass over them in phase 2.  One barrier per block, like every other role.
 // ------------------------------------------------------------------------------------------------
-// (measured: 1/3/4 for two label positions per lane, 2/3/2 for one -- the chain is half as long there)
+// (fused::P1Split, ctc_lane_ops.h.  Measured: 1/3/4 for two label positions per lane, 2/3/2 for one -- the chain is half as long there)
 template <int BLK, int NH, int NL>
-struct P1Split {
-  // NH = 4 (12-frame blocks): X / X / Y / Y / R as above.  NH = 2 (6-frame blocks of the 4-positions-per-lane variant):
-  // the two helpers and the recompute wavefront take a third each.
-  // NH = 1 (3-frame blocks of the 8-positions-per-lane variant): two frames for the helper, one for the recompute wavefront.
-  static constexpr int X = NH == 4 ? (NL == 1 ? 2 : 1) : NH == 2 ? BLK / 3 : 2, Y = NH == 4 ? 3 : NH == 2 ? BLK / 3 : 0;
-  static constexpr int R = NH == 4 ? BLK - 2 * X - 2 * Y : NH == 2 ? BLK - X - Y : BLK - X;
-  static_assert(NH == 4 || NH == 2 || NH == 1, "helpers per side");
-  static_assert(X >= 0 && Y >= 0 && R >= 0 && X <= 6 && Y <= 6 && R <= 6, "phase-1 split: at most 6 frames per worker");
-  // worker: 0 .. NH-1 = helpers, NH = recompute wavefront
-  static constexpr int count(int worker) {
-    if (NH == 4) return worker < 2 ? X : worker < 4 ? Y : R;
-    if (NH == 1) return worker == 0 ? X : R;
-    return worker == 0 ? X : worker == 1 ? Y : R;
-  }
-  static constexpr int first(int worker) {
-    int f = 0;
-    for (int w = 0; w < worker; ++w) f += count(w);
-    return f;
-  }
-};
+using P1Split = fused::P1Split<BLK, NH, NL == 1 ? 2 : 1, 3>;
 
 template <int KIND, int NL, int NH, int BLK, int VPL, int SIDE, int P0, int NQ, class S_t>
 __device__ __forceinline__ void estage1(const S_t &S, Lds<KIND, NL, NH, BLK, VPL> &lds, const Geo<BLK> &geo,

@@ -56,50 +56,19 @@ namespace fused6 {
 
 using namespace ctc::fused;
 
-using linear::DEAD; using linear::GAP; using linear::GAP_WIDE; using linear::DOWN_MAX; using linear::DECAY_MAX; using linear::KK_MAX;
-using linear::KK_MAX2; using linear::EMIS_MIN; using linear::MASS_TOL;  // (ctc_linear_flags.h: shared with ctc_hvp_fused.hip)
+using namespace ctc::linear;  // the number format's constants and the flag bits D1..D10 (ctc_linear_flags.h: shared with ctc_hvp_fused.hip)
 // Gap to which a lane that HOLDS mass is lifted towards its upstream neighbour.  It has to be the adoption gap: r04 tried 80 (a live
 // lane's own thin values then survive 2^64 deeper -- tests/tools/linear_model.py shows the mass of tests/golden/soak_case_endloss_u128.npz
 // intact with it), but mantissas then reach 2^120 where a steep front crosses thin live lanes, the posterior PRODUCTS of phase 2
 // overflow, and between the frames D6 samples that went unnoticed: a gradient 3.0 off, unflagged (tests/tools/flag_stats.py, cell
 // sigma 5, V = 3, U = 32, slack 2).  With 16 per level and LV levels a mantissa stays below 2^55 and a product below 2^110.
 constexpr int GAP_LIVE = 16;
-// GAP_WIDE (ctc_linear_flags.h):      // ... when ONE level suffices (a lane of 4 or 8 label positions is never crossed within a period):
-                                  // neighbouring lanes then differ by 2^100 and more on benign inputs, and lifting a lane to
-                                  // 2^-16 of its neighbour pushed its own values towards the float32 underflow (D4)
-// D3 / D4: a lane's own values pushed 2^-96 below its exponent (by a larger inflow scale / by decay).  A float32 mantissa
-// holds them down to 2^-126, so nothing is lost yet; the margin is for what happens before the next renormalisation.  (64
-// was too tight once a lane spans eight label positions: neighbouring lanes then differ by more than 2^64 on benign inputs
-// and every loss-only call at U > 256 went to the log domain.)
-// DOWN_MAX (ctc_linear_flags.h):      // D3
-// DECAY_MAX (ctc_linear_flags.h):     // D4
-// KK_MAX (ctc_linear_flags.h):        // Posterior scale 2^KK_MAX at most in ONE factor.  The posterior of a state is (alpha mantissa)(beta
-                                  // mantissa) 2^(kA + kB - log2 P); the mantissa PRODUCT underflows below 2^-126, which is harmless
-                                  // while the scale stays below 2^90 (the lost term is < 2^-5 units of 2^-30) and fatal beyond --
-                                  // sharp logits on a nearly forced alignment get there in the frames just before a renormalisation,
-                                  // and so do benign long utterances (T >= 3000: a lane whose two label positions differ by more than
-                                  // 2^90 in alpha and by as much the other way in beta while the alignment crosses between them).
-                                  // Beyond KK_MAX the scale is applied in TWO factors: the excess 2^(k - KK_MAX) goes onto the chain's
-                                  // own operand BEFORE the product (then nothing that matters underflows), the rest after it as before;
-                                  // a wave-uniform branch per frame, taken only while some lane of the wavefront needs it.
-// KK_MAX2 (ctc_linear_flags.h):      // D5: beyond this even the pre-scaled operand would leave float32
-// EMIS_MIN (ctc_linear_flags.h):  // 2^-120 (D2)
 // where the forward half of a pair trusts the linear sweeps (see the meeting point): at least BIND_SLACK spare frames, at most
 // DWELL_MAX frames per label position, P decaying by at most RATE_MAX_X4 / 4 bits per frame (per lattice kind)
 // (decay rate, north-star shape: classic 9.0 bits per frame at N(0, 3^2) -- nothing redone; 9.8 at 3.25^2 -- nothing; 10.5 at 3.5^2 --
 // 5 %; 12.1 at 4^2 -- 51 %.  Simplified: 10.7 / 11.6 -- nothing; 12.4 -- 6 %; 13.3 -- 50 %.)
 constexpr int BIND_SLACK = 64, DWELL_MAX = 12, RATE_MAX_X4_CLASSIC = 40, RATE_MAX_X4_SIMPLIFIED = 47;
 constexpr int DWELL_HARD = 40;      // D10: loss-only calls with more frames per label position than this take the log-domain roles
-constexpr int D10_DWELL = 2048;
-// D7 (loss-only calls): a needed emission below 2^-16 of its row maximum -- "sharp" logits.  The r03 soak runs found utterances with
-// logits N(0, 3^2) on nearly forced alignments (2..15 frames more than labels) whose linear-domain sweeps lose mass that matters later
-// WITHOUT tripping D1..D5 (loss off by 1e-4 .. 3e-2 relative): a call with a gradient sees it in the posterior mass (D6) and redoes the
-// utterance, a loss-only call has nothing to check against.  Every such case had a needed emission below 2^-18.9; N(0,1) logits stay
-// above 2^-13 (the 4.5-sigma tail of 129 000 draws).  So a loss-only call hands sharp utterances to the log domain.
-using linear::EMIS_SOFT;                           // 2^-16 (D7)
-// D6: tolerated deviation of a frame's posterior mass from 1.  The gradient of an unflagged utterance is off by about as much, and the
-// bar is 1e-4: with a tolerance of 1e-4 the soak runs measured up to 9.0e-5 on unflagged utterances -- no margin (r03).
-// MASS_TOL (ctc_linear_flags.h):
 
 #ifdef CTC_F6_STAMPS
 // diagnostic build: cycles of work / of waiting at the block barriers, per wavefront and phase (thread-private registers)
@@ -111,7 +80,7 @@ __device__ Stamps *g_stamps_dummy;
 #define F6_ST_ARG , st_
 #define F6_STAMP_DECL Stamps st_; st_.t0 = __builtin_amdgcn_s_memtime();
 #define F6_STAMP_PHASE2 st_.ph = 1;
-#define F6_BARRIER() do { __builtin_amdgcn_s_waitcnt(0xC07F); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_.work[st_.ph] += t_ - st_.t0; block_barrier_raw(); \
+#define F6_BARRIER() do { __builtin_amdgcn_s_waitcnt(0xC07F); unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_.work[st_.ph] += t_ - st_.t0; block_barrier(); \
     unsigned long long u_ = __builtin_amdgcn_s_memtime(); st_.wait[st_.ph] += u_ - t_; st_.t0 = u_; } while (0)
 #define F6_WAIT(expr) do { unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_.work[st_.ph] += t_ - st_.t0; expr; \
     unsigned long long u_ = __builtin_amdgcn_s_memtime(); st_.wait[st_.ph] += u_ - t_; st_.t0 = u_; } while (0)
@@ -121,43 +90,13 @@ __device__ Stamps *g_stamps_dummy;
 #define F6_ST_ARG
 #define F6_STAMP_DECL
 #define F6_STAMP_PHASE2
-#define F6_BARRIER() block_barrier_raw()
+#define F6_BARRIER() block_barrier()
 #define F6_WAIT(expr) do { expr; } while (0)
 #define F6_STAMP_DUMP(wave)
 #endif
-__device__ __forceinline__ void block_barrier_raw() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed; vmcnt untouched
-  __builtin_amdgcn_s_barrier();
-}
-
 // One block barrier per block in phase 1.  Producer / consumer words in LDS in its place were built and measured in r04: no gain
 // (134.7-137.6 against 135.3-136.0 us), and racy as written; profiles/r04_kernel_experiments.md, profiles/r04_p1sync_stamps.txt.
-// Flag bits 256 (D8: such a wait timed out) and 512 (D9: a checked renormalisation saw a value leave its lane's range -- flagged 60 %
-// of benign utterances and still missed a harmful one, tests/tools/flag_stats.py) are retired, never set, and stay reserved.
-constexpr int D8_RETIRED = 256, D9_RETIRED = 512;  // still in the masks of the meeting point and in flag_or(): the same device code
-
-__device__ __forceinline__ int from_prev_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int from_next_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x130, 0xf, 0xf, false); }
-__device__ __forceinline__ float ldexp_f(float x, int e) { return __builtin_ldexpf(x, e); }
-__device__ __forceinline__ int frexp_e(float x) { return __builtin_amdgcn_frexp_expf(x); }
-__device__ __forceinline__ int readlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-// Packed float32 pairs (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: two label positions per instruction; a wavefront issues one
-// vector instruction per ~8 cycles whatever its width, profiles/r03_issue_rate.txt) for the two-positions-per-lane classic chains --
-// the roles whose time is their own dependent instruction stream.  NOT for the helpers: their E / G stage arithmetic packed the same
-// way (r04: 263 -> 238 instructions per block) made phase 1 two microseconds SLOWER and phase 2 no faster -- a packed operation
-// occupies the SIMD for two passes, and the helpers share their SIMDs' pipes with the chains (profiles/r04_kernel_experiments.md).
-typedef float f2v __attribute__((ext_vector_type(2)));
-// acc += (x of the upstream neighbour lane) * sc in ONE instruction (v_fmac_f32 with a DPP source; was v_mov_b32_dpp + v_ldexp_f32 +
-// v_add_f32).  The lane without an upstream neighbour (0 for wave_shr, 63 for wave_shl) is left unchanged (bound_ctrl off: the
-// lane is disabled).  `s_nop 1`: a DPP source written by the preceding VALU instruction needs two wait states, and the compiler
-// does not look into inline assembly.
-template <int DIR>
-__device__ __forceinline__ void fmac_from_upstream(float &acc, float x, float sc) {
-  if constexpr (DIR == 0) asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
-  else asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
-}
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+// (block_barrier itself, the lane helpers, f2v, fmac_from_upstream, Geo<BLK>, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h)
 
 // renormalisation period inside a block and the number of lanes the lattice front can cross in one period
 template <int BLK, int NL>
@@ -221,70 +160,6 @@ struct Lds {
   float lossval;            // loss[b] as written at the meeting point and whether it has been added to the running sum there
   int added;                // (ctc_amd_loss_grad_sum; an utterance flagged later takes it back at the end of the kernel)
 };
-
-// Block geometry shared by every wavefront of the workgroup (identical to ctc_fused5.hip).
-template <int BLK>
-struct Geo {
-  int len, G, tmb, tm, NB;
-  __device__ __forceinline__ void init(int len_) {
-    len = len_;
-    G = (len + BLK - 1) / BLK;
-    tmb = G / 2;
-    tm = tmb * BLK;
-    NB = G - tmb;
-  }
-  __device__ __forceinline__ int nvof(int g) const { int r = len - BLK * g; return r < BLK ? r : BLK; }
-  __device__ __forceinline__ int nblocks(int phase, int side) const { return (phase == 1) == (side == 0) ? tmb : G - tmb; }
-  __device__ __forceinline__ int absblock(int phase, int side, int j) const {
-    if (phase == 1) return side == 0 ? j : G - 1 - j;
-    return side == 0 ? tmb + j : tmb - 1 - j;
-  }
-  __device__ __forceinline__ int frame(int side, int g, int d) const { return side == 0 ? BLK * g + d : BLK * g + nvof(g) - 1 - d; }
-  // checkpoint slot of lattice time t (multiples of BLK, and `len`): distinct per direction
-  __device__ __forceinline__ int slot(int t) const { return (t + BLK - 1) / BLK; }
-};
-
-// NL consecutive floats (or pairs) of this lane in an LDS / HBM row
-template <int NL>
-__device__ __forceinline__ void ld_slots(const float *p, float (&v)[NL]) {
-  if constexpr (NL == 1) v[0] = p[0];
-  else if constexpr (NL == 2) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; }
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 4; ++q) {
-      const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-  }
-}
-template <int NL>
-__device__ __forceinline__ void st_slots(float *p, const float (&v)[NL]) {
-  if constexpr (NL == 1) p[0] = v[0];
-  else if constexpr (NL == 2) *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 4; ++q) *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-  }
-}
-template <int NL>
-__device__ __forceinline__ void ld_pairs(const float *p, float (&a)[NL], float (&b)[NL]) {
-  if constexpr (NL == 1) { const float2 t = *reinterpret_cast<const float2 *>(p); a[0] = t.x; b[0] = t.y; }
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 2; ++q) {
-      const float4 t = *reinterpret_cast<const float4 *>(p + 4 * q);
-      a[2 * q] = t.x; b[2 * q] = t.y; a[2 * q + 1] = t.z; b[2 * q + 1] = t.w;
-    }
-  }
-}
-template <int NL>
-__device__ __forceinline__ void st_pairs(float *p, const float (&a)[NL], const float (&b)[NL]) {
-  if constexpr (NL == 1) *reinterpret_cast<float2 *>(p) = make_float2(a[0], b[0]);
-  else {
-#pragma unroll
-    for (int q = 0; q < NL / 2; ++q) *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(a[2 * q], b[2 * q], a[2 * q + 1], b[2 * q + 1]);
-  }
-}
 
 // per-frame emissions, linear: y[j] = exp(x[label[i]] - rowmax) (0 beyond label_length), bl = exp(x[blank] - rowmax)
 template <int NL>
@@ -499,7 +374,7 @@ struct Chain {
     // (D3 only for a lane that has had mass for a few periods: at the lattice front the first thin paths of a lane are
     // legitimately swamped when the bulk arrives, ~1 in 256 benign utterances)
     age = (live && alive) ? age + 1 : 0;
-    flag |= (live && age >= 3 && d < -DOWN_MAX ? 4 : 0) | (live && fe < -DECAY_MAX ? 8 : 0) | (!live && alive ? 16 : 0);
+    flag |= (live && age >= 3 && d < -DOWN_MAX ? D3_DOWN : 0) | (live && fe < -DECAY_MAX ? D4_DECAY : 0) | (!live && alive ? D4_DIED : 0);
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       c[j] = ldexp_f(c[j], d);
@@ -534,7 +409,7 @@ struct Chain {
   __device__ __forceinline__ int flag_or() const {
     int f = 0;
 #pragma unroll
-    for (int bit = 4; bit <= 16; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
+    for (int bit = D3_DOWN; bit <= D4_DIED; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
     f |= (__builtin_amdgcn_ballot_w64((flag & D9_RETIRED) != 0) != 0) ? D9_RETIRED : 0;  // (never set; the compiler cannot always tell)
     return f;
   }
@@ -750,30 +625,14 @@ struct Rows {
 // point): positions P0 .. P0+NQ-1 of every block of side SIDE.  Records (mxl, inv) per frame for phase 2, accumulates
 // log2 sum exp of its frames in double and tracks the smallest needed emission (D2).
 // ------------------------------------------------------------------------------------------------
-// Frames of a block per E-stage worker of a side: NH = 4 (12-frame blocks) X / X / Y / Y for the helpers and R for the recompute wavefront.
+// Frames of a block per E-stage worker of a side (fused::P1Split, ctc_lane_ops.h): 2 / 2 / 2 / 2 for the four helpers of a 12-frame block.
+// (NH = 3 for the six-frame blocks of the four-positions-per-lane variant -- 2, 2, 1 frames for the helpers, 1 for the recompute
+// wavefront -- was built and measured in r04: 227 us against 211 at U = 256: those shapes are bound by their chains, and more
+// helpers only take issue slots from them.  NH = 6 for the 12-frame blocks, sixteen wavefronts, two frames per helper: r03, 134
+// against 127 us at B = 64, 161 against 151 at B = 256 -- the main chains lose more to two extra wavefronts on their SIMDs than
+// the helpers gain.  Other splits for NH = 4: profiles/r04_kernel_experiments.md.)
 template <int BLK, int NH, int NL>
-struct P1Split {
-  // (NH = 1, the 3-frame blocks of the 8-positions-per-lane variant: two frames for the helper, one for the recompute wavefront)
-  // (NH = 3 for the six-frame blocks of the four-positions-per-lane variant -- 2, 2, 1 frames for the helpers, 1 for the recompute
-  // wavefront -- was built and measured in r04: 227 us against 211 at U = 256: those shapes are bound by their chains, and more
-  // helpers only take issue slots from them.  NH = 6 for the 12-frame blocks, sixteen wavefronts, two frames per helper: r03, 134
-  // against 127 us at B = 64, 161 against 151 at B = 256 -- the main chains lose more to two extra wavefronts on their SIMDs than
-  // the helpers gain.  Other splits for NH = 4: profiles/r04_kernel_experiments.md.)
-  static constexpr int X = NH == 4 ? 2 : NH == 2 ? BLK / 3 : 2, Y = NH == 4 ? 2 : NH == 2 ? BLK / 3 : 0;
-  static constexpr int R = NH == 4 ? BLK - 2 * X - 2 * Y : NH == 2 ? BLK - X - Y : BLK - X;
-  static_assert(NH == 4 || NH == 2 || NH == 1, "helpers per side");
-  static_assert(X >= 0 && Y >= 0 && R >= 0 && X <= 6 && Y <= 6 && R <= 6, "phase-1 split: at most 6 frames per worker");
-  static constexpr int count(int worker) {
-    if (NH == 4) return worker < 2 ? X : worker < 4 ? Y : R;
-    if (NH == 1) return worker == 0 ? X : R;
-    return worker == 0 ? X : worker == 1 ? Y : R;
-  }
-  static constexpr int first(int worker) {
-    int f = 0;
-    for (int w = 0; w < worker; ++w) f += count(w);
-    return f;
-  }
-};
+using P1Split = fused::P1Split<BLK, NH, 2, 2>;
 
 template <int KIND, int NL, int NH, int BLK, int VPL, int XT, int SIDE, int P0, int NQ>
 __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KIND, NL, NH, BLK, VPL> &lds, const Geo<BLK> &geo,
@@ -912,11 +771,11 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL, VPL, XT> &S, Lds<KI
   bool bad = !(zb >= EMIS_MIN) || !(acc - acc == 0.0);  // (a NaN or +inf logit makes the row sum, hence acc, non-finite)
 #pragma unroll
   for (int j = 0; j < NL; ++j) bad = bad || (S.valid[j] && !(zmin[j] >= EMIS_MIN));
-  if (NQ > 0 && nb > 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(&lds.flag, 2);
+  if (NQ > 0 && nb > 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(&lds.flag, D2_EMIS);
   bool sharp = !(zb >= EMIS_SOFT);  // D7 (honoured by loss-only calls)
 #pragma unroll
   for (int j = 0; j < NL; ++j) sharp = sharp || (S.valid[j] && !(zmin[j] >= EMIS_SOFT));
-  if (NQ > 0 && nb > 0 && __builtin_amdgcn_ballot_w64(sharp) != 0 && lane == 0) atomicOr(&lds.flag, 128);
+  if (NQ > 0 && nb > 0 && __builtin_amdgcn_ballot_w64(sharp) != 0 && lane == 0) atomicOr(&lds.flag, D7_SHARP);
   if (lane == 0) lds.l2s[wave] = acc;
 }
 
@@ -1044,7 +903,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
     const bool okP = shape_ok && EX > DEAD / 2 && s > 0.f && s < 3.0e38f;
     double sl2 = 0.0;
     for (int w = 2; w < LD::NW; ++w) sl2 += lds.l2s[w];
-    // D3 / D4 (bits 4, 8, 16) and D7 (128) send a loss-only call to the log-domain kernel; with a gradient the mass check D6 decides.
+    // D3 / D4 and D7 (SOFT_FLAGS) send a loss-only call to the log-domain kernel; with a gradient the mass check D6 decides.
     // (D9, the exact "a nonzero value left its lane's range" at every renormalisation, was tried and retired: benign utterances flush
     // irrelevant values all the time -- the thin front ahead of the bulk, the tail behind it -- so it flagged 60 % of the N(0,1)
     // utterances at T = 1000 and still missed one harmful case in 30 000; tests/tools/flag_stats.py)
@@ -1065,14 +924,14 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
     const int decay = -(EX + frexp_e(s));                      // bits by which the unnormalised P has decayed over the utterance
     const bool trusted = p.resume == 2 && NL <= 2 && slack >= BIND_SLACK && len <= DWELL_MAX * (ll + 1) &&
                          4 * decay <= (KIND == 0 ? RATE_MAX_X4_CLASSIC : RATE_MAX_X4_SIMPLIFIED) * len;
-    const int soft = trusted ? 0 : (28 | 128);
+    const int soft = trusted ? 0 : SOFT_FLAGS;
     // D10 (every loss-only call, two and more label positions per lane): more than DWELL_HARD frames per label position.  The soft
     // signs miss what long dwell does to MILD logits -- N(0, 2^2), 2 labels in 512 frames under a label bound of 128: 17-40 % of
     // the utterances fail the mass check of a call with a gradient, 22 % show no soft sign, and 2 of 256 stand-alone loss-only
     // calls returned a loss more than 1e-4 off (r04, tests/tools/flag_stats_short_labels.py; r03's rules had the same hole).
     // Nothing is redone at 30 frames per label position, 0-1.6 % at 57.
     const int hard = (!want_grad && NL >= 2 && okP && len > DWELL_HARD * (ll + 1)) ? D10_DWELL : 0;
-    const int fl = (lds.flag & (want_grad ? (3 | D8_RETIRED) : (3 | soft | D8_RETIRED))) | (okP ? 0 : 1) | hard;
+    const int fl = (lds.flag & (want_grad ? (HARD_FLAGS | D8_RETIRED) : (HARD_FLAGS | soft | D8_RETIRED))) | (okP ? 0 : D1_NO_P) | hard;
     if (lane == 0) {
       const double dlogp = (double)flog2(s) + (double)EX - sl2;
       logp_ws[b] = okP ? dlogp : -INFINITY;
@@ -1336,7 +1195,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
       }
       F6_BARRIER();
     }
-    if (__builtin_amdgcn_ballot_w64(kflag != 0) != 0 && lane == 0) atomicOr(&lds.flag, 32);  // D5
+    if (__builtin_amdgcn_ballot_w64(kflag != 0) != 0 && lane == 0) atomicOr(&lds.flag, D5_SCALE);
   }
   __syncthreads();  // every role's phase-2 flags are in
   if (DIR == 0 && lane == 0) flag_ws[b] = lds.flag;
@@ -1726,7 +1585,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
         if (it0 + decltype(R)::value <= geo.NB + 2) body(R, std::false_type{}, it0 + decltype(R)::value);
       });
     }
-    if (massbad && lane == 0) atomicOr(&lds.flag, 64);  // D6
+    if (massbad && lane == 0) atomicOr(&lds.flag, D6_MASS);
   }
   __syncthreads();
   F6_STAMP_DUMP(wave);

@@ -1,11 +1,12 @@
-// Building blocks shared by the fused loss+gradient kernels (ctc_fused.hip: two self-contained wavefronts per
-// utterance; ctc_fused4.hip: chain + helper wavefronts; ctc_fused5.hip: chains + recompute chains + helpers) and by the
-// Hessian sweeps (ctc_hessian.hip).  See those files for the algorithms.
+// Building blocks shared by the fused loss+gradient kernels (ctc_fused5.hip / ctc_fused5_roles.h: log-domain chains + recompute
+// chains + helpers; ctc_fused6.hip: the same roles in the linear domain) and by the Hessian kernels (ctc_hessian.hip: the sweeps;
+// ctc_hvp.hip / ctc_hvp_device.h and ctc_hvp_fused.hip: the Hessian-vector products).  See those files for the algorithms.
 #pragma once
 #include <type_traits>
 
 #include "ctc_common.h"
 #include "ctc_dpp_batch.h"
+#include "ctc_lane_ops.h"
 
 namespace ctc {
 
@@ -48,33 +49,11 @@ struct SRow {
 template <int KIND, int NL>
 __device__ __forceinline__ void load_srow(SRow<KIND, NL> &r, const float *__restrict__ row, int lane, int UP) {
   if constexpr (KIND == 0) {
-    const float *p = row + 2 * lane * NL;
-    if constexpr (NL == 1) {
-      float2 v = *reinterpret_cast<const float2 *>(p);
-      r.a[0] = v.x; r.b[0] = v.y;
-    } else {
-#pragma unroll
-      for (int q = 0; q < NL / 2; ++q) {
-        float4 v = *reinterpret_cast<const float4 *>(p + 4 * q);
-        r.a[2 * q] = v.x; r.b[2 * q] = v.y; r.a[2 * q + 1] = v.z; r.b[2 * q + 1] = v.w;
-      }
-    }
+    ld_pairs<NL>(row + 2 * lane * NL, r.a, r.b);
     r.tail = *reinterpret_cast<const float4 *>(row + 2 * UP);
     r.stat = *reinterpret_cast<const float2 *>(row + 2 * UP + 4);
   } else {
-    const float *p = row + lane * NL;
-    if constexpr (NL == 1) {
-      r.a[0] = p[0];
-    } else if constexpr (NL == 2) {
-      float2 v = *reinterpret_cast<const float2 *>(p);
-      r.a[0] = v.x; r.a[1] = v.y;
-    } else {
-#pragma unroll
-      for (int q = 0; q < NL / 4; ++q) {
-        float4 v = *reinterpret_cast<const float4 *>(p + 4 * q);
-        r.a[4 * q] = v.x; r.a[4 * q + 1] = v.y; r.a[4 * q + 2] = v.z; r.a[4 * q + 3] = v.w;
-      }
-    }
+    ld_slots<NL>(row + lane * NL, r.a);
     r.tail = *reinterpret_cast<const float4 *>(row + UP);
     r.stat = *reinterpret_cast<const float2 *>(row + UP + 4);
   }
@@ -83,34 +62,12 @@ __device__ __forceinline__ void load_srow(SRow<KIND, NL> &r, const float *__rest
 template <int KIND, int NL>
 __device__ __forceinline__ void store_srow(float *__restrict__ row, int lane, int UP, const float (&a)[NL],
                                            const float (&b)[NL], float4 tail, float2 stat) {
-  if constexpr (KIND == 0) {
-    float *p = row + 2 * lane * NL;
-    if constexpr (NL == 1) {
-      *reinterpret_cast<float2 *>(p) = make_float2(a[0], b[0]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < NL / 2; ++q)
-        *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(a[2 * q], b[2 * q], a[2 * q + 1], b[2 * q + 1]);
-    }
-    // 32-byte wave-uniform tail in ONE store instruction: even lanes write the first half, odd lanes the second
-    const bool odd = lane & 1;
-    *reinterpret_cast<float4 *>(row + 2 * UP + (odd ? 4 : 0)) =
-        make_float4(odd ? stat.x : tail.x, odd ? stat.y : tail.y, odd ? 0.f : tail.z, odd ? 0.f : tail.w);
-  } else {
-    float *p = row + lane * NL;
-    if constexpr (NL == 1) {
-      p[0] = a[0];
-    } else if constexpr (NL == 2) {
-      *reinterpret_cast<float2 *>(p) = make_float2(a[0], a[1]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < NL / 4; ++q)
-        *reinterpret_cast<float4 *>(p + 4 * q) = make_float4(a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
-    }
-    const bool odd = lane & 1;
-    *reinterpret_cast<float4 *>(row + UP + (odd ? 4 : 0)) =
-        make_float4(odd ? stat.x : tail.x, odd ? stat.y : tail.y, odd ? 0.f : tail.z, odd ? 0.f : tail.w);
-  }
+  if constexpr (KIND == 0) st_pairs<NL>(row + 2 * lane * NL, a, b);
+  else st_slots<NL>(row + lane * NL, a);
+  // 32-byte wave-uniform tail in ONE store instruction: even lanes write the first half, odd lanes the second
+  const bool odd = lane & 1;
+  *reinterpret_cast<float4 *>(row + (KIND == 0 ? 2 : 1) * UP + (odd ? 4 : 0)) =
+      make_float4(odd ? stat.x : tail.x, odd ? stat.y : tail.y, odd ? 0.f : tail.z, odd ? 0.f : tail.w);
 }
 
 // Per-frame emissions in base-2 logs.

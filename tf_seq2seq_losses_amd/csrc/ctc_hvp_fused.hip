@@ -44,28 +44,8 @@ using namespace ctc::fused;
 
 constexpr int BLK = HVPF_BLK, NH = 3, RN = 3, NG = BLK / RN, NW = 4 + 2 * NH;  // 10 wavefronts: 4 chains + 3 helpers a side
 constexpr int V = 256;
-using linear::DEAD; using linear::GAP; using linear::GAP_WIDE; using linear::DOWN_MAX; using linear::DECAY_MAX; using linear::KK_MAX;
-using linear::EMIS_MIN; using linear::MASS_TOL;  // (ctc_linear_flags.h: one copy for this kernel and ctc_fused6.hip)
-
-// packed float32 pairs and the one-instruction inflow for the classic two-positions-per-lane chains (as ctc_fused6.hip, r04)
-typedef float f2v __attribute__((ext_vector_type(2)));
-template <int DIR>
-__device__ __forceinline__ void fmac_from_upstream(float &acc, float x, float sc) {
-  if constexpr (DIR == 0) asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
-  else asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
-}
-
-__device__ __forceinline__ void block_barrier_raw() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed; vmcnt untouched
-  __builtin_amdgcn_s_barrier();
-}
-__device__ __forceinline__ int from_prev_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int from_next_lane_i(int x, int fill) { return __builtin_amdgcn_update_dpp(fill, x, 0x130, 0xf, 0xf, false); }
-__device__ __forceinline__ float ldexp_f(float x, int e) { return __builtin_ldexpf(x, e); }
-__device__ __forceinline__ int frexp_e(float x) { return __builtin_amdgcn_frexp_expf(x); }
-__device__ __forceinline__ int readlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
+using namespace ctc::linear;  // the number format's constants and the flag bits (ctc_linear_flags.h: one copy for this kernel and ctc_fused6.hip)
+// (the lane helpers, f2v and the one-instruction inflow fmac_from_upstream, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h)
 
 template <int NL> struct Cfg {
   static constexpr int UP = 64 * NL;
@@ -90,47 +70,16 @@ struct Lds {
   float cf, dlp;
 };
 
-struct Geo {
-  int len, G, tmb, tm, NB;
+struct Geo : fused::Geo<BLK> {
   // NI1 / NI2: block iterations (= workgroup barriers) of phase 1 / phase 2, the same for every wavefront: NB + 1 / NB + 3 rounded
   // up to the depth of the register rings of the wavefronts that load rows (4 / 3), so that their unrolled loops need no guard
   // per slot (see estage1)
   int NI1, NI2;
   __device__ __forceinline__ void init(int len_) {
-    len = len_; G = (len + BLK - 1) / BLK; tmb = G / 2; tm = tmb * BLK; NB = G - tmb;
+    fused::Geo<BLK>::init(len_);
     NI1 = (NB + 1 + 3) / 4 * 4; NI2 = (NB + 3 + 2) / 3 * 3;
   }
-  __device__ __forceinline__ int nvof(int g) const { int r = len - BLK * g; return r < BLK ? r : BLK; }
-  __device__ __forceinline__ int nblocks(int phase, int side) const { return (phase == 1) == (side == 0) ? tmb : G - tmb; }
-  __device__ __forceinline__ int absblock(int phase, int side, int j) const {
-    if (phase == 1) return side == 0 ? j : G - 1 - j;
-    return side == 0 ? tmb + j : tmb - 1 - j;
-  }
-  __device__ __forceinline__ int frame(int side, int g, int d) const { return side == 0 ? BLK * g + d : BLK * g + nvof(g) - 1 - d; }
-  __device__ __forceinline__ int slot(int t) const { return (t + BLK - 1) / BLK; }
 };
-
-// a lane's (first, second) pairs: 2 NL floats at p
-template <int NL>
-__device__ __forceinline__ void ld_pairs(const float *p, float (&a)[NL], float (&b)[NL]) {
-  if constexpr (NL == 1) { const float2 t = *reinterpret_cast<const float2 *>(p); a[0] = t.x; b[0] = t.y; }
-  else { const float4 t = *reinterpret_cast<const float4 *>(p); a[0] = t.x; b[0] = t.y; a[1] = t.z; b[1] = t.w; }
-}
-template <int NL>
-__device__ __forceinline__ void st_pairs(float *p, const float (&a)[NL], const float (&b)[NL]) {
-  if constexpr (NL == 1) *reinterpret_cast<float2 *>(p) = make_float2(a[0], b[0]);
-  else *reinterpret_cast<float4 *>(p) = make_float4(a[0], b[0], a[1], b[1]);
-}
-template <int NL>
-__device__ __forceinline__ void ld_slots(const float *p, float (&v)[NL]) {
-  if constexpr (NL == 1) v[0] = p[0];
-  else { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; }
-}
-template <int NL>
-__device__ __forceinline__ void st_slots(float *p, const float (&v)[NL]) {
-  if constexpr (NL == 1) p[0] = v[0];
-  else *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-}
 
 // per-frame emissions, linear: y[j] = exp(x[label[i]] - rowmax), bl = exp(x[blank] - rowmax); w[j] = v[label[i]] - v[blank]
 template <int NL>
@@ -358,7 +307,7 @@ struct Chain {
     kn = imax(kn, DEAD);
     const int d = k - kn;
     age = (live && alive) ? age + 1 : 0;
-    flag |= (live && age >= 3 && d < -DOWN_MAX ? 4 : 0) | (live && fe < -DECAY_MAX ? 8 : 0) | (!live && alive ? 16 : 0);
+    flag |= (live && age >= 3 && d < -DOWN_MAX ? D3_DOWN : 0) | (live && fe < -DECAY_MAX ? D4_DECAY : 0) | (!live && alive ? D4_DIED : 0);
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       c[j] = ldexp_f(c[j], d); dc[j] = ldexp_f(dc[j], d);
@@ -374,7 +323,7 @@ struct Chain {
   __device__ __forceinline__ int flag_or() const {
     int f = 0;
 #pragma unroll
-    for (int bit = 4; bit <= 16; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
+    for (int bit = D3_DOWN; bit <= D4_DIED; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
     return f;
   }
 };
@@ -599,7 +548,7 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL> &S, Lds<KIND, NL> &
     // s_waitcnt vmcnt(0) behind each load, nothing ever in flight across an iteration, 136 us for a phase 1 whose loads take 89.
 #pragma unroll
     for (int q = 0; q < NQ; ++q) S.load_xv(xb[r][q], vb[r][q], fr(j + PFD, P0 + q));
-    block_barrier_raw();
+    block_barrier();
   };
   static_assert(4 % PFD == 0, "Geo::NI1 is rounded to a multiple of four iterations");
   for (int it0 = 0; it0 < geo.NI1; it0 += PFD) {
@@ -608,7 +557,7 @@ __device__ __forceinline__ void estage1(const Rows<KIND, NL> &S, Lds<KIND, NL> &
   bool bad = !(zb >= EMIS_MIN) || !(acc - acc == 0.0);
 #pragma unroll
   for (int j = 0; j < NL; ++j) bad = bad || (S.valid[j] && !(zmin[j] >= EMIS_MIN));
-  if (nb > 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(&lds.flag, 2);
+  if (nb > 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) atomicOr(&lds.flag, D2_EMIS);
   if (lane == 0) lds.l2s[wave] = acc;
 }
 
@@ -664,7 +613,7 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
           }
         }
       }
-      block_barrier_raw();
+      block_barrier();
     }
   }
   spill(geo.slot(geo.tm));
@@ -705,7 +654,7 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
     const bool okP = shape_ok && EX > DEAD / 2 && s > 0.f && s < 3.0e38f && (ds - ds == 0.f);
     double sl2 = 0.0;
     for (int w = 2; w < NW; ++w) sl2 += lds.l2s[w];
-    const int fl = (lds.flag & 3) | (okP ? 0 : 1);
+    const int fl = (lds.flag & HARD_FLAGS) | (okP ? 0 : D1_NO_P);
     if (lane == 0) {
       const double dlogp = (double)flog2(s) + (double)EX - sl2;
       if (fl == 0) loss[b] = (float)(-dlogp * LN2_D);  // (flagged utterances: the log-domain pipeline writes theirs)
@@ -857,9 +806,9 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
           }
         }
       }
-      block_barrier_raw();
+      block_barrier();
     }
-    if (__builtin_amdgcn_ballot_w64(kflag != 0) != 0 && lane == 0) atomicOr(&lds.flag, 32);  // D5
+    if (__builtin_amdgcn_ballot_w64(kflag != 0) != 0 && lane == 0) atomicOr(&lds.flag, D5_SCALE);
   }
   __syncthreads();
   if (DIR == 0 && lane == 0) flag_ws[b] = lds.mode ? 0 : lds.flag;
@@ -957,7 +906,7 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const float *__r
         }
       }
     }
-    block_barrier_raw();
+    block_barrier();
   }
   __syncthreads();
 }
@@ -1031,7 +980,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, float4 *__restrict_
   const bool idle = (lds.mode & 4) != 0;
   auto body = [&](auto R, int it) __attribute__((always_inline)) {
     constexpr int r = decltype(R)::value;  // = it mod 3
-    if (idle) { block_barrier_raw(); return; }
+    if (idle) { block_barrier(); return; }
     const int gj = it - 3;
     const bool do_g = gj >= 0 && gj < nb;
     // what this iteration's G stage (block it-3) works on: kept by that block's E stage in this very ring slot
@@ -1107,12 +1056,12 @@ __device__ __forceinline__ void run_helper(const Problem &p, float4 *__restrict_
         }
       }
     }
-    block_barrier_raw();
+    block_barrier();
   };
   for (int it0 = 0; it0 < geo.NI2; it0 += 3) {
     static_for<0, 3>([&](auto R) { body(R, it0 + decltype(R)::value); });
   }
-  if (massbad && lane == 0) atomicOr(&lds.flag, 64);  // D6
+  if (massbad && lane == 0) atomicOr(&lds.flag, D6_MASS);
   __syncthreads();
 }
 
