@@ -1,6 +1,7 @@
 """Host-side model of the linear-domain chains of csrc/ctc_fused6.hip (test infrastructure).
 
-`Chain` restates Chain<KIND, NL, DIR>::step / renorm / start of the kernel in NumPy float32, lane for lane (64 lanes x NL label
+`Chain` restates Chain<KIND, NL, DIR>::step (ctc_fused6.hip) and ChainCore<KIND, NL, DIR>::renorm / start (ctc_linear_chain.h, the
+copy the kernel shares with ctc_hvp_fused.hip) in NumPy float32, lane for lane (64 lanes x NL label
 positions, one integer exponent per lane, the upstream neighbour's value rescaled by 2^dk, renormalisation every RN frames with the
 adoption rule for lanes without mass), so that what the format loses can be looked at frame by frame against the float64 oracle:
 `sweep` runs a chain over the whole utterance and returns its lattice rows as float64 values (mantissa * 2^exponent), in the
@@ -25,7 +26,7 @@ F = np.float32
 
 
 def cadence(NL):
-    """(BLK, RN, LV) of the instantiation with NL label positions per lane at V <= 256 (ctc_fused6.hip: Cad, CTC_F6_ENTRY)"""
+    """(BLK, RN, LV) of the instantiation with NL label positions per lane at V <= 256 (ctc_linear_chain.h: Cad; ctc_fused6.hip: CTC_F6_ENTRY)"""
     BLK = 12 if NL <= 2 else 6 if NL == 4 else 3
     RN = (6 if NL == 2 else 4) if BLK % 4 == 0 else 3
     return BLK, RN, (RN + NL - 1) // NL

@@ -3,6 +3,7 @@
 // and by ctc_fused6.hip (fallback for flagged utterances inside the same launch).
 #pragma once
 #include "ctc_fused_common.h"
+#include "ctc_linear_chain.h"  // LabelTok: one sentinel convention for the log-domain and the linear-domain chains
 
 #ifndef CTC_FUSED_KIND
 #error "compile with -DCTC_FUSED_KIND=0 (classic) or 1 (simplified)"
@@ -123,7 +124,7 @@ __device__ __forceinline__ void restore_state(S_t &S, const SRow<KIND, NL> &r) {
 template <int KIND, int NL, class S_t>
 __device__ __forceinline__ void init_labels(S_t &S, const Problem &p, int b, int lane, int ll) {
   const int32_t *lab = p.labels + (long)b * p.label_stride;
-  auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
+  const LabelTok tok{ll, p, lab};
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     int i = lane * NL + j;

@@ -33,8 +33,8 @@
 //   D5  a lane's alpha and beta exponents exceed log2 P by more than 90 in the posterior: mantissa products that underflow
 //       would no longer be negligible (see KK_MAX)
 //   D3, D4 (calls WITHOUT a gradient have no phase 2 to check the mass in; they fall back on conservative local signs)
-//       D3 a renormalisation scales a lane's own live values down by more than 2^-64; D4 a lane's maximum decays by more
-//       than 2^-64 within one renormalisation period, or a live lane goes to zero
+//       D3 a renormalisation scales a lane's own live values down by more than 2^-DOWN_MAX; D4 a lane's maximum decays by more
+//       than 2^-DECAY_MAX within one renormalisation period, or a live lane goes to zero
 //   D7  (calls WITHOUT a gradient) a needed emission below 2^-16 of its row maximum: sharp logits (see EMIS_SOFT)
 //
 // References: classic_ctc_loss.py:310-462,565-669, simplified_ctc_loss.py:291-438,456-534, base_loss.py:262-298,328-344,
@@ -42,6 +42,7 @@
 #include "ctc_fused_common.h"
 #include "ctc_swap_reduce.h"
 #include "ctc_linear_flags.h"
+#include "ctc_linear_chain.h"  // ChainCore (state, start, renormalisation policy), Cad, r_group: shared with ctc_hvp_fused.hip
 #include "ctc_launch.h"
 #include "ctc_fused5_roles.h"  // the log-domain roles: run inside this kernel for the utterances it flags
 
@@ -57,12 +58,6 @@ namespace fused6 {
 using namespace ctc::fused;
 
 using namespace ctc::linear;  // the number format's constants and the flag bits D1..D10 (ctc_linear_flags.h: shared with ctc_hvp_fused.hip)
-// Gap to which a lane that HOLDS mass is lifted towards its upstream neighbour.  It has to be the adoption gap: r04 tried 80 (a live
-// lane's own thin values then survive 2^64 deeper -- tests/tools/linear_model.py shows the mass of tests/golden/soak_case_endloss_u128.npz
-// intact with it), but mantissas then reach 2^120 where a steep front crosses thin live lanes, the posterior PRODUCTS of phase 2
-// overflow, and between the frames D6 samples that went unnoticed: a gradient 3.0 off, unflagged (tests/tools/flag_stats.py, cell
-// sigma 5, V = 3, U = 32, slack 2).  With 16 per level and LV levels a mantissa stays below 2^55 and a product below 2^110.
-constexpr int GAP_LIVE = 16;
 // where the forward half of a pair trusts the linear sweeps (see the meeting point): at least BIND_SLACK spare frames, at most
 // DWELL_MAX frames per label position, P decaying by at most RATE_MAX_X4 / 4 bits per frame (per lattice kind)
 // (decay rate, north-star shape: classic 9.0 bits per frame at N(0, 3^2) -- nothing redone; 9.8 at 3.25^2 -- nothing; 10.5 at 3.5^2 --
@@ -96,20 +91,8 @@ __device__ Stamps *g_stamps_dummy;
 #endif
 // One block barrier per block in phase 1.  Producer / consumer words in LDS in its place were built and measured in r04: no gain
 // (134.7-137.6 against 135.3-136.0 us), and racy as written; profiles/r04_kernel_experiments.md, profiles/r04_p1sync_stamps.txt.
-// (block_barrier itself, the lane helpers, f2v, fmac_from_upstream, Geo<BLK>, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h)
-
-// renormalisation period inside a block and the number of lanes the lattice front can cross in one period
-template <int BLK, int NL>
-struct Cad {
-  // 12-frame blocks: two label positions per lane renormalise every 6 frames (r03: with the posterior scale in two factors the
-  // longer period no longer raises D5 on long utterances; -4 us at the north-star shape), one position per lane every 4
-  static constexpr int RN12 = 6;  // other periods were measured as build variants, profiles/r04_kernel_experiments.md
-  static constexpr int RN = (BLK % 4 == 0) ? (NL == 2 ? RN12 : 4) : 3;
-  static constexpr int NG = BLK / RN;            // exponent groups of the rows of one block
-  static constexpr int LV = (RN + NL - 1) / NL;  // adoption levels: lanes the lattice front can cross in one period
-  static constexpr int NSEG = 2 * NG + 1;        // posterior-scale segments of one block (kl_segment)
-  static_assert(BLK % RN == 0, "block length must be a multiple of the renormalisation period");
-};
+// (block_barrier itself, the lane helpers, f2v, fmac_from_upstream, Geo<BLK>, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h;
+// the cadence Cad<BLK, NL>, r_group, GAP_LIVE and the chain's state and renormalisation: ctc_linear_chain.h)
 
 // The per-lane posterior scale of the main chain's S rows (run_main) changes when the R rows enter a new exponent group -- before
 // the products of that group's first frame -- and after every renormalisation of the main chain; it is written once per such
@@ -123,8 +106,7 @@ template <int KIND, int DIR, int RN>
 __device__ __forceinline__ constexpr int kl_segment(int d, int nv) {
   int seg = -1, q = -1;
   for (int dd = 0; dd <= d; ++dd) {
-    const int s = (KIND == 0 && DIR == 1) ? nv - dd : nv - 1 - dd;
-    const int qd = (s > 0 ? s - 1 : 0) / RN;
+    const int qd = r_group<KIND, DIR, RN>(dd, nv);
     bool open = qd != q;
     q = qd;
     if (dd > 0 && (dd + ren_shift<KIND, DIR>()) % RN == 0) open = true;  // the main chain renormalised after position dd - 1
@@ -202,59 +184,14 @@ __device__ __forceinline__ void write_R(float *row, float *dump, int lane, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// The lattice state of one direction: mantissas + one exponent per lane.  Slot i = lane*NL + j is label position i.
-//   classic    A (DIR 0): c[j] = closed(l=i+1), o[j] = open(l=i+1), cx = closed(l=0)
-//              B (DIR 1): c[j] = closed(l=i),   o[j] = open(l=i+1), cx = closed(l=UP)
-//   simplified A: c[j] = a(l=i+1), cx = a(l=0);   B: c[j] = b(l=i), cx = b(l=UP)
-// true value = mantissa * 2^k (lanes) / 2^kx (cx).  dk = (exponent of the upstream neighbour) - k: what the one value a
-// lane receives per step has to be shifted by (upstream = previous lane for A, next lane for B; cx for the first / last).
+// The lattice state of one direction (ChainCore, ctc_linear_chain.h: slots, exponents, start, renormalisation) and its step.
 // ------------------------------------------------------------------------------------------------
 template <int KIND, int NL, int DIR>
-struct Chain {
-  float c[NL], o[NL], cx;
-  int k, kx, dk;
-  bool norep[NL], norep_next[NL];
-  int flag;
-  static constexpr bool PACKED = KIND == 0 && NL == 2;
-  float nrf[NL];  // PACKED: 1.0 where the repeat rule lets the diagonal pass (norep_next for A, norep for B), else 0.0
-  float sc, scb;  // PACKED: 2^dk as a float (0 below 2^-126: what v_ldexp_f32 would flush), and the same on the boundary lane only
-
-  __device__ __forceinline__ void init_labels(const Problem &p, int b, int lane, int ll) {
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
-    auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const int i = lane * NL + j;
-      const int tk = tok(i);
-      norep[j] = (i == 0) || tk != tok(i - 1);
-      norep_next[j] = tok(i + 1) != tk;
-      nrf[j] = ((DIR == 0) ? norep_next[j] : norep[j]) ? 1.f : 0.f;
-      c[j] = 0.f;
-      o[j] = 0.f;
-    }
-    cx = 0.f; k = DEAD; kx = DEAD; dk = 0; flag = 0; sc = 1.f;
-    scb = (lane == (DIR == 0 ? 0 : 63)) ? 1.f : 0.f;
-    boundary = lane == (DIR == 0 ? 0 : 63);
-    relevant = lane * NL <= ll;  // the lane holds a label position that can carry mass (lanes beyond the label stay empty for good)
-  }
-
-  // starting state: alpha[0] = delta(closed(l=0)) / beta[len] = delta(closed(l=ll)) + delta(open(l=ll))
-  template <int LV>
-  __device__ __forceinline__ void start(int lane, int ll, int UP) {
-    if constexpr (DIR == 0) {
-      cx = 1.f; kx = 0;
-    } else {
-      if (ll == UP) { cx = 1.f; kx = 0; }
-#pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const int i = lane * NL + j;
-        if (i == ll) { c[j] = 1.f; k = 0; }
-        if (KIND == 0 && i == ll - 1) { o[j] = 1.f; k = 0; }
-      }
-    }
-    renorm<LV>();
-    flag = 0;
-  }
+struct Chain : ChainCore<KIND, NL, DIR> {
+  using Core = ChainCore<KIND, NL, DIR>;
+  using Core::PACKED;
+  using Core::c; using Core::o; using Core::cx; using Core::dk; using Core::norep; using Core::norep_next; using Core::nrf;
+  using Core::sc; using Core::scb; using Core::flag;
 
   // one lattice step (the recursions of Side::step in ctc_fused_common.h with log-sum-exp -> +, + -> *)
   __device__ __forceinline__ void step(const Emis<NL> &e) {
@@ -333,83 +270,9 @@ struct Chain {
     }
   }
 
-  // per-lane renormalisation: k <- exponent of the lane maximum (lanes without mass adopt the upstream exponent - GAP so
-  // that what flows in during the next period is representable), cx to its own exponent, dk refreshed
-  template <int LV>
-  __device__ __forceinline__ void renorm() {
-    float m = c[0];
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      if constexpr (KIND == 0) m = (j == 0) ? vmax_raw(m, o[0]) : vmax3_raw(m, c[j], o[j]);
-      else if (j > 0) m = vmax_raw(m, c[j]);
-    }
-    const bool live = m > 0.f;
-    const int fe = frexp_e(m);
-    const int e_own = live ? fe + k : DEAD;
-    const bool xlive = cx > 0.f;
-    const int ex = xlive ? frexp_e(cx) + kx : DEAD;
-    int kn = e_own;
-    // the first level: a lane far below its upstream neighbour is lifted to that neighbour's exponent - GAP (a lane that holds mass:
-    // - GAP_LIVE at least); lanes without mass get an exponent this way before the front reaches them
-    {
-      const int nb = (DIR == 0) ? from_prev_lane_i(kn, ex) : from_next_lane_i(kn, ex);
-      kn = imax(kn, nb - (live ? imax(GAP_LIVE, LV == 1 ? GAP_WIDE : GAP) : (LV == 1 ? GAP_WIDE : GAP)));
-    }
-    // ALL levels for every lane, with or without mass (until r04 the further levels ran only while some lane of the wavefront was
-    // empty): a STEEP profile of live lanes -- each 2^-100 below its upstream neighbour: sharp logits -- kept, after the one level,
-    // exponents 2^100 apart two lanes down (each lane had been lifted against its neighbour's exponent BEFORE that neighbour's own
-    // lift), and when the bulk crossed two lanes within a period the inflow arrived scaled by 2^100: mantissas of 2^60 .. 2^127,
-    // inf at the meeting point (D1).  19 of 256 N(0, 3^2) utterances at the north-star shape were in that state at the meeting
-    // point and 4 overflowed (tests/tools/linear_model.py); with every level applied dk <= GAP holds for every lane.
-    {
-#pragma unroll
-      for (int lv = 1; lv < LV; ++lv) {
-        const int nb = (DIR == 0) ? from_prev_lane_i(kn, ex) : from_next_lane_i(kn, ex);
-        kn = imax(kn, nb - GAP);
-      }
-    }
-    kn = imax(kn, DEAD);
-    const int d = k - kn;
-    // D3: own live values crushed by a much larger inflow scale; D4: decayed by more than 2^-DECAY_MAX, or live -> zero
-    // (D3 only for a lane that has had mass for a few periods: at the lattice front the first thin paths of a lane are
-    // legitimately swamped when the bulk arrives, ~1 in 256 benign utterances)
-    age = (live && alive) ? age + 1 : 0;
-    flag |= (live && age >= 3 && d < -DOWN_MAX ? D3_DOWN : 0) | (live && fe < -DECAY_MAX ? D4_DECAY : 0) | (!live && alive ? D4_DIED : 0);
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      c[j] = ldexp_f(c[j], d);
-      if constexpr (KIND == 0) o[j] = ldexp_f(o[j], d);
-    }
-    k = kn;
-    cx = ldexp_f(cx, kx - ex);
-    kx = ex;
-    dk = ((DIR == 0) ? from_prev_lane_i(k, kx) : from_next_lane_i(k, kx)) - k;
-    set_scale();
-    alive = live;
-  }
-  bool boundary = false;
-  // dk as the factor the packed step multiplies by (after every change of dk)
-  __device__ __forceinline__ void set_scale() {
-    if constexpr (PACKED) {
-      sc = (dk < -126) ? 0.f : ldexp_f(1.f, imin(dk, 127));
-      scb = boundary ? sc : 0.f;
-    }
-  }
-  bool alive = false;  // the lane had mass at its last renormalisation
-  int age = 0;         // consecutive renormalisations with mass
-  bool relevant = true;
-  // number of label positions 1 .. ll-1 that repeat their predecessor (classic: each costs one more frame); wave-uniform
-  __device__ __forceinline__ int repeats(int ll, int lane) const {
-    int n = 0;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(!norep[j] && lane * NL + j < ll));
-    return n;
-  }
   // OR of the lanes' flags (wave-uniform)
   __device__ __forceinline__ int flag_or() const {
-    int f = 0;
-#pragma unroll
-    for (int bit = D3_DOWN; bit <= D4_DIED; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
+    int f = Core::flag_or();
     f |= (__builtin_amdgcn_ballot_w64((flag & D9_RETIRED) != 0) != 0) ? D9_RETIRED : 0;  // (never set; the compiler cannot always tell)
     return f;
   }
@@ -450,12 +313,7 @@ __device__ __forceinline__ void restore(Chain<KIND, NL, DIR> &S, const CkRow<KIN
 #pragma unroll
   for (int j = 0; j < NL; ++j) { S.c[j] = r.c[j]; S.o[j] = r.o[j]; }
   S.cx = r.cx; S.k = r.k; S.kx = r.kx;
-  S.dk = ((DIR == 0) ? from_prev_lane_i(S.k, S.kx) : from_next_lane_i(S.k, S.kx)) - S.k;
-  S.set_scale();
-  float m = 0.f;
-#pragma unroll
-  for (int j = 0; j < NL; ++j) m = fmaxf(m, fmaxf(r.c[j], r.o[j]));
-  S.alive = m > 0.f;  // (a lane that only adopted its neighbour's exponent has no mass yet)
+  S.restored();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -973,12 +831,6 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
         const float(*E)[LD::ES] = lds.E[DIR][j % 3];
         float(*RR)[LD::RS] = lds.R[DIR][j % 3];
         const int(*KG)[64] = lds.kg[DIR][j % 3];
-        // exponent group of the R row at position d: rows are written BEFORE the recompute chain renormalises, s steps
-        // after its checkpoint -> group max(s-1, 0) / RN.  s = nv-1-d (A, simplified B) / nv-d (classic B).
-        auto grp = [&](int d) -> int {
-          const int s = (KIND == 0 && DIR == 1) ? nv - d : nv - 1 - d;
-          return (s > 0 ? s - 1 : 0) / RN;
-        };
         // The R row holds the other direction's state in ITS slot order and lane exponents (group q); this chain needs it
         // one label position over, so one value per lane comes from the neighbour lane and carries that lane's exponent:
         // products with it ("shifted" parts) are scaled here, with their own scale KS; the others ("aligned") stay raw and
@@ -988,6 +840,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
         //   NL = 2 : [token parts[2], aligned blank part, shifted blank part]
         //   NL = 1 : [token part, shifted blank part]
         // the carrier lane's shifted blank part also holds the posterior of the boundary state (scaled with its own K0).
+        auto grp = [&](int d) -> int { return r_group<KIND, DIR, RN>(d, nv); };  // (a lambda: see LabelTok, ctc_linear_chain.h)
         float(*KLr)[64] = lds.kl[DIR][j % 3];
         int q = -1, kR = DEAD, ks = DEAD, seg = -1;
         float KL = 0.f, KS = 0.f, K0 = 0.f;
@@ -1152,10 +1005,8 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
               constexpr int d = decltype(Dc)::value;
               if constexpr (d >= BLK) return BLK;
               else {
-                constexpr int sA = (KIND == 0 && DIR == 1) ? BLK - d : BLK - 1 - d;
-                constexpr int qd = (sA > 0 ? sA - 1 : 0) / RN;
-                constexpr int sP = (KIND == 0 && DIR == 1) ? BLK - (d - 1) : BLK - 1 - (d - 1);
-                constexpr int qp = (d == 0) ? -1 : (sP > 0 ? sP - 1 : 0) / RN;
+                constexpr int qd = r_group<KIND, DIR, RN>(d, BLK);
+                constexpr int qp = (d == 0) ? -1 : r_group<KIND, DIR, RN>(d - 1, BLK);
                 constexpr bool renp = d > 0 && (d + ren_shift<KIND, DIR>()) % RN == 0;  // this chain renormalised after frame d - 1
                 if constexpr (d + PR < BLK) read_R<KIND, NL, LD>(RR[d + PR], lane, rb[d + PR]);
                 if constexpr (qd != qp || renp) {  // a segment opens here
@@ -1185,8 +1036,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
           static_for<0, BLK>([&](auto D) {
             constexpr int d = decltype(D)::value;
             if constexpr (d + PR < BLK) read_R<KIND, NL, LD>(RR[d + PR], lane, rb[d + PR]);
-            constexpr int s = (KIND == 0 && DIR == 1) ? BLK - d : BLK - 1 - d;
-            constexpr int qd = (s > 0 ? s - 1 : 0) / RN;
+            constexpr int qd = r_group<KIND, DIR, RN>(d, BLK);
             one(std::false_type{}, d, qd, (d + 1 + ren_shift<KIND, DIR>()) % RN == 0, eb[d], rb[d], kq[qd]);
           });
         } else {

@@ -1,6 +1,8 @@
 // Building blocks shared by the fused loss+gradient kernels (ctc_fused5.hip / ctc_fused5_roles.h: log-domain chains + recompute
 // chains + helpers; ctc_fused6.hip: the same roles in the linear domain) and by the Hessian kernels (ctc_hessian.hip: the sweeps;
 // ctc_hvp.hip / ctc_hvp_device.h and ctc_hvp_fused.hip: the Hessian-vector products).  See those files for the algorithms.
+// (ctc_lane_ops.h: lane and LDS primitives of the fused tiers; ctc_linear_flags.h and ctc_linear_chain.h: the number format, the
+// chain state and the renormalisation policy of the two linear-domain kernels.)
 #pragma once
 #include <type_traits>
 

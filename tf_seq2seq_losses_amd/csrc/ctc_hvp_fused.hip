@@ -29,6 +29,7 @@
 #include "ctc_swap_reduce.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_linear_flags.h"
+#include "ctc_linear_chain.h"  // ChainCore (state, start, renormalisation policy), Cad, r_group: shared with ctc_fused6.hip
 #include "ctc_launch.h"
 #include "ctc_v1_device.h"   // emit_row, scan_body: the log-domain building blocks, run in this launch for flagged utterances
 #include "ctc_hvp_device.h"  // temit_row, tscan_body, hvp_out_row
@@ -42,16 +43,17 @@ namespace hvpf {
 
 using namespace ctc::fused;
 
-constexpr int BLK = HVPF_BLK, NH = 3, RN = 3, NG = BLK / RN, NW = 4 + 2 * NH;  // 10 wavefronts: 4 chains + 3 helpers a side
+constexpr int BLK = HVPF_BLK, NH = 3, NW = 4 + 2 * NH;  // 10 wavefronts: 4 chains + 3 helpers a side
 constexpr int V = 256;
 using namespace ctc::linear;  // the number format's constants and the flag bits (ctc_linear_flags.h: one copy for this kernel and ctc_fused6.hip)
-// (the lane helpers, f2v and the one-instruction inflow fmac_from_upstream, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h)
+// (the lane helpers, f2v and the one-instruction inflow fmac_from_upstream, ld_slots / st_slots / ld_pairs / st_pairs: ctc_lane_ops.h;
+// the cadence Cad<BLK, NL>, r_group and the chain's state and renormalisation: ctc_linear_chain.h)
 
-template <int NL> struct Cfg {
+template <int NL> struct Cfg : Cad<BLK, NL> {  // RN, NG, LV: the cadence of the 6-frame blocks
+  static_assert(Cad<BLK, NL>::RN == 3, "6-frame blocks renormalise every three frames; the kernel has been run with no other period");
   static constexpr int UP = 64 * NL;
   static constexpr int ES = 2 * UP + 4;   // E row: y[UP], bl at [UP], w[UP] at [UP + 4]
   static constexpr int RS = 4 * UP + 8;   // R row / checkpoint row: per lane (c, o) pairs then (dc, do) pairs; tail (cx, kx, dcx, -)
-  static constexpr int LV = (RN + NL - 1) / NL;
 };
 
 template <int KIND, int NL>
@@ -59,7 +61,7 @@ struct Lds {
   using C = Cfg<NL>;
   float E[2][3][BLK][C::ES];
   float R[2][3][BLK][C::RS];
-  int kg[2][3][NG][64];
+  int kg[2][3][C::NG][64];
   float kl[2][3][BLK][64];
   float xcopy[2 * NH + 2][V + 4];  // gather copies: helpers, then the two recompute wavefronts (E stage of phase 1)
   float vcopy[2 * NH + 2][V + 4];
@@ -117,62 +119,27 @@ __device__ __forceinline__ void read_R(const float *row, int lane, RRow<NL> &r) 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Lattice state of one direction with tangents (slot / state conventions of ctc_fused6.hip Chain<>).
+// Lattice state of one direction with tangents: ChainCore (ctc_linear_chain.h: slots, exponents, start, renormalisation -- all
+// decided by the values) plus a tangent beside every mantissa, which shares its value's exponent.
 // ------------------------------------------------------------------------------------------------
-template <int KIND, int NL, int DIR>
-struct Chain {
+template <int NL>
+struct TangentMantissas {
   float c[NL], o[NL], dc[NL], dob[NL], cx, dcx;
-  int k, kx, dk;
-  bool norep[NL], norep_next[NL];
-  int flag;
-  static constexpr bool PACKED = KIND == 0 && NL == 2;
-  float nrf[NL];  // PACKED: 1.0 where the repeat rule lets the diagonal pass (norep_next for A, norep for B)
-  float sc = 1.f, scb = 0.f;  // PACKED: 2^dk as a float (0 below 2^-126), and the same on the boundary lane only
-  bool boundary = false;
-  __device__ __forceinline__ void set_scale() {
-    if constexpr (PACKED) {
-      sc = (dk < -126) ? 0.f : ldexp_f(1.f, dk < 127 ? dk : 127);
-      scb = boundary ? sc : 0.f;
-    }
-  }
-  bool alive = false;
-  int age = 0;
-  bool relevant = true;
+};
+template <int KIND, int NL, int DIR>
+struct Chain : ChainCore<KIND, NL, DIR, TangentMantissas<NL>> {
+  using Core = ChainCore<KIND, NL, DIR, TangentMantissas<NL>>;
+  using Core::PACKED;
+  using Core::c; using Core::o; using Core::cx; using Core::dk; using Core::norep; using Core::norep_next; using Core::nrf;
+  using Core::sc; using Core::scb; using Core::dc; using Core::dob; using Core::dcx;
 
   __device__ __forceinline__ void init_labels(const Problem &p, int b, int lane, int ll) {
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
-    auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
+    Core::init_labels(p, b, lane, ll);
 #pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const int i = lane * NL + j;
-      const int tk = tok(i);
-      norep[j] = (i == 0) || tk != tok(i - 1);
-      norep_next[j] = tok(i + 1) != tk;
-      nrf[j] = ((DIR == 0) ? norep_next[j] : norep[j]) ? 1.f : 0.f;
-      c[j] = 0.f; o[j] = 0.f; dc[j] = 0.f; dob[j] = 0.f;
-    }
-    cx = 0.f; dcx = 0.f; k = DEAD; kx = DEAD; dk = 0; flag = 0;
-    boundary = lane == (DIR == 0 ? 0 : 63);
-    set_scale();
-    relevant = lane * NL <= ll;
+    for (int j = 0; j < NL; ++j) { dc[j] = 0.f; dob[j] = 0.f; }
+    dcx = 0.f;
   }
-
-  __device__ __forceinline__ void start(int lane, int ll) {
-    constexpr int UP = Cfg<NL>::UP;
-    if constexpr (DIR == 0) {
-      cx = 1.f; kx = 0;
-    } else {
-      if (ll == UP) { cx = 1.f; kx = 0; }
-#pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const int i = lane * NL + j;
-        if (i == ll) { c[j] = 1.f; k = 0; }
-        if (KIND == 0 && i == ll - 1) { o[j] = 1.f; k = 0; }
-      }
-    }
-    renorm();
-    flag = 0;
-  }
+  __device__ __forceinline__ void start(int lane, int ll) { Core::template start<Cfg<NL>::LV>(lane, ll, Cfg<NL>::UP); }
 
   // one lattice step, values and tangents (blank gauge: d bl = 0, d y = y w)
   __device__ __forceinline__ void step(const Emis<NL> &e) {
@@ -277,54 +244,15 @@ struct Chain {
     }
   }
 
-  // per-lane renormalisation, decided by the VALUES; the tangents follow with the same shift
+  // per-lane renormalisation, decided by the VALUES; the tangents follow with the same shifts
   __device__ __forceinline__ void renorm() {
-    constexpr int LV = Cfg<NL>::LV;
-    float m = c[0];
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      if constexpr (KIND == 0) m = (j == 0) ? vmax_raw(m, o[0]) : vmax3_raw(m, c[j], o[j]);
-      else if (j > 0) m = vmax_raw(m, c[j]);
-    }
-    const bool live = m > 0.f;
-    const int fe = frexp_e(m);
-    const int e_own = live ? fe + k : DEAD;
-    const bool xlive = cx > 0.f;
-    const int ex = xlive ? frexp_e(cx) + kx : DEAD;
-    int kn = e_own;
-    {
-      const int nb = (DIR == 0) ? from_prev_lane_i(kn, ex) : from_next_lane_i(kn, ex);
-      kn = imax(kn, nb - (LV == 1 ? GAP_WIDE : GAP));
-    }
-    {  // every level for every lane, with or without mass (r04, as ctc_fused6.hip: a steep profile of live lanes kept exponents 2^100
-       // apart two lanes down after the one level, and the inflow overflowed when the bulk crossed two lanes within a period)
-#pragma unroll
-      for (int lv = 1; lv < LV; ++lv) {
-        const int nb = (DIR == 0) ? from_prev_lane_i(kn, ex) : from_next_lane_i(kn, ex);
-        kn = imax(kn, nb - GAP);
+    Core::template renorm<Cfg<NL>::LV>([&](int j, int d) {
+      if (j == Core::SLOT_CX) dcx = ldexp_f(dcx, d);
+      else {
+        dc[j] = ldexp_f(dc[j], d);
+        if constexpr (KIND == 0) dob[j] = ldexp_f(dob[j], d);
       }
-    }
-    kn = imax(kn, DEAD);
-    const int d = k - kn;
-    age = (live && alive) ? age + 1 : 0;
-    flag |= (live && age >= 3 && d < -DOWN_MAX ? D3_DOWN : 0) | (live && fe < -DECAY_MAX ? D4_DECAY : 0) | (!live && alive ? D4_DIED : 0);
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      c[j] = ldexp_f(c[j], d); dc[j] = ldexp_f(dc[j], d);
-      if constexpr (KIND == 0) { o[j] = ldexp_f(o[j], d); dob[j] = ldexp_f(dob[j], d); }
-    }
-    k = kn;
-    cx = ldexp_f(cx, kx - ex); dcx = ldexp_f(dcx, kx - ex);
-    kx = ex;
-    dk = ((DIR == 0) ? from_prev_lane_i(k, kx) : from_next_lane_i(k, kx)) - k;
-    set_scale();
-    alive = live;
-  }
-  __device__ __forceinline__ int flag_or() const {
-    int f = 0;
-#pragma unroll
-    for (int bit = D3_DOWN; bit <= D4_DIED; bit <<= 1) f |= (__builtin_amdgcn_ballot_w64((flag & bit) != 0) != 0) ? bit : 0;
-    return f;
+    });
   }
 };
 
@@ -355,16 +283,12 @@ __device__ __forceinline__ void load_ck(CkRow<NL> &ck, const float *__restrict__
 }
 template <int KIND, int NL, int DIR>
 __device__ __forceinline__ void restore(Chain<KIND, NL, DIR> &S, const CkRow<NL> &ck) {
-  float m = 0.f;
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     S.c[j] = ck.r.c[j]; S.o[j] = (KIND == 0) ? ck.r.o[j] : 0.f; S.dc[j] = ck.r.dc[j]; S.dob[j] = (KIND == 0) ? ck.r.dob[j] : 0.f;
-    m = fmaxf(m, fmaxf(S.c[j], S.o[j]));
   }
   S.cx = ck.r.cx; S.dcx = ck.r.dcx; S.k = ck.k; S.kx = ck.r.kx;
-  S.dk = ((DIR == 0) ? from_prev_lane_i(S.k, S.kx) : from_next_lane_i(S.k, S.kx)) - S.k;
-  S.set_scale();
-  S.alive = m > 0.f;
+  S.restored();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -568,7 +492,7 @@ template <int KIND, int NL, int DIR>
 __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ rows_ws, int *__restrict__ kexp_ws, int nslot,
                                          float *__restrict__ loss, int *__restrict__ flag_ws, Lds<KIND, NL> &lds, const Geo &geo, int b) {
   using C = Cfg<NL>;
-  constexpr int UP = C::UP, RS = C::RS;
+  constexpr int UP = C::UP, RS = C::RS, RN = C::RN, NG = C::NG;
   Chain<KIND, NL, DIR> S;
   const int lane = threadIdx.x & 63;
   int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
@@ -689,10 +613,7 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
         float(*RR)[RS] = lds.R[DIR][j % 3];
         const int(*KG)[64] = lds.kg[DIR][j % 3];
         float(*KLr)[64] = lds.kl[DIR][j % 3];
-        auto grp = [&](int d) -> int {
-          const int s = (KIND == 0 && DIR == 1) ? nv - d : nv - 1 - d;
-          return (s > 0 ? s - 1 : 0) / RN;
-        };
+        auto grp = [&](int d) -> int { return r_group<KIND, DIR, RN>(d, nv); };
         int q = -1, kR = DEAD, ks = DEAD, k0r = DEAD;
         float KL = 0.f, KS = 0.f, K0 = 0.f;
         auto setK = [&]() __attribute__((always_inline)) {
@@ -791,8 +712,7 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
           static_for<0, BLK>([&](auto D) {
             constexpr int d = decltype(D)::value;
             if constexpr (d + PR < BLK) read_R<NL>(RR[d + PR], lane, rb[d + PR]);
-            constexpr int sst = (KIND == 0 && DIR == 1) ? BLK - d : BLK - 1 - d;
-            constexpr int qd = (sst > 0 ? sst - 1 : 0) / RN;
+            constexpr int qd = r_group<KIND, DIR, RN>(d, BLK);
             one(d, qd, (d + 1) % RN == 0, eb[d], rb[d], kq[qd]);
           });
         } else {
@@ -822,7 +742,7 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const float *__r
                                               float4 *__restrict__ stats_ws, const float *vec, Lds<KIND, NL> &lds, const Geo &geo, int b) {
   constexpr int RDIR = 1 - SIDE;
   using C = Cfg<NL>;
-  constexpr int RS = C::RS;
+  constexpr int RS = C::RS, RN = C::RN;
   const int lane = threadIdx.x & 63;
   int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
   if (ll > p.U || ll > C::UP) ll = 0;
