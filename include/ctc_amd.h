@@ -355,6 +355,40 @@ int ctc_amd_best_path(int kind, int wrt,
                       float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Greedy decoding (added under ABI v6: two new entry points, nothing existing changed): which label sequence the model emits.
+ * The frame-wise argmax path -- the unconstrained optimum of sum_t lp[b, t, pi_t], lp = log_softmax(logits)
+ * (CTC_AMD_WRT_LOGPROBS: the input as it stands) -- and the label sequence it stands for under the collapse of `kind`.
+ * The reference has no counterpart.  No labels are passed in.  T_b = logit_length[b] clamped to [0, T].
+ *   tokens[B][T]          int32:   tokens[b, t] = the LOWEST k with x[b, t, k] = max_k x[b, t, k] (values compared as the float32
+ *                                  the element type converts to; ties go to the lowest token index: specified, unlike the tie
+ *                                  rule of ctc_amd_best_path); -1 for t >= T_b
+ *   score[B]              float32: sum_{t < T_b} lp[b, t, tokens[b, t]], accumulated in float64; 0 for T_b == 0.  A frame whose
+ *                                  maximum is -inf makes it -inf (tokens is still the lowest index, the call completes normally).
+ *   decoded[B][T]         int32:   tokens[b, :T_b] collapsed -- CTC_AMD_CLASSIC: equal neighbours merged, then blanks dropped;
+ *                                  CTC_AMD_SIMPLIFIED: blanks dropped only (every non-blank frame is a label); -1 beyond
+ *                                  decoded_length[b].  There is no U: a decoding has at most T_b labels, hence the width T.
+ *   decoded_length[B]     int32
+ *   frames[B][T]          int32:   first frame of each decoded label, -1 padding.  May be NULL.
+ *   label_score[B][T]     float32: sum of lp over the run of each decoded label, in time order in float64 -- classic: the unbroken
+ *                                  repeat of that token starting at frames[b, i]; simplified: that one frame -- -inf padding.
+ *                                  Blank frames count towards `score` only.  May be NULL.
+ * decoded / decoded_length can be handed to ctc_amd_loss_grad* and ctc_amd_best_path as labels / label_length
+ * (label_stride = T) while decoded_length <= CTC_AMD_MAX_U.  Results for NaN inputs are unspecified (the call completes).
+ * 0 <= blank_index < V; no vocabulary limit (no row is staged in LDS).  Logits in the producer formats of ctc_amd_loss_grad_ex
+ * (element type, element strides >= V, token axis contiguous): 16-byte (float32) / 8-byte (16-bit types) row accesses when V,
+ * the strides and the base pointer allow them, element-wise accesses with identical results otherwise.
+ * Workspace: ctc_amd_greedy_decode_workspace_bytes (the float32 lp[B][T], rounded up to 256 bytes).  Two launches (frame-parallel
+ * row statistics, then one wavefront per utterance for the collapse), asynchronous on `stream`, capturable.
+ */
+int ctc_amd_greedy_decode_workspace_bytes(int B, int T, size_t *out_bytes /*host*/);
+int ctc_amd_greedy_decode(int kind, int wrt,
+                          const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                          const int32_t *logit_length, int blank_index, int B, int T, int V,
+                          float *score, int32_t *tokens, int32_t *decoded, int32_t *decoded_length,
+                          int32_t *frames /* may be NULL */, float *label_score /* may be NULL */,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,11 @@ SIGNATURES = {
     "ctc_amd_hvp": (_c_int, _COMMON + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),
     "ctc_amd_best_path": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # score, tokens, label_index, ws, bytes, stream
+    "ctc_amd_greedy_decode_workspace_bytes": (_c_int, [_c_int, _c_int, ctypes.POINTER(_c_size_t)]),
+    "ctc_amd_greedy_decode": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, _c_int64, _c_int64,      # kind, wrt, logits, dtype, stride_b, stride_t
+                                       _c_void_p, _c_int, _c_int, _c_int, _c_int,                  # logit_length, blank_index, B, T, V
+                                       _c_void_p, _c_void_p, _c_void_p, _c_void_p,                 # score, tokens, decoded, decoded_length
+                                       _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),    # frames, label_score, ws, bytes, stream
 }
 
 _lib = None
@@ -137,4 +142,10 @@ def workspace_bytes(what: int, kind: int, B: int, T: int, V: int, U: int) -> int
 def best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_best_path_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def greedy_decode_workspace_bytes(B: int, T: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_greedy_decode_workspace_bytes(B, T, ctypes.byref(out)), "ctc_amd_greedy_decode_workspace_bytes")
     return int(out.value)

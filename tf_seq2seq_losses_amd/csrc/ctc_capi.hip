@@ -570,4 +570,35 @@ int ctc_amd_best_path(int kind, int wrt, const void *logits, int logits_dtype, i
   return CTC_AMD_OK;
 }
 
+int ctc_amd_greedy_decode_workspace_bytes(int B, int T, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (B < 0 || T < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d", B, T);
+  *out_bytes = ctc::decode_workspace_bytes(B, T);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_best_path: common arguments (it takes no labels: an empty label tensor stands in for them),
+// element type, B == 0, strides; then the outputs and the workspace.  No vocabulary limit: no row is staged in LDS.
+int ctc_amd_greedy_decode(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                          const int32_t *logit_length, int blank_index, int B, int T, int V, float *score, int32_t *tokens,
+                          int32_t *decoded, int32_t *decoded_length, int32_t *frames, float *label_score, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  // (label_length: only its null check applies, and logit_length answers it)
+  const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!score || !decoded_length || (T > 0 && (!tokens || !decoded)))
+    return fail(CTC_AMD_EINVAL, "null score / tokens / decoded / decoded_length pointer");
+  if (((long long)B * T + 15) / 16 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const size_t need = ctc::decode_workspace_bytes(B, T);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_decode(p, static_cast<char *>(workspace), score, tokens, decoded, decoded_length, frames, label_score,
+                          static_cast<hipStream_t>(stream)), "greedy decode launch");
+  return CTC_AMD_OK;
+}
+
 }  // extern "C"

@@ -41,6 +41,11 @@ hipError_t run_hvp_fused_simplified(const Problem &p, const Layout &L, char *ws,
 size_t align_workspace_bytes(int B, int T, int U);
 hipError_t run_align(const Problem &p, char *ws, float *score, int *tokens, int *label_index, hipStream_t st);
 
+// ctc_decode.hip: greedy decoding; the workspace holds the float32 log-probability of every frame's token ([B][T])
+size_t decode_workspace_bytes(int B, int T);
+hipError_t run_decode(const Problem &p, char *ws, float *score, int *tokens, int *decoded, int *decoded_length, int *frames,
+                      float *label_score, hipStream_t st);
+
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
 extern int g_wide_diag;  // timing diagnostics (results are then meaningless)

@@ -260,6 +260,55 @@ def ctc_alignment_from_logproba(labels, logprobas, label_length, logit_length, b
 
 
 # --------------------------------------------------------------------------------------------------
+# greedy decoding: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcDecoding(NamedTuple):
+    """score [batch] float32: log-probability of the frame-wise argmax path (the best of ALL paths);
+    tokens [batch, max_length] int32: the token of every frame on it, ties to the lowest index (-1 beyond logit_length);
+    labels [batch, max_length] int32: the path collapsed as the lattice reads it (-1 beyond label_length);
+    label_length [batch] int32;
+    frames [batch, max_length] int32: the first frame of every decoded label (-1 padding);
+    label_score [batch, max_length] float32: the log-probability of every decoded label's frames -- classic: the unbroken repeat
+    that starts at its first frame; simplified: that one frame (-inf padding).
+    labels and label_length can be passed straight to the loss and alignment functions of the same lattice."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    labels: torch.Tensor
+    label_length: torch.Tensor
+    frames: torch.Tensor
+    label_score: torch.Tensor
+
+
+def _decode(kind_name: str, wrt: int, x, logit_length, blank_index) -> CtcDecoding:
+    x = _as_tensor(x)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    assert x.dim() == 3
+    assert x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    assert logit_length.dim() == 1
+    assert x.shape[0] == logit_length.shape[0]
+    with torch.no_grad():  # a decoding is not differentiable: the result is detached
+        return CtcDecoding(*ops.greedy_decode(ops.KINDS[kind_name], wrt, x.detach(), logit_length, _blank(blank_index)))
+
+
+def classic_ctc_greedy_decode(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0) -> CtcDecoding:
+    """Greedy decoding on the classic lattice: the most probable token of every frame, repeats merged, then blanks dropped.
+    logits [batch, max_length, num_tokens] float32 / bfloat16 / float16 (any batch / time strides), logit_length [batch];
+    returns CtcDecoding(score, tokens, labels, label_length, frames, label_score), not differentiable."""
+    return _decode("classic", _lib.WRT_LOGITS, logits, logit_length, blank_index)
+
+
+def simplified_ctc_greedy_decode(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0) -> CtcDecoding:
+    """Greedy decoding on the simplified lattice (blanks are dropped, repeats are not merged: every non-blank frame is a label).
+    Same arguments and return value as classic_ctc_greedy_decode."""
+    return _decode("simplified", _lib.WRT_LOGITS, logits, logit_length, blank_index)
+
+
+def ctc_greedy_decode_from_logproba(logprobas, logit_length, blank_index, ctc_loss_data_cls) -> CtcDecoding:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+    return _decode(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, logprobas, logit_length, blank_index)
+
+
+# --------------------------------------------------------------------------------------------------
 # loss-data objects (what the reference's unit tests poke at directly)
 # --------------------------------------------------------------------------------------------------
 class BaseCtcLossData:

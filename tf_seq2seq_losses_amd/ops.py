@@ -426,6 +426,42 @@ def best_path(kind: int, wrt: int, p: Prepared) -> Tuple[torch.Tensor, torch.Ten
     return score, tokens, label_index
 
 
+def greedy_decode(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor, blank: int):
+    """(score[B] float32, tokens[B,T] int32, labels[B,T] int32, label_length[B] int32, frames[B,T] int32, label_score[B,T] float32):
+    the frame-wise argmax path and the labels it collapses to (ctc_amd_greedy_decode).  Takes the logits as they stand -- float32 /
+    bfloat16 / float16, any batch and time strides with a contiguous token axis, read in place; anything else is copied to
+    contiguous float32 once -- passes no labels and does not synchronise."""
+    _require_gpu(x)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if not (x.dtype in _DTYPES and (x.numel() == 0 or (x.stride(2) == 1 and x.stride(0) >= V and x.stride(1) >= V))):
+        x = x.to(torch.float32).contiguous()
+    if x.numel() == 0:
+        x = torch.empty((B, T, V), dtype=x.dtype if x.dtype in _DTYPES else torch.float32, device=dev)
+    if not (logit_length.dtype == torch.int32 and logit_length.device == dev and logit_length.is_contiguous()):
+        logit_length = logit_length.to(device=dev, dtype=torch.int32).contiguous()
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    labels = torch.empty((B, T), dtype=torch.int32, device=dev)
+    label_length = torch.empty(B, dtype=torch.int32, device=dev)
+    frames = torch.empty((B, T), dtype=torch.int32, device=dev)
+    label_score = torch.empty((B, T), dtype=torch.float32, device=dev)
+    if B == 0:
+        return score, tokens, labels, label_length, frames, label_score
+    key = ("greedy_decode", B, T)
+    n = _WS_BYTES.get(key)
+    if n is None:
+        n = _WS_BYTES[key] = _lib.greedy_decode_workspace_bytes(B, T)
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_greedy_decode(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(logit_length), int(blank),
+                                       B, T, V, _ptr(score), _ptr(tokens), _ptr(labels), _ptr(label_length), _ptr(frames),
+                                       _ptr(label_score), ws.data_ptr(), ws.numel(), _stream(dev))
+    _lib.check(rc, "ctc_amd_greedy_decode")
+    return score, tokens, labels, label_length, frames, label_score
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
