@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void wide_kernel(Problem p, Layout L, float *_
     float *oring = ering + Rings<NL>::ER * ERS_C;
     if (threadIdx.x < 8) lds_words[threadIdx.x] = 0u;
     __syncthreads();
-    const int len = v1_clampi(p.logit_length[b], 0, p.T);
+    const int len = frame_count(p, b);
     const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
     const bool skip = ll > p.U;  // contract violation: reported as an infeasible sample, no row is written (the gradient stage writes zeros)
     float *rows = (dir == 0 ? alpha : beta) + (long)b * (p.T + 1) * L.SRS;
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void wide_kernel(Problem p, Layout L, float *_
     int j, b;
     task_of(rid >> 2, p.B, j, b);
     if (j >= NQ) continue;
-    const int len = v1_clampi(p.logit_length[b], 0, p.T);
+    const int len = frame_count(p, b);
     const int nq = (len + 3) / 4;
     if (id < NR) {
       if (j >= nq) continue;

@@ -22,6 +22,9 @@
  *   - `U` is a static upper bound on label_length (the reference uses the dynamic max(label_length),
  *     base_loss.py:482-486; any U >= max(label_length) gives identical loss/gradient/Hessian because
  *     the extra lattice states stay at log 0).  A sample with label_length[b] > U gets loss = +inf.
+ *   - What the kernels make of out-of-range lengths and labels (logit_length outside [0, T], negative label_length,
+ *     label_length > U, label positions beyond label_stride, labels outside [0, V) or equal to the blank) is ONE contract for
+ *     every entry point: DESIGN.md section 5.8; its code is csrc/ctc_common.h behind struct Problem.
  *   - Return value: 0 on success, negative CTC_AMD_E* code otherwise; ctc_amd_last_error() has text.
  *     Not errors (reference semantics, classic_ctc_loss.py:50-52, base_loss.py:240-245,283-288):
  *     infeasible alignment => loss = +inf, gradient = 0, Hessian = 0; B == 0; T == 0.
@@ -123,7 +126,8 @@ int ctc_amd_reduce_loss(const float *loss, int B, float *out2, void *stream);
 /*
  * Opt-in validation of the labels (the ONLY entry point that synchronises the stream and allocates -- a few bytes from the
  * stream-ordered pool; keep it off the hot path).  Returns CTC_AMD_ELABEL if any label inside label_length (and inside
- * U / label_stride) lies outside [0, V) or equals blank_index.  Without this check such a label is not an error in the
+ * label_stride) lies outside [0, V) or equals blank_index; a row with label_length > U is infeasible as a whole (DESIGN.md
+ * section 5.8) and none of its labels is looked at.  Without this check such a label is not an error in the
  * compute entry points: it is an impossible emission, the sample comes out infeasible (loss +inf, zero gradient).
  * Replaces: the InvalidArgumentError of tf.gather on TF-CPU for out-of-range labels (base_loss.py:328-344).
  */
@@ -337,8 +341,8 @@ int ctc_amd_hvp(int kind, int wrt,
  *   tokens[B][T]        int32:   pi_t; -1 for t >= T_b
  *   label_index[B][T]   int32:   index into labels[b] of the label the frame emits (classic: or continues by repeating it),
  *                                -1 on blank frames and for t >= T_b.  May be NULL.
- * An infeasible utterance (too few frames, label_length > U, a label equal to the blank or outside [0, V), no path of finite
- * value) gets score = -inf and -1 in every frame.  label_length == 0: the all-blank path.  T_b == 0: score 0 for an empty
+ * An infeasible utterance (too few frames, no path of finite value, or infeasible by the input contract, DESIGN.md
+ * section 5.8) gets score = -inf and -1 in every frame.  label_length == 0: the all-blank path.  T_b == 0: score 0 for an empty
  * label, -inf otherwise.  Among paths of equal value the choice is deterministic (the same bits every run) but unspecified.
  * The recursion runs on the raw logits in float64, so the path is the exact optimum of the float32 inputs; the error of
  * `score` is that of the float32 row log-sum-exps (none for CTC_AMD_WRT_LOGPROBS) plus its own rounding.

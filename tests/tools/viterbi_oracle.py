@@ -100,8 +100,9 @@ def best_path_one(kind, label, x, blank=0, wrt=0):
 
 
 def best_path(kind, labels, x, ll, tl, blank=0, wrt=0):
-    """Batch: labels[B, U], x[B, T, V], ll[B], tl[B].  Returns (score[B] float64, [path or None] * B); an utterance with
-    label_length > U is infeasible, logit_length is clamped to [0, T], as the loss does."""
+    """Batch: labels[B, U], x[B, T, V], ll[B], tl[B].  Returns (score[B] float64, [path or None] * B).  Lengths and labels are
+    read by the input contract of DESIGN.md section 5.8, with U = the width of `labels`: logit_length clamped to [0, T], a negative
+    label_length as 0, label_length > U infeasible, a label outside [0, V) or equal to the blank infeasible (best_path_one)."""
     labels, x = np.asarray(labels), np.asarray(x)
     B, T = x.shape[0], x.shape[1]
     scores, paths = np.full(B, -np.inf), []

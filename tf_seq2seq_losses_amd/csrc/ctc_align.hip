@@ -44,16 +44,12 @@ constexpr int bp_word_bytes(int NL) { return NL <= 2 ? 1 : NL / 2; }
 // frames per back-trace block: two blocks of (frames x 64 lanes x word) fit the LDS the ring used (32 KB)
 constexpr int trace_frames(int NL) { return NL == 16 ? 32 : 64; }
 
-// elements k .. k+3 / element k of a row of element type dt (0 = float32, 1 = bfloat16, 2 = float16) as float32
+// elements k .. k+3 of a row of element type dt (0 = float32, 1 = bfloat16, 2 = float16) as float32 (row_load1: ctc_common.h)
 __device__ __forceinline__ float4 row_load4(const char *row, int k, int dt) {
   if (dt == 0) return *reinterpret_cast<const float4 *>(row + (size_t)k * 4);
   const uint2 u = *reinterpret_cast<const uint2 *>(row + (size_t)k * 2);
   return make_float4(h16_to_f32((unsigned short)(u.x & 0xffffu), dt), h16_to_f32((unsigned short)(u.x >> 16), dt),
                      h16_to_f32((unsigned short)(u.y & 0xffffu), dt), h16_to_f32((unsigned short)(u.y >> 16), dt));
-}
-__device__ __forceinline__ float row_load1(const char *row, int k, int dt) {
-  if (dt == 0) return reinterpret_cast<const float *>(row)[k];
-  return h16_to_f32(reinterpret_cast<const unsigned short *>(row)[k], dt);
 }
 
 // running (max, sum of exp(x - max)) of one lane: one more element
@@ -95,17 +91,15 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_kernel(const Problem p, c
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int T = p.T, V = p.V, blank = p.blank, dt = p.xdtype;
-  int Tb = p.logit_length[b];
-  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
-  int L = p.label_length[b];
-  L = L < 0 ? 0 : L;
-  const bool too_long = L > p.U;
+  const int Tb = frame_count(p, b);
+  int L = label_count(p, b);
+  const bool too_long = too_many_labels(p, L);
   if (too_long) L = 0;  // (nothing of such an utterance is read; it is reported infeasible below)
 
   for (int i = tid; i < UP; i += ALIGN_THREADS) {
     int tok = -1;
-    if (i < L) tok = i < p.label_stride ? p.labels[(long)b * p.label_stride + i] : blank;
-    lab_s[i] = (tok >= 0 && tok < V && tok != blank) ? tok : -1;
+    if (i < L) tok = label_at(p, label_row(p, b), i);
+    lab_s[i] = emits(p, tok) ? tok : -1;
   }
   __syncthreads();
 

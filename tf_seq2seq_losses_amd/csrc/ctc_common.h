@@ -194,6 +194,32 @@ struct Problem {
   int align_bits = 0;
 };
 
+// ---- The per-utterance input contract: what every kernel makes of the caller's lengths and labels ----
+//   * frame_count: logit_length[b] clamped to [0, T];   * label_count: a negative label_length[b] counts as 0;
+//   * too_many_labels: label_length[b] > U makes the utterance infeasible.  What a site then does is its own: go on with no labels
+//     (another role reports the utterance), or report it (loss +inf, -inf rows) or write zeros, and stop;
+//   * label_at: a label position (below label_count) beyond label_stride, the width of the labels tensor, reads as the blank;
+//   * emits: a label outside [0, V) or equal to the blank is an impossible emission.  in_vocab alone is the memory guard of sites
+//     that index a V-wide row with the token and leave the verdict to another kernel;   * LabelTok: sentinels outside the label.
+__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+__device__ __forceinline__ int frame_count(const Problem &p, int b) { return clampi(p.logit_length[b], 0, p.T); }
+__device__ __forceinline__ int label_count(const Problem &p, int b) { return p.label_length[b] < 0 ? 0 : p.label_length[b]; }
+__device__ __forceinline__ bool too_many_labels(const Problem &p, int ll) { return ll > p.U; }
+__device__ __forceinline__ const int32_t *label_row(const Problem &p, int b) { return p.labels + (long)b * p.label_stride; }
+__device__ __forceinline__ int label_at(const Problem &p, const int32_t *lab, int i) { return (i < p.label_stride) ? lab[i] : p.blank; }
+__device__ __forceinline__ bool in_vocab(const Problem &p, int tok) { return tok >= 0 && tok < p.V; }
+__device__ __forceinline__ bool emits(const Problem &p, int tok) { return tok >= 0 && tok < p.V && tok != p.blank; }
+// tok(i): the token of label position i of an utterance with ll labels at `lab`; distinct sentinels outside the label (-2 before it,
+// -1 behind it: neither equals a token, nor each other), the blank beyond the labels tensor's row.  `const LabelTok tok{ll, p, lab};`
+// (Its shape -- a struct of references with a plain call operator, which is to the compiler what a `[&]` lambda is -- keeps the device
+// code of the fused tiers byte for byte what it was with a lambda at every site: profiles/linear_chain_core.md.)
+struct LabelTok {
+  const int &ll;
+  const Problem &p;
+  const int32_t *const &lab;
+  __device__ int operator()(int i) const { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); }
+};
+
 // element offset of row (b, t) of the logits / of the gradient
 __device__ __forceinline__ long logits_off(const Problem &p, int b, int t) {
   return (p.row0 ? (long)p.row0[b] * p.xst : (long)b * p.xsb) + (long)t * p.xst;
@@ -206,6 +232,11 @@ __device__ __forceinline__ float f16_to_f32(unsigned short h) { return (float)__
 __device__ __forceinline__ unsigned short f32_to_f16(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
 // 16-bit element of type dt (1 = bfloat16, 2 = float16) <-> float32
 __device__ __forceinline__ float h16_to_f32(unsigned short h, int dt) { return dt == 2 ? f16_to_f32(h) : __uint_as_float((unsigned)h << 16); }
+// element k of a row of type dt (0 = float32, 1 = bfloat16, 2 = float16).  (row_load4 is not shared: ctc_decode.hip's is non-temporal.)
+__device__ __forceinline__ float row_load1(const char *row, int k, int dt) {
+  if (dt == 0) return reinterpret_cast<const float *>(row)[k];
+  return h16_to_f32(reinterpret_cast<const unsigned short *>(row)[k], dt);
+}
 
 // bfloat16 <-> float32 (round to nearest even on the way back)
 __device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }

@@ -28,7 +28,7 @@ constexpr int COLLAPSE_S = 4;                        // 64-frame steps of the co
 constexpr float FLT_LOWEST = -3.402823466e38f;
 constexpr int NO_INDEX = 0x7fffffff;
 
-// elements k .. k+3 / element k of a row of element type dt (0 = float32, 1 = bfloat16, 2 = float16) as float32
+// elements k .. k+3 of a row of element type dt (0 = float32, 1 = bfloat16, 2 = float16) as float32 (row_load1: ctc_common.h)
 // (non-temporal: every row is read exactly once -- measured against the default policy in profiles/decode_time.md)
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
@@ -40,10 +40,6 @@ __device__ __forceinline__ float4 row_load4(const char *row, int k, int dt) {
   const v2u u = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(row + (size_t)k * 2));
   return make_float4(h16_to_f32((unsigned short)(u.x & 0xffffu), dt), h16_to_f32((unsigned short)(u.x >> 16), dt),
                      h16_to_f32((unsigned short)(u.y & 0xffffu), dt), h16_to_f32((unsigned short)(u.y >> 16), dt));
-}
-__device__ __forceinline__ float row_load1(const char *row, int k, int dt) {
-  if (dt == 0) return reinterpret_cast<const float *>(row)[k];
-  return h16_to_f32(reinterpret_cast<const unsigned short *>(row)[k], dt);
 }
 
 // Running statistic of one lane: m = the maximum so far (-inf before the first element), idx = the lowest index holding it,
@@ -90,9 +86,7 @@ __global__ __launch_bounds__(64 * DECODE_WAVES) void decode_rows_kernel(const Pr
       live[g] = false;
       row[g] = nullptr;
       if (r0 + g < rows) {
-        int Tb = p.logit_length[b];
-        Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
-        if (t < Tb) {
+        if (t < frame_count(p, b)) {
           live[g] = true;
           row[g] = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb + (long)t * p.xst) * esz;
           if (!any) any = row[g];
@@ -171,8 +165,7 @@ __global__ __launch_bounds__(64) void decode_collapse_kernel(const Problem p, co
                                                              int *__restrict__ frames, float *__restrict__ label_score) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int T = p.T, blank = p.blank;
-  int Tb = p.logit_length[b];
-  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  const int Tb = frame_count(p, b);
   const size_t base = (size_t)b * T;
   const int *const tok_in = tokens + base;
   const float *const lp_in = lp + base;

@@ -3,7 +3,6 @@
 // and by ctc_fused6.hip (fallback for flagged utterances inside the same launch).
 #pragma once
 #include "ctc_fused_common.h"
-#include "ctc_linear_chain.h"  // LabelTok: one sentinel convention for the log-domain and the linear-domain chains
 
 #ifndef CTC_FUSED_KIND
 #error "compile with -DCTC_FUSED_KIND=0 (classic) or 1 (simplified)"
@@ -123,7 +122,7 @@ __device__ __forceinline__ void restore_state(S_t &S, const SRow<KIND, NL> &r) {
 
 template <int KIND, int NL, class S_t>
 __device__ __forceinline__ void init_labels(S_t &S, const Problem &p, int b, int lane, int ll) {
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
+  const int32_t *lab = label_row(p, b);
   const LabelTok tok{ll, p, lab};
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
@@ -131,6 +130,7 @@ __device__ __forceinline__ void init_labels(S_t &S, const Problem &p, int b, int
     int tk = tok(i);
     S.norep[j] = (i == 0) || tk != tok(i - 1);
     S.norep_next[j] = tok(i + 1) != tk;
+    // (emits(p, tk) with the instantiation's own bound inside, written out: `emits(p, tk) && tk < S_t::V` compiles to other code)
     S.tokoff[j] = 4 * ((tk >= 0 && tk < p.V && tk < S_t::V && tk != p.blank) ? tk : S_t::V);
     S.c[j] = NEG;
     S.o[j] = NEG;
@@ -247,8 +247,8 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
   S.lane = lane; S.UP = UP; S.blank = p.blank; S.SRS = L.SRS;
   const int len = geo.len;
   S.len = len;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  const bool shape_ok = (ll <= p.U);
+  int ll = label_count(p, b);
+  const bool shape_ok = !too_many_labels(p, ll);
   if (!shape_ok) ll = 0;
   S.ll = ll;
   S.own_rows = (DIR == 0 ? alpha_ws : beta_ws) + (long)b * L.rows_b * L.SRS;
@@ -387,8 +387,8 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const Layout &L,
   const int lane = threadIdx.x & 63;
   const int T = p.T, UP = L.UP;
   S.lane = lane; S.UP = UP; S.blank = p.blank; S.SRS = L.SRS;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) ll = 0;
   S.ll = ll;
   S.off = 0.0;
   S.cx = NEG;
@@ -500,8 +500,8 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
   const int T = p.T;
   S.lane = lane; S.UP = L.UP; S.blank = p.blank;
   const int len = geo.len;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) ll = 0;
   S.ll = ll;
   if constexpr (XT != 2) {
     S.xbase = p.logits + (long)b * p.xsb;
@@ -690,7 +690,7 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
 template <int BLK>
 __device__ __forceinline__ void run_idle(const Problem &p, bool want_grad, int b) {
   Geo<BLK> geo;
-  geo.init(clampi(p.logit_length[b], 0, p.T));
+  geo.init(frame_count(p, b));
   for (int it = 0; it <= geo.NB; ++it) block_barrier();
   __syncthreads();
   __syncthreads();
@@ -704,7 +704,7 @@ __device__ __forceinline__ void run_roles(const Problem &p, const Layout &L, flo
                                           const float *__restrict__ d_loss, float *__restrict__ grad, void *stamp_ws,
                                           Lds<KIND, NL, NH, BLK, VPL> &lds, int w, int b) {
   Geo<BLK> geo;  // every wavefront derives the same block schedule: the barrier counts match by construction
-  geo.init(clampi(p.logit_length[b], 0, p.T));
+  geo.init(frame_count(p, b));
   if (w == 0) {
     __builtin_amdgcn_s_setprio(3);  // the sequential chains win issue arbitration against co-resident helpers
     run_main<KIND, NL, NH, BLK, VPL, 0>(p, L, alpha_ws, beta_ws, logp_ws, loss, lds, geo, stamp_ws, grad != nullptr, b);

@@ -344,10 +344,12 @@ struct Rows {
     }
     io.xst = p.xst; io.gst = p.gst; io.Vr = p.V;
     dl = d_loss ? d_loss[b] : 1.0f;
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
+    const int32_t *lab = label_row(p, b);
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       const int i = lane * NL + j;
+      // (label_at and emits with this instantiation's own bound inside, written out: the helpers move this unit's code; one
+      // sentinel does for every position outside the label, since only the test below reads tk)
       const int tk = (i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1;
       valid[j] = i < ll;
       tokoff[j] = 4 * ((tk >= 0 && tk < p.V && tk < V && tk != p.blank) ? tk : V);
@@ -652,8 +654,8 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
   const int lane = threadIdx.x & 63;
   const int T = p.T, UP = L.UP, SRS = L.SRS;
   const int len = geo.len;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  const bool shape_ok = (ll <= p.U);
+  int ll = label_count(p, b);
+  const bool shape_ok = !too_many_labels(p, ll);
   if (!shape_ok) ll = 0;
   const int nslot = L.nslot;  // checkpoint slots per direction
   float *own_rows = (DIR == 0 ? alpha_ws : beta_ws) + (long)b * L.rows_b * SRS;
@@ -840,7 +842,7 @@ __device__ __forceinline__ void run_main(const Problem &p, const Layout &L, floa
         //   NL = 2 : [token parts[2], aligned blank part, shifted blank part]
         //   NL = 1 : [token part, shifted blank part]
         // the carrier lane's shifted blank part also holds the posterior of the boundary state (scaled with its own K0).
-        auto grp = [&](int d) -> int { return r_group<KIND, DIR, RN>(d, nv); };  // (a lambda: see LabelTok, ctc_linear_chain.h)
+        auto grp = [&](int d) -> int { return r_group<KIND, DIR, RN>(d, nv); };  // (a lambda: see r_group, ctc_linear_chain.h)
         float(*KLr)[64] = lds.kl[DIR][j % 3];
         int q = -1, kR = DEAD, ks = DEAD, seg = -1;
         float KL = 0.f, KS = 0.f, K0 = 0.f;
@@ -1072,8 +1074,8 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const Layout &L,
   constexpr int RN = CD::RN, LV = CD::LV;
   const int lane = threadIdx.x & 63;
   const int T = p.T, UP = L.UP, SRS = L.SRS;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) ll = 0;
   const int nslot = L.nslot;
   const float *ck_rows = (RDIR == 0 ? alpha_ws : beta_ws) + (long)b * L.rows_b * SRS;
   const int *ck_k = kexp_ws + ((long)b * 2 + RDIR) * nslot * 64;
@@ -1191,8 +1193,8 @@ __device__ __forceinline__ void run_helper(const Problem &p, const Layout &L, fl
   const int lane = threadIdx.x & 63;
   const int T = p.T;
   const int len = geo.len;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) ll = 0;
   S.init(p, b, lane, ll, d_loss, grad);
   S.set_lds(lds.xcopy[DIR * NH + h], lds.bins[DIR * NH + h]);
   if (lane == 0) S.xs[V] = 0.f;  // pad slot of the gather copy
@@ -1461,7 +1463,7 @@ __global__ __launch_bounds__(64 * (4 + 2 * NH)) void fused6_kernel(Problem p, La
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = perm ? perm[blockIdx.x] : (int)blockIdx.x;
   Geo<BLK> geo;
-  geo.init(clampi(p.logit_length[b], 0, p.T));
+  geo.init(frame_count(p, b));
   if (threadIdx.x == 0) {
     lds.flag = 0; lds.feasible = 0; lds.lossval = INFINITY; lds.added = 0;
     lds.p1_unused[16] = 0; lds.p1_unused[17] = 0;  // (this order of the stores: the one the measured code has)

@@ -29,8 +29,6 @@ constexpr int PF = 16;   // logits rows of look-ahead (= unrolled block length =
 constexpr int PFS = 8;   // spilled lattice rows of look-ahead in phase 2 (keeps the kernel inside 256 VGPRs)
 constexpr int NPACE = 48; // pacing stores after a ring prologue (see Side::pace)
 
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // (wave64 DPP reductions wave_sum_dpp / wave_max_dpp: ctc_common.h)
 __device__ __forceinline__ double readlane_f(double v, int l) {  // (float64 state of the log-domain roles: the two halves)
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));

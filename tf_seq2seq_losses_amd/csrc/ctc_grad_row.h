@@ -34,11 +34,11 @@ __device__ __forceinline__ void grad_row(const Problem &p, const Layout &L, cons
     v4f v = {r.x, r.y, r.z, r.w};
     __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(g + k));
   };
-  const int len = v1_clampi(p.logit_length[b], 0, p.T);
-  const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int len = frame_count(p, b);
+  const int ll = label_count(p, b);
   if (t >= len && p.row0 != nullptr) return;  // packed batches: rows beyond the length do not exist
-  bool zero = t >= len || ll > p.U;  // padded frames, contract violations: exactly zero (base_loss.py:283-298)
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
+  bool zero = t >= len || too_many_labels(p, ll);  // padded frames, contract violations: exactly zero (base_loss.py:283-298)
+  const int32_t *lab = label_row(p, b);
   float *qf = reinterpret_cast<float *>(qtab);
   float inv = 0.f, qblank = 0.f;
   const float *x = p.logits + logits_off(p, b, t);
@@ -136,8 +136,8 @@ __device__ __forceinline__ void grad_row(const Problem &p, const Layout &L, cons
     for (int q = 0; q < 4; ++q) *reinterpret_cast<uint4 *>(bins + lane * 4 + 256 * q) = make_uint4(0u, 0u, 0u, 0u);
     wave_lds_fence();
     for (int i = lane; i < ll; i += 64) {
-      const int tok = (i < p.label_stride) ? lab[i] : p.blank;
-      const unsigned r = (unsigned)(tok - c0);
+      const int tok = label_at(p, lab, i);
+      const unsigned r = (unsigned)(tok - c0);  // (below: emits(p, tok) written out, the helper orders the four tests differently)
       if (tok >= 0 && tok < V && tok != p.blank && r < (unsigned)CH) atomicAdd(&bins[r], (unsigned)(qf[i] * fix + 0.5f));
     }
     if (lane == 0 && p.blank >= c0 && p.blank < c0 + CH && p.blank < V) bins[p.blank - c0] = qbfix;

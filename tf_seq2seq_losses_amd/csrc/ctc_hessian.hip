@@ -54,11 +54,11 @@ __global__ __launch_bounds__(256) void hess_slab_kernel(Problem p, Layout L, con
   const int b = (int)((task / T) % p.B);
   const int k1 = order[(long)b * V + idx];
   float *out = hess + (((long)b * T + t1) * V + k1) * ((long)T * V);
-  const int len = clampi(p.logit_length[b], 0, T);
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int len = frame_count(p, b);
+  int ll = label_count(p, b);
   const double lp = logp[b];
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
-  auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
+  const int32_t *lab = label_row(p, b);
+  const LabelTok tok{ll, p, lab};
 
   auto zero_rows = [&](int t_from, int t_to) {
     if (t_to <= t_from) return;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void hess_slab_kernel(Problem p, Layout L, con
       for (long k = lane; k < n; k += 64) nt_store(q + k, 0.f);
     }
   };
-  const bool valid = (t1 < len) && (lp != -INFINITY) && (ll <= p.U);
+  const bool valid = (t1 < len) && (lp != -INFINITY) && !too_many_labels(p, ll);
   if (!valid) {  // padded frame or infeasible sample: the whole slab is zero (base_loss.py:240-258)
     zero_rows(0, T);
     return;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void hess_slab_kernel(Problem p, Layout L, con
     const int i = lane * NL + j;
     const int tk = tok(i);
     sel[j] = (k1 != p.blank) && tk == k1;
-    tokb[j] = 4 * ((tk >= 0 && tk < V && tk != p.blank) ? tk : V);
+    tokb[j] = 4 * ((tk >= 0 && tk < V && tk != p.blank) ? tk : V);  // (emits(p, tk), written out: the helper moves this kernel's code)
     any = any || sel[j];
   }
   any = __any(any);
@@ -296,14 +296,14 @@ __global__ __launch_bounds__(256) void hess_slab_kernel(Problem p, Layout L, con
 __global__ __launch_bounds__(64) void hess_plan_kernel(Problem p, int *__restrict__ order, int *__restrict__ npres) {
   extern __shared__ unsigned char flag[];
   const int lane = threadIdx.x, b = blockIdx.x, V = p.V;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) ll = 0;
   for (int k = lane; k < V; k += 64) flag[k] = 0;
   __syncthreads();
   if (lane == 0) flag[p.blank] = 1;
   for (int i = lane; i < ll && i < p.label_stride; i += 64) {
-    const int tk = p.labels[(long)b * p.label_stride + i];
-    if (tk >= 0 && tk < V) flag[tk] = 1;
+    const int tk = label_row(p, b)[i];
+    if (in_vocab(p, tk)) flag[tk] = 1;  // (a label equal to the blank marks the blank, which is marked anyway)
   }
   __syncthreads();
   int base = 0;
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
   const int pair = (int)(task / ((long)p.B * T));
   const int t1 = (int)(task % T);
   const int b = (int)((task / T) % p.B);
-  const int len = clampi(p.logit_length[b], 0, T);
-  const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int len = frame_count(p, b);
+  const int ll = label_count(p, b);
   const double lp = logp[b];
   const long slab = (long)T * V;
   const int idx = 2 * pair + hf;
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
     fill_zero(out_a + (long)t_from * V, (long)(t_to - t_from) * V);
     if (have_b) fill_zero(out_b + (long)t_from * V, (long)(t_to - t_from) * V);
   };
-  const bool valid = (t1 < len) && (lp != -INFINITY) && (ll <= p.U);
+  const bool valid = (t1 < len) && (lp != -INFINITY) && !too_many_labels(p, ll);
   if (!valid) {  // padded frame or infeasible sample: all V slabs are zero (base_loss.py:240-258); this wavefront's share
     for (int i = (int)(((long)pair * V) / npair); i < (int)(((long)(pair + 1) * V) / npair); ++i)
       fill_zero(hess + (((long)b * T + t1) * V + i) * slab, slab);
@@ -398,8 +398,8 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
   // sweeps are VALU-bound, the fills HBM-bound; run back to back they did not overlap: 5.4 ms = 3.5 + 1.9).
   const int nh = (npres[b] + 1) / 2;   // pairs with at least one present token (the blank is always present)
   if (pair >= nh) return;
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
-  auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
+  const int32_t *lab = label_row(p, b);
+  const LabelTok tok{ll, p, lab};
   const int tk = tok(hl);
   const bool sel = have && (k1 != p.blank) && tk == k1;
   const bool isblank = have && (k1 == p.blank);
@@ -502,7 +502,7 @@ __global__ __launch_bounds__(256, 6) void hess_pair_kernel(Problem p, Layout L, 
   float *stage = wl + 2 * (V + 4) + hf * (SR * V);                    // this half's SR staged rows
   auto tofix = [](float q) -> unsigned { return (unsigned)(fminf(q, 1.0f) * 1073741824.0f + 0.5f); };
   for (int k = hl; k < V + 4; k += W) ubin[k] = 0u;
-  char *abin = reinterpret_cast<char *>(ubin) + 4 * ((tk >= 0 && tk < V && tk != p.blank) ? tk : V);
+  char *abin = reinterpret_cast<char *>(ubin) + 4 * ((tk >= 0 && tk < V && tk != p.blank) ? tk : V);  // (emits(p, tk), written out: as above)
 
   auto half_bcast = [&](float v) -> float {  // value of lane 31 / 63 to every lane of the half
     const float a = readlane_f(v, 31), bb = readlane_f(v, 63);

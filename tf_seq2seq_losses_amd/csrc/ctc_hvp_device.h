@@ -28,9 +28,9 @@ __host__ __device__ static inline HvpLayout make_hvp_layout(const Layout &L, int
 __device__ __forceinline__ void temit_row(const Problem &p, const Layout &L, const float *__restrict__ emis, const float *__restrict__ vec,
                                           float *__restrict__ demis, int b, int t, int lane) {
   const long row = (long)b * p.T + t;
-  const int len = clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   if (t >= len) return;
-  const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int ll = label_count(p, b);
   const int V = p.V;
   const float *v = vec + row * (long)V;
   float sv = 0.f;
@@ -52,8 +52,8 @@ __device__ __forceinline__ void temit_row(const Problem &p, const Layout &L, con
   for (int i = lane; i < L.UP; i += 64) {
     float d = 0.f;
     if (i < ll) {
-      int tok = (i < p.label_stride) ? p.labels[(long)b * p.label_stride + i] : p.blank;
-      if (tok >= 0 && tok < V) d = v[tok] - sv;
+      const int tok = label_at(p, label_row(p, b), i);
+      if (in_vocab(p, tok)) d = v[tok] - sv;  // (not emits: a label equal to the blank makes the utterance infeasible, its tangents unread)
     }
     drow[i] = d;
   }
@@ -73,9 +73,9 @@ __device__ __forceinline__ void tscan_body(const Problem &p, const Layout &L, co
                                            float *__restrict__ dalpha, float *__restrict__ dbeta,
                                            float *__restrict__ dlogp, int b, int dir, int lane) {
   const int T = p.T, UP = L.UP;
-  const int len = clampi(p.logit_length[b], 0, T);
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U || logp[b] == -INFINITY) {
+  const int len = frame_count(p, b);
+  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];  // (label_count, written out: profiles/utterance_contract.md)
+  if (too_many_labels(p, ll) || logp[b] == -INFINITY) {
     if (dir == 0 && lane == 0) dlogp[b] = 0.f;
     return;  // infeasible: hvp_out_kernel writes zeros
   }
@@ -83,8 +83,8 @@ __device__ __forceinline__ void tscan_body(const Problem &p, const Layout &L, co
   const int tailpos = PAIR * UP;
   bool norep[NL], norep_next[NL];
   {
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
-    auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
+    const int32_t *lab = label_row(p, b);
+    const LabelTok tok{ll, p, lab};
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       int i = lane * NL + j;
@@ -309,10 +309,10 @@ __device__ __forceinline__ void hvp_out_row(const Problem &p, const Layout &L, c
   const long row = (long)b * p.T + t;
   const int V = p.V, UP = L.UP;
   float *o = out + row * (long)V;
-  const int len = clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   const double lp = logp[b];
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (t >= len || lp == -INFINITY || ll > p.U) {
+  int ll = label_count(p, b);
+  if (t >= len || lp == -INFINITY || too_many_labels(p, ll)) {
     for (int k = lane; k < V; k += 64) __builtin_nontemporal_store(0.f, o + k);  // the Hessian vanishes there (base_loss.py:240-258)
     return;
   }
@@ -320,7 +320,7 @@ __device__ __forceinline__ void hvp_out_row(const Problem &p, const Layout &L, c
   wave_lds_fence();
   constexpr int PAIR = (KIND == 0) ? 2 : 1;
   const int tailpos = PAIR * UP;
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
+  const int32_t *lab = label_row(p, b);
   const long ra_i = ((long)b * (p.T + 1) + (KIND == 0 ? t + 1 : t)) * L.SRS, rb_i = ((long)b * (p.T + 1) + t + 1) * L.SRS;
   const float *ra = alpha + ra_i, *rb = beta + rb_i, *da = dalpha + ra_i, *db = dbeta + rb_i;
   // Posterior q_s = alpha beta / P of a lattice state and its tangent dq_s = q_s (d_s - dlogP), d_s = dalpha_s + dbeta_s (+ the
@@ -378,8 +378,8 @@ __device__ __forceinline__ void hvp_out_row(const Problem &p, const Layout &L, c
     dblank += fexp2(tb - m) * inv * (db_ - dmean);
     if (i < ll) {
       const float dq = fexp2(tt - m) * inv * (dt_ - dmean);
-      const int tok = (i < p.label_stride) ? lab[i] : p.blank;
-      if (tok >= 0 && tok < V && tok != p.blank) atomicAdd(&bin[tok], dq);
+      const int tok = label_at(p, lab, i);
+      if (emits(p, tok)) atomicAdd(&bin[tok], dq);
     }
   }
   dblank = wave_sum(dblank);

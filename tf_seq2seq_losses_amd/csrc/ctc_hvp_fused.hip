@@ -312,10 +312,11 @@ struct Rows {
     xbase = p.logits + (long)b * p.T * p.V;
     vbase = vec + (long)b * p.T * p.V;
     obase = out + (long)b * p.T * p.V;
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
+    const int32_t *lab = label_row(p, b);
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
       const int i = lane * NL + j;
+      // (label_at and emits, written out: the helpers move this unit's code; one sentinel does, only the test below reads tk)
       const int tk = (i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1;
       valid[j] = i < ll;
       tokoff[j] = 4 * ((tk >= 0 && tk < p.V && tk != p.blank) ? tk : V);
@@ -495,8 +496,8 @@ __device__ __forceinline__ void run_main(const Problem &p, float *__restrict__ r
   constexpr int UP = C::UP, RS = C::RS, RN = C::RN, NG = C::NG;
   Chain<KIND, NL, DIR> S;
   const int lane = threadIdx.x & 63;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  const bool shape_ok = (ll <= p.U) && (ll <= UP);
+  int ll = label_count(p, b);
+  const bool shape_ok = (ll <= p.U) && (ll <= UP);  // (!too_many_labels, written out, and no more than this instantiation holds)
   if (!shape_ok) ll = 0;
   float *own_rows = rows_ws + ((long)b * 2 + DIR) * nslot * RS;
   const float *oth_rows = rows_ws + ((long)b * 2 + (1 - DIR)) * nslot * RS;
@@ -744,8 +745,8 @@ __device__ __forceinline__ void run_recompute(const Problem &p, const float *__r
   using C = Cfg<NL>;
   constexpr int RS = C::RS, RN = C::RN;
   const int lane = threadIdx.x & 63;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U || ll > C::UP) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll) || ll > C::UP) ll = 0;  // (C::UP: as in run_main)
   const float *ck_rows = rows_ws + ((long)b * 2 + RDIR) * nslot * RS;
   const int *ck_k = kexp_ws + ((long)b * 2 + RDIR) * nslot * 64;
   float *dump = lds.dump[2 + SIDE];
@@ -846,8 +847,8 @@ __device__ __forceinline__ void run_helper(const Problem &p, float4 *__restrict_
   Rows<KIND, NL> S;
   const int lane = threadIdx.x & 63;
   const int len = geo.len;
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U || ll > C::UP) ll = 0;
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll) || ll > C::UP) ll = 0;  // (C::UP: as in run_main)
   S.init(p, b, lane, ll, vec, out);
   S.xs = lds.xcopy[DIR * NH + slot];
   S.vs = lds.vcopy[DIR * NH + slot];
@@ -1029,7 +1030,7 @@ __global__ __launch_bounds__(64 * NW) void hvp_fused_kernel(Problem p, Layout L,
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x;
   Geo geo;
-  geo.init(clampi(p.logit_length[b], 0, p.T));
+  geo.init(frame_count(p, b));
   if (threadIdx.x == 0) { lds.flag = 0; lds.feasible = 0; lds.mode = mode; }
   if (threadIdx.x < NW) lds.l2s[threadIdx.x] = 0.0;
   __syncthreads();

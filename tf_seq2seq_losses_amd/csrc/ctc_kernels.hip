@@ -20,9 +20,6 @@
 
 namespace ctc {
 
-
-__device__ __forceinline__ int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // ------------------------------------------------------------------------------------------------
 // emit
 // ------------------------------------------------------------------------------------------------
@@ -43,9 +40,9 @@ __global__ __launch_bounds__(256) void emit4_kernel(Problem p, Layout L, float *
   const long id = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (id >= (long)p.B * nq) return;
   const int b = (int)(id / nq), t0 = 4 * (int)(id % nq);
-  const int len = clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   if (t0 >= len) return;  // padded frames are never read downstream
-  const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int ll = label_count(p, b);
   const int V = p.V;
   const float *xb = p.logits + (long)b * p.xsb;
   const float *xr[4];
@@ -93,8 +90,8 @@ __global__ __launch_bounds__(256) void emit4_kernel(Problem p, Layout L, float *
   float *erow = emis + ((long)b * p.T + t0) * (long)L.ERS;
   for (int i = lane; i < L.UP; i += 64) {
     int tok = -1;
-    if (i < ll) tok = (i < p.label_stride) ? p.labels[(long)b * p.label_stride + i] : p.blank;
-    const bool ok = tok >= 0 && tok < V && tok != p.blank;  // (a label equal to the blank: impossible emission, see emit_kernel)
+    if (i < ll) tok = label_at(p, label_row(p, b), i);
+    const bool ok = emits(p, tok);  // (a label equal to the blank: impossible emission, see emit_kernel)
     float g[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) g[r] = ok ? xr[r][tok] : 0.f;
@@ -120,10 +117,7 @@ __global__ __launch_bounds__(256) void emit4_kernel(Problem p, Layout L, float *
 }
 
 // ------------------------------------------------------------------------------------------------
-// scan
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
-// grad
+// grad  (scan: ctc_v1_device.h)
 // ------------------------------------------------------------------------------------------------
 // Posterior of "frame t emits token k".  Classic: the lattice state at t+1 names the token emitted at t
 // (closed <=> blank, open(l) <=> label[l-1]), so post = sum over states of alpha[t+1] * beta[t+1] / P, which is
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(256) void grad_kernel(Problem p, Layout L, const fl
     __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(g + k));
   };
   const bool gvec = !gbf && ((V | goff) & 3) == 0 && (p.align_bits & 15) == 0;
-  const int len = clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   const double lp = logp[b];
   if (t >= len && p.row0 != nullptr) return;  // packed batches: rows beyond the length do not exist
   if (t >= len || lp == -INFINITY) {
@@ -166,7 +160,7 @@ __global__ __launch_bounds__(256) void grad_kernel(Problem p, Layout L, const fl
     else for (int k = lane; k < V; k += 64) gput(k, 0.f);
     return;
   }
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  int ll = label_count(p, b);
   // posterior scatter with fixed-point integer LDS atomics (2^-30 resolution; ds_add_f32 is far slower on gfx950)
   float *bin = lds + (long)w * V;
   unsigned *ubin = reinterpret_cast<unsigned *>(bin);
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(256) void grad_kernel(Problem p, Layout L, const fl
   for (int k = lane; k < V; k += 64) ubin[k] = 0u;
   wave_lds_fence();
 
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
+  const int32_t *lab = label_row(p, b);
   const float *ra = alpha + ((long)b * (p.T + 1) + (KIND == 0 ? t + 1 : t)) * L.SRS;
   const float *rb = beta + ((long)b * (p.T + 1) + t + 1) * L.SRS;
   // Posteriors normalised by the frame's OWN mass sum_s alpha_t[s] beta_t[s] (= P for every t: the invariant of the reference's
@@ -222,8 +216,8 @@ __global__ __launch_bounds__(256) void grad_kernel(Problem p, Layout L, const fl
     terms(i, tb, tt);
     qblank += fexp2(tb - m) * inv;
     if (i < ll) {
-      const int tok = (i < p.label_stride) ? lab[i] : p.blank;
-      if (tok >= 0 && tok < V && tok != p.blank) atomicAdd(&ubin[tok], tofix(fexp2(tt - m) * inv));
+      const int tok = label_at(p, lab, i);
+      if (emits(p, tok)) atomicAdd(&ubin[tok], tofix(fexp2(tt - m) * inv));
     }
   }
   qblank = wave_sum(qblank);
@@ -289,10 +283,10 @@ __global__ __launch_bounds__(256) void logpost_kernel(Problem p, Layout L, const
   const int b = (int)(row / p.T), t = (int)(row % p.T);
   const int V = p.V, UP = L.UP;
   float *o = out + row * (long)V;
-  const int len = clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   const double lp = logp[b];
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (t >= len || lp == -INFINITY || ll > p.U) {
+  int ll = label_count(p, b);
+  if (t >= len || lp == -INFINITY || too_many_labels(p, ll)) {
     for (int k = lane; k < V; k += 64) o[k] = -INFINITY;
     return;
   }
@@ -301,7 +295,7 @@ __global__ __launch_bounds__(256) void logpost_kernel(Problem p, Layout L, const
   const int KEY_NONE = order_key(-3.0e38f);
   for (int k = lane; k < V; k += 64) { kmax[k] = KEY_NONE; ksum[k] = 0u; }
   wave_lds_fence();
-  const int32_t *lab = p.labels + (long)b * p.label_stride;
+  const int32_t *lab = label_row(p, b);
   const float *ra = alpha + ((long)b * (p.T + 1) + (KIND == 0 ? t + 1 : t)) * L.SRS;
   const float *rb = beta + ((long)b * (p.T + 1) + t + 1) * L.SRS;
   const int offpos = (KIND == 0 ? 2 * UP : UP) + 2;
@@ -338,8 +332,8 @@ __global__ __launch_bounds__(256) void logpost_kernel(Problem p, Layout L, const
   for (int n = 0; n < MAXI; ++n) {
     const int i = lane + 64 * n;
     if (i < ll && qtok[n] > NEG_THR) {
-      const int tok = (i < p.label_stride) ? lab[i] : p.blank;
-      if (tok >= 0 && tok < V && tok != p.blank) atomicMax(&kmax[tok], order_key(qtok[n]));
+      const int tok = label_at(p, lab, i);
+      if (emits(p, tok)) atomicMax(&kmax[tok], order_key(qtok[n]));
     }
   }
   wave_lds_fence();
@@ -348,8 +342,8 @@ __global__ __launch_bounds__(256) void logpost_kernel(Problem p, Layout L, const
   for (int n = 0; n < MAXI; ++n) {
     const int i = lane + 64 * n;
     if (i < ll && qtok[n] > NEG_THR) {
-      const int tok = (i < p.label_stride) ? lab[i] : p.blank;
-      if (tok >= 0 && tok < V && tok != p.blank) {
+      const int tok = label_at(p, lab, i);
+      if (emits(p, tok)) {
         const float mx = key_value(kmax[tok]);
         atomicAdd(&ksum[tok], (unsigned)(fexp2(qtok[n] - mx) * 1048576.0f + 0.5f));
       }
@@ -421,10 +415,10 @@ __global__ void convert_kernel(Problem p, Layout L, const float *__restrict__ ws
     int l = (int)(r % Lr); r /= Lr;
     int t = (int)(r % (p.T + 1));
     int b = (int)(r / (p.T + 1));
-    const int len = clampi(p.logit_length[b], 0, p.T);
-    int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+    const int len = frame_count(p, b);
+    int ll = label_count(p, b);
     float val;
-    if (ll > p.U) {
+    if (too_many_labels(p, ll)) {
       val = -INFINITY;
     } else if (is_beta && t >= len) {
       val = (l == ll) ? 0.f : -INFINITY;  // beta on padded frames: blank self-loops keep the one-hot
@@ -561,7 +555,7 @@ hipError_t run_convert(const Problem &p, const Layout &L, char *ws, float *alpha
 static __global__ __launch_bounds__(256) void order_kernel(const int *__restrict__ logit_length, int B, int T,
                                                            int *__restrict__ perm) {
   __shared__ int len_s[8192];
-  for (int j = threadIdx.x; j < B; j += 256) len_s[j] = (logit_length[j] < 0 ? 0 : (logit_length[j] > T ? T : logit_length[j]));
+  for (int j = threadIdx.x; j < B; j += 256) len_s[j] = clampi(logit_length[j], 0, T);
   __syncthreads();
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
@@ -580,7 +574,7 @@ hipError_t run_order(const Problem &p, const Layout &L, char *ws, hipStream_t st
   return hipGetLastError();
 }
 
-// labels[b][i] for i < min(label_length[b], U, label_stride) must lie in [0, V) and differ from the blank: counts the offenders
+// labels[b][i], i < min(label_length[b], label_stride), label_length[b] <= U, must emit (ctc_common.h, written out): counts the others
 static __global__ __launch_bounds__(256) void check_labels_kernel(const int32_t *__restrict__ labels, int label_stride,
                                                                   const int32_t *__restrict__ label_length, int blank, int B, int V,
                                                                   int U, int *__restrict__ bad) {

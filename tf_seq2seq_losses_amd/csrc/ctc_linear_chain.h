@@ -2,8 +2,7 @@
 // (ctc_hvp_fused.hip): the state of one direction (float32 mantissas, one integer exponent per lane), its start, its
 // RENORMALISATION POLICY, the block cadence of the renormalisations and the exponent group of an R row.  One copy: until r04 each
 // kernel carried its own, and every defect found in one had to be carried to the other by hand.  Each kernel derives its Chain from
-// ChainCore and adds its own step() (values only / values and tangents side by side).  LabelTok also serves the log-domain roles
-// (ctc_fused5_roles.h).  Everything here is __forceinline__ or constexpr, but for LabelTok's call operator (see there).
+// ChainCore and adds its own step() (values only / values and tangents side by side).  Everything here is __forceinline__ or constexpr.
 #pragma once
 #include "ctc_lane_ops.h"
 #include "ctc_linear_flags.h"
@@ -12,17 +11,6 @@ namespace ctc {
 namespace fused {
 
 using namespace ctc::linear;  // the number format's constants and the flag bits
-
-// tok(i): the token of label position i of an utterance with ll labels at `lab`; distinct sentinels outside the label (-2 before it,
-// -1 behind it: neither equals a token, nor each other), the blank beyond the labels tensor's row.  `const LabelTok tok{ll, p, lab};`
-// (Its shape, the reference arguments of r_group and the `grp` lambda in ctc_fused6.hip keep the device code of fused5 and fused6 byte
-// for byte what it was before this header existed: profiles/linear_chain_core.md.)
-struct LabelTok {
-  const int &ll;
-  const Problem &p;
-  const int32_t *const &lab;
-  __device__ int operator()(int i) const { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); }
-};
 
 // renormalisation period inside a block and the number of lanes the lattice front can cross in one period
 template <int BLK, int NL>
@@ -39,6 +27,7 @@ struct Cad {
 
 // exponent group of the R row at position d of a block with nv frames: rows are written BEFORE the recompute chain renormalises,
 // s steps after its checkpoint -> group max(s-1, 0) / RN.  s = nv-1-d (A, simplified B) / nv-d (classic B).
+// (The reference arguments and the `grp` lambda around the call in ctc_fused6.hip keep fused6's device code: profiles/linear_chain_core.md.)
 template <int KIND, int DIR, int RN>
 __device__ __forceinline__ constexpr int r_group(const int &d, const int &nv) {
   const int s = (KIND == 0 && DIR == 1) ? nv - d : nv - 1 - d;
@@ -82,7 +71,7 @@ struct ChainCore : M {
   bool relevant = true;
 
   __device__ __forceinline__ void init_labels(const Problem &p, int b, int lane, int ll) {
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
+    const int32_t *lab = label_row(p, b);
     const LabelTok tok{ll, p, lab};
 #pragma unroll
     for (int j = 0; j < NL; ++j) {

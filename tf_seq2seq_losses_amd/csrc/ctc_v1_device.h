@@ -9,16 +9,14 @@
 
 namespace ctc {
 
-__device__ __forceinline__ int v1_clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
 // one frame (b, t) by one wavefront (COH: the row is read by other workgroups of the same launch, ctc_common.h; MAXI: label
 // positions per lane the caller can meet; DEPTH: 16-byte loads per lane in flight while the row is read)
 template <bool COH = false, int MAXI = CTC_AMD_MAX_U / 64, int DEPTH = 8>
 __device__ __forceinline__ void emit_row(const Problem &p, const Layout &L, float *__restrict__ emis, int b, int t, int lane) {
   const long row = (long)b * p.T + t;
-  const int len = v1_clampi(p.logit_length[b], 0, p.T);
+  const int len = frame_count(p, b);
   if (t >= len) return;  // padded frames are never read downstream
-  const int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
+  const int ll = label_count(p, b);
   const int V = p.V;
   // element accessor of this frame's row: float32 or bfloat16, any batch/time stride (producer formats)
   const long xoff = logits_off(p, b, t);
@@ -35,7 +33,7 @@ __device__ __forceinline__ void emit_row(const Problem &p, const Layout &L, floa
   for (int n = 0; n < MAXI; ++n) {
     const int i = lane + 64 * n;
     tokv[n] = -1;
-    if (i < L.UP && i < ll) tokv[n] = (i < p.label_stride) ? p.labels[(long)b * p.label_stride + i] : p.blank;
+    if (i < L.UP && i < ll) tokv[n] = label_at(p, label_row(p, b), i);
   }
   const bool blank_ok = p.blank >= 0 && p.blank < V;
 
@@ -89,7 +87,7 @@ __device__ __forceinline__ void emit_row(const Problem &p, const Layout &L, floa
     if (i < L.UP) {
       // (a label equal to the blank id is unsupported input in the reference; every tier treats it as an impossible
       // emission: the sample comes out infeasible, loss +inf, gradient 0)
-      const bool ok = tokv[n] >= 0 && tokv[n] < V && tokv[n] != p.blank;
+      const bool ok = emits(p, tokv[n]);
       float e = ok ? fmaxf((xat(ok ? tokv[n] : 0) - mx) * LOG2E - log2sum, NEG) : NEG;
       if (!(e == e)) e = NEG;
       st1<COH>(erow + i, e);
@@ -328,16 +326,16 @@ __device__ __forceinline__ void scan_body(const Problem &p, const Layout &L, con
                                           float *__restrict__ rows_all, double *__restrict__ logp,
                                           float *__restrict__ loss, int b, int lane) {
   const int T = p.T, UP = L.UP;
-  const int len = v1_clampi(p.logit_length[b], 0, T);
-  int ll = p.label_length[b] < 0 ? 0 : p.label_length[b];
-  if (ll > p.U) {  // contract violation: reported as an infeasible sample
+  const int len = frame_count(p, b);
+  int ll = label_count(p, b);
+  if (too_many_labels(p, ll)) {  // contract violation: reported as an infeasible sample
     if (DIR == 0 && lane == 0) { logp[b] = -INFINITY; loss[b] = INFINITY; }
     return;
   }
   Scan<KIND, NL, DIR> S;
   S.off = 0.0;
   {
-    const int32_t *lab = p.labels + (long)b * p.label_stride;
+    const int32_t *lab = label_row(p, b);  // (tok: LabelTok as a lambda -- the struct moves the code of scan_kernel<classic, 1>)
     auto tok = [&](int i) -> int { return (i >= 0 && i < ll) ? ((i < p.label_stride) ? lab[i] : p.blank) : -1 - (i < 0); };
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
