@@ -25,6 +25,9 @@
  *   - What the kernels make of out-of-range lengths and labels (logit_length outside [0, T], negative label_length,
  *     label_length > U, label positions beyond label_stride, labels outside [0, V) or equal to the blank) is ONE contract for
  *     every entry point: DESIGN.md section 5.8; its code is csrc/ctc_common.h behind struct Problem.
+ *   - Frames at or beyond logit_length[b], label positions at or beyond label_length[b] and the elements between V and the row
+ *     stride are never interpreted (they may hold NaN or anything else), and the workspace and the outputs may hold anything on
+ *     entry: none of it changes a bit of any result ("Ownership").
  *   - Return value: 0 on success, negative CTC_AMD_E* code otherwise; ctc_amd_last_error() has text.
  *     Not errors (reference semantics, classic_ctc_loss.py:50-52, base_loss.py:240-245,283-288):
  *     infeasible alignment => loss = +inf, gradient = 0, Hessian = 0; B == 0; T == 0.
