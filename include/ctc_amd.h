@@ -396,6 +396,47 @@ int ctc_amd_greedy_decode(int kind, int wrt,
                           int32_t *frames /* may be NULL */, float *label_score /* may be NULL */,
                           void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Prefix beam search (added under ABI v6: two new entry points, nothing existing changed): the most probable label sequences,
+ * each summed over its alignments inside the beam.  The reference has no counterpart.  No labels are passed in.
+ * T_b = logit_length[b] clamped to [0, T]; lp = log_softmax(logits) (CTC_AMD_WRT_LOGPROBS: the input as it stands).
+ *   Candidates of a frame: the blank, and the min(top_k, V - 1) non-blank tokens with the largest x[b, t, k] (values compared as
+ *   the float32 the element type converts to, ties to the lowest index -- the rule of ctc_amd_greedy_decode).  A non-blank token
+ *   outside the cut is not considered at that frame, neither to extend a prefix nor to repeat its last label.
+ *   CTC_AMD_CLASSIC: a hypothesis is a prefix y with the masses pb (paths ending in blank) and pnb (paths ending in y's last label
+ *   e), starting from the empty prefix with pb = 1.  Per frame, with tot = pb + pnb: y keeps pb' += tot * p[blank] and, if e is a
+ *   candidate, pnb' += pnb * p[e]; y + c gets pnb' += (c == e ? pb : tot) * p[c] for every non-blank candidate c.
+ *   CTC_AMD_SIMPLIFIED: one mass per prefix; y keeps p' += p * p[blank], y + c gets p' += p * p[c].
+ *   Contributions to the same prefix add, on both lattices (an extension that meets a hypothesis already in the beam).
+ *   Hypotheses of zero mass are dropped; of the rest the beam_width of largest total mass survive the frame.  After the last
+ *   frame they are ordered by total mass, descending; among equal masses the choice is deterministic but unspecified.
+ *   score[B][nbest]            float32: ln of the hypothesis' total mass; -inf for a missing hypothesis (fewer alive than nbest)
+ *   decoded[B][nbest][T]       int32:   its labels, -1 beyond decoded_length (a missing hypothesis: all -1)
+ *   decoded_length[B][nbest]   int32
+ * T_b == 0 gives one hypothesis, the empty one, with score 0.  A frame whose every candidate is -inf kills the whole beam.
+ * Results for NaN inputs are unspecified (the call completes).  decoded[b][n] / decoded_length[b][n] can be handed to
+ * ctc_amd_loss_grad* and ctc_amd_best_path as labels / label_length (label_stride = nbest * T) while decoded_length <= CTC_AMD_MAX_U.
+ * The masses are linear-domain float64 relative to the row maxima (rescaled by exact powers of two), so the ranking is that of a
+ * float64 evaluation of the definition up to reassociation; the error of `score` is that of the float32 row log-sum-exps (none
+ * for CTC_AMD_WRT_LOGPROBS) plus its own rounding.  Assumption: two prefixes are taken for the same one when their 64-bit
+ * hashes (of the whole label sequence) are equal; a collision among the at most 64 prefixes of a beam would merge two
+ * hypotheses silently (about 2^-52 per frame at full width), and is not detected.
+ * 1 <= beam_width <= CTC_AMD_BEAM_MAX_WIDTH, 1 <= top_k <= CTC_AMD_BEAM_MAX_TOP_K, 1 <= nbest <= beam_width, 0 <= blank_index < V,
+ * V <= CTC_AMD_MAX_V.  Logits in the producer formats of ctc_amd_loss_grad_ex, with the access paths of ctc_amd_greedy_decode.
+ * Workspace: ctc_amd_beam_search_workspace_bytes (per frame 16 + 8 * min(top_k, V - 1) bytes of candidates, per utterance
+ * 8 * (1 + beam_width * T) bytes of prefix trie).  Two launches (frame-parallel candidate selection, then one wavefront per
+ * utterance for the search), asynchronous on `stream`, capturable.
+ */
+#define CTC_AMD_BEAM_MAX_WIDTH 64
+#define CTC_AMD_BEAM_MAX_TOP_K 32
+int ctc_amd_beam_search_workspace_bytes(int B, int T, int V, int beam_width, int top_k, size_t *out_bytes /*host*/);
+int ctc_amd_beam_search(int kind, int wrt,
+                        const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                        const int32_t *logit_length, int blank_index, int B, int T, int V,
+                        int beam_width, int top_k, int nbest,
+                        float *score, int32_t *decoded, int32_t *decoded_length,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

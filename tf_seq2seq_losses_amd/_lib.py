@@ -66,6 +66,12 @@ SIGNATURES = {
                                        _c_void_p, _c_int, _c_int, _c_int, _c_int,                  # logit_length, blank_index, B, T, V
                                        _c_void_p, _c_void_p, _c_void_p, _c_void_p,                 # score, tokens, decoded, decoded_length
                                        _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),    # frames, label_score, ws, bytes, stream
+    "ctc_amd_beam_search_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, T, V, W, K
+    "ctc_amd_beam_search": (_c_int, [_c_int, _c_int, _c_void_p, _c_int, _c_int64, _c_int64,        # kind, wrt, logits, dtype, stride_b, stride_t
+                                     _c_void_p, _c_int, _c_int, _c_int, _c_int,                    # logit_length, blank_index, B, T, V
+                                     _c_int, _c_int, _c_int,                                       # beam_width, top_k, nbest
+                                     _c_void_p, _c_void_p, _c_void_p,                              # score, decoded, decoded_length
+                                     _c_void_p, _c_size_t, _c_void_p]),                            # ws, bytes, stream
 }
 
 _lib = None
@@ -148,4 +154,10 @@ def best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
 def greedy_decode_workspace_bytes(B: int, T: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_greedy_decode_workspace_bytes(B, T, ctypes.byref(out)), "ctc_amd_greedy_decode_workspace_bytes")
+    return int(out.value)
+
+
+def beam_search_workspace_bytes(B: int, T: int, V: int, beam_width: int, top_k: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_beam_search_workspace_bytes(B, T, V, beam_width, top_k, ctypes.byref(out)), "ctc_amd_beam_search_workspace_bytes")
     return int(out.value)

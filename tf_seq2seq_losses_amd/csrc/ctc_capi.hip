@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "ctc_amd.h"
+#include "ctc_beam.h"
 #include "ctc_common.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_launch.h"
@@ -598,6 +599,46 @@ int ctc_amd_greedy_decode(int kind, int wrt, const void *logits, int logits_dtyp
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_decode(p, static_cast<char *>(workspace), score, tokens, decoded, decoded_length, frames, label_score,
                           static_cast<hipStream_t>(stream)), "greedy decode launch");
+  return CTC_AMD_OK;
+}
+
+// what ctc_amd_beam_search and its size query take beyond a shape
+int check_beam(int V, int beam_width, int top_k) {
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the beam search", V, MAX_V_GRAD);
+  if (beam_width < 1 || beam_width > CTC_AMD_BEAM_MAX_WIDTH) return fail(CTC_AMD_EINVAL, "beam_width %d outside [1, %d]", beam_width, CTC_AMD_BEAM_MAX_WIDTH);
+  if (top_k < 1 || top_k > CTC_AMD_BEAM_MAX_TOP_K) return fail(CTC_AMD_EINVAL, "top_k %d outside [1, %d]", top_k, CTC_AMD_BEAM_MAX_TOP_K);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_beam_search_workspace_bytes(int B, int T, int V, int beam_width, int top_k, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (B < 0 || T < 0 || V <= 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d V=%d", B, T, V);
+  if (int rc = check_beam(V, beam_width, top_k)) return rc;
+  *out_bytes = ctc::beam_workspace_bytes(B, T, V, beam_width, top_k);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_greedy_decode: common arguments, element type, B == 0, strides; then what only it takes (the
+// vocabulary limit, beam_width, top_k, nbest), the outputs and the workspace.
+int ctc_amd_beam_search(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                        const int32_t *logit_length, int blank_index, int B, int T, int V, int beam_width, int top_k, int nbest,
+                        float *score, int32_t *decoded, int32_t *decoded_length, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (int rc = check_beam(V, beam_width, top_k)) return rc;
+  if (nbest < 1 || nbest > beam_width) return fail(CTC_AMD_EINVAL, "nbest %d outside [1, beam_width = %d]", nbest, beam_width);
+  if (!score || !decoded_length || (T > 0 && !decoded)) return fail(CTC_AMD_EINVAL, "null score / decoded / decoded_length pointer");
+  if (((long long)B * T + 15) / 16 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  if ((long long)beam_width * T + 1 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "beam_width * T = %lld prefix nodes exceed 2^31", (long long)beam_width * T);
+  const size_t need = ctc::beam_workspace_bytes(B, T, V, beam_width, top_k);
+  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_beam(p, beam_width, top_k, nbest, static_cast<char *>(workspace), score, decoded, decoded_length,
+                        static_cast<hipStream_t>(stream)), "beam search launch");
   return CTC_AMD_OK;
 }
 

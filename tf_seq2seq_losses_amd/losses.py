@@ -309,6 +309,53 @@ def ctc_greedy_decode_from_logproba(logprobas, logit_length, blank_index, ctc_lo
 
 
 # --------------------------------------------------------------------------------------------------
+# prefix beam search: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcBeamDecoding(NamedTuple):
+    """score [batch, nbest] float32: ln of each hypothesis' probability, summed over its alignments inside the beam, best first
+    (-inf: fewer than nbest hypotheses are alive);
+    labels [batch, nbest, max_length] int32 (-1 beyond label_length); label_length [batch, nbest] int32.
+    labels[:, n] and label_length[:, n] can be passed straight to the loss and alignment functions of the same lattice."""
+    score: torch.Tensor
+    labels: torch.Tensor
+    label_length: torch.Tensor
+
+
+def _beam(kind_name: str, wrt: int, x, logit_length, blank_index, beam_width, top_k, nbest) -> CtcBeamDecoding:
+    x = _as_tensor(x)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    assert x.dim() == 3
+    assert x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    assert logit_length.dim() == 1
+    assert x.shape[0] == logit_length.shape[0]
+    with torch.no_grad():  # a decoding is not differentiable: the result is detached
+        return CtcBeamDecoding(*ops.beam_search(ops.KINDS[kind_name], wrt, x.detach(), logit_length, _blank(blank_index),
+                                                beam_width, top_k, nbest))
+
+
+def classic_ctc_beam_search(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                            beam_width: int = 16, top_k: int = 16, nbest: int = 1) -> CtcBeamDecoding:
+    """Prefix beam search on the classic lattice: the `nbest` most probable label sequences among the `beam_width` kept per
+    frame, each frame extending prefixes by the blank and its `top_k` most probable non-blank tokens only.
+    logits [batch, max_length, num_tokens] float32 / bfloat16 / float16 (any batch / time strides), logit_length [batch];
+    beam_width <= 64, top_k <= 32, nbest <= beam_width.  Returns CtcBeamDecoding(score, labels, label_length), not differentiable."""
+    return _beam("classic", _lib.WRT_LOGITS, logits, logit_length, blank_index, beam_width, top_k, nbest)
+
+
+def simplified_ctc_beam_search(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                               beam_width: int = 16, top_k: int = 16, nbest: int = 1) -> CtcBeamDecoding:
+    """Prefix beam search on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
+    classic_ctc_beam_search."""
+    return _beam("simplified", _lib.WRT_LOGITS, logits, logit_length, blank_index, beam_width, top_k, nbest)
+
+
+def ctc_beam_search_from_logproba(logprobas, logit_length, blank_index, ctc_loss_data_cls, *, beam_width: int = 16, top_k: int = 16,
+                                  nbest: int = 1) -> CtcBeamDecoding:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+    return _beam(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, logprobas, logit_length, blank_index, beam_width, top_k, nbest)
+
+
+# --------------------------------------------------------------------------------------------------
 # loss-data objects (what the reference's unit tests poke at directly)
 # --------------------------------------------------------------------------------------------------
 class BaseCtcLossData:

@@ -462,6 +462,40 @@ def greedy_decode(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tens
     return score, tokens, labels, label_length, frames, label_score
 
 
+def beam_search(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor, blank: int, beam_width: int, top_k: int, nbest: int):
+    """(score[B, nbest] float32, labels[B, nbest, T] int32, label_length[B, nbest] int32): the nbest most probable prefixes of a
+    prefix beam search (ctc_amd_beam_search).  Takes the logits as greedy_decode does, passes no labels and does not synchronise."""
+    _require_gpu(x)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    beam_width, top_k, nbest = int(beam_width), int(top_k), int(nbest)
+    if not (x.dtype in _DTYPES and (x.numel() == 0 or (x.stride(2) == 1 and x.stride(0) >= V and x.stride(1) >= V))):
+        x = x.to(torch.float32).contiguous()
+    if x.numel() == 0:
+        x = torch.empty((B, T, V), dtype=x.dtype if x.dtype in _DTYPES else torch.float32, device=dev)
+    if not (logit_length.dtype == torch.int32 and logit_length.device == dev and logit_length.is_contiguous()):
+        logit_length = logit_length.to(device=dev, dtype=torch.int32).contiguous()
+    key = ("beam_search", B, T, V, beam_width, top_k)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, beam_width and top_k, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.beam_search_workspace_bytes(B, T, V, beam_width, top_k)
+    if not 1 <= nbest <= beam_width:
+        raise ValueError(f"ctc_amd_beam_search: nbest {nbest} outside [1, beam_width = {beam_width}]")
+    score = torch.empty((B, nbest), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+    label_length = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+    if B == 0:
+        return score, labels, label_length
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_beam_search(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(logit_length), int(blank),
+                                     B, T, V, beam_width, top_k, nbest, _ptr(score), _ptr(labels), _ptr(label_length),
+                                     ws.data_ptr(), ws.numel(), _stream(dev))
+    _lib.check(rc, "ctc_amd_beam_search")
+    return score, labels, label_length
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
