@@ -437,6 +437,45 @@ int ctc_amd_beam_search(int kind, int wrt,
                         float *score, int32_t *decoded, int32_t *decoded_length,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * N-best rescoring (added under ABI v6: two new entry points, nothing existing changed): the exact loss of N label sequences
+ * per utterance, summed over ALL alignments (the scores of ctc_amd_beam_search are sums inside the beam: lower bounds).
+ *   loss[b, n] = -ln P(labels[b, n, :label_length[b, n]] | logits[b])        float32 [B][N]
+ * on the lattice of `kind`, with lp = log_softmax(logits) (CTC_AMD_WRT_LOGPROBS: the input as it stands).  It replaces nothing in
+ * the reference, which has no counterpart; it replaces N calls of ctc_amd_loss_grad_ex (grad = NULL) on N copies of the logits.
+ * Hypothesis (b, n) lies at labels + (b * N + n) * label_stride, its length at label_length[b * N + n]: the layout
+ * ctc_amd_beam_search writes (decoded[B][nbest][T] with label_stride = T, decoded_length[B][nbest]).  Every utterance's logits
+ * rows are read once per group of CTC_AMD_NBEST_GROUP hypotheses.  Forward only: there is no gradient.
+ * Padding and edges, per hypothesis (the input contract of every entry point): labels beyond
+ * label_length are not read (the -1 padding of the beam search included); label_length <= 0 is the all-blank path; a label
+ * position beyond label_stride reads as the blank; a label outside [0, V) or equal to blank_index inside label_length, a
+ * label_length > U, too few frames and a path set of zero mass (-inf log-probabilities, a frame that is -inf everywhere) all
+ * give loss = +inf for THAT hypothesis and change nothing else.  T_b = logit_length[b] clamped to [0, T]; frames beyond it are not
+ * read; T_b == 0 gives 0 for an empty hypothesis and +inf otherwise.  B == 0 returns CTC_AMD_OK without a launch.
+ * loss[b, n] has the same bits whatever N is, whatever the other hypotheses are and wherever in the list it stands.
+ * Results for NaN and +inf inputs are unspecified (the call completes).
+ * The lattice state is the float64 logarithm of the forward mass (nothing is rescaled, so nothing can be flushed); the error of
+ * `loss` is that of the float32 row log-sum-exps (none for CTC_AMD_WRT_LOGPROBS) and of the float32 exp / log of float64
+ * differences on the chain, about 1e-7 per frame and unbiased, plus its own rounding.
+ * 1 <= N <= CTC_AMD_NBEST_MAX, B * N < 2^31, U <= CTC_AMD_MAX_U bounds every hypothesis, 0 <= blank_index < V,
+ * V <= CTC_AMD_MAX_V (no row is staged in LDS; the limit is the ABI's, kept uniform).  Logits in the producer formats of
+ * ctc_amd_loss_grad_ex (element type, element strides >= V, token axis contiguous): 16-byte (float32) / 8-byte (16-bit types) row
+ * accesses when V, the strides and the base pointer allow them, element-wise accesses with identical results otherwise.
+ * Workspace: none.  ctc_amd_nbest_loss_workspace_bytes returns 0 for every valid shape (it exists so that a caller written
+ * against it keeps working should that change) and `workspace` may be NULL.  One launch of B * ceil(N / CTC_AMD_NBEST_GROUP)
+ * workgroups, asynchronous on `stream`, capturable.
+ */
+#define CTC_AMD_NBEST_MAX 64   /* = CTC_AMD_BEAM_MAX_WIDTH */
+#define CTC_AMD_NBEST_GROUP 8  /* hypotheses that share one read of the logits */
+int ctc_amd_nbest_loss_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes /*host*/);
+int ctc_amd_nbest_loss(int kind, int wrt,
+                       const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                       const int32_t *labels, int label_stride,
+                       const int32_t *label_length /* [B][N] */, const int32_t *logit_length, int blank_index,
+                       int B, int T, int V, int U, int N,
+                       float *loss /* [B][N] */,
+                       void *workspace /* may be NULL */, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ WRT_LOGITS, WRT_LOGPROBS = 0, 1
 WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
+NBEST_MAX, NBEST_GROUP = 64, 8  # CTC_AMD_NBEST_MAX, CTC_AMD_NBEST_GROUP: hypotheses per utterance, and per workgroup (one logits read)
 
 _c_int, _c_int64, _c_void_p, _c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 
@@ -72,6 +73,8 @@ SIGNATURES = {
                                      _c_int, _c_int, _c_int,                                       # beam_width, top_k, nbest
                                      _c_void_p, _c_void_p, _c_void_p,                              # score, decoded, decoded_length
                                      _c_void_p, _c_size_t, _c_void_p]),                            # ws, bytes, stream
+    "ctc_amd_nbest_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
+    "ctc_amd_nbest_loss": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # N, loss, ws, bytes, stream
 }
 
 _lib = None
@@ -160,4 +163,10 @@ def greedy_decode_workspace_bytes(B: int, T: int) -> int:
 def beam_search_workspace_bytes(B: int, T: int, V: int, beam_width: int, top_k: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_beam_search_workspace_bytes(B, T, V, beam_width, top_k, ctypes.byref(out)), "ctc_amd_beam_search_workspace_bytes")
+    return int(out.value)
+
+
+def nbest_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_nbest_loss_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_loss_workspace_bytes")
     return int(out.value)

@@ -642,4 +642,41 @@ int ctc_amd_beam_search(int kind, int wrt, const void *logits, int logits_dtype,
   return CTC_AMD_OK;
 }
 
+// what ctc_amd_nbest_loss and its size query take beyond a shape
+int check_nbest(int B, int V, int N) {
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the N-best loss", V, MAX_V_GRAD);
+  if (N < 1 || N > CTC_AMD_NBEST_MAX) return fail(CTC_AMD_EINVAL, "N %d outside [1, %d]", N, CTC_AMD_NBEST_MAX);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld hypotheses exceed 2^31", (long long)B * N);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_nbest_loss_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_nbest(B, V, N)) return rc;
+  *out_bytes = ctc::nbest_workspace_bytes(kind, B, T, V, U, N);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_best_path: common arguments, element type, B == 0, strides; then what only it takes (the
+// vocabulary limit, N) and the output.  No workspace: the pointer may be null.
+int ctc_amd_nbest_loss(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                       const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                       int blank_index, int B, int T, int V, int U, int N, float *loss, void *workspace, size_t workspace_bytes,
+                       void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (int rc = check_nbest(B, V, N)) return rc;
+  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
+  const size_t need = ctc::nbest_workspace_bytes(kind, B, T, V, U, N);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_nbest(p, N, loss, static_cast<hipStream_t>(stream)), "N-best loss launch");
+  return CTC_AMD_OK;
+}
+
 }  // extern "C"

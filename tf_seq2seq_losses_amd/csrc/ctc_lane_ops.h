@@ -38,7 +38,8 @@ __device__ __forceinline__ void fmac_from_upstream(float &acc, float x, float sc
   else asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(sc));
 }
 
-// NL consecutive floats (or NL consecutive (a, b) pairs) of this lane in an LDS / HBM row, NL = 1, 2, 4, 8: widest accesses
+// NL consecutive floats (or NL consecutive (a, b) pairs) of this lane in an LDS / HBM row, NL = 1, 2, 4, 8 (ld_slots / st_slots: any
+// multiple of 4; ctc_nbest.hip reads 16): widest accesses
 template <int NL>
 __device__ __forceinline__ void ld_slots(const float *p, float (&v)[NL]) {
   if constexpr (NL == 1) v[0] = p[0];

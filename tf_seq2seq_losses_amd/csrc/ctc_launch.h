@@ -46,6 +46,12 @@ size_t decode_workspace_bytes(int B, int T);
 hipError_t run_decode(const Problem &p, char *ws, float *score, int *tokens, int *decoded, int *decoded_length, int *frames,
                       float *label_score, hipStream_t st);
 
+// ctc_nbest.hip: exact loss of N hypotheses per utterance; one workgroup per utterance and group of NBEST_G hypotheses
+// (= CTC_AMD_NBEST_GROUP, include/ctc_amd.h).  Everything lives in registers and LDS: no workspace (the size is 0 bytes)
+constexpr int NBEST_G = 8;
+size_t nbest_workspace_bytes(int kind, int B, int T, int V, int U, int N);
+hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st);
+
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
 extern int g_wide_diag;  // timing diagnostics (results are then meaningless)

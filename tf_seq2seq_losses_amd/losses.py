@@ -356,6 +356,84 @@ def ctc_beam_search_from_logproba(logprobas, logit_length, blank_index, ctc_loss
 
 
 # --------------------------------------------------------------------------------------------------
+# N-best rescoring: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcNbestLoss(NamedTuple):
+    """loss [batch, nbest] float32: -ln P(hypothesis | logits), summed over ALL alignments (+inf: infeasible, malformed or masked);
+    log_posterior [batch, nbest] float32: -loss - logsumexp(-loss) over the list: the confidence of every hypothesis within ITS
+    LIST (-inf where the loss is +inf; a list without a feasible hypothesis is -inf throughout).  The list is taken as it stands:
+    a hypothesis that appears twice is counted twice."""
+    loss: torch.Tensor
+    log_posterior: torch.Tensor
+
+
+def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, hypothesis_mask=None,
+           max_label_length=None) -> CtcNbestLoss:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    assert x.dim() == 3
+    assert x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    assert labels.dim() == 3
+    assert label_length.dim() == 2
+    assert logit_length.dim() == 1
+    assert x.shape[0] == labels.shape[0] == label_length.shape[0] == logit_length.shape[0]
+    assert labels.shape[1] == label_length.shape[1]
+    U = None if max_label_length is None else max(0, min(int(labels.shape[2]), int(max_label_length)))
+    with torch.no_grad():  # forward only: the result is detached
+        loss = ops.nbest_loss(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), U)
+        if hypothesis_mask is not None:
+            mask = _as_tensor(hypothesis_mask).to(device=loss.device, dtype=torch.bool)
+            assert tuple(mask.shape) == tuple(loss.shape)
+            loss = torch.where(mask, loss, torch.full_like(loss, float("inf")))
+        # (a list of +inf alone: logsumexp is -inf and -inf - -inf would be NaN)
+        lse = torch.logsumexp(-loss, dim=1, keepdim=True) if loss.shape[1] else loss.new_zeros((loss.shape[0], 1))
+        logp = torch.where(torch.isinf(loss) & (loss > 0), torch.full_like(loss, float("-inf")), -loss - lse)
+        return CtcNbestLoss(loss, logp)
+
+
+def classic_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                           blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
+                           max_label_length: Optional[int] = None) -> CtcNbestLoss:
+    """The exact classic CTC loss of N label sequences per utterance against the same logits, the logits read once per group of
+    eight hypotheses instead of once each: what re-ranks an N-best list (the scores of classic_ctc_beam_search are sums inside
+    the beam: lower bounds) and turns it into confidences.
+
+    Args:
+        labels:       [batch, nbest, max_label_length] int32 -- a CtcBeamDecoding's `labels` as it stands (padding is not read)
+        logits:       [batch, max_length, num_tokens] float32 / bfloat16 / float16 (any batch / time strides)
+        label_length: [batch, nbest] int32
+        logit_length: [batch] int32
+        blank_index:  int
+        hypothesis_mask: (keyword only) [batch, nbest] bool; where False the loss is +inf and the entry takes no part in the
+            normalisation -- pass `isfinite(score)` for the missing hypotheses of a CtcBeamDecoding.
+        max_label_length: (keyword only) as in classic_ctc_loss: an upper bound on label_length known on the host.
+    Returns: CtcNbestLoss(loss, log_posterior), both [batch, nbest] float32, not differentiable (logits that require grad are
+        accepted; the result is detached).  A duplicate hypothesis is counted twice in log_posterior.  nbest <= 64; a
+        hypothesis that is infeasible or malformed (a label outside [0, num_tokens) or equal to the blank, a negative length
+        counts as empty) has loss +inf and changes no other entry."""
+    return _nbest("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length)
+
+
+def simplified_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                              blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
+                              max_label_length: Optional[int] = None) -> CtcNbestLoss:
+    """The same on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
+    classic_ctc_nbest_loss."""
+    return _nbest("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length)
+
+
+def ctc_nbest_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *,
+                                 hypothesis_mask: Optional[TensorLike] = None, max_label_length: Optional[int] = None) -> CtcNbestLoss:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+    return _nbest(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                  hypothesis_mask, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # loss-data objects (what the reference's unit tests poke at directly)
 # --------------------------------------------------------------------------------------------------
 class BaseCtcLossData:

@@ -496,6 +496,51 @@ def beam_search(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor
     return score, labels, label_length
 
 
+def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+               blank: int, U: Optional[int] = None) -> torch.Tensor:
+    """loss[B, N] float32: the exact loss of the N label sequences labels[b, n, :label_length[b, n]] of every utterance against the
+    same logits[b] (ctc_amd_nbest_loss), the logits read once per group of _lib.NBEST_GROUP hypotheses.  labels [B, N, W] and
+    label_length [B, N] in the layout beam_search returns; U bounds every label_length (a longer hypothesis is +inf; default: the
+    labels' width W, or the maximum inside when W is large, as Prepared finds it).  Takes the logits as greedy_decode does and does not synchronise."""
+    _require_gpu(x)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if labels.dim() != 3 or label_length.dim() != 2 or int(labels.shape[0]) != B or tuple(label_length.shape) != tuple(labels.shape[:2]):
+        raise ValueError(f"nbest_loss: labels must be [B, N, W] and label_length [B, N] with B = {B}, got {tuple(labels.shape)} and "
+                         f"{tuple(label_length.shape)}")
+    N, W = int(labels.shape[1]), int(labels.shape[2])
+    if U is None:  # as Prepared: the width always works; a wide tensor is worth one look at the maximum inside (a beam search's is T wide)
+        U = W
+        if U > WIDTH_WORTH_A_LOOK and label_length.numel() > 0:
+            if not label_length.is_cuda:
+                U = max(0, min(U, int(label_length.max())))
+            elif not torch.cuda.is_current_stream_capturing():
+                U = max(0, min(U, _device_max_label_length(label_length)))
+    U = int(U)
+    if not (x.dtype in _DTYPES and (x.numel() == 0 or (x.stride(2) == 1 and x.stride(0) >= V and x.stride(1) >= V))):
+        x = x.to(torch.float32).contiguous()
+    if x.numel() == 0:
+        x = torch.empty((B, T, V), dtype=x.dtype if x.dtype in _DTYPES else torch.float32, device=dev)
+
+    def i32(t):
+        return t if (t.dtype == torch.int32 and t.device == dev and t.is_contiguous()) else t.to(device=dev, dtype=torch.int32).contiguous()
+    labels, label_length, logit_length = i32(labels), i32(label_length), i32(logit_length)
+    key = ("nbest_loss", kind, B, T, V, U, N)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, U and N, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.nbest_loss_workspace_bytes(kind, B, T, V, U, N)
+    loss = torch.empty((B, N), dtype=torch.float32, device=dev)
+    if B == 0:
+        return loss
+    ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None
+    with _on_device(dev):
+        rc = lib.ctc_amd_nbest_loss(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W, _ptr(label_length),
+                                    _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(loss), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_nbest_loss")
+    return loss
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
