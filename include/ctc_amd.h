@@ -476,6 +476,47 @@ int ctc_amd_nbest_loss(int kind, int wrt,
                        float *loss /* [B][N] */,
                        void *workspace /* may be NULL */, size_t workspace_bytes, void *stream);
 
+/*
+ * Gradient of N-best rescoring (added under ABI v6: two new entry points, nothing existing changed): what MWER-style training
+ * (minimum word error rate, expected risk over a beam) needs, without N copies of the logits and N gradient tensors.  With
+ * loss[b, n] exactly as ctc_amd_nbest_loss defines it (the SAME BITS for the same inputs; it is written as well) and x the logits:
+ *   grad[b, t, k] = sum over the n with a finite loss[b, n] of  weight[b, n] * d loss[b, n] / d x[b, t, k]        for t < T_b
+ *                 = sum_n' weight[b, n] * (softmax(x[b, t])[k] - gamma_n[t, k])                   CTC_AMD_WRT_LOGITS
+ *                 = - sum_n' weight[b, n] * gamma_n[t, k]                                         CTC_AMD_WRT_LOGPROBS
+ *   grad[b, t, :] = 0 exactly                                                                     for T_b <= t < T
+ * gamma_n[t, k] is the posterior that frame t emits token k given hypothesis n.  A hypothesis whose loss is +inf (infeasible,
+ * malformed, too long, too few frames, zero mass) contributes exactly zero and its weight[b, n] is NOT INTERPRETED: it may be NaN
+ * or infinite (what the backward of a `where` / logsumexp in front of the call hands down).  An utterance without a feasible
+ * hypothesis gets a zero gradient.  The weights of feasible hypotheses must be finite.
+ *   weight[B][N] float32 (in), loss[B][N] float32 (out), grad (out) of element type grad_dtype in {CTC_AMD_F32, CTC_AMD_BF16,
+ *   CTC_AMD_F16} with element strides grad_stride_b / grad_stride_t >= V, token axis contiguous: every row t < T of every utterance
+ *   is written, elements between V and the stride are not.  All three must be non-NULL when B > 0 (CTC_AMD_EINVAL; a caller who
+ *   wants the loss alone has ctc_amd_nbest_loss).
+ * Inputs, padding, edges, limits and validation are those of ctc_amd_nbest_loss (checked in the same order; the gradient's element
+ * type and strides are checked with the logits'); in addition B * T < 2^33 (the row stage's launch grid).  B == 0 returns
+ * CTC_AMD_OK without a launch.
+ * The same bits on every run: the posteriors of a row are summed as 64-bit integers in units of 2^(e - 40), 2^e > max_n
+ * |weight[b, n]| over the feasible hypotheses, so no order of arrival enters; no floating-point atomics anywhere.
+ * Numerics: the alpha and beta sweeps carry float64 base-2 logarithms, as ctc_amd_nbest_loss; a posterior is the float32 exp2 of a
+ * float64 difference; the softmax comes from the float32 row statistics.
+ * Workspace (may hold anything on entry; too small: CTC_AMD_EWORKSPACE before any launch), with S = 2 (classic) or 1 (simplified),
+ * NL the smallest power of two with 64 * NL >= U (1 for U <= 64) and r256(x) = x rounded up to a multiple of 256:
+ *   ctc_amd_nbest_loss_grad_workspace_bytes = r256(8 * B * N * T * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B * N)
+ * -- every chain's float64 state of every frame (overwritten by the posteriors), the row statistics, log2 P.  B = 256, T = 1000,
+ * U = 128, N = 8: 4.23 GB classic, 2.13 GB simplified (section 7 names what would cut it).
+ * Three launches (T == 0: one): the alpha sweep that keeps its rows and the beta sweep, B * ceil(N / CTC_AMD_NBEST_GROUP) workgroups
+ * each, then one wavefront per row (b, t).  No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_nbest_loss_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes /*host*/);
+int ctc_amd_nbest_loss_grad(int kind, int wrt,
+                            const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride,
+                            const int32_t *label_length /* [B][N] */, const int32_t *logit_length, int blank_index,
+                            int B, int T, int V, int U, int N,
+                            const float *weight /* [B][N] */, float *loss /* [B][N] */,
+                            void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

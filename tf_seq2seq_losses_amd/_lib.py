@@ -75,6 +75,8 @@ SIGNATURES = {
                                      _c_void_p, _c_size_t, _c_void_p]),                            # ws, bytes, stream
     "ctc_amd_nbest_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
     "ctc_amd_nbest_loss": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # N, loss, ws, bytes, stream
+    "ctc_amd_nbest_loss_grad_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
+    "ctc_amd_nbest_loss_grad": (_c_int, _COMMON_EX + [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),  # N, weight, loss .. grad strides, ws, bytes, stream
 }
 
 _lib = None
@@ -169,4 +171,10 @@ def beam_search_workspace_bytes(B: int, T: int, V: int, beam_width: int, top_k: 
 def nbest_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_nbest_loss_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_loss_workspace_bytes")
+    return int(out.value)
+
+
+def nbest_loss_grad_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_nbest_loss_grad_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_loss_grad_workspace_bytes")
     return int(out.value)

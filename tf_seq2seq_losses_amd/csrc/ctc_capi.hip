@@ -679,4 +679,36 @@ int ctc_amd_nbest_loss(int kind, int wrt, const void *logits, int logits_dtype, 
   return CTC_AMD_OK;
 }
 
+int ctc_amd_nbest_loss_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_nbest(B, V, N)) return rc;
+  *out_bytes = ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_nbest_loss (both element types with the logits', the gradient's strides with the logits'); then
+// the three tensors only this call takes, the row stage's launch grid and the workspace.
+int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                            int blank_index, int B, int T, int V, int U, int N, const float *weight, float *loss, void *grad,
+                            int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, true)) return rc;
+  if (int rc = check_nbest(B, V, N)) return rc;
+  if (!weight || !loss || !grad) return fail(CTC_AMD_EINVAL, "null weight / loss / grad pointer");
+  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const size_t need = ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
+  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_nbest_grad(p, N, weight, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+          "N-best loss gradient launch");
+  return CTC_AMD_OK;
+}
+
 }  // extern "C"

@@ -51,6 +51,10 @@ hipError_t run_decode(const Problem &p, char *ws, float *score, int *tokens, int
 constexpr int NBEST_G = 8;
 size_t nbest_workspace_bytes(int kind, int B, int T, int V, int U, int N);
 hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st);
+// ... and the gradient of sum_n weight[b, n] * loss[b, n]: alpha sweep that keeps its rows, beta sweep, row stage.  The workspace
+// holds the float64 rows of every hypothesis and frame, the row statistics and log2 P
+size_t nbest_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N);
+hipError_t run_nbest_grad(const Problem &p, int N, const float *weight, float *loss, void *grad, char *ws, hipStream_t st);
 
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only

@@ -20,6 +20,23 @@
 //   S'[i] = lse(S[i] + e[blank], S[i-1] + e[label[i]])
 // The result of hypothesis (b, n) is a function of its own labels and of the ring rows of utterance b, which are the same bits
 // for every group, position and N: no hypothesis can see another.
+//
+// The gradient of sum_n weight[b, n] * loss[b, n] (ctc_amd_nbest_loss_grad) runs the same kernel body three
+// times over (template parameter MODE) and one row kernel behind it:
+//   MODE 0  the loss alone, as above;
+//   MODE 1  the same alpha sweep, bit for bit, that also stores every chain's state of every frame (float64) and the final log2 P,
+//           and the producers' row statistics, to the workspace;
+//   MODE 2  the beta sweep: same grid and roles, frames from T_b - 1 down (the producers gather in reverse order).  Per frame a
+//           chain reads its own saved row, forms the posteriors 2^(alpha + beta - log2 P) in float64 and writes them as float32
+//           pairs over the slots it has just read (only the chain's own lane touches a slot), then steps beta back over the frame;
+//   nbest_grad_row_kernel  one wavefront per row (b, t): adds weight * posterior of every label position of every feasible
+//           hypothesis into 64-bit fixed-point LDS bins by token (integer atomics: no arrival order in the sum), the vocabulary
+//           in passes of 1024 columns, and streams the row out: softmax from the saved statistics times the weight sum, minus bins.
+// A saved row of hypothesis (b, n) and frame t: per label position i the pair (O, C) (classic, AFTER frame t) or S (simplified,
+// BEFORE frame t), then the start state; (2 or 1) * UP + 2 doubles.  After the beta sweep the first 8 bytes of position i hold
+//   classic:    (posterior of O[i] after frame t = frame t emits label i,   posterior of C[i] = a blank behind label i)
+//   simplified: (alpha_{t-1}[i-1] e_t[label i] beta_t[i] / P,               alpha_{t-1}[i] e_t[blank] beta_t[i] / P)
+// and the start state's slot its blank posterior: .x goes to the token's column, .y to the blank's, on both lattices.
 #include "ctc_common.h"
 #include "ctc_lane_ops.h"
 #include "ctc_launch.h"
@@ -73,9 +90,20 @@ __device__ __forceinline__ int nb_token(const Problem &p, long row, int L, int i
   return emits(p, tok) ? tok : -1;
 }
 
-template <int KIND, int NL>
-__global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, const int N, float *__restrict__ loss) {
+// the gradient's workspace (MODE 0: unused)
+struct NbWs {
+  double *rows;  // [B * N][T][SRD] saved alpha rows, then the posteriors
+  float *stat;   // [B][T][4] x[blank], row max, log2 sum exp(x - max) of every frame
+  double *logp;  // [B * N] log2 P, -inf for an infeasible hypothesis
+};
+constexpr int nb_row_doubles(int kind, int UP) { return (kind == 0 ? 2 : 1) * UP + 2; }
+
+template <int KIND, int NL, int MODE>
+__global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, const int N, float *__restrict__ loss, const NbWs ws) {
   constexpr int UP = 64 * NL;
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;        // doubles of a saved row per lane
+  constexpr int SRD = nb_row_doubles(KIND, UP);
+  constexpr bool PF = NL <= 4;                        // MODE 2: the next frame's saved row is requested one frame ahead
   constexpr int F = NBEST_RING / UP;                  // frames per ring buffer: 16, 8, 4, 2, 1
   constexpr int FR = NBEST_G * UP;                    // ring floats per frame: the eight hypotheses' emissions
   constexpr int CNT = FR / NBEST_PT;                  // gathers per producer thread and frame: 2 NL
@@ -129,6 +157,25 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
         prev = tok;
       }
     }
+    double *const myrows = MODE != 0 ? ws.rows + (size_t)hrow * p.T * SRD : nullptr;  // (n >= N: never dereferenced)
+    // MODE 2: O / C / cs hold beta, the mass of the frames still to come; behind the last frame only the end states have any
+    double lP = 0.0;
+    bool active = n < N;
+    int allow_nx = 0;  // classic: the `allow` bit of the next lane's first position
+    if constexpr (MODE == 2) {
+      if (active) lP = ws.logp[hrow];
+      active = active && lP > NINF && lP < -NINF;
+#pragma unroll
+      for (int j = 0; j < NL; ++j) O[j] = C[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
+      cs = L == 0 ? 0.0 : NINF;
+      if (KIND == 0) allow_nx = fused::from_next_lane_i((int)(allow & 1u), 0);
+    }
+    auto load_row = [&](int t, double (&A)[NS], double &Acs) {
+      const double *const r = myrows + (size_t)t * SRD;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) A[q] = r[lane * NS + q];
+      Acs = r[SRD - 2];
+    };
 
     auto consume = [&](int kb) {
       const int t0 = kb * F;
@@ -143,6 +190,12 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
         const double eb = fma((double)sv.x - Md, LOG2E_D, nl2s);
         // (the emission of position j in the lattice's units, made where it is used: no float64 copy of the row stays live)
         auto em = [&](int j) { return fma((double)e[j] - Md, LOG2E_D, nl2s); };
+        double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
+        if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
+#pragma unroll
+          for (int j = 0; j < NL; ++j) r[lane * NS + j] = C[j];
+          if (lane == 0) r[SRD - 2] = cs;
+        }
         if (KIND == 0) {
           const double pO = from_prev_lane(O[NL - 1], NINF);
           const double pC = from_prev_lane(C[NL - 1], cs);
@@ -164,17 +217,94 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
           }
         }
         cs += eb;
+        if (MODE == 1 && KIND == 0) {  // the state AFTER the frame
+#pragma unroll
+          for (int j = 0; j < NL; ++j) *reinterpret_cast<double2 *>(r + lane * NS + 2 * j) = make_double2(O[j], C[j]);
+          if (lane == 0) r[SRD - 2] = cs;
+        }
+      }
+    };
+
+    // MODE 2: block kb holds the frames T_b - 1 - kb F downwards
+    double An[NS], Acsn = 0.0;
+    auto consume_back = [&](int kb) {
+      const int t0 = kb * F;
+      const int nf = Tb - t0 < F ? Tb - t0 : F;
+      const float *const rb = ring + (kb & 1) * F * FR + wave * UP + lane * NL;
+      const float *const sb = stat + (kb & 1) * F * 4;
+      for (int f = 0; f < nf; ++f) {
+        const int t = Tb - 1 - (t0 + f);
+        float e[NL];
+        fused::ld_slots<NL>(rb + f * FR, e);
+        const float4 sv = *reinterpret_cast<const float4 *>(sb + f * 4);
+        const double Md = (double)sv.y, nl2s = -(double)sv.z;
+        const double eb = fma((double)sv.x - Md, LOG2E_D, nl2s);
+        auto em = [&](int j) { return fma((double)e[j] - Md, LOG2E_D, nl2s); };
+        double A[NS], Acs;
+        if constexpr (PF) {
+#pragma unroll
+          for (int q = 0; q < NS; ++q) A[q] = An[q];
+          Acs = Acsn;
+          if (t > 0) load_row(t - 1, An, Acsn);
+        } else {
+          load_row(t, A, Acs);
+        }
+        double *const r = myrows + (size_t)t * SRD;
+        auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+        if (KIND == 0) {
+#pragma unroll
+          for (int j = 0; j < NL; ++j)
+            *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(post(A[2 * j] + O[j]), post(A[2 * j + 1] + C[j]));
+          if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
+          // beta back over frame t: x = what entering O[i] with this frame is worth
+          double x = O[0] + em(0);
+          const double xl = from_next_lane(x, NINF);
+          cs = nb_lse(cs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? O[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+            const double cb = C[j] + eb;
+            O[j] = nb_lse(x, cb, al ? xn : NINF);
+            C[j] = nb_lse(cb, xn);
+            x = xn;
+          }
+        } else {
+          const double ap0 = from_prev_lane(A[NL - 1], Acs);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+            *reinterpret_cast<float2 *>(r + lane * NS + j) = make_float2(post(ap + em(j) + C[j]), post(A[j] + eb + C[j]));
+          }
+          if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
+          double x = C[0] + em(0);
+          const double xl = from_next_lane(x, NINF);
+          cs = nb_lse(cs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? C[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            C[j] = nb_lse(C[j] + eb, xn);
+            x = xn;
+          }
+        }
       }
     };
 
     fused::block_barrier();
+    if constexpr (MODE == 2 && PF) {
+      if (active && Tb > 0) load_row(Tb - 1, An, Acsn);
+    }
     for (int kb = 0; kb < nb; ++kb) {
-      if (n < N) consume(kb);
+      if constexpr (MODE == 2) {
+        if (active) consume_back(kb);
+      } else {
+        if (n < N) consume(kb);
+      }
       fused::block_barrier();
     }
 
     // the end state
-    if (n < N) {
+    if (MODE != 2 && n < N) {
       const int i = L - 1, jj = i & (NL - 1);
       double cv = C[0], ov = O[0];
 #pragma unroll
@@ -183,7 +313,10 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
       double v = cs;
       if (L > 0) v = KIND == 0 ? nb_lse(ov, cv) : cv;
       if (too_long) v = NINF;
-      if (lane == (L > 0 ? i / NL : 0)) loss[hrow] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
+      if (lane == (L > 0 ? i / NL : 0)) {
+        loss[hrow] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
+        if (MODE == 1) ws.logp[hrow] = v;
+      }
     }
   } else {
     // ---- the producers (waves 8..11): the labels a thread gathers are the same every frame ----
@@ -199,8 +332,13 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
       goff[c] = (unsigned)(tok >= 0 ? tok : blank) * (unsigned)esz;
       if (tok >= 0) gvalid |= 1u << c;
     }
-    // row t of the utterance; past its end the last row, valid memory whose results are never stored
-    auto frame_row = [&](int t) { return xb + (size_t)((long)(t < Tb ? t : Tb - 1) * p.xst) * esz; };
+    // the frame a block's position stands for (MODE 2 runs backwards); past the utterance's end its last, valid memory whose
+    // results are never stored
+    auto real_t = [&](int t) {
+      const int c = t < Tb ? t : Tb - 1;
+      return MODE == 2 ? Tb - 1 - c : c;
+    };
+    auto frame_row = [&](int t) { return xb + (size_t)((long)real_t(t) * p.xst) * esz; };
 
     auto produce = [&](int kb) {
       const int t0 = kb * F;
@@ -242,7 +380,7 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
 #pragma unroll
       for (int q = 0; q < FPW; ++q) {
         const int f = pw + NBEST_PW * q;
-        const int t = (f < F && t0 + f < Tb) ? t0 + f : Tb - 1;
+        const int t = real_t(f < F ? t0 + f : Tb);
         row[q] = xb + (size_t)((long)t * p.xst) * esz;
         ebl[q] = row_load1(row[q], blank, dt);
         m[q] = -3.402823466e38f; s[q] = 0.f;
@@ -266,7 +404,10 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
           l2s = flog2(S);
           if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
         }
-        if (lane == 0 && f < F && t0 + f < Tb) *reinterpret_cast<float4 *>(sb + f * 4) = make_float4(ebl[q], M, l2s, 0.f);
+        if (lane == 0 && f < F && t0 + f < Tb) {
+          *reinterpret_cast<float4 *>(sb + f * 4) = make_float4(ebl[q], M, l2s, 0.f);
+          if (MODE == 1 && blockIdx.y == 0) *reinterpret_cast<float4 *>(ws.stat + ((size_t)b * p.T + t0 + f) * 4) = make_float4(ebl[q], M, l2s, 0.f);
+        }
       }
     };
 
@@ -279,25 +420,164 @@ __global__ __launch_bounds__(NBEST_THREADS) void nbest_kernel(const Problem p, c
   }
 }
 
-template <int KIND, int NL>
-hipError_t launch_nbest(const Problem &p, int N, float *loss, hipStream_t st) {
-  hipLaunchKernelGGL((nbest_kernel<KIND, NL>), dim3(p.B, (N + NBEST_G - 1) / NBEST_G), dim3(NBEST_THREADS), 0, st, p, N, loss);
+// ---- the gradient's row stage: one wavefront per row (b, t), four per workgroup ----
+constexpr int NBG_WAVES = 4;
+constexpr int NBG_CH = 1024;     // columns per pass
+constexpr int NBG_FIX = 40;      // fixed point: units of 2^(e - 40) with 2^e > max_n |weight[b, n]|, so |bin| < N 2^40
+
+template <int KIND>
+__global__ __launch_bounds__(64 * NBG_WAVES) void nbest_grad_row_kernel(const Problem p, const int N, const int UP,
+                                                                        const float *__restrict__ weight, const NbWs ws,
+                                                                        void *__restrict__ grad) {
+  constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are (token, blank) posteriors
+  __shared__ unsigned long long bins_all[NBG_WAVES][NBG_CH];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long row = (long)blockIdx.x * NBG_WAVES + wv;
+  if (row >= (long)p.B * p.T) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
+  unsigned long long *const bins = bins_all[wv];
+  const int b = (int)(row / p.T), t = (int)(row % p.T);
+  const int V = p.V, blank = p.blank, xdt = p.xdtype, gdt = p.gdtype;
+  const int Tb = frame_count(p, b);
+  const int xesz = xdt == 0 ? 4 : 2, gesz = gdt == 0 ? 4 : 2;
+  const char *const x = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb + (long)t * p.xst) * xesz;
+  char *const g = reinterpret_cast<char *>(grad) + (size_t)((long)b * p.gsb + (long)t * p.gst) * gesz;
+  const bool xvec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (xdt == 0 ? 15 : 7)) == 0;
+  const bool gvec = ((V | p.gsb | p.gst) & 3) == 0 && (reinterpret_cast<uintptr_t>(grad) & (gdt == 0 ? 15 : 7)) == 0;
+
+  // four consecutive elements of the gradient row from column k (k + 3 < V on the vector path; both paths convert alike)
+  auto gput4 = [&](int k, const float4 r) {
+    if (gdt == 0) {
+      if (gvec) { *reinterpret_cast<float4 *>(g + (size_t)k * 4) = r; return; }
+      float *const o = reinterpret_cast<float *>(g);
+      o[k] = r.x;
+      if (k + 1 < V) o[k + 1] = r.y;
+      if (k + 2 < V) o[k + 2] = r.z;
+      if (k + 3 < V) o[k + 3] = r.w;
+      return;
+    }
+    auto cv = [&](float f) { return gdt == 1 ? f32_to_bf16(f) : f32_to_f16(f); };
+    const unsigned short h0 = cv(r.x), h1 = cv(r.y), h2 = cv(r.z), h3 = cv(r.w);
+    if (gvec) {
+      *reinterpret_cast<uint2 *>(g + (size_t)k * 2) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
+      return;
+    }
+    unsigned short *const o = reinterpret_cast<unsigned short *>(g);
+    o[k] = h0;
+    if (k + 1 < V) o[k + 1] = h1;
+    if (k + 2 < V) o[k + 2] = h2;
+    if (k + 3 < V) o[k + 3] = h3;
+  };
+
+  // the weights of the hypotheses that count (lane n: hypothesis n; N <= 64): an infinite loss contributes nothing and its weight
+  // is not interpreted
+  float wn = 0.f;
+  if (lane < N && t < Tb) {
+    const double lp = ws.logp[(long)b * N + lane];
+    if (lp > -__builtin_inf() && lp < __builtin_inf()) wn = weight[(long)b * N + lane];
+  }
+  const float wsum = wave_sum(wn);
+  const float wmax = wave_max(fabsf(wn));
+  if (!(t < Tb) || !(wmax > 0.f)) {  // a padded frame, no feasible hypothesis (or zero weights alone): exactly zero
+    for (int k = lane * 4; k < V; k += 256) gput4(k, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  const int fe = __builtin_amdgcn_frexp_expf(wmax);  // wmax = m 2^fe, m in [0.5, 1)
+  const float4 sv = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
+  const float mx = sv.y, l2s = sv.z;
+  const bool wrt_logits = p.wrt == 0;
+  constexpr int SRD_B = 8;  // bytes per double
+  const size_t srd = (size_t)nb_row_doubles(KIND, UP) * SRD_B;
+
+  float blk = 0.f;  // the blank's share, lane-wise partial sums in a fixed order
+  for (int c0 = 0; c0 < V; c0 += NBG_CH) {
+#pragma unroll
+    for (int q = 0; q < NBG_CH / 64; ++q) bins[lane + 64 * q] = 0ull;
+    wave_lds_fence();
+    for (int n = 0; n < N; ++n) {
+      const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wn), n));
+      if (w == 0.f) continue;
+      const long hrow = (long)b * N + n;
+      const int L = label_count(p, (int)hrow);  // (feasible: L <= U <= UP)
+      const char *const r = reinterpret_cast<const char *>(ws.rows) + ((size_t)hrow * p.T + t) * srd;
+      const int32_t *const lab = p.labels + hrow * p.label_stride;
+      for (int i = lane; i < L; i += 64) {
+        const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+        const int tok = label_at(p, lab, i);
+        const unsigned rel = (unsigned)(tok - c0);
+        if (emits(p, tok) && rel < (unsigned)NBG_CH)
+          atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(w * pq.x, NBG_FIX - fe)));
+        if (c0 == 0) blk += w * pq.y;
+      }
+      if (c0 == 0 && lane == 0) blk += w * *reinterpret_cast<const float *>(r + (size_t)UP * SLOT);
+    }
+    if (c0 == 0) blk = wave_sum(blk);
+    wave_lds_fence();
+#pragma unroll
+    for (int q = 0; q < NBG_CH / 256; ++q) {
+      const int k = c0 + lane * 4 + 256 * q;
+      if (k < V) {
+        float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (wrt_logits) xv = xvec ? nb_row_load4(x, k, xdt) : nb_row_load4_elem(x, k, V, xdt);
+        float r[4];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[k - c0 + c]), fe - NBG_FIX) + (k + c == blank ? blk : 0.f);
+          // WRT_LOGITS: sum_n w_n (softmax(x)[k] - gamma_n[k]);  WRT_LOGPROBS: - sum_n w_n gamma_n[k]
+          r[c] = wrt_logits ? wsum * fexp2((xs[c] - mx) * LOG2E - l2s) - bin : -bin;
+        }
+        gput4(k, make_float4(r[0], r[1], r[2], r[3]));
+      }
+    }
+    wave_lds_fence();
+  }
+}
+
+template <int KIND, int NL, int MODE>
+hipError_t launch_nbest(const Problem &p, int N, float *loss, const NbWs &ws, hipStream_t st) {
+  hipLaunchKernelGGL((nbest_kernel<KIND, NL, MODE>), dim3(p.B, (N + NBEST_G - 1) / NBEST_G), dim3(NBEST_THREADS), 0, st, p, N, loss, ws);
   return hipGetLastError();
 }
+
+template <int MODE>
+hipError_t run_nbest_mode(const Problem &p, int N, float *loss, const NbWs &ws, hipStream_t st) {
+  typedef hipError_t Launch(const Problem &, int, float *, const NbWs &, hipStream_t);
+  static Launch *const table[2][5] = {
+      {launch_nbest<0, 1, MODE>, launch_nbest<0, 2, MODE>, launch_nbest<0, 4, MODE>, launch_nbest<0, 8, MODE>, launch_nbest<0, 16, MODE>},
+      {launch_nbest<1, 1, MODE>, launch_nbest<1, 2, MODE>, launch_nbest<1, 4, MODE>, launch_nbest<1, 8, MODE>, launch_nbest<1, 16, MODE>}};
+  const int NL = nl_for(p.U);
+  const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
+  if (lg < 0 || p.kind < 0 || p.kind > 1 || N < 1) return hipErrorInvalidValue;
+  return table[p.kind][lg](p, N, loss, ws, st);
+}
+
+inline size_t nb_al(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace
 
 size_t nbest_workspace_bytes(int, int, int, int, int, int) { return 0; }
 
-hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st) {
-  typedef hipError_t Launch(const Problem &, int, float *, hipStream_t);
-  static Launch *const table[2][5] = {
-      {launch_nbest<0, 1>, launch_nbest<0, 2>, launch_nbest<0, 4>, launch_nbest<0, 8>, launch_nbest<0, 16>},
-      {launch_nbest<1, 1>, launch_nbest<1, 2>, launch_nbest<1, 4>, launch_nbest<1, 8>, launch_nbest<1, 16>}};
-  const int NL = nl_for(p.U);
-  const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
-  if (lg < 0 || p.kind < 0 || p.kind > 1 || N < 1) return hipErrorInvalidValue;
-  return table[p.kind][lg](p, N, loss, st);
+hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st) { return run_nbest_mode<0>(p, N, loss, NbWs{nullptr, nullptr, nullptr}, st); }
+
+// saved rows, then the row statistics, then log2 P: each region rounded up to 256 bytes (include/ctc_amd.h has the formula)
+size_t nbest_grad_workspace_bytes(int kind, int B, int T, int, int U, int N) {
+  const size_t rows = (size_t)B * N * T * nb_row_doubles(kind, 64 * nl_for(U)) * 8;
+  return nb_al(rows) + nb_al((size_t)B * T * 16) + nb_al((size_t)B * N * 8);
+}
+
+hipError_t run_nbest_grad(const Problem &p, int N, const float *weight, float *loss, void *grad, char *wsp, hipStream_t st) {
+  const int UP = 64 * nl_for(p.U);
+  const size_t rows = nb_al((size_t)p.B * N * p.T * nb_row_doubles(p.kind, UP) * 8);
+  const NbWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + rows),
+                reinterpret_cast<double *>(wsp + rows + nb_al((size_t)p.B * p.T * 16))};
+  if (hipError_t e = run_nbest_mode<1>(p, N, loss, ws, st)) return e;
+  if (p.T == 0) return hipSuccess;  // no rows
+  if (hipError_t e = run_nbest_mode<2>(p, N, loss, ws, st)) return e;
+  const unsigned blocks = (unsigned)(((long)p.B * p.T + NBG_WAVES - 1) / NBG_WAVES);
+  if (p.kind == 0) hipLaunchKernelGGL((nbest_grad_row_kernel<0>), dim3(blocks), dim3(64 * NBG_WAVES), 0, st, p, N, UP, weight, ws, grad);
+  else hipLaunchKernelGGL((nbest_grad_row_kernel<1>), dim3(blocks), dim3(64 * NBG_WAVES), 0, st, p, N, UP, weight, ws, grad);
+  return hipGetLastError();
 }
 
 }  // namespace ctc

@@ -367,8 +367,40 @@ class CtcNbestLoss(NamedTuple):
     log_posterior: torch.Tensor
 
 
+class _NbestLossFn(torch.autograd.Function):
+    """loss[B, N] of ops.nbest_loss with a gradient for the logits: forward is the forward-only launch and keeps nothing but the
+    inputs; backward is ONE ops.nbest_loss_grad call with weight = d_loss (where the loss is +inf the incoming gradient is not
+    interpreted: the NaN / inf that the backward of `where` and `logsumexp` produce there do no harm).  Backward is not itself
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U):
+        ctx.save_for_backward(x, labels, label_length, logit_length)
+        ctx.call = (kind, wrt, blank, U)
+        return ops.nbest_loss(kind, wrt, labels, x, label_length, logit_length, blank, U)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss):
+        x, labels, label_length, logit_length = ctx.saved_tensors
+        kind, wrt, blank, U = ctx.call
+        _, grad = ops.nbest_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype)
+        return grad, None, None, None, None, None, None, None
+
+
+def _nbest_tail(loss, hypothesis_mask) -> CtcNbestLoss:
+    if hypothesis_mask is not None:
+        mask = _as_tensor(hypothesis_mask).to(device=loss.device, dtype=torch.bool)
+        assert tuple(mask.shape) == tuple(loss.shape)
+        loss = torch.where(mask, loss, torch.full_like(loss, float("inf")))
+    # (a list of +inf alone: logsumexp is -inf and -inf - -inf would be NaN)
+    lse = torch.logsumexp(-loss, dim=1, keepdim=True) if loss.shape[1] else loss.new_zeros((loss.shape[0], 1))
+    logp = torch.where(torch.isinf(loss) & (loss > 0), torch.full_like(loss, float("-inf")), -loss - lse)
+    return CtcNbestLoss(loss, logp)
+
+
 def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, hypothesis_mask=None,
-           max_label_length=None) -> CtcNbestLoss:
+           max_label_length=None, differentiable=False) -> CtcNbestLoss:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -383,21 +415,18 @@ def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blan
     assert x.shape[0] == labels.shape[0] == label_length.shape[0] == logit_length.shape[0]
     assert labels.shape[1] == label_length.shape[1]
     U = None if max_label_length is None else max(0, min(int(labels.shape[2]), int(max_label_length)))
+    if differentiable and x.requires_grad and torch.is_grad_enabled():
+        # the mask and the log_posterior arithmetic are ordinary torch operations on the attached loss
+        loss = _NbestLossFn.apply(x, labels, label_length, logit_length, ops.KINDS[kind_name], wrt, _blank(blank_index), U)
+        return _nbest_tail(loss, hypothesis_mask)
     with torch.no_grad():  # forward only: the result is detached
         loss = ops.nbest_loss(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), U)
-        if hypothesis_mask is not None:
-            mask = _as_tensor(hypothesis_mask).to(device=loss.device, dtype=torch.bool)
-            assert tuple(mask.shape) == tuple(loss.shape)
-            loss = torch.where(mask, loss, torch.full_like(loss, float("inf")))
-        # (a list of +inf alone: logsumexp is -inf and -inf - -inf would be NaN)
-        lse = torch.logsumexp(-loss, dim=1, keepdim=True) if loss.shape[1] else loss.new_zeros((loss.shape[0], 1))
-        logp = torch.where(torch.isinf(loss) & (loss > 0), torch.full_like(loss, float("-inf")), -loss - lse)
-        return CtcNbestLoss(loss, logp)
+        return _nbest_tail(loss, hypothesis_mask)
 
 
 def classic_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                            blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
-                           max_label_length: Optional[int] = None) -> CtcNbestLoss:
+                           max_label_length: Optional[int] = None, differentiable: bool = False) -> CtcNbestLoss:
     """The exact classic CTC loss of N label sequences per utterance against the same logits, the logits read once per group of
     eight hypotheses instead of once each: what re-ranks an N-best list (the scores of classic_ctc_beam_search are sums inside
     the beam: lower bounds) and turns it into confidences.
@@ -411,26 +440,35 @@ def classic_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length:
         hypothesis_mask: (keyword only) [batch, nbest] bool; where False the loss is +inf and the entry takes no part in the
             normalisation -- pass `isfinite(score)` for the missing hypotheses of a CtcBeamDecoding.
         max_label_length: (keyword only) as in classic_ctc_loss: an upper bound on label_length known on the host.
-    Returns: CtcNbestLoss(loss, log_posterior), both [batch, nbest] float32, not differentiable (logits that require grad are
-        accepted; the result is detached).  A duplicate hypothesis is counted twice in log_posterior.  nbest <= 64; a
+        differentiable: (keyword only) False (default): the result is detached, whatever the logits require.  True, with logits
+            that require grad: `loss` and `log_posterior` carry a gradient for the logits, so that an expected-risk (MWER-style)
+            objective such as (log_posterior.exp() * risk).sum() trains end to end.  Backward is ONE call, whatever nbest is: the
+            gradient of sum_n d_loss[b, n] * loss[b, n], to which a hypothesis with loss +inf contributes exactly zero.  First
+            derivatives only: backward is not itself differentiable.  The values are the same bits either way.
+    Returns: CtcNbestLoss(loss, log_posterior), both [batch, nbest] float32 (detached unless `differentiable`; logits that
+        require grad are accepted either way).  A duplicate hypothesis is counted twice in log_posterior.  nbest <= 64; a
         hypothesis that is infeasible or malformed (a label outside [0, num_tokens) or equal to the blank, a negative length
         counts as empty) has loss +inf and changes no other entry."""
-    return _nbest("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length)
+    return _nbest("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length,
+                  differentiable)
 
 
 def simplified_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                               blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
-                              max_label_length: Optional[int] = None) -> CtcNbestLoss:
+                              max_label_length: Optional[int] = None, differentiable: bool = False) -> CtcNbestLoss:
     """The same on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
-    classic_ctc_nbest_loss."""
-    return _nbest("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length)
+    classic_ctc_nbest_loss, `differentiable` (first derivatives only) included."""
+    return _nbest("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length,
+                  differentiable)
 
 
 def ctc_nbest_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *,
-                                 hypothesis_mask: Optional[TensorLike] = None, max_label_length: Optional[int] = None) -> CtcNbestLoss:
-    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+                                 hypothesis_mask: Optional[TensorLike] = None, max_label_length: Optional[int] = None,
+                                 differentiable: bool = False) -> CtcNbestLoss:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba).  With `differentiable` the
+    gradient is the one with respect to the log-probabilities (first derivatives only: backward is not itself differentiable)."""
     return _nbest(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                  hypothesis_mask, max_label_length)
+                  hypothesis_mask, max_label_length, differentiable)
 
 
 # --------------------------------------------------------------------------------------------------

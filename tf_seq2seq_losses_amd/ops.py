@@ -496,18 +496,13 @@ def beam_search(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor
     return score, labels, label_length
 
 
-def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
-               blank: int, U: Optional[int] = None) -> torch.Tensor:
-    """loss[B, N] float32: the exact loss of the N label sequences labels[b, n, :label_length[b, n]] of every utterance against the
-    same logits[b] (ctc_amd_nbest_loss), the logits read once per group of _lib.NBEST_GROUP hypotheses.  labels [B, N, W] and
-    label_length [B, N] in the layout beam_search returns; U bounds every label_length (a longer hypothesis is +inf; default: the
-    labels' width W, or the maximum inside when W is large, as Prepared finds it).  Takes the logits as greedy_decode does and does not synchronise."""
+def _nbest_args(what: str, labels, x, label_length, logit_length, U):
+    """The inputs of the two N-best entry points as the C ABI takes them: (labels, x, label_length, logit_length, U, N, W)."""
     _require_gpu(x)
-    lib = _lib.load()
     dev = x.device
     B, T, V = (int(s) for s in x.shape)
     if labels.dim() != 3 or label_length.dim() != 2 or int(labels.shape[0]) != B or tuple(label_length.shape) != tuple(labels.shape[:2]):
-        raise ValueError(f"nbest_loss: labels must be [B, N, W] and label_length [B, N] with B = {B}, got {tuple(labels.shape)} and "
+        raise ValueError(f"{what}: labels must be [B, N, W] and label_length [B, N] with B = {B}, got {tuple(labels.shape)} and "
                          f"{tuple(label_length.shape)}")
     N, W = int(labels.shape[1]), int(labels.shape[2])
     if U is None:  # as Prepared: the width always works; a wide tensor is worth one look at the maximum inside (a beam search's is T wide)
@@ -525,7 +520,19 @@ def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label
 
     def i32(t):
         return t if (t.dtype == torch.int32 and t.device == dev and t.is_contiguous()) else t.to(device=dev, dtype=torch.int32).contiguous()
-    labels, label_length, logit_length = i32(labels), i32(label_length), i32(logit_length)
+    return i32(labels), x, i32(label_length), i32(logit_length), U, N, W
+
+
+def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+               blank: int, U: Optional[int] = None) -> torch.Tensor:
+    """loss[B, N] float32: the exact loss of the N label sequences labels[b, n, :label_length[b, n]] of every utterance against the
+    same logits[b] (ctc_amd_nbest_loss), the logits read once per group of _lib.NBEST_GROUP hypotheses.  labels [B, N, W] and
+    label_length [B, N] in the layout beam_search returns; U bounds every label_length (a longer hypothesis is +inf; default: the
+    labels' width W, or the maximum inside when W is large, as Prepared finds it).  Takes the logits as greedy_decode does and does not synchronise."""
+    labels, x, label_length, logit_length, U, N, W = _nbest_args("nbest_loss", labels, x, label_length, logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
     key = ("nbest_loss", kind, B, T, V, U, N)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and N, which an empty batch would otherwise skip)
@@ -539,6 +546,44 @@ def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label
                                     _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(loss), _ptr(ws), n, _stream(dev))
     _lib.check(rc, "ctc_amd_nbest_loss")
     return loss
+
+
+def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+                    blank: int, weight: torch.Tensor, U: Optional[int] = None,
+                    grad_dtype: Optional[torch.dtype] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(loss[B, N] float32, grad[B, T, V]): the losses of nbest_loss, bit for bit, and the gradient of sum_n weight[b, n] * loss[b, n]
+    with respect to x (ctc_amd_nbest_loss_grad).  A hypothesis whose loss is +inf contributes nothing and its weight is not
+    interpreted (it may be NaN or infinite).  Arguments as nbest_loss; weight [B, N]; grad is contiguous, of grad_dtype (default:
+    the element type the logits are passed in).  Does not synchronise."""
+    labels, x, label_length, logit_length, U, N, W = _nbest_args("nbest_loss_grad", labels, x, label_length, logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if tuple(weight.shape) != (B, N):
+        raise ValueError(f"nbest_loss_grad: weight must be [B, N] = {(B, N)}, got {tuple(weight.shape)}")
+    if not (weight.dtype == torch.float32 and weight.device == dev and weight.is_contiguous()):
+        weight = weight.to(device=dev, dtype=torch.float32).contiguous()
+    if grad_dtype is None:
+        grad_dtype = x.dtype
+    if grad_dtype not in _DTYPES:
+        raise ValueError(f"nbest_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
+    key = ("nbest_loss_grad", kind, B, T, V, U, N)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, U and N, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.nbest_loss_grad_workspace_bytes(kind, B, T, V, U, N)
+    loss = torch.empty((B, N), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, T, V), dtype=grad_dtype, device=dev)
+    if B == 0:
+        return loss, grad
+    if T == 0:  # no row to write (and no gradient pointer to pass): the loss alone
+        return nbest_loss(kind, wrt, labels, x, label_length, logit_length, blank, U), grad
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_nbest_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                         _ptr(label_length), _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(weight), _ptr(loss),
+                                         _ptr(grad), _DTYPES[grad_dtype], T * V, V, _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_nbest_loss_grad")
+    return loss, grad
 
 
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
