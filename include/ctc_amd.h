@@ -517,6 +517,51 @@ int ctc_amd_nbest_loss_grad(int kind, int wrt,
                             void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * N-best forced alignment (added under ABI v6: two new entry points, nothing existing changed): where each of N label sequences
+ * per utterance lies in time.  What N calls of ctc_amd_best_path on labels + n * label_stride would give, from one read of the
+ * logits per group of CTC_AMD_NBEST_GROUP hypotheses and with eight chains per workgroup.  Hypothesis (b, n) lies at
+ * labels + (b * N + n) * label_stride, its length at label_length[b * N + n]: the layout ctc_amd_beam_search writes and
+ * ctc_amd_nbest_loss reads.  Per hypothesis, for the utterance logits[b]:
+ *   score[B][N]             float32: as ctc_amd_best_path documents it; -inf when no path exists
+ *   tokens[B][N][T]         int32:   as ctc_amd_best_path: pi_t, -1 for t >= T_b
+ *   label_index[B][N][T]    int32:   as ctc_amd_best_path: -1 on blank frames and for t >= T_b.  May be NULL.
+ *   first_frame[B][N][U]    int32:   the first frame whose label_index is i, for i < label_length[b, n]; -1 for
+ *   last_frame[B][N][U]     int32:   label_length[b, n] <= i < U.  ... and the last.  On the simplified lattice the two are equal.
+ *                                    Each may be NULL.
+ * An infeasible hypothesis gets score = -inf and -1 in every frame and label, and changes nothing else.  The infeasible cases
+ * are those of ctc_amd_nbest_loss: too few frames, label_length > U, a label outside [0, V) or equal to blank_index inside
+ * label_length, a label position beyond label_stride, no path of finite value.  label_length <= 0 is the all-blank path; labels
+ * beyond label_length are not read.  T_b = logit_length[b] clamped to [0, T]; frames beyond it are not read; T_b == 0 gives score 0
+ * for an empty hypothesis and -inf otherwise.  B == 0 returns CTC_AMD_OK without a launch.
+ * Every output of (b, n) has the same bits whatever N is, whatever the other hypotheses are and wherever in the list it stands,
+ * and on every run: no floating-point atomics anywhere, every element has one writer.
+ * Ties: among paths of equal float64 value the choice is deterministic but unspecified, in the words of ctc_amd_best_path.  That
+ * is the guarantee.  The recursion, its candidate order and its strict comparisons are those of ctc_amd_best_path, so in practice
+ * the path is the one that call chooses; the tests hold the two equal on random inputs, the ABI does not promise it.  `score` may
+ * differ from ctc_amd_best_path's in its last bits (the float64 sum of the rows' log-sum-exps is taken in another order).
+ * Results for NaN and +inf inputs are unspecified (the call completes).
+ * Limits and validation are those of ctc_amd_nbest_loss, checked in the same order: 1 <= N <= CTC_AMD_NBEST_MAX, B * N < 2^31,
+ * U <= CTC_AMD_MAX_U, 0 <= blank_index < V, V <= CTC_AMD_MAX_V (no row is staged in LDS), the producer formats of
+ * ctc_amd_loss_grad_ex with both access paths; then score and tokens must be non-NULL (CTC_AMD_EINVAL), then the workspace.
+ * Workspace (may hold anything on entry; too small: CTC_AMD_EWORKSPACE before any launch): the back-pointers alone.  With NL the
+ * smallest power of two with 64 * NL >= U (1 for U <= 64), word = 1, 1, 2, 4, 8 bytes for NL = 1, 2, 4, 8, 16 and r256(x) = x
+ * rounded up to a multiple of 256:
+ *   ctc_amd_nbest_best_path_workspace_bytes = r256(B * N * T * 64 * word)
+ * B = 256, T = 1000, U = 128, N = 8: 131 MB.  One launch of B * ceil(N / CTC_AMD_NBEST_GROUP) workgroups (sweep and back-trace
+ * in the same kernel), asynchronous on `stream`, capturable.  No allocation, copy or synchronisation.
+ */
+int ctc_amd_nbest_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes /*host*/);
+int ctc_amd_nbest_best_path(int kind, int wrt,
+                            const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride,
+                            const int32_t *label_length /* [B][N] */, const int32_t *logit_length, int blank_index,
+                            int B, int T, int V, int U, int N,
+                            float *score /* [B][N] */, int32_t *tokens /* [B][N][T] */,
+                            int32_t *label_index /* [B][N][T], may be NULL */,
+                            int32_t *first_frame /* [B][N][U], may be NULL */, int32_t *last_frame /* [B][N][U], may be NULL */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,9 @@ SIGNATURES = {
     "ctc_amd_nbest_loss": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),  # N, loss, ws, bytes, stream
     "ctc_amd_nbest_loss_grad_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
     "ctc_amd_nbest_loss_grad": (_c_int, _COMMON_EX + [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),  # N, weight, loss .. grad strides, ws, bytes, stream
+    "ctc_amd_nbest_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
+    "ctc_amd_nbest_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # N, score, tokens, label_index, first_frame, last_frame
+                                                      _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
 }
 
 _lib = None
@@ -177,4 +180,10 @@ def nbest_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int
 def nbest_loss_grad_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_nbest_loss_grad_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_loss_grad_workspace_bytes")
+    return int(out.value)
+
+
+def nbest_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_nbest_best_path_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_best_path_workspace_bytes")
     return int(out.value)

@@ -9,6 +9,7 @@
 #include "ctc_common.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_launch.h"
+#include "ctc_nbest_align.h"
 
 namespace ctc {
 // diagnostic override read by ctc_hessian.hip (ctc_amd_debug_override): process-wide, written only by tests / benchmarks between calls
@@ -708,6 +709,36 @@ int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dt
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_nbest_grad(p, N, weight, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
           "N-best loss gradient launch");
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_nbest_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_nbest(B, V, N)) return rc;
+  *out_bytes = ctc::nbest_align_workspace_bytes(B, T, U, N);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_nbest_loss: common arguments, element type, B == 0, strides, the vocabulary limit and N; then the
+// two outputs that must exist and the workspace.
+int ctc_amd_nbest_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                            int blank_index, int B, int T, int V, int U, int N, float *score, int32_t *tokens, int32_t *label_index,
+                            int32_t *first_frame, int32_t *last_frame, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (int rc = check_nbest(B, V, N)) return rc;
+  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
+  const size_t need = ctc::nbest_align_workspace_bytes(B, T, U, N);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_nbest_align(p, N, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                               static_cast<hipStream_t>(stream)), "N-best alignment launch");
   return CTC_AMD_OK;
 }
 

@@ -472,6 +472,92 @@ def ctc_nbest_loss_from_logproba(labels, logprobas, label_length, logit_length, 
 
 
 # --------------------------------------------------------------------------------------------------
+# N-best forced alignment: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcNbestAlignment(NamedTuple):
+    """score [batch, nbest] float32: log-probability of each hypothesis' best path (-inf: infeasible, malformed or masked);
+    tokens [batch, nbest, max_length] int32: the token every frame emits on it (-1 beyond logit_length);
+    label_index [batch, nbest, max_length] int32: index into labels[b, n] of the label the frame emits -- on the classic lattice
+    also of the label it continues by repeating it -- and -1 on blank frames and beyond logit_length;
+    first_frame, last_frame [batch, nbest, max_label_length] int32: the first and the last frame of every label (equal on the
+    simplified lattice), -1 beyond label_length.
+    An infeasible, malformed or masked hypothesis has score = -inf and -1 in every frame and label."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    label_index: torch.Tensor
+    first_frame: torch.Tensor
+    last_frame: torch.Tensor
+
+
+def _nbest_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, hypothesis_mask=None,
+                 max_label_length=None) -> CtcNbestAlignment:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    assert x.dim() == 3
+    assert x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+    assert labels.dim() == 3
+    assert label_length.dim() == 2
+    assert logit_length.dim() == 1
+    assert x.shape[0] == labels.shape[0] == label_length.shape[0] == logit_length.shape[0]
+    assert labels.shape[1] == label_length.shape[1]
+    U = None if max_label_length is None else max(0, min(int(labels.shape[2]), int(max_label_length)))
+    with torch.no_grad():  # a path is not differentiable: the result is detached
+        out = ops.nbest_best_path(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), U)
+        if hypothesis_mask is not None:  # a masked hypothesis reads as infeasible
+            score = out[0]
+            mask = _as_tensor(hypothesis_mask).to(device=score.device, dtype=torch.bool)
+            assert tuple(mask.shape) == tuple(score.shape)
+            out = (torch.where(mask, score, torch.full_like(score, float("-inf"))),
+                   *(torch.where(mask[:, :, None], t, torch.full_like(t, -1)) for t in out[1:]))
+        return CtcNbestAlignment(*out)
+
+
+def classic_ctc_nbest_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
+                                max_label_length: Optional[int] = None) -> CtcNbestAlignment:
+    """Forced alignment of N label sequences per utterance on the classic lattice, in one call: what classic_ctc_alignment gives
+    for labels[:, n], for every n, with the logits read once per group of eight hypotheses, plus the first and last frame of
+    every label.  Timestamps for an N-best list.
+
+    Args:
+        labels:       [batch, nbest, max_label_length] int32 -- a CtcBeamDecoding's `labels` as it stands (padding is not read)
+        logits:       [batch, max_length, num_tokens] float32 / bfloat16 / float16 (any batch / time strides)
+        label_length: [batch, nbest] int32
+        logit_length: [batch] int32
+        blank_index:  int
+        hypothesis_mask: (keyword only) [batch, nbest] bool; where False the hypothesis reads as infeasible (score -inf, -1
+            everywhere) -- pass `isfinite(score)` for the missing hypotheses of a CtcBeamDecoding.
+        max_label_length: (keyword only) as in classic_ctc_loss: an upper bound on label_length known on the host; it is also the
+            width of first_frame / last_frame (default: the width of `labels`, or the largest label_length when that is large).
+    Returns: CtcNbestAlignment(score, tokens, label_index, first_frame, last_frame), not differentiable.  nbest <= 64; a hypothesis
+        that is infeasible or malformed has score -inf and -1 everywhere and changes no other entry.  Among paths of equal value
+        the choice is deterministic but unspecified."""
+    return _nbest_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask,
+                        max_label_length)
+
+
+def simplified_ctc_nbest_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                   blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
+                                   max_label_length: Optional[int] = None) -> CtcNbestAlignment:
+    """The same on the simplified lattice (every non-blank frame emits exactly one label: first_frame equals last_frame).  Same
+    arguments and return value as classic_ctc_nbest_alignment."""
+    return _nbest_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask,
+                        max_label_length)
+
+
+def ctc_nbest_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *,
+                                      hypothesis_mask: Optional[TensorLike] = None,
+                                      max_label_length: Optional[int] = None) -> CtcNbestAlignment:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba)."""
+    return _nbest_align(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                        hypothesis_mask, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # loss-data objects (what the reference's unit tests poke at directly)
 # --------------------------------------------------------------------------------------------------
 class BaseCtcLossData:

@@ -586,6 +586,36 @@ def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     return loss, grad
 
 
+def nbest_best_path(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+                    blank: int, U: Optional[int] = None):
+    """(score[B, N] float32, tokens[B, N, T] int32, label_index[B, N, T] int32, first_frame[B, N, U] int32, last_frame[B, N, U] int32):
+    the best path of every one of the N label sequences labels[b, n, :label_length[b, n]] against the same logits[b], and the first
+    and last frame of every label on it (ctc_amd_nbest_best_path), the logits read once per group of _lib.NBEST_GROUP hypotheses.
+    Arguments as nbest_loss; U (default as there) is also the width of first_frame / last_frame.  Does not synchronise."""
+    labels, x, label_length, logit_length, U, N, W = _nbest_args("nbest_best_path", labels, x, label_length, logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    key = ("nbest_best_path", kind, B, T, V, U, N)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, U and N, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.nbest_best_path_workspace_bytes(kind, B, T, V, U, N)
+    score = torch.empty((B, N), dtype=torch.float32, device=dev)
+    tokens = torch.empty((B, N, T), dtype=torch.int32, device=dev)
+    label_index = torch.empty((B, N, T), dtype=torch.int32, device=dev)
+    first_frame = torch.empty((B, N, U), dtype=torch.int32, device=dev)
+    last_frame = torch.empty((B, N, U), dtype=torch.int32, device=dev)
+    if B == 0:
+        return score, tokens, label_index, first_frame, last_frame
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_nbest_best_path(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                         _ptr(label_length), _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(score), _ptr(tokens),
+                                         _ptr(label_index), _ptr(first_frame), _ptr(last_frame), ws.data_ptr(), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_nbest_best_path")
+    return score, tokens, label_index, first_frame, last_frame
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
