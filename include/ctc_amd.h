@@ -562,6 +562,40 @@ int ctc_amd_nbest_best_path(int kind, int wrt,
                             int32_t *first_frame /* [B][N][U], may be NULL */, int32_t *last_frame /* [B][N][U], may be NULL */,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Edit distance of N-best lists (added under ABI v6: two new entry points, nothing existing changed): the Levenshtein distance --
+ * unit cost for insertion, deletion and substitution -- of every hypothesis to its utterance's reference transcript, the risk of
+ * MWER-style training (minimum word error rate: expected risk over a beam) and the numerator of a token error rate.
+ *   distance[b, n] = D(hyp[b, n, :h], ref[b, :r])                                int32 [B][N], exact
+ * Hypothesis (b, n) lies at hyp + (b * N + n) * hyp_stride, its length at hyp_length[b * N + n]: the layout ctc_amd_beam_search
+ * writes (decoded[B][nbest][T] with hyp_stride = T, decoded_length[B][nbest]) and ctc_amd_nbest_loss reads.  The reference of
+ * utterance b lies at ref + b * ref_stride, its length at ref_length[b].  It replaces nothing in the reference implementation,
+ * which has no counterpart; it replaces a copy of the hypotheses to the host, a dynamic programme there and a copy back.
+ * Tokens are arbitrary int32 values compared for equality: there is no vocabulary limit and no blank, so word ids mapped on the host
+ * work as well as characters or sub-word units.
+ * Lengths: h = hyp_length[b, n] clamped to [0, hyp_stride], r = ref_length[b] clamped to [0, ref_stride]; elements beyond h and r
+ * are not read (the -1 padding of the beam search included).  h == 0 gives r and r == 0 gives h.
+ * R bounds every reference length, 0 <= R <= CTC_AMD_MAX_U: an utterance with r > R gets distance = -1 for all its hypotheses
+ * and changes nothing else (the counterpart of "label_length > U gives +inf").  The hypothesis length has no limit other than the
+ * stride, 0 <= hyp_stride <= CTC_AMD_EDIT_MAX_STRIDE.  N >= 1 (no upper limit), B * N < 2^31.  B == 0 returns CTC_AMD_OK without a
+ * launch.
+ * Validation before any launch (CTC_AMD_EINVAL, ctc_amd_last_error): negative B, R or strides, R or hyp_stride beyond its limit,
+ * N < 1, the product limit, then null pointers (hyp / ref may be NULL when their stride is 0).
+ * Every element of `distance` has one writer; distance[b, n] is the same whatever N is, whatever the other hypotheses are and
+ * wherever in the list it stands, and on every run.
+ * Workspace: none.  ctc_amd_edit_distance_workspace_bytes returns 0 for every valid shape (it exists so that a caller written
+ * against it keeps working should that change) and `workspace` may be NULL.  One launch of ceil(B * N / 4) workgroups, one
+ * wavefront per pair, h + ceil(r / NL) - 1 <= h + 63 sequential steps each with NL the smallest power of two with 64 * NL >= R
+ * (DESIGN.md section 5.13); asynchronous on `stream`, capturable, no allocation, copy or synchronisation.
+ */
+#define CTC_AMD_EDIT_MAX_STRIDE 2147479552 /* 2^31 - 4096: row indices and distances stay inside int32 */
+int ctc_amd_edit_distance_workspace_bytes(int B, int N, int R, size_t *out_bytes /*host*/);
+int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length /* [B][N] */,
+                          const int32_t *ref, int ref_stride, const int32_t *ref_length /* [B] */,
+                          int B, int N, int R,
+                          int32_t *distance /* [B][N] */,
+                          void *workspace /* may be NULL */, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,10 @@ SIGNATURES = {
     "ctc_amd_nbest_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
     "ctc_amd_nbest_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # N, score, tokens, label_index, first_frame, last_frame
                                                       _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
+    "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
+    "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
+                                       _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
+                                       _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
 }
 
 _lib = None
@@ -186,4 +190,10 @@ def nbest_loss_grad_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N
 def nbest_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_nbest_best_path_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def edit_distance_workspace_bytes(B: int, N: int, R: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_edit_distance_workspace_bytes(B, N, R, ctypes.byref(out)), "ctc_amd_edit_distance_workspace_bytes")
     return int(out.value)

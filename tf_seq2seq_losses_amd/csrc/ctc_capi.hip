@@ -742,4 +742,42 @@ int ctc_amd_nbest_best_path(int kind, int wrt, const void *logits, int logits_dt
   return CTC_AMD_OK;
 }
 
+// what ctc_amd_edit_distance and its size query take as a shape
+int check_edit(int B, int N, int R) {
+  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
+  if (R > MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, MAX_U);
+  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_edit_distance_workspace_bytes(int B, int N, int R, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (int rc = check_edit(B, N, R)) return rc;
+  *out_bytes = 0;
+  return CTC_AMD_OK;
+}
+
+// Checked before any launch: the sizes and R, B == 0, then N and the number of pairs, the strides, the pointers.  No workspace: the
+// pointer may be null.
+int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length, const int32_t *ref, int ref_stride,
+                          const int32_t *ref_length, int B, int N, int R, int32_t *distance, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
+  if (R > MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, MAX_U);
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = check_edit(B, N, R)) return rc;
+  if (hyp_stride < 0 || ref_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d ref_stride=%d", hyp_stride, ref_stride);
+  if (hyp_stride > CTC_AMD_EDIT_MAX_STRIDE) return fail(CTC_AMD_EINVAL, "hyp_stride=%d exceeds the supported maximum %d", hyp_stride, CTC_AMD_EDIT_MAX_STRIDE);
+  if (!hyp_length || !ref_length) return fail(CTC_AMD_EINVAL, "null length pointer");
+  if (hyp_stride > 0 && !hyp) return fail(CTC_AMD_EINVAL, "null hyp pointer");
+  if (ref_stride > 0 && !ref) return fail(CTC_AMD_EINVAL, "null ref pointer");
+  if (!distance) return fail(CTC_AMD_EINVAL, "null distance pointer");
+  CTC_TRY(ctc::run_edit_distance(hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length, B, N, R, distance,
+                                 static_cast<hipStream_t>(stream)), "edit distance launch");
+  return CTC_AMD_OK;
+}
+
 }  // extern "C"

@@ -56,6 +56,10 @@ hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st);
 size_t nbest_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N);
 hipError_t run_nbest_grad(const Problem &p, int N, const float *weight, float *loss, void *grad, char *ws, hipStream_t st);
 
+// ctc_edit.hip: edit distance of every hypothesis (b, n) to its utterance's reference; one wavefront per pair, one launch, no workspace
+hipError_t run_edit_distance(const int *hyp, int hyp_stride, const int *hyp_length, const int *ref, int ref_stride, const int *ref_length,
+                             int B, int N, int R, int *distance, hipStream_t st);
+
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
 extern int g_wide_diag;  // timing diagnostics (results are then meaningless)

@@ -558,6 +558,143 @@ def ctc_nbest_alignment_from_logproba(labels, logprobas, label_length, logit_len
 
 
 # --------------------------------------------------------------------------------------------------
+# edit distance of N-best lists and the MWER loss: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcEditDistance(NamedTuple):
+    """distance [batch, nbest] int32: the Levenshtein distance (unit cost for insertion, deletion and substitution) of every
+    hypothesis to its utterance's reference, -1 where masked;
+    error_rate [batch, nbest] float32: distance / max(reference_length, 1), NaN where masked.
+    Both are [batch] when the hypotheses were passed as [batch, width]."""
+    distance: torch.Tensor
+    error_rate: torch.Tensor
+
+
+def ctc_edit_distance(hypotheses: TensorLike, hypothesis_length: TensorLike, references: TensorLike, reference_length: TensorLike, *,
+                      hypothesis_mask: Optional[TensorLike] = None) -> CtcEditDistance:
+    """How wrong a decoding is: the edit distance of every hypothesis to the reference transcript of its utterance, on the device,
+    in one launch and without a synchronisation.  Tokens are any int32 values compared for equality (characters, sub-word units,
+    word ids mapped on the host); there is no blank and no vocabulary limit.
+
+    Args:
+        hypotheses:        [batch, nbest, width] int32 -- a CtcBeamDecoding's `labels` as it stands (padding is not read) -- or
+                           [batch, width] with a [batch] length: one hypothesis per utterance, e.g. a CtcDecoding's `labels` (the
+                           token error rate of greedy decoding); the result is then [batch].
+        hypothesis_length: [batch, nbest] (or [batch]) int32
+        references:        [batch, max_label_length] int32, at most 1024 wide
+        reference_length:  [batch] int32
+        hypothesis_mask:   (keyword only) [batch, nbest] (or [batch]) bool; where False the distance is -1 and the error rate NaN
+                           -- pass `isfinite(score)` for the missing hypotheses of a CtcBeamDecoding.
+    Returns: CtcEditDistance(distance, error_rate), not differentiable."""
+    hyp = _as_tensor(hypotheses, torch.int32)
+    hyp_length = _as_tensor(hypothesis_length, torch.int32)
+    ref = _as_tensor(references, torch.int32)
+    ref_length = _as_tensor(reference_length, torch.int32)
+    single = hyp.dim() == 2
+    if single:
+        assert hyp_length.dim() == 1
+        hyp, hyp_length = hyp[:, None, :], hyp_length[:, None]
+    assert hyp.dim() == 3
+    assert hyp_length.dim() == 2
+    assert ref.dim() == 2
+    assert ref_length.dim() == 1
+    assert hyp.shape[0] == hyp_length.shape[0] == ref.shape[0] == ref_length.shape[0]
+    assert hyp.shape[1] == hyp_length.shape[1]
+    with torch.no_grad():
+        distance = ops.edit_distance(hyp, hyp_length, ref, ref_length)
+        ref_length = ref_length.to(device=distance.device)
+        # (the lengths as the kernel reads them: clamped to the tensor's width)
+        rate = distance.to(torch.float32) / ref_length.clamp(1, max(int(ref.shape[1]), 1)).to(torch.float32)[:, None]
+        if hypothesis_mask is not None:
+            mask = _as_tensor(hypothesis_mask).to(device=distance.device, dtype=torch.bool)
+            if single:
+                mask = mask[:, None]
+            assert tuple(mask.shape) == tuple(distance.shape)
+            distance = torch.where(mask, distance, torch.full_like(distance, -1))
+            rate = torch.where(mask, rate, torch.full_like(rate, float("nan")))
+        if single:
+            distance, rate = distance[:, 0], rate[:, 0]
+        return CtcEditDistance(distance, rate)
+
+
+class CtcMwerLoss(NamedTuple):
+    """loss [batch] float32: the expected risk of the N-best list relative to its mean risk (differentiable);
+    risk [batch, nbest] float32: the edit distance of every hypothesis to the labels (a constant);
+    log_posterior [batch, nbest] float32: the confidence of every hypothesis within its list, as a CtcNbestLoss defines it
+    (differentiable; -inf for a masked or infeasible hypothesis);
+    hypotheses: the CtcBeamDecoding the list was taken from."""
+    loss: torch.Tensor
+    risk: torch.Tensor
+    log_posterior: torch.Tensor
+    hypotheses: CtcBeamDecoding
+
+
+def _mwer(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, beam_width, top_k, nbest, hypotheses,
+          max_label_length) -> CtcMwerLoss:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    if hypotheses is None:  # (on the detached logits, under no_grad: the search leaves the logits' graph alone)
+        hypotheses = _beam(kind_name, wrt, x, logit_length, blank_index, beam_width, top_k, nbest)
+    else:
+        hypotheses = CtcBeamDecoding(_as_tensor(hypotheses[0]), _as_tensor(hypotheses[1], torch.int32), _as_tensor(hypotheses[2], torch.int32))
+    mask = torch.isfinite(hypotheses.score)
+    with torch.no_grad():
+        risk = ops.edit_distance(hypotheses.labels, hypotheses.label_length, labels, label_length).to(torch.float32)
+    nb = _nbest(kind_name, wrt, hypotheses.labels, x, hypotheses.label_length, logit_length, blank_index, mask, max_label_length,
+                differentiable=True)
+    used = torch.isfinite(nb.loss)  # unmasked and feasible
+    zero = torch.zeros_like(risk)
+    mean = torch.where(used, risk, zero).sum(dim=1, keepdim=True) / used.sum(dim=1, keepdim=True).clamp(min=1).to(torch.float32)
+    loss = torch.where(used, nb.log_posterior.exp() * (risk - mean), zero).sum(dim=1)
+    return CtcMwerLoss(loss, risk, nb.log_posterior, hypotheses)
+
+
+def classic_ctc_mwer_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                          blank_index: Union[int, torch.Tensor] = 0, *, beam_width: int = 16, top_k: int = 16, nbest: int = 8,
+                          hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None) -> CtcMwerLoss:
+    """Minimum word error rate (expected risk) training on the classic lattice, end to end on the device: an N-best list, the edit
+    distance of every hypothesis to the labels as its risk, the exact posterior of every hypothesis within the list, and
+        loss[b] = sum over the used n of  exp(log_posterior[b, n]) * (risk[b, n] - mean risk of the used hypotheses of b)
+    (Prabhavalkar et al. 2018).  A hypothesis is used when it is not missing from the list (finite `score`) and feasible on the
+    lattice (finite loss); an utterance without a used hypothesis has loss 0 and a zero gradient.
+
+    Args:
+        labels, logits, label_length, logit_length, blank_index: as classic_ctc_loss (labels at most 1024 wide)
+        beam_width, top_k, nbest: (keyword only) the arguments of classic_ctc_beam_search, which the function runs on the detached
+            logits when `hypotheses` is not given.
+        hypotheses: (keyword only) a CtcBeamDecoding to take the list from instead: (score [batch, nbest], labels [batch, nbest,
+            width], label_length [batch, nbest]); an entry whose score is not finite is masked.
+        max_label_length: (keyword only) an upper bound, known on the host, on the HYPOTHESES' lengths, as
+            classic_ctc_nbest_loss takes it (a beam search's label tensor is as wide as the logits are long).
+    Returns: CtcMwerLoss(loss [batch], risk [batch, nbest], log_posterior [batch, nbest], hypotheses).  The gradient reaches the
+        logits through log_posterior only (risk is a constant); backward is the one call of classic_ctc_nbest_loss's.  First
+        derivatives only.  No host synchronisation beyond the one look at max(label_length) that classic_ctc_nbest_loss takes for
+        a wide label tensor without `max_label_length`."""
+    return _mwer("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, beam_width, top_k, nbest,
+                 hypotheses, max_label_length)
+
+
+def simplified_ctc_mwer_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                             blank_index: Union[int, torch.Tensor] = 0, *, beam_width: int = 16, top_k: int = 16, nbest: int = 8,
+                             hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None) -> CtcMwerLoss:
+    """The same on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
+    classic_ctc_mwer_loss."""
+    return _mwer("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, beam_width, top_k, nbest,
+                 hypotheses, max_label_length)
+
+
+def ctc_mwer_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *, beam_width: int = 16,
+                                top_k: int = 16, nbest: int = 8, hypotheses: Optional[CtcBeamDecoding] = None,
+                                max_label_length: Optional[int] = None) -> CtcMwerLoss:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba); the gradient is the one with
+    respect to the log-probabilities."""
+    return _mwer(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                 beam_width, top_k, nbest, hypotheses, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # loss-data objects (what the reference's unit tests poke at directly)
 # --------------------------------------------------------------------------------------------------
 class BaseCtcLossData:

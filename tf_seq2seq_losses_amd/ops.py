@@ -616,6 +616,39 @@ def nbest_best_path(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     return score, tokens, label_index, first_frame, last_frame
 
 
+def edit_distance(hyp: torch.Tensor, hyp_length: torch.Tensor, ref: torch.Tensor, ref_length: torch.Tensor,
+                  R: Optional[int] = None) -> torch.Tensor:
+    """distance[B, N] int32: the Levenshtein distance (unit costs) of every hypothesis hyp[b, n, :hyp_length[b, n]] to its utterance's
+    reference ref[b, :ref_length[b]] (ctc_amd_edit_distance).  hyp [B, N, W] and hyp_length [B, N] in the layout beam_search
+    returns; ref [B, Wr], ref_length [B]; tokens are any int32 values.  R bounds every ref_length (an utterance with a longer
+    reference gets -1 throughout; default: the reference tensor's width Wr).  One launch, no workspace; does not synchronise."""
+    _require_gpu(hyp)
+    dev = hyp.device
+    if (hyp.dim() != 3 or hyp_length.dim() != 2 or ref.dim() != 2 or ref_length.dim() != 1
+            or tuple(hyp_length.shape) != tuple(hyp.shape[:2]) or int(ref.shape[0]) != int(hyp.shape[0])
+            or int(ref_length.shape[0]) != int(hyp.shape[0])):
+        raise ValueError(f"edit_distance: hyp must be [B, N, W], hyp_length [B, N], ref [B, Wr] and ref_length [B], got "
+                         f"{tuple(hyp.shape)}, {tuple(hyp_length.shape)}, {tuple(ref.shape)} and {tuple(ref_length.shape)}")
+    B, N, W = (int(s) for s in hyp.shape)
+    Wr = int(ref.shape[1])
+    R = Wr if R is None else int(R)
+    key = ("edit_distance", B, N, R)
+    if key not in _WS_BYTES:  # (0 bytes; the check of N and R, which an empty batch would otherwise skip)
+        _WS_BYTES[key] = _lib.edit_distance_workspace_bytes(B, N, R)
+
+    def i32(t):
+        return t if (t.dtype == torch.int32 and t.device == dev and t.is_contiguous()) else t.to(device=dev, dtype=torch.int32).contiguous()
+    hyp, hyp_length, ref, ref_length = i32(hyp), i32(hyp_length), i32(ref), i32(ref_length)
+    distance = torch.empty((B, N), dtype=torch.int32, device=dev)
+    if B == 0:
+        return distance
+    with _on_device(dev):
+        rc = _lib.load().ctc_amd_edit_distance(_ptr(hyp), W, _ptr(hyp_length), _ptr(ref), Wr, _ptr(ref_length), B, N, R,
+                                               _ptr(distance), None, 0, _stream(dev))
+    _lib.check(rc, "ctc_amd_edit_distance")
+    return distance
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
