@@ -596,6 +596,62 @@ int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp
                           int32_t *distance /* [B][N] */,
                           void *workspace /* may be NULL */, size_t workspace_bytes, void *stream);
 
+/*
+ * CTC prefix scores (added under ABI v6: four new entry points, nothing existing changed): the step-wise scorer of
+ * label-synchronous decoding (Watanabe et al. 2017, algorithm 2) -- joint CTC / attention decoding, shallow fusion with a
+ * language model whose state stays on the caller's side.  It replaces nothing in the reference, which has no counterpart.
+ * With lp = log_softmax(logits[b]) (CTC_AMD_WRT_LOGPROBS: the input as it stands), T_b = logit_length[b] clamped to [0, T], k0 the
+ * blank and a prefix g of m labels, rn[t] / rb[t] = ln P(frames 0..t emit exactly g and frame t is a label / a blank):
+ *   empty prefix   rn[t] = -inf, rb[t] = sum_{tau <= t} lp[tau, k0]
+ *   entry weight   phi[0] = 0 if m == 0 else -inf;  phi[t] = lse(rb[t-1], rn[t-1]) for t >= 1, on the classic lattice
+ *                  rb[t-1] alone when c == last(g)
+ *   prefix score   ln psi(g.c) = lse_{t < T_b}(phi[t] + lp[t, c]): the mass of ALL label sequences that start with g.c
+ *   extension      classic rn'[t] = lse(rn'[t-1], phi[t]) + lp[t, c];  simplified rn'[t] = phi[t] + lp[t, c];
+ *                  both rb'[t] = lse(rb'[t-1], rn'[t-1]) + lp[t, k0]
+ *   full score     ln P(g) = lse(rn[T_b-1], rb[T_b-1]);  T_b == 0: 0 for the empty prefix, -inf otherwise
+ * so that psi(g) = P(g) + sum_c psi(g.c).  c == k0 or c outside [0, V) is an impossible emission: score -inf, extension dead.
+ *
+ * A beam is N hypotheses per utterance in four buffers of the caller: state (float64, ctc_amd_prefix_workspace_bytes'
+ * state_bytes = 8 * B * N * (2 * T + 2), opaque), last_token, length (int32 [B][N]; a dead hypothesis has -1 in both) and
+ * full_score (float32 [B][N], natural logarithm).
+ *   ctc_amd_prefix_rows    the row maximum and log-sum-exp of every frame into `rows` (rows_bytes = 8 * B * T), ONCE per logits
+ *                          tensor; the other two calls read them every decoding step.  CTC_AMD_WRT_LOGPROBS needs none: it is not
+ *                          called and `rows` may be NULL there.
+ *   ctc_amd_prefix_extend  new hypothesis (b, n) = hypothesis (b, parent[b, n]) of the input beam extended by token[b, n].
+ *                          parent == -2: the empty prefix (token not read; state_in / last_in / length_in may then be NULL: this is
+ *                          how a beam starts); parent == -1, any other parent outside [0, N), a dead parent or an impossible token:
+ *                          a dead hypothesis.  parent may repeat and permute; the output buffers must not overlap the input's.
+ *   ctc_amd_prefix_score   score[b, n, c] = ln psi(g_{b,n} . c), float32 [B][N][V]: -inf in the blank's column and for a dead
+ *                          hypothesis.  The logits are read once per group of CTC_AMD_PREFIX_GROUP hypotheses.
+ * Every result of hypothesis (b, n) has the same bits whatever N is, whatever the other hypotheses are and wherever it stands.
+ * Numerics as ctc_amd_nbest_loss: float64 state, float32 exp / log of float64 differences, a true -inf, emissions from
+ * (double)x - (double)max.  Results for NaN and +inf inputs are unspecified (the calls complete).
+ * 1 <= N <= CTC_AMD_PREFIX_MAX, B * N < 2^31, V <= CTC_AMD_MAX_V, 0 <= blank_index < V, logits in the producer formats of
+ * ctc_amd_loss_grad_ex.  Checked in the order of ctc_amd_nbest_loss: common arguments, element type, B == 0 (CTC_AMD_OK, no launch),
+ * strides, V and N; then null pointers (CTC_AMD_EINVAL) and the buffer sizes (CTC_AMD_EWORKSPACE).
+ * One launch each, asynchronous on `stream`, capturable, no allocation, copy or synchronisation.
+ */
+#define CTC_AMD_PREFIX_MAX 64   /* = CTC_AMD_NBEST_MAX */
+#define CTC_AMD_PREFIX_GROUP 8  /* hypotheses that share one read of the logits in ctc_amd_prefix_score */
+int ctc_amd_prefix_workspace_bytes(int B, int T, int V, int N, size_t *rows_bytes /*host*/, size_t *state_bytes /*host*/);
+int ctc_amd_prefix_rows(const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                        const int32_t *logit_length, int B, int T, int V,
+                        void *rows, size_t rows_bytes, void *stream);
+int ctc_amd_prefix_extend(int kind, int wrt,
+                          const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                          const int32_t *logit_length, int blank_index, int B, int T, int V, int N,
+                          const void *rows, size_t rows_bytes,
+                          const void *state_in, const int32_t *last_token_in, const int32_t *length_in,
+                          const int32_t *parent /* [B][N] */, const int32_t *token /* [B][N] */,
+                          void *state_out, size_t state_bytes, int32_t *last_token_out, int32_t *length_out,
+                          float *full_score /* [B][N] */, void *stream);
+int ctc_amd_prefix_score(int kind, int wrt,
+                         const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                         const int32_t *logit_length, int blank_index, int B, int T, int V, int N,
+                         const void *rows, size_t rows_bytes,
+                         const void *state, size_t state_bytes, const int32_t *last_token, const int32_t *length,
+                         float *score /* [B][N][V] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ WRT_LOGITS, WRT_LOGPROBS = 0, 1
 WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
+PREFIX_MAX, PREFIX_GROUP = 64, 8  # CTC_AMD_PREFIX_MAX, CTC_AMD_PREFIX_GROUP
 NBEST_MAX, NBEST_GROUP = 64, 8  # CTC_AMD_NBEST_MAX, CTC_AMD_NBEST_GROUP: hypotheses per utterance, and per workgroup (one logits read)
 
 _c_int, _c_int64, _c_void_p, _c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
@@ -32,6 +33,11 @@ _COMMON_EX = [_c_int, _c_int,                               # kind, wrt
               _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,  # labels, label_stride, label_length, logit_length, blank_index
               _c_int, _c_int, _c_int, _c_int]               # B, T, V, U
 _OUT_EX = [_c_void_p, _c_void_p, _c_int, _c_int64, _c_int64]  # loss, grad, dtype, stride_b, stride_t
+
+# the two step calls of the prefix scorer: no labels, N behind the shape, then the row statistics
+_PREFIX_EX = [_c_int, _c_int, _c_void_p, _c_int, _c_int64, _c_int64,  # kind, wrt, logits, dtype, stride_b, stride_t
+              _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int,      # logit_length, blank_index, B, T, V, N
+              _c_void_p, _c_size_t]                                   # rows, bytes
 
 # every symbol include/ctc_amd.h declares, with its argument types
 SIGNATURES = {
@@ -84,6 +90,12 @@ SIGNATURES = {
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
                                        _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
+    "ctc_amd_prefix_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),  # B, T, V, N, rows, state
+    "ctc_amd_prefix_rows": (_c_int, [_c_void_p, _c_int, _c_int64, _c_int64, _c_void_p, _c_int, _c_int, _c_int,  # logits, dtype, stride_b, stride_t, logit_length, B, T, V
+                                     _c_void_p, _c_size_t, _c_void_p]),                                      # rows, bytes, stream
+    "ctc_amd_prefix_extend": (_c_int, _PREFIX_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # state_in, last_in, length_in, parent, token
+                                                    _c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),  # state_out, bytes, last_out, length_out, full_score, stream
+    "ctc_amd_prefix_score": (_c_int, _PREFIX_EX + [_c_void_p, _c_size_t, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),  # state, bytes, last, length, score, stream
 }
 
 _lib = None
@@ -197,3 +209,10 @@ def edit_distance_workspace_bytes(B: int, N: int, R: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_edit_distance_workspace_bytes(B, N, R, ctypes.byref(out)), "ctc_amd_edit_distance_workspace_bytes")
     return int(out.value)
+
+
+def prefix_workspace_bytes(B: int, T: int, V: int, N: int):
+    """(rows_bytes, state_bytes) of the prefix scorer."""
+    rows, state = _c_size_t(0), _c_size_t(0)
+    check(load().ctc_amd_prefix_workspace_bytes(B, T, V, N, ctypes.byref(rows), ctypes.byref(state)), "ctc_amd_prefix_workspace_bytes")
+    return int(rows.value), int(state.value)

@@ -10,6 +10,7 @@
 #include "ctc_hvp_fused.h"
 #include "ctc_launch.h"
 #include "ctc_nbest_align.h"
+#include "ctc_prefix.h"
 
 namespace ctc {
 // diagnostic override read by ctc_hessian.hip (ctc_amd_debug_override): process-wide, written only by tests / benchmarks between calls
@@ -777,6 +778,97 @@ int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp
   if (!distance) return fail(CTC_AMD_EINVAL, "null distance pointer");
   CTC_TRY(ctc::run_edit_distance(hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length, B, N, R, distance,
                                  static_cast<hipStream_t>(stream)), "edit distance launch");
+  return CTC_AMD_OK;
+}
+
+// what the prefix scorer's entry points take beyond a shape
+int check_prefix(int B, int V, int N) {
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the prefix scorer", V, MAX_V_GRAD);
+  if (N < 1 || N > CTC_AMD_PREFIX_MAX) return fail(CTC_AMD_EINVAL, "N %d outside [1, %d]", N, CTC_AMD_PREFIX_MAX);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld hypotheses exceed 2^31", (long long)B * N);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_prefix_workspace_bytes(int B, int T, int V, int N, size_t *rows_bytes, size_t *state_bytes) {
+  if (!rows_bytes || !state_bytes) return fail(CTC_AMD_EINVAL, "rows_bytes or state_bytes is null");
+  if (B < 0 || T < 0 || V <= 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d V=%d", B, T, V);
+  if (int rc = check_prefix(B, V, N)) return rc;
+  *rows_bytes = ctc::prefix_rows_bytes(B, T);
+  *state_bytes = ctc::prefix_state_bytes(B, T, N);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_greedy_decode: common arguments (no labels, no blank: column 0 stands in), element type, B == 0,
+// strides; then the vocabulary limit, the launch grid and the buffer.
+int ctc_amd_prefix_rows(const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                        const int32_t *logit_length, int B, int T, int V, void *rows, size_t rows_bytes, void *stream) {
+  const Common c{CTC_AMD_CLASSIC, CTC_AMD_WRT_LOGITS, logits, nullptr, 0, logit_length, logit_length, 0, B, T, V, 0};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (int rc = check_prefix(B, V, 1)) return rc;
+  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const size_t need = ctc::prefix_rows_bytes(B, T);
+  if (rows_bytes < need || (need > 0 && !rows)) return fail(CTC_AMD_EWORKSPACE, "rows buffer too small: %zu < %zu", rows_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_prefix_rows(p, rows, static_cast<hipStream_t>(stream)), "prefix rows launch");
+  return CTC_AMD_OK;
+}
+
+// the checks the two step calls share, in the order of ctc_amd_nbest_loss; then the row statistics, which only logits need
+int check_prefix_step(const Common &c, const Format &f, int N, const void *rows, size_t rows_bytes) {
+  if (int rc = f.check_strides(c.V, false)) return rc;
+  if (int rc = check_prefix(c.B, c.V, N)) return rc;
+  if (c.wrt == CTC_AMD_WRT_LOGITS && c.T > 0) {
+    if (!rows) return fail(CTC_AMD_EINVAL, "null rows pointer (ctc_amd_prefix_rows fills it once per logits tensor)");
+    const size_t need = ctc::prefix_rows_bytes(c.B, c.T);
+    if (rows_bytes < need) return fail(CTC_AMD_EWORKSPACE, "rows buffer too small: %zu < %zu", rows_bytes, need);
+  }
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_prefix_extend(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                          const int32_t *logit_length, int blank_index, int B, int T, int V, int N, const void *rows, size_t rows_bytes,
+                          const void *state_in, const int32_t *last_token_in, const int32_t *length_in, const int32_t *parent,
+                          const int32_t *token, void *state_out, size_t state_bytes, int32_t *last_token_out, int32_t *length_out,
+                          float *full_score, void *stream) {
+  const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = check_prefix_step(c, f, N, rows, rows_bytes)) return rc;
+  if (!parent || !token || !state_out || !last_token_out || !length_out || !full_score)
+    return fail(CTC_AMD_EINVAL, "null parent / token / state_out / last_token_out / length_out / full_score pointer");
+  if (state_in && (!last_token_in || !length_in)) return fail(CTC_AMD_EINVAL, "state_in without last_token_in / length_in");
+  if (state_in == state_out) return fail(CTC_AMD_EINVAL, "state_out must not be state_in");
+  const size_t need = ctc::prefix_state_bytes(B, T, N);
+  if (state_bytes < need) return fail(CTC_AMD_EWORKSPACE, "state buffer too small: %zu < %zu", state_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_prefix_extend(p, N, rows, static_cast<const double *>(state_in), last_token_in, length_in, parent, token,
+                                 static_cast<double *>(state_out), last_token_out, length_out, full_score,
+                                 static_cast<hipStream_t>(stream)), "prefix extend launch");
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_prefix_score(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                         const int32_t *logit_length, int blank_index, int B, int T, int V, int N, const void *rows, size_t rows_bytes,
+                         const void *state, size_t state_bytes, const int32_t *last_token, const int32_t *length, float *score,
+                         void *stream) {
+  const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = check_prefix_step(c, f, N, rows, rows_bytes)) return rc;
+  if (!state || !last_token || !length || !score) return fail(CTC_AMD_EINVAL, "null state / last_token / length / score pointer");
+  const size_t need = ctc::prefix_state_bytes(B, T, N);
+  if (state_bytes < need) return fail(CTC_AMD_EWORKSPACE, "state buffer too small: %zu < %zu", state_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_prefix_score(p, N, rows, static_cast<const double *>(state), last_token, length, score,
+                                static_cast<hipStream_t>(stream)), "prefix score launch");
   return CTC_AMD_OK;
 }
 

@@ -356,6 +356,115 @@ def ctc_beam_search_from_logproba(logprobas, logit_length, blank_index, ctc_loss
 
 
 # --------------------------------------------------------------------------------------------------
+# CTC prefix scores, the step-wise scorer of label-synchronous decoding: an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcPrefixState(NamedTuple):
+    """A beam of N prefixes per utterance.  state [batch, N, 2 * max_length + 2] float64: opaque, the forward variables of every
+    prefix; last_token, length [batch, N] int32 (-1 and -1: a dead slot); full_score [batch, N] float32: ln P(prefix | logits), the
+    probability of the prefix as the whole label sequence; parent [batch, N] int32: the slot of the beam it was extended from
+    (what a caller reorders its own decoder or language-model state by; None for an initial state)."""
+    state: torch.Tensor
+    last_token: torch.Tensor
+    length: torch.Tensor
+    full_score: torch.Tensor
+    parent: Optional[torch.Tensor] = None
+
+
+class CtcPrefixScorer:
+    """The CTC head as a step-wise scorer (Watanabe et al. 2017): score(state)[b, n, c] = ln psi(g . c), the probability of all
+    label sequences that start with prefix g of slot (b, n) followed by token c, and extend(state, parent, token) carries the
+    beam forward.  The row statistics of the logits are computed once, here; nothing is differentiable."""
+
+    def __init__(self, kind_name: str, wrt: int, x, logit_length, blank_index):
+        x = _as_tensor(x)
+        logit_length = _as_tensor(logit_length, torch.int32)
+        assert x.dim() == 3
+        assert x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+        assert logit_length.dim() == 1
+        assert x.shape[0] == logit_length.shape[0]
+        self.kind_name, self.kind, self.wrt, self.blank = kind_name, ops.KINDS[kind_name], wrt, _blank(blank_index)
+        with torch.no_grad():
+            self.x, self.logit_length, self.rows = ops.prefix_prepare(wrt, x.detach(), logit_length)
+        self.batch, self.max_length, self.num_tokens = (int(s) for s in self.x.shape)
+
+    def _args(self):
+        return self.kind, self.wrt, self.x, self.logit_length, self.blank, self.rows
+
+    def initial_state(self, N: int) -> CtcPrefixState:
+        """N slots per utterance: the empty prefix in slot 0, the others dead."""
+        N = int(N)
+        parent = torch.full((self.batch, N), -1, dtype=torch.int32, device=self.x.device)
+        parent[:, :1] = -2
+        with torch.no_grad():
+            return CtcPrefixState(*ops.prefix_extend(*self._args(), N, None, None, None, parent, torch.zeros_like(parent)))
+
+    def score(self, state: CtcPrefixState) -> torch.Tensor:
+        """[batch, N, num_tokens] float32; -inf in the blank's column and in every dead slot."""
+        with torch.no_grad():
+            return ops.prefix_score(*self._args(), int(state.state.shape[1]), state.state, state.last_token, state.length)
+
+    def extend(self, state: CtcPrefixState, parent: TensorLike, token: TensorLike) -> CtcPrefixState:
+        """New slot (b, n) = slot (b, parent[b, n]) of `state` extended by token[b, n]; parent -1 (or a dead parent, the blank, a
+        token outside the vocabulary) gives a dead slot, parent -2 the empty prefix.  parent may repeat and permute."""
+        parent, token = _as_tensor(parent, torch.int32), _as_tensor(token, torch.int32)
+        with torch.no_grad():
+            out = ops.prefix_extend(*self._args(), int(state.state.shape[1]), state.state, state.last_token, state.length, parent, token)
+        return CtcPrefixState(*out, parent)
+
+
+def classic_ctc_prefix_scorer(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0) -> CtcPrefixScorer:
+    """Prefix scorer on the classic lattice.  logits [batch, max_length, num_tokens] float32 / bfloat16 / float16 (any batch / time
+    strides, read in place every step), logit_length [batch]; num_tokens <= 16384, at most 64 slots per utterance."""
+    return CtcPrefixScorer("classic", _lib.WRT_LOGITS, logits, logit_length, blank_index)
+
+
+def simplified_ctc_prefix_scorer(logits: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0) -> CtcPrefixScorer:
+    """Prefix scorer on the simplified lattice (every non-blank frame is a label).  Same arguments as classic_ctc_prefix_scorer."""
+    return CtcPrefixScorer("simplified", _lib.WRT_LOGITS, logits, logit_length, blank_index)
+
+
+def ctc_prefix_scorer_from_logproba(logproba: TensorLike, logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                                    simplified: bool = False) -> CtcPrefixScorer:
+    """The same for log-probabilities used as they stand (no row statistics are computed)."""
+    return CtcPrefixScorer("simplified" if simplified else "classic", _lib.WRT_LOGPROBS, logproba, logit_length, blank_index)
+
+
+def ctc_label_sync_beam_search(scorer: CtcPrefixScorer, beam_width: int, max_length: int, *, extra_score=None,
+                               ctc_weight: float = 1.0) -> CtcBeamDecoding:
+    """The textbook label-synchronous beam search over a CtcPrefixScorer: per step the prefix scores of the beam, times ctc_weight,
+    plus the running sum of extra_score(state) [batch, beam_width, num_tokens] (a language model, an attention decoder, a length
+    bonus: the caller's) select the beam_width best extensions among beam_width * num_tokens.  Every prefix visited is a
+    candidate result, ranked by ctc_weight * full_score + its sum of extra scores.  Returns the beam_width best as
+    CtcBeamDecoding(score, labels [batch, beam_width, max_length], label_length); nothing is copied to the host on the way."""
+    N, V, B = int(beam_width), scorer.num_tokens, scorer.batch
+    dev = scorer.x.device
+    state = scorer.initial_state(N)
+    extra = torch.zeros((B, N), dtype=torch.float32, device=dev)           # the beam's sums of extra scores
+    labels = torch.full((B, N, int(max_length)), -1, dtype=torch.int32, device=dev)
+    best = (torch.where(state.length >= 0, ctc_weight * state.full_score, -torch.inf), labels, state.length.clamp(min=0))
+    for step in range(int(max_length)):
+        cand = ctc_weight * scorer.score(state) + extra[:, :, None]
+        step_extra = None if extra_score is None else extra_score(state).to(torch.float32)
+        if step_extra is not None:
+            cand = cand + step_extra
+        top, idx = cand.reshape(B, N * V).topk(N, dim=1)
+        parent = torch.where(top > -torch.inf, idx // V, -1).to(torch.int32)  # (nothing left to extend: a dead slot)
+        token = (idx % V).to(torch.int32)
+        src = parent.clamp(min=0).long()
+        labels = labels.gather(1, src[:, :, None].expand(-1, -1, labels.shape[2]))
+        labels[:, :, step] = torch.where(parent >= 0, token, -1)
+        extra = extra.gather(1, src)
+        if step_extra is not None:
+            extra = extra + torch.nan_to_num(step_extra.reshape(B, N * V).gather(1, idx), neginf=0.0)
+        state = scorer.extend(state, parent, token)
+        final = torch.where(state.length >= 0, ctc_weight * state.full_score + extra, -torch.inf)
+        pool = (torch.cat([best[0], final], 1), torch.cat([best[1], labels], 1), torch.cat([best[2], state.length.clamp(min=0)], 1))
+        keep = pool[0].topk(N, dim=1).indices
+        best = (pool[0].gather(1, keep), pool[1].gather(1, keep[:, :, None].expand(-1, -1, labels.shape[2])), pool[2].gather(1, keep))
+    return CtcBeamDecoding(*best)
+
+
+# --------------------------------------------------------------------------------------------------
 # N-best rescoring: an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcNbestLoss(NamedTuple):

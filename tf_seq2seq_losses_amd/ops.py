@@ -649,6 +649,79 @@ def edit_distance(hyp: torch.Tensor, hyp_length: torch.Tensor, ref: torch.Tensor
     return distance
 
 
+def prefix_prepare(wrt: int, x: torch.Tensor, logit_length: torch.Tensor):
+    """(x, logit_length, rows) of a prefix scorer: the logits as greedy_decode takes them and, for logits, the row statistics
+    (ctc_amd_prefix_rows: one launch, once per scorer); rows is None for log-probabilities."""
+    _require_gpu(x)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if not (x.dtype in _DTYPES and (x.numel() == 0 or (x.stride(2) == 1 and x.stride(0) >= V and x.stride(1) >= V))):
+        x = x.to(torch.float32).contiguous()
+    if x.numel() == 0:
+        x = torch.empty((B, T, V), dtype=x.dtype if x.dtype in _DTYPES else torch.float32, device=dev)
+    if not (logit_length.dtype == torch.int32 and logit_length.device == dev and logit_length.is_contiguous()):
+        logit_length = logit_length.to(device=dev, dtype=torch.int32).contiguous()
+    _lib.prefix_workspace_bytes(B, T, V, 1)  # (the check of V, which an empty batch would otherwise skip)
+    if wrt != _lib.WRT_LOGITS:
+        return x, logit_length, None
+    rows = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
+    if B > 0:
+        with _on_device(dev):
+            rc = lib.ctc_amd_prefix_rows(_ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(logit_length), B, T, V,
+                                         _ptr(rows), rows.numel() * 4, _stream(dev))
+        _lib.check(rc, "ctc_amd_prefix_rows")
+    return x, logit_length, rows
+
+
+def _prefix_common(kind: int, wrt: int, x, logit_length, blank: int, N: int, rows):
+    B, T, V = (int(s) for s in x.shape)
+    return (kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(logit_length), int(blank), B, T, V, int(N),
+            _ptr(rows), 0 if rows is None else rows.numel() * 4)
+
+
+def prefix_extend(kind: int, wrt: int, x, logit_length, blank: int, rows, N: int, state, last_token, length, parent, token):
+    """(state [B, N, 2 T + 2] float64, last_token [B, N] int32, length [B, N] int32, full_score [B, N] float32) of the hypotheses
+    (parent[b, n], token[b, n]) of the beam (state, last_token, length); state None starts a beam (ctc_amd_prefix_extend)."""
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    _lib.prefix_workspace_bytes(B, T, V, N)
+
+    def i32(t):
+        if tuple(t.shape) != (B, N):
+            raise ValueError(f"prefix_extend: parent and token must be [B, N] = [{B}, {N}], got {tuple(t.shape)}")
+        return t if (t.dtype == torch.int32 and t.device == dev and t.is_contiguous()) else t.to(device=dev, dtype=torch.int32).contiguous()
+    parent, token = i32(parent), i32(token)
+    new_state = torch.empty((B, N, 2 * T + 2), dtype=torch.float64, device=dev)
+    new_last = torch.empty((B, N), dtype=torch.int32, device=dev)
+    new_length = torch.empty((B, N), dtype=torch.int32, device=dev)
+    full = torch.empty((B, N), dtype=torch.float32, device=dev)
+    if B == 0:
+        return new_state, new_last, new_length, full
+    with _on_device(dev):
+        rc = lib.ctc_amd_prefix_extend(*_prefix_common(kind, wrt, x, logit_length, blank, N, rows), _ptr(state), _ptr(last_token),
+                                       _ptr(length), _ptr(parent), _ptr(token), _ptr(new_state), new_state.numel() * 8,
+                                       _ptr(new_last), _ptr(new_length), _ptr(full), _stream(dev))
+    _lib.check(rc, "ctc_amd_prefix_extend")
+    return new_state, new_last, new_length, full
+
+
+def prefix_score(kind: int, wrt: int, x, logit_length, blank: int, rows, N: int, state, last_token, length) -> torch.Tensor:
+    """score [B, N, V] float32: ln psi(g . c) of every hypothesis of the beam and every token (ctc_amd_prefix_score)."""
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    score = torch.empty((B, N, V), dtype=torch.float32, device=dev)
+    if B == 0:
+        return score
+    with _on_device(dev):
+        rc = lib.ctc_amd_prefix_score(*_prefix_common(kind, wrt, x, logit_length, blank, N, rows), _ptr(state), state.numel() * 8,
+                                      _ptr(last_token), _ptr(length), _ptr(score), _stream(dev))
+    _lib.check(rc, "ctc_amd_prefix_score")
+    return score
+
+
 def check_labels(labels, label_length, num_tokens: int, blank_index: int = 0) -> None:
     """Opt-in validation (off the hot path: synchronises): raises ValueError if a label inside its `label_length` lies
     outside [0, num_tokens) or equals `blank_index` -- what TF-CPU's gather reports as InvalidArgumentError for
