@@ -652,6 +652,74 @@ int ctc_amd_prefix_score(int kind, int wrt,
                          const void *state, size_t state_bytes, const int32_t *last_token, const int32_t *length,
                          float *score /* [B][N][V] */, void *stream);
 
+/*
+ * Forced alignment of partial transcripts: wildcard labels (added under ABI v6: two new entry points, nothing existing changed).
+ * ctc_amd_best_path forces every frame onto the given labels or the blank; here a label may be a wildcard that takes up whatever
+ * else was said: untranscribed speech before, after or inside the known words, a passage the annotator could not make out, the
+ * rest of an utterance around a keyword.  The reference has no counterpart.
+ *
+ * Wildcard value.  One reserved label value, CTC_AMD_WILDCARD = -2, marks a wildcard position.  It applies inside label_length
+ * only.  Everything else follows the input contract of the other entry points: any other label outside
+ * [0, V) or equal to the blank makes the utterance infeasible; label_length > U makes it infeasible; logit_length is clamped to
+ * [0, T] (T_b below).
+ * Emission and tokens.  With x the input row (logits, or log-probabilities for CTC_AMD_WRT_LOGPROBS):
+ *   m_t = max_k x[t, k] over all tokens, the blank included;
+ *   a_t = the lowest k that attains it, compared as the float32 the element type converts to: the tie rule of ctc_amd_greedy_decode.
+ * A wildcard position stands for any non-empty run of frames with any tokens on them.  In the (max, +) semiring that run is worth
+ * sum m_t, and the tokens reported for it are a_t.
+ * Classic lattice.  The recursion of ctc_amd_best_path (open state: the last frame emitted label i; closed state: labels 0..i are
+ * done and the last frame was blank) changes as follows for wildcard position i: its emission is m_t; the transition from an open
+ * position i - 1 straight into an open wildcard is always allowed, wildcard or not; the transition from an open wildcard i into an
+ * open position i + 1 is always allowed, whatever token the wildcard last showed.  Its closed state is the ordinary one.  The
+ * frames of a wildcard are therefore contiguous, and each wildcard takes at least one frame.
+ * Simplified lattice.  For wildcard position i: entering it costs m_t; while "labels 0..i are emitted" is the current state, the
+ * horizontal step costs m_t instead of x[t, blank].  Every frame from the entry until the next label's frame therefore belongs to
+ * the wildcard: label_index is i on those frames and tokens is a_t.
+ * Labels and edges.  Non-wildcard positions behave exactly as in ctc_amd_best_path.  Adjacent wildcards are allowed, and each
+ * takes at least one frame.  Free start and end are a wildcard as the first and last label; there is no separate switch.
+ * Score.  score is the maximum of sum_t lp[t, pi_t] over admissible paths, lp = x - LSE_t for logits and x as it stands for
+ * log-probabilities, with pi_t = a_t on wildcard frames.  Among paths of equal value the choice is deterministic (the same bits
+ * every run) but unspecified, in the words of ctc_amd_best_path.
+ * Degenerate cases.  label_length == 0: the all-blank path.  T_b == 0: score 0 for an empty label, -inf otherwise.  An infeasible
+ * utterance (also: fewer frames than the positions need -- a wildcard needs a frame of its own): score -inf, and -1 (or -inf)
+ * everywhere.  A row that is -inf throughout makes every path through it -inf.  NaN and +inf inputs: unspecified, the call completes.
+ *
+ *   score[B]            float32
+ *   tokens[B][T]        int32:   pi_t; -1 for t >= T_b
+ *   label_index[B][T]   int32:   as ctc_amd_best_path documents it; i on every frame of wildcard i, including frames where a_t
+ *                                happens to be the blank.  May be NULL.
+ *   first_frame[B][U]   int32:   the first frame whose label_index is i, for i < label_length; -1 from label_length on (the
+ *   last_frame[B][U]    int32:   convention of ctc_amd_nbest_best_path).  ... and the last.  Each may be NULL.
+ *   label_score[B][U]   float32: the sum of lp over the frames whose label_index is i, taken in time order in float64; -inf from
+ *                                label_length on and for an infeasible utterance.  Blank frames outside any label count towards
+ *                                score only: sum_i label_score + sum over those frames of lp[t, blank] = score.  May be NULL.
+ * The recursion runs on the raw inputs in float64, so the path is the exact optimum of the float32 inputs; the error of score and
+ * label_score is that of the float32 row log-sum-exps (none for CTC_AMD_WRT_LOGPROBS) plus the rounding of the outputs.
+ * Validation and limits are those of ctc_amd_best_path, in its order and with its messages: common arguments (kind, wrt, sizes,
+ * 0 <= blank_index < V, U <= CTC_AMD_MAX_U, null pointers), element type, B == 0 (CTC_AMD_OK without a launch), strides, then
+ * score and tokens non-NULL, V <= CTC_AMD_MAX_V (CTC_AMD_EINVAL each), then the workspace (CTC_AMD_EWORKSPACE before any launch).
+ * Logits in the producer formats of ctc_amd_loss_grad_ex, read in place with both access paths (16-byte / 8-byte row accesses
+ * when V, the strides and the base pointer allow them, element-wise with identical results otherwise).
+ * Workspace (may hold anything on entry): the back-pointers of ctc_amd_best_path, the float64 log-probability of the path's token
+ * on every frame and the int32 a_t of every frame.  With NL the smallest power of two with 64 * NL >= U (1 for U <= 64),
+ * word = 1, 1, 2, 4, 8 bytes for NL = 1, 2, 4, 8, 16 and r256(x) = x rounded up to a multiple of 256:
+ *   ctc_amd_wildcard_best_path_workspace_bytes = r256(B * T * 64 * word) + r256(B * T * 8) + r256(B * T * 4)
+ * B = 256, T = 1000, U = 128: 19.5 MB.  One launch of B workgroups (row pass, sweep, back-trace and the per-label sums in the same
+ * kernel), asynchronous on `stream`, capturable.  No allocation, copy or synchronisation.  Every element has one writer, there
+ * are no floating-point atomics: the same bits on every run.
+ */
+#define CTC_AMD_WILDCARD (-2)
+int ctc_amd_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_wildcard_best_path(int kind, int wrt,
+                               const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride,
+                               const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                               int B, int T, int V, int U,
+                               float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                               int32_t *first_frame /* [B][U], may be NULL */, int32_t *last_frame /* [B][U], may be NULL */,
+                               float *label_score /* [B][U], may be NULL */,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ WRT_LOGITS, WRT_LOGPROBS = 0, 1
 WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
+WILDCARD = -2  # CTC_AMD_WILDCARD: the label value of a wildcard position (ctc_amd_wildcard_best_path)
 PREFIX_MAX, PREFIX_GROUP = 64, 8  # CTC_AMD_PREFIX_MAX, CTC_AMD_PREFIX_GROUP
 NBEST_MAX, NBEST_GROUP = 64, 8  # CTC_AMD_NBEST_MAX, CTC_AMD_NBEST_GROUP: hypotheses per utterance, and per workgroup (one logits read)
 
@@ -86,6 +87,9 @@ SIGNATURES = {
     "ctc_amd_nbest_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, N
     "ctc_amd_nbest_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # N, score, tokens, label_index, first_frame, last_frame
                                                       _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
+    "ctc_amd_wildcard_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
+    "ctc_amd_wildcard_best_path": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # score, tokens, label_index, first_frame, last_frame, label_score
+                                                         _c_void_p, _c_size_t, _c_void_p]),                              # ws, bytes, stream
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
@@ -202,6 +206,12 @@ def nbest_loss_grad_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N
 def nbest_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_nbest_best_path_workspace_bytes(kind, B, T, V, U, N, ctypes.byref(out)), "ctc_amd_nbest_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def wildcard_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_wildcard_best_path_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_wildcard_best_path_workspace_bytes")
     return int(out.value)
 
 

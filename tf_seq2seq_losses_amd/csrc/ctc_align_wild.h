@@ -1,0 +1,16 @@
+// Host launcher of ctc_align_wild.hip (forced alignment with wildcard labels), for that unit and ctc_capi.hip.  Host declarations only.
+#pragma once
+#include "ctc_common.h"
+
+namespace ctc {
+
+constexpr int ALIGN_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h): the label value of a wildcard position
+
+// one workgroup per utterance; the workspace holds, each rounded up to 256 bytes, the back-pointers of ctc_align.hip ([B][T][64]
+// words of 1 .. 8 bytes), the float64 log-probability of the path's token on every frame ([B][T]; during the sweep: the frame's
+// log-sum-exp) and the int32 argmax token of every frame ([B][T])
+size_t align_wild_workspace_bytes(int B, int T, int U);
+hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
+                          float *label_score, hipStream_t st);
+
+}  // namespace ctc

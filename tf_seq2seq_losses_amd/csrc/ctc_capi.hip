@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ctc_align_wild.h"
 #include "ctc_amd.h"
 #include "ctc_beam.h"
 #include "ctc_common.h"
@@ -740,6 +741,39 @@ int ctc_amd_nbest_best_path(int kind, int wrt, const void *logits, int logits_dt
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_nbest_align(p, N, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
                                static_cast<hipStream_t>(stream)), "N-best alignment launch");
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::ALIGN_WILDCARD == CTC_AMD_WILDCARD, "the kernel's wildcard label is the ABI's");
+
+int ctc_amd_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  *out_bytes = ctc::align_wild_workspace_bytes(B, T, U);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_best_path, with its messages: common arguments, element type, B == 0, strides; then the two outputs
+// that must exist, the vocabulary limit and the workspace.
+int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                               int blank_index, int B, int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index,
+                               int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
+  const size_t need = ctc::align_wild_workspace_bytes(B, T, U);
+  if (!workspace || workspace_bytes < need) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_align_wild(p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
+                              static_cast<hipStream_t>(stream)), "wildcard alignment launch");
   return CTC_AMD_OK;
 }
 

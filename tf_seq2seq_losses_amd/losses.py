@@ -260,6 +260,75 @@ def ctc_alignment_from_logproba(labels, logprobas, label_length, logit_length, b
 
 
 # --------------------------------------------------------------------------------------------------
+# forced alignment of partial transcripts (wildcard labels): an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+WILDCARD = _lib.WILDCARD  # -2: the label value of a wildcard position
+
+
+class CtcWildcardAlignment(NamedTuple):
+    """score [batch] float32: log-probability of the best path, the frame-wise best token on wildcard frames (-inf: no path);
+    tokens [batch, max_length] int32: the token of every frame on it -- on the frames of a wildcard the frame's argmax, ties to the
+    lowest index (-1 beyond logit_length);
+    label_index [batch, max_length] int32: index into labels[b] of the label the frame belongs to, a wildcard's index on all of
+    its frames; -1 on blank frames outside any label and beyond logit_length;
+    first_frame, last_frame [batch, U] int32: the first and last frame of every label (-1 from label_length on), U the bound on the
+    label length the call ran with (the width of `labels`, or max_label_length);
+    label_score [batch, U] float32: the log-probability of every label's frames (-inf from label_length on).
+    An infeasible sample has score = -inf, -1 in every frame and label and -inf in label_score."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    label_index: torch.Tensor
+    first_frame: torch.Tensor
+    last_frame: torch.Tensor
+    label_score: torch.Tensor
+
+
+def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index,
+                    max_label_length=None) -> CtcWildcardAlignment:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    with torch.no_grad():  # a path is not differentiable: the result is detached
+        prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
+                            host_max_label_length=max_label_length)
+        return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep))
+
+
+def classic_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                   blank_index: Union[int, torch.Tensor] = 0, *,
+                                   max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+    """Forced alignment of a partial transcript on the classic lattice.  As classic_ctc_alignment, but a label equal to WILDCARD
+    (-2) stands for any non-empty run of frames with any tokens on them: untranscribed speech before, after or inside the known
+    words (free start and end are a wildcard as the first and last label).  A wildcard's frames score their best token and report
+    it in `tokens`; adjacent wildcards take at least one frame each.  Arguments as classic_ctc_alignment (float32 / bfloat16 /
+    float16 logits, any batch / time strides, read in place); returns CtcWildcardAlignment, not differentiable.
+    check_labels keeps rejecting -2: it validates transcripts for the loss functions, where a wildcard is an impossible emission."""
+    return _wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+
+
+def simplified_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                      blank_index: Union[int, torch.Tensor] = 0, *,
+                                      max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+    """The same on the simplified lattice (every other non-blank frame emits exactly one label): a wildcard owns every frame from
+    its entry until the next label's frame.  Same arguments and return value as classic_ctc_wildcard_alignment; check_labels keeps
+    rejecting -2 here as well."""
+    return _wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+
+
+def ctc_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                         max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_alignment_from_logproba); ctc_loss_data_cls
+    selects the lattice (default: ClassicCtcLossData).  check_labels keeps rejecting -2 here as well."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                           max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # greedy decoding: an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcDecoding(NamedTuple):

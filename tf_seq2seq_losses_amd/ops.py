@@ -426,6 +426,32 @@ def best_path(kind: int, wrt: int, p: Prepared) -> Tuple[torch.Tensor, torch.Ten
     return score, tokens, label_index
 
 
+def wildcard_best_path(kind: int, wrt: int, p: Prepared):
+    """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
+    label_score[B,U] float32): the best path of the lattice whose labels may be wildcards (_lib.WILDCARD), and where every label
+    lies on it (ctc_amd_wildcard_best_path).  Reads the logits in the format `p` holds them in, as best_path does."""
+    lib = _lib.load()
+    score = torch.empty(p.B, dtype=torch.float32, device=p.device)
+    tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    label_index = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    first_frame = torch.empty((p.B, p.U), dtype=torch.int32, device=p.device)
+    last_frame = torch.empty((p.B, p.U), dtype=torch.int32, device=p.device)
+    label_score = torch.empty((p.B, p.U), dtype=torch.float32, device=p.device)
+    out = (score, tokens, label_index, first_frame, last_frame, label_score)
+    if p.B == 0:
+        return out
+    key = ("wildcard_best_path", kind, p.B, p.T, p.V, p.U)
+    n = _WS_BYTES.get(key)
+    if n is None:
+        n = _WS_BYTES[key] = _lib.wildcard_best_path_workspace_bytes(kind, p.B, p.T, p.V, p.U)
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    with _on_device(p.device):
+        rc = lib.ctc_amd_wildcard_best_path(*p.common_ex(kind, wrt), *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(),
+                                            _stream(p.device))
+    _lib.check(rc, "ctc_amd_wildcard_best_path")
+    return out
+
+
 def greedy_decode(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor, blank: int):
     """(score[B] float32, tokens[B,T] int32, labels[B,T] int32, label_length[B] int32, frames[B,T] int32, label_score[B,T] float32):
     the frame-wise argmax path and the labels it collapses to (ctc_amd_greedy_decode).  Takes the logits as they stand -- float32 /
