@@ -720,6 +720,74 @@ int ctc_amd_wildcard_best_path(int kind, int wrt,
                                float *label_score /* [B][U], may be NULL */,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * CTC loss and gradient with wildcard labels: training on partial transcripts (added under ABI v6: two new entry points, nothing
+ * existing changed).  The training-side counterpart of ctc_amd_wildcard_best_path: the same lattice, summed over all its paths
+ * instead of maximised, with its analytic gradient.  In the literature: wildcard CTC (W-CTC) and star temporal classification
+ * (STC, which adds the per-frame penalty below).  The reference has no counterpart.
+ *
+ * Labels, lengths, blank, formats and every degenerate case follow the input contract of the other entry points (DESIGN.md section
+ * 5.8) and ctc_amd_wildcard_best_path.  A label equal to CTC_AMD_WILDCARD inside label_length marks a wildcard position: any
+ * non-empty run of frames with any tokens on them.
+ * Emission.  Let lp = log_softmax(x) for CTC_AMD_WRT_LOGITS and x as it stands for CTC_AMD_WRT_LOGPROBS, and w =
+ * wildcard_log_weight, a finite float <= 0 (a positive, NaN or infinite w: CTC_AMD_EINVAL).  A wildcard frame emits
+ *   e_w(t) = w + ln sum_k exp(lp[t, k])    -- w exactly for logits, w + LSE_k x[t, k] for log-probabilities.
+ * The lattices are those of ctc_amd_wildcard_best_path with e_w(t) in place of the row maximum m_t.
+ * Classic lattice: 2 L + 1 states.  A wildcard's open state emits e_w; the step from open position i - 1 straight into open
+ * position i is allowed when the two labels differ or either is a wildcard; a wildcard's closed state is the ordinary one (blank).
+ * The end states are the last two.
+ * Simplified lattice: L + 1 states.  Entering label i costs its emission, e_w for a wildcard; staying in the state behind a
+ * wildcard costs e_w instead of lp[t, blank].
+ * Both: adjacent wildcards take at least one frame each; free start and end are a wildcard as the first and last label.
+ *   Z[b] = sum over all state sequences of the product of their emissions,        loss[b] = -ln Z[b]   (float32 [B])
+ * Z IS A SUM OVER LATTICE PATHS, NOT A PROBABILITY: one token sequence can match the lattice under several segmentations (a
+ * wildcard's frames may show the neighbouring label's token), so Z may exceed 1 and the loss may be negative.  w < 0 is the
+ * per-frame penalty STC uses against that.  This is the known property of W-CTC and STC, not a defect.
+ * Gradient.  Let gamma_t(k) be the posterior that frame t sits in an ordinary state (label or blank) emitting token k, and Gamma_t
+ * the posterior that it sits in a wildcard emission (classic: the wildcard's open state; simplified: the entry into a wildcard or
+ * a stay behind one): sum_k gamma_t(k) + Gamma_t = 1.  Then
+ *   grad[b, t, k] = d_loss[b] * ((1 - Gamma_t) * softmax(x[b, t])[k] - gamma_t(k))        CTC_AMD_WRT_LOGITS,   t < T_b
+ *                 = d_loss[b] * (-gamma_t(k) - Gamma_t * exp(x[b, t, k] - LSE_t))         CTC_AMD_WRT_LOGPROBS, t < T_b
+ *                 = 0 exactly                                                              T_b <= t < T
+ * Infeasible utterances are those of ctc_amd_wildcard_best_path: too few frames (each wildcard needs a frame of its own),
+ * label_length > U, a label outside [0, V) other than CTC_AMD_WILDCARD, a label equal to the blank, a position beyond label_stride,
+ * zero mass (also a row that is -inf throughout).  Such an utterance gets loss = +inf and an exactly zero gradient, its d_loss[b]
+ * is NOT INTERPRETED (it may be NaN), and it changes nothing else in the batch.  label_length <= 0 is the all-blank path.
+ * T_b == 0: loss 0 for an empty transcript, +inf otherwise.  NaN and +inf inputs: unspecified, the call completes.
+ * ctc_amd_check_labels keeps rejecting CTC_AMD_WILDCARD: it describes what the plain losses accept.
+ *   d_loss[B] float32 (in; NULL = ones), loss[B] float32 (out), grad (out; NULL = forward only, one launch) of element type
+ *   grad_dtype with element strides grad_stride_b / grad_stride_t >= V, token axis contiguous: every row t < T of every utterance
+ *   is written, elements between V and the stride are not.
+ * Validation in the order of ctc_amd_nbest_loss_grad: common arguments, element types, B == 0 (CTC_AMD_OK without a launch),
+ * strides (the gradient's only when grad != NULL), then wildcard_log_weight, loss non-NULL, V <= CTC_AMD_MAX_V, B * T < 2^33 when
+ * grad != NULL (the row stage's launch grid) (CTC_AMD_EINVAL each), then the workspace (CTC_AMD_EWORKSPACE before any launch).
+ * Logits in the producer formats of ctc_amd_loss_grad_ex, read in place with both access paths (16-byte / 8-byte row accesses when
+ * V, the strides and the base pointer allow them, element-wise with identical results otherwise).
+ * Numerics: the alpha and beta sweeps carry float64 base-2 logarithms, as ctc_amd_nbest_loss; a posterior is the float32 exp2 of a
+ * float64 difference; the softmax comes from the float32 row statistics.  The same bits on every run: the posteriors of the label
+ * positions that name one token are summed as 64-bit integers in units of 2^-40, Gamma_t and the blank's share lane-wise in a fixed
+ * order; no floating-point atomics anywhere.
+ * Workspace (may hold anything on entry).  want_grad == 0 (grad == NULL): 0 bytes, the pointer may be NULL.  Otherwise, with S = 2
+ * (classic) or 1 (simplified), NL the smallest power of two with 64 * NL >= U (1 for U <= 64) and r256(x) = x rounded up to a
+ * multiple of 256:
+ *   ctc_amd_wildcard_loss_workspace_bytes = r256(8 * B * T * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B)
+ * -- the chain's float64 state of every frame (overwritten by the posteriors), the row statistics, log2 Z.  B = 256, T = 1000,
+ * U = 128: 532.5 MB classic, 270.3 MB simplified (section 7 names what would cut it).  A call with
+ * grad == NULL accepts any workspace; one with grad != NULL needs the want_grad size.
+ * One launch of B workgroups without a gradient; with one, the alpha sweep that keeps its rows, the beta sweep (B workgroups each)
+ * and one wavefront per row (b, t) (T == 0: the first alone).  No allocation, copy or synchronisation; asynchronous on `stream`,
+ * capturable.
+ */
+int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_wildcard_loss_grad(int kind, int wrt,
+                               const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride,
+                               const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                               float wildcard_log_weight, int B, int T, int V, int U,
+                               const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
+                               void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

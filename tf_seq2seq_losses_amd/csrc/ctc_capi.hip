@@ -12,6 +12,7 @@
 #include "ctc_launch.h"
 #include "ctc_nbest_align.h"
 #include "ctc_prefix.h"
+#include "ctc_wild_loss.h"
 
 namespace ctc {
 // diagnostic override read by ctc_hessian.hip (ctc_amd_debug_override): process-wide, written only by tests / benchmarks between calls
@@ -774,6 +775,43 @@ int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_align_wild(p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
                               static_cast<hipStream_t>(stream)), "wildcard alignment launch");
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::WILD_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the loss kernel's wildcard label is the ABI's");
+
+int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  *out_bytes = ctc::wild_loss_workspace_bytes(kind, B, T, U, want_grad != 0);
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_nbest_loss_grad: common arguments, element types, B == 0, strides (the gradient's only when there
+// is one); then what only this call takes (the wildcard weight), the output, the vocabulary limit, the row stage's launch grid and
+// the workspace.
+int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                               int blank_index, float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss,
+                               void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
+  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
+    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
+  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
+  if (grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_wild_loss(p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+          "wildcard loss launch");
   return CTC_AMD_OK;
 }
 

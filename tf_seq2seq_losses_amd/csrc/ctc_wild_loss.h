@@ -1,0 +1,15 @@
+// Host launcher of ctc_wild_loss.hip (CTC loss and gradient with wildcard labels), for that unit and ctc_capi.hip.  Host declarations only.
+#pragma once
+#include "ctc_common.h"
+
+namespace ctc {
+
+constexpr int WILD_LOSS_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h): the label value of a wildcard position
+
+// forward only: no workspace.  With a gradient, each rounded up to 256 bytes: the chain's float64 state of every frame ([B][T][S * 64 *
+// NL + 2] doubles, S = 2 classic / 1 simplified; overwritten by the posteriors), the float32 row statistics ([B][T][4]) and log2 Z ([B])
+size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad);
+// grad == nullptr: one launch, the loss alone.  Otherwise the alpha sweep, the beta sweep and the row stage (T == 0: the first alone).
+hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws, hipStream_t st);
+
+}  // namespace ctc

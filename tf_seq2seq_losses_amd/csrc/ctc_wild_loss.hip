@@ -1,0 +1,538 @@
+// CTC loss and gradient with wildcard labels (W-CTC / star CTC) on both lattices: ctc_amd_wildcard_loss_grad (include/ctc_amd.h),
+// DESIGN.md section 5.16.  The training-side counterpart of ctc_align_wild.hip: the same lattice, summed over all its paths.
+//
+// The decomposition of ctc_nbest.hip for ONE transcript per utterance (its file-local helpers are repeated here; that file stays as
+// it is).  One workgroup per utterance, five wavefronts:
+//   wave 0      the chain: NL label positions per lane (position i = lane * NL + j), neighbours by DPP, the state in registers as
+//               float64 base-2 logarithms with a true -inf as log(0): nothing is rescaled, nothing can be flushed;
+//   waves 1..4  producers, one block of frames ahead through an LDS ring: each lane gathers x[t, label[i]] of its own NL positions
+//               and the wavefront streams the row once for (max, sum of exp).  No V-wide row is staged in LDS: any V costs no LDS.
+// A label equal to WILD_LOSS_WILDCARD marks a wildcard position.  Its emission is the wave-uniform e_w(t) = w + ln sum_k exp(lp[t, k]):
+// the constant w for logits, w plus the row's log-sum-exp for log-probabilities.  What differs from the plain recursion:
+//     O'[i] = lse(O[i], C[i-1], O[i-1] if label[i] != label[i-1] or either is a wildcard) + e[i]     e[i] = e_w for a wildcard
+//     C'[i] = lse(C[i], O[i]) + e[blank]
+//     S'[i] = lse(S[i] + (e_w if i is a wildcard else e[blank]), S[i-1] + e[i])
+// -- classic: two more sources of the `allow` bits, set once; simplified: one select per position for the horizontal weight.
+//
+// The kernel body runs in three modes (template parameter MODE), as ctc_nbest.hip's:
+//   MODE 0  the loss alone;
+//   MODE 1  the same alpha sweep, bit for bit, that also stores the chain's state of every frame (float64), log2 Z and the row
+//           statistics to the workspace;
+//   MODE 2  the beta sweep, frames from T_b - 1 down: per frame the chain reads its saved row, forms the posteriors
+//           2^(alpha + beta - log2 Z) and writes them as float32 pairs over the slots it has just read, then steps beta back;
+//   wild_grad_row_kernel  one wavefront per row (b, t): the posteriors of ordinary positions go into 64-bit fixed-point LDS bins by
+//           token (integer atomics: no arrival order in the sum), those of wildcard positions and of the blank into per-lane sums
+//           in a fixed order; the vocabulary in passes of 1024 columns; the row streams out as d_loss * (c * softmax - bins) with
+//           c = 1 - Gamma_t (logits) or -Gamma_t (log-probabilities; softmax is then exp(x - LSE_t)).
+// A saved row of frame t: per position i the pair (O, C) (classic, AFTER frame t) or S (simplified, BEFORE frame t), then the start
+// state: (2 or 1) * UP + 2 doubles.  After the beta sweep the first 8 bytes of position i hold
+//   classic:    (posterior of O[i] after frame t,  posterior of C[i] = a blank behind label i)
+//   simplified: (posterior of entering i at t,     posterior of staying in S[i] at t)
+// and the start state's slot its blank posterior.  .x belongs to the token's column, or to Gamma_t for a wildcard; .y to the blank's
+// column, or (simplified, behind a wildcard) to Gamma_t.
+#include "ctc_wild_loss.h"
+
+namespace ctc {
+namespace {
+
+constexpr int WL_PW = 4;                      // producer wavefronts
+constexpr int WL_THREADS = 64 * (1 + WL_PW);  // + the chain
+constexpr int WL_RING = 4096;                 // label emissions per ring buffer (two buffers): frames per block = 4096 / UP
+constexpr double LOG2E_D = 1.44269504088896340736;
+
+__device__ __forceinline__ float4 wl_row_load4(const char *row, int k, int dt) {
+  if (dt == 0) return *reinterpret_cast<const float4 *>(row + (size_t)k * 4);
+  const uint2 u = *reinterpret_cast<const uint2 *>(row + (size_t)k * 2);
+  return make_float4(h16_to_f32((unsigned short)(u.x & 0xffffu), dt), h16_to_f32((unsigned short)(u.x >> 16), dt),
+                     h16_to_f32((unsigned short)(u.y & 0xffffu), dt), h16_to_f32((unsigned short)(u.y >> 16), dt));
+}
+// the same four elements one by one (unaligned rows, V no multiple of 4): -inf past the row, which adds nothing to either statistic
+__device__ __forceinline__ float4 wl_row_load4_elem(const char *row, int k, int V, int dt) {
+  const float ninf = -__builtin_inff();
+  return make_float4(row_load1(row, k, dt), k + 1 < V ? row_load1(row, k + 1, dt) : ninf, k + 2 < V ? row_load1(row, k + 2, dt) : ninf,
+                     k + 3 < V ? row_load1(row, k + 3, dt) : ninf);
+}
+// running (max, sum of exp(x - max)) of one lane: four more elements (both access paths end here: identical bits)
+__device__ __forceinline__ void wl_stat_add4(float &m, float &s, const float4 v) {
+  const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+  s = s * fexp2((m - mn) * LOG2E) +
+      ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
+  m = mn;
+}
+
+// base-2 log(2^a + 2^b [+ 2^c]) of float64 operands that may be -inf (log 0): differences against the maximum, or against 0
+// when every operand is -inf (then every term is exp2(-inf) = 0 and the result log2(0) = -inf, without a NaN on the way)
+__device__ __forceinline__ double wl_lse(double a, double b) {
+  const double m = fmax(a, b);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2(fexp2((float)(a - mm)) + fexp2((float)(b - mm)));
+}
+__device__ __forceinline__ double wl_lse(double a, double b, double c) {
+  const double m = fmax(fmax(a, b), c);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm)));
+}
+
+// the gradient's workspace (MODE 0: unused)
+struct WlWs {
+  double *rows;  // [B][T][SRD] saved alpha rows, then the posteriors
+  float *stat;   // [B][T][4] x[blank], row max, log2 sum exp(x - max) of every frame
+  double *logp;  // [B] log2 Z, -inf for an infeasible utterance
+};
+constexpr int wl_row_doubles(int kind, int UP) { return (kind == 0 ? 2 : 1) * UP + 2; }
+
+template <int KIND, int NL, int MODE>
+__global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss, const WlWs ws) {
+  constexpr int UP = 64 * NL;
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
+  constexpr int SRD = wl_row_doubles(KIND, UP);
+  constexpr bool PF = NL <= 4;                  // MODE 2: the next frame's saved row is requested one frame ahead
+  constexpr int F = WL_RING / UP;               // frames per ring buffer: 64, 32, 16, 8, 4
+  constexpr int RS = UP + 4;                    // ring row: UP label emissions, then x[blank], the row max, log2 sum exp(x - max)
+  constexpr int FPW = F / WL_PW;                // frames per producer wavefront and block
+  constexpr int G = FPW < 4 ? FPW : 4;          // ... of which G are in flight together
+  const double NINF = -__builtin_inf();
+
+  __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
+  __shared__ int lab_s[UP];  // validated labels (-1: no emission, WILD_LOSS_WILDCARD: a wildcard)
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = p.V, blank = p.blank, dt = p.xdtype;
+  const bool lpin = p.wrt != 0;  // log-probability input
+  const int Tb = frame_count(p, b);
+  int L = label_count(p, b);
+  const bool too_long = too_many_labels(p, L);
+  if (too_long) L = 0;  // (nothing of such an utterance is read; it is reported infeasible below)
+
+  double lP = 0.0;
+  if constexpr (MODE == 2) {  // an infeasible utterance has no posteriors: the row stage writes its zeros without them
+    lP = ws.logp[b];
+    if (!(lP > NINF && lP < -NINF)) return;  // (the same in every thread)
+  }
+
+  for (int i = tid; i < UP; i += WL_THREADS) {
+    int tok = -1;
+    if (i < L) tok = label_at(p, label_row(p, b), i);
+    lab_s[i] = tok == WILD_LOSS_WILDCARD ? WILD_LOSS_WILDCARD : emits(p, tok) ? tok : -1;
+  }
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0;  // bit j = position lane * NL + j is a wildcard
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    lab[j] = lab_s[lane * NL + j];
+    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+  }
+
+  const int esz = dt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  // vector row accesses (16 bytes of float32, 8 bytes of 16-bit elements) need aligned rows; element-wise otherwise
+  const bool vec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
+  double *const myrows = MODE != 0 ? ws.rows + (size_t)b * p.T * SRD : nullptr;
+
+  // ---- chain state (wave 0) ----
+  double O[NL], C[NL];  // simplified: C is S, O unused.  MODE 2: beta, the mass of the frames still to come
+  unsigned allow = 0;   // classic: bit j = label[i] differs from label[i-1], or one of the two is a wildcard
+  int allow_nx = 0;     // ... of the next lane's first position (MODE 2)
+  double cs = 0.0;      // the start state: blank so far
+  auto allowed = [&](int i) {
+    if (i <= 0 || i >= UP) return false;
+    const int a = lab_s[i], q = lab_s[i - 1];
+    return a != q || a == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD;
+  };
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    O[j] = NINF; C[j] = NINF;
+    if (KIND == 0 && allowed(lane * NL + j)) allow |= 1u << j;
+  }
+  if constexpr (MODE == 2) {  // behind the last frame only the end states have any mass
+#pragma unroll
+    for (int j = 0; j < NL; ++j) O[j] = C[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
+    cs = L == 0 ? 0.0 : NINF;
+    if (KIND == 0) allow_nx = allowed((lane + 1) * NL) ? 1 : 0;
+  }
+
+  // the frame a block's position stands for (MODE 2 runs backwards); past the utterance's end its last, valid memory whose
+  // results are never stored
+  auto real_t = [&](int q) {
+    const int c = q < Tb ? q : Tb - 1;
+    return MODE == 2 ? Tb - 1 - c : c;
+  };
+
+  auto produce = [&](int kb) {
+    const int pw = wave - 1, q0 = kb * F;
+    float *const rb = ring + (kb & 1) * F * RS;
+    for (int f0 = pw * FPW; f0 < (pw + 1) * FPW; f0 += G) {
+      if (q0 + f0 >= Tb) break;
+      const char *row[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) row[g] = xb + (size_t)((long)real_t(q0 + f0 + g) * p.xst) * esz;
+      float e[G][NL], eb[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const float v = row_load1(row[g], lab[j] >= 0 ? lab[j] : blank, dt);
+          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+        }
+        eb[g] = row_load1(row[g], blank, dt);
+      }
+      // the row pass.  Both access paths give a lane the same elements in the same order: identical bits
+      float m[G], s[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) { m[g] = -3.402823466e38f; s[g] = 0.f; }
+      for (int k = lane * 4; k < V; k += 256) {
+        float4 v[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[g] = vec ? wl_row_load4(row[g], k, dt) : wl_row_load4_elem(row[g], k, V, dt);
+#pragma unroll
+        for (int g = 0; g < G; ++g) wl_stat_add4(m[g], s[g], v[g]);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float M = wave_max(m[g]);
+        const float S = wave_sum(s[g] * fexp2((m[g] - M) * LOG2E));
+        float l2s = flog2(S);
+        if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+        if (q0 + f0 + g < Tb) {
+          float *const r = rb + (f0 + g) * RS;
+#pragma unroll
+          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          if (lane == 0) {
+            *reinterpret_cast<float4 *>(r + UP) = make_float4(eb[g], M, l2s, 0.f);
+            if (MODE == 1) *reinterpret_cast<float4 *>(ws.stat + ((size_t)b * p.T + real_t(q0 + f0 + g)) * 4) = make_float4(eb[g], M, l2s, 0.f);
+          }
+        }
+      }
+    }
+  };
+
+  // what a ring row says about its frame, in the lattice's units (base-2 logarithms of lp)
+  struct Frame {
+    double Md, nl2s, eb, ew;
+  };
+  auto frame_of = [&](const float *r) {
+    const float4 sv = *reinterpret_cast<const float4 *>(r + UP);
+    Frame fr;
+    // logits: lp = x - max - ln sum; log-probabilities: lp = x
+    fr.Md = lpin ? 0.0 : (double)sv.y;
+    fr.nl2s = lpin ? 0.0 : -(double)sv.z;
+    fr.eb = fma((double)sv.x - fr.Md, LOG2E_D, fr.nl2s);
+    // e_w = w + ln sum_k exp(lp[t, k]): w for logits, w + LSE_t for log-probabilities; a row of -inf emits nothing
+    fr.ew = sv.z == __builtin_inff() ? NINF : lpin ? w2 + fma((double)sv.y, LOG2E_D, (double)sv.z) : w2;
+    return fr;
+  };
+
+  auto load_row = [&](int t, double (&A)[NS], double &Acs) {
+    const double *const r = myrows + (size_t)t * SRD;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) A[q] = r[lane * NS + q];
+    Acs = r[SRD - 2];
+  };
+
+  auto consume = [&](int kb) {
+    const int t0 = kb * F;
+    const int nf = Tb - t0 < F ? Tb - t0 : F;
+    const float *const rb = ring + (kb & 1) * F * RS;
+    for (int f = 0; f < nf; ++f) {
+      const float *const rr = rb + f * RS;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const Frame fr = frame_of(rr);
+      const double eb = fr.eb;
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
+      if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) r[lane * NS + j] = C[j];
+        if (lane == 0) r[SRD - 2] = cs;
+      }
+      if (KIND == 0) {
+        const double pO = from_prev_lane(O[NL - 1], NINF);
+        const double pC = from_prev_lane(C[NL - 1], cs);
+#pragma unroll
+        for (int j = NL - 1; j >= 0; --j) {
+          const double qO = j > 0 ? O[j > 0 ? j - 1 : 0] : pO;
+          const double qC = j > 0 ? C[j > 0 ? j - 1 : 0] : pC;
+          const double a2 = ((allow >> j) & 1u) ? qO : NINF;
+          const double o = wl_lse(O[j], qC, a2) + em(j);
+          C[j] = wl_lse(C[j], O[j]) + eb;
+          O[j] = o;
+        }
+      } else {
+        const double pS = from_prev_lane(C[NL - 1], cs);
+#pragma unroll
+        for (int j = NL - 1; j >= 0; --j) {
+          const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
+          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? fr.ew : eb), q + em(j));
+        }
+      }
+      cs += eb;
+      if (MODE == 1 && KIND == 0) {  // the state AFTER the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) *reinterpret_cast<double2 *>(r + lane * NS + 2 * j) = make_double2(O[j], C[j]);
+        if (lane == 0) r[SRD - 2] = cs;
+      }
+    }
+  };
+
+  // MODE 2: block kb holds the frames T_b - 1 - kb F downwards
+  double An[NS], Acsn = 0.0;
+  auto consume_back = [&](int kb) {
+    const int t0 = kb * F;
+    const int nf = Tb - t0 < F ? Tb - t0 : F;
+    const float *const rb = ring + (kb & 1) * F * RS;
+    for (int f = 0; f < nf; ++f) {
+      const int t = Tb - 1 - (t0 + f);
+      const float *const rr = rb + f * RS;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const Frame fr = frame_of(rr);
+      const double eb = fr.eb;
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      double A[NS], Acs;
+      if constexpr (PF) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) A[q] = An[q];
+        Acs = Acsn;
+        if (t > 0) load_row(t - 1, An, Acsn);
+      } else {
+        load_row(t, A, Acs);
+      }
+      double *const r = myrows + (size_t)t * SRD;
+      auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+      if (KIND == 0) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+          *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(post(A[2 * j] + O[j]), post(A[2 * j + 1] + C[j]));
+        if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
+        // beta back over frame t: x = what entering O[i] with this frame is worth
+        double x = O[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        cs = wl_lse(cs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? O[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+          const double cb = C[j] + eb;
+          O[j] = wl_lse(x, cb, al ? xn : NINF);
+          C[j] = wl_lse(cb, xn);
+          x = xn;
+        }
+      } else {
+        const double ap0 = from_prev_lane(A[NL - 1], Acs);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          const double h = ((wild >> j) & 1u) ? fr.ew : eb;
+          *reinterpret_cast<float2 *>(r + lane * NS + j) = make_float2(post(ap + em(j) + C[j]), post(A[j] + h + C[j]));
+        }
+        if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
+        double x = C[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        cs = wl_lse(cs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? C[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? fr.ew : eb), xn);
+          x = xn;
+        }
+      }
+    }
+  };
+
+  const int nb = (Tb + F - 1) / F;
+  if (wave > 0 && nb > 0) produce(0);
+  if constexpr (MODE == 2 && PF) {
+    if (wave == 0 && Tb > 0) load_row(Tb - 1, An, Acsn);
+  }
+  __syncthreads();
+  for (int kb = 0; kb < nb; ++kb) {
+    if (wave == 0) {
+      if constexpr (MODE == 2) consume_back(kb);
+      else consume(kb);
+    } else if (kb + 1 < nb) {
+      produce(kb + 1);
+    }
+    __syncthreads();
+  }
+
+  // ---- the end state ----
+  if (MODE != 2 && wave == 0) {
+    const int i = L - 1, jj = i & (NL - 1);
+    double cv = C[0], ov = O[0];
+#pragma unroll
+    for (int j = 1; j < NL; ++j)
+      if (j == jj) { cv = C[j]; ov = O[j]; }
+    double v = cs;
+    if (L > 0) v = KIND == 0 ? wl_lse(ov, cv) : cv;
+    if (too_long) v = NINF;
+    if (lane == (L > 0 ? i / NL : 0)) {
+      loss[b] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
+      if (MODE == 1) ws.logp[b] = v;
+    }
+  }
+}
+
+// ---- the gradient's row stage: one wavefront per row (b, t), four per workgroup ----
+constexpr int WLG_WAVES = 4;
+constexpr int WLG_CH = 1024;  // columns per pass
+constexpr int WLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units of 2^-40, so |bin| < U 2^40
+
+template <int KIND>
+__global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Problem p, const int UP, const float *__restrict__ d_loss,
+                                                                       const WlWs ws, void *__restrict__ grad) {
+  constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
+  __shared__ unsigned long long bins_all[WLG_WAVES][WLG_CH];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long row = (long)blockIdx.x * WLG_WAVES + wv;
+  if (row >= (long)p.B * p.T) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
+  unsigned long long *const bins = bins_all[wv];
+  const int b = (int)(row / p.T), t = (int)(row % p.T);
+  const int V = p.V, blank = p.blank, xdt = p.xdtype, gdt = p.gdtype;
+  const int Tb = frame_count(p, b);
+  const int xesz = xdt == 0 ? 4 : 2, gesz = gdt == 0 ? 4 : 2;
+  const char *const x = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb + (long)t * p.xst) * xesz;
+  char *const g = reinterpret_cast<char *>(grad) + (size_t)((long)b * p.gsb + (long)t * p.gst) * gesz;
+  const bool xvec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (xdt == 0 ? 15 : 7)) == 0;
+  const bool gvec = ((V | p.gsb | p.gst) & 3) == 0 && (reinterpret_cast<uintptr_t>(grad) & (gdt == 0 ? 15 : 7)) == 0;
+
+  // four consecutive elements of the gradient row from column k (k + 3 < V on the vector path; both paths convert alike)
+  auto gput4 = [&](int k, const float4 r) {
+    if (gdt == 0) {
+      if (gvec) { *reinterpret_cast<float4 *>(g + (size_t)k * 4) = r; return; }
+      float *const o = reinterpret_cast<float *>(g);
+      o[k] = r.x;
+      if (k + 1 < V) o[k + 1] = r.y;
+      if (k + 2 < V) o[k + 2] = r.z;
+      if (k + 3 < V) o[k + 3] = r.w;
+      return;
+    }
+    auto cv = [&](float f) { return gdt == 1 ? f32_to_bf16(f) : f32_to_f16(f); };
+    const unsigned short h0 = cv(r.x), h1 = cv(r.y), h2 = cv(r.z), h3 = cv(r.w);
+    if (gvec) {
+      *reinterpret_cast<uint2 *>(g + (size_t)k * 2) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
+      return;
+    }
+    unsigned short *const o = reinterpret_cast<unsigned short *>(g);
+    o[k] = h0;
+    if (k + 1 < V) o[k + 1] = h1;
+    if (k + 2 < V) o[k + 2] = h2;
+    if (k + 3 < V) o[k + 3] = h3;
+  };
+
+  // an infinite loss contributes nothing and its d_loss is not interpreted
+  const double lp = ws.logp[b];
+  const bool feasible = lp > -__builtin_inf() && lp < __builtin_inf();
+  if (!(t < Tb) || !feasible) {  // a padded frame, an infeasible utterance: exactly zero
+    for (int k = lane * 4; k < V; k += 256) gput4(k, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  const float dl = d_loss ? d_loss[b] : 1.f;
+  const float4 sv = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
+  const float mx = sv.y, l2s = sv.z;
+  const int L = label_count(p, b);  // (feasible: L <= U <= UP)
+  const char *const r = reinterpret_cast<const char *>(ws.rows) + ((size_t)b * p.T + t) * ((size_t)wl_row_doubles(KIND, UP) * 8);
+  const int32_t *const lab = label_row(p, b);
+
+  float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
+  for (int c0 = 0; c0 < V; c0 += WLG_CH) {
+#pragma unroll
+    for (int q = 0; q < WLG_CH / 64; ++q) bins[lane + 64 * q] = 0ull;
+    wave_lds_fence();
+    for (int i = lane; i < L; i += 64) {
+      const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+      const int tok = label_at(p, lab, i);
+      const bool w = tok == WILD_LOSS_WILDCARD;
+      const unsigned rel = (unsigned)(tok - c0);
+      if (!w && emits(p, tok) && rel < (unsigned)WLG_CH)
+        atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, WLG_FIX)));
+      if (c0 == 0) {
+        if (w) gam += pq.x;
+        if (KIND == 1 && w) gam += pq.y;
+        else blk += pq.y;
+      }
+    }
+    if (c0 == 0) {
+      if (lane == 0) blk += *reinterpret_cast<const float *>(r + (size_t)UP * SLOT);
+      blk = wave_sum(blk);
+      gam = wave_sum(gam);
+    }
+    wave_lds_fence();
+    // logits: (1 - Gamma) softmax - gamma;  log-probabilities: -Gamma exp(x - LSE) - gamma
+    const float c = p.wrt == 0 ? 1.f - gam : -gam;
+#pragma unroll
+    for (int q = 0; q < WLG_CH / 256; ++q) {
+      const int k = c0 + lane * 4 + 256 * q;
+      if (k < V) {
+        const float4 xv = xvec ? wl_row_load4(x, k, xdt) : wl_row_load4_elem(x, k, V, xdt);
+        float o[4];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[k - c0 + cc]), -WLG_FIX) + (k + cc == blank ? blk : 0.f);
+          const float sm = c == 0.f ? 0.f : c * fexp2((xs[cc] - mx) * LOG2E - l2s);
+          o[cc] = dl * (sm - bin);
+        }
+        gput4(k, make_float4(o[0], o[1], o[2], o[3]));
+      }
+    }
+    wave_lds_fence();
+  }
+}
+
+template <int KIND, int NL, int MODE>
+hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlWs &ws, hipStream_t st) {
+  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws);
+  return hipGetLastError();
+}
+
+template <int MODE>
+hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlWs &ws, hipStream_t st) {
+  typedef hipError_t Launch(const Problem &, double, float *, const WlWs &, hipStream_t);
+  static Launch *const table[2][5] = {
+      {launch_wild_loss<0, 1, MODE>, launch_wild_loss<0, 2, MODE>, launch_wild_loss<0, 4, MODE>, launch_wild_loss<0, 8, MODE>,
+       launch_wild_loss<0, 16, MODE>},
+      {launch_wild_loss<1, 1, MODE>, launch_wild_loss<1, 2, MODE>, launch_wild_loss<1, 4, MODE>, launch_wild_loss<1, 8, MODE>,
+       launch_wild_loss<1, 16, MODE>}};
+  const int NL = nl_for(p.U);
+  const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
+  if (lg < 0 || p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
+  return table[p.kind][lg](p, w2, loss, ws, st);
+}
+
+inline size_t wl_al(size_t x) { return (x + 255) & ~size_t(255); }
+
+}  // namespace
+
+// saved rows, then the row statistics, then log2 Z: each region rounded up to 256 bytes (include/ctc_amd.h has the formula)
+size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad) {
+  if (!want_grad) return 0;
+  const size_t rows = (size_t)B * T * wl_row_doubles(kind, 64 * nl_for(U)) * 8;
+  return wl_al(rows) + wl_al((size_t)B * T * 16) + wl_al((size_t)B * 8);
+}
+
+hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
+                         hipStream_t st) {
+  const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, st);
+  const int UP = 64 * nl_for(p.U);
+  const size_t rows = wl_al((size_t)p.B * p.T * wl_row_doubles(p.kind, UP) * 8);
+  const WlWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + rows),
+                reinterpret_cast<double *>(wsp + rows + wl_al((size_t)p.B * p.T * 16))};
+  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, st)) return e;
+  if (p.T == 0) return hipSuccess;  // no rows
+  if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, st)) return e;
+  const unsigned blocks = (unsigned)(((long)p.B * p.T + WLG_WAVES - 1) / WLG_WAVES);
+  if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
+  else hipLaunchKernelGGL((wild_grad_row_kernel<1>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
+  return hipGetLastError();
+}
+
+}  // namespace ctc

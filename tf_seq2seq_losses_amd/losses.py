@@ -329,6 +329,85 @@ def ctc_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_
 
 
 # --------------------------------------------------------------------------------------------------
+# training on partial transcripts (wildcard labels): an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class _WildcardLossFn(torch.autograd.Function):
+    """loss[B] of ops.wildcard_loss_grad with a gradient for the input: forward is the forward-only launch and keeps nothing but
+    the inputs; backward is ONE ops.wildcard_loss_grad call with d_loss (where the loss is +inf the incoming gradient is not
+    interpreted).  Backward is not itself differentiable: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight):
+        ctx.save_for_backward(x, labels, label_length, logit_length)
+        ctx.call = (kind, wrt, blank, U, weight)
+        return ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
+                                      wildcard_log_weight=weight, want_grad=False)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss):
+        x, labels, label_length, logit_length = ctx.saved_tensors
+        kind, wrt, blank, U, weight = ctx.call
+        _, grad = ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
+                                         wildcard_log_weight=weight)
+        return grad, None, None, None, None, None, None, None, None
+
+
+def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
+                   max_label_length=None) -> torch.Tensor:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    weight = float(wildcard_log_weight)
+    if not (weight <= 0.0) or weight == float("-inf"):
+        raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
+    U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    kind = ops.KINDS[kind_name]
+    if x.requires_grad and torch.is_grad_enabled():
+        return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight)
+    with torch.no_grad():  # forward only: the result is detached
+        return ops.wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
+                                      wildcard_log_weight=weight, want_grad=False)[0]
+
+
+def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                              blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                              max_label_length: Optional[int] = None) -> torch.Tensor:
+    """CTC loss of a partial transcript on the classic lattice (wildcard CTC / star temporal classification).  As classic_ctc_loss,
+    but a label equal to WILDCARD (-2) stands for any non-empty run of frames with any tokens on them: the lattice of
+    classic_ctc_wildcard_alignment, summed over all its paths instead of maximised.  Returns loss [batch] float32 = -ln Z, with a
+    first-order gradient when the logits require one (float32 / bfloat16 / float16 logits, any batch / time strides, read in place;
+    the gradient comes back in the logits' dtype and layout; a second derivative raises).  Z is a sum over lattice paths, NOT a
+    probability: one token sequence can match under several segmentations, so the loss may be negative.  wildcard_log_weight <= 0
+    is added to the log-emission of every wildcard frame (STC's per-frame penalty against that).  An infeasible sample (too few
+    frames -- every wildcard needs one --, a malformed label) has loss +inf and a zero gradient.  check_labels keeps rejecting -2."""
+    return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                          max_label_length)
+
+
+def simplified_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                 blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                 max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same on the simplified lattice: entering a wildcard and every stay behind it emit the wildcard's weight instead of a
+    token's or the blank's probability.  Same arguments and return value as classic_ctc_wildcard_loss."""
+    return _wildcard_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                          max_label_length)
+
+
+def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                    wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same for log-probabilities used as they stand: a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]);
+    ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                          wildcard_log_weight, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # greedy decoding: an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcDecoding(NamedTuple):

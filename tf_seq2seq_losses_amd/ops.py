@@ -612,6 +612,53 @@ def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     return loss, grad
 
 
+def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+                       blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
+                       grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
+                       want_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(loss[B] float32, grad[B, T, V] or None): the CTC loss of transcripts whose labels may be wildcards (_lib.WILDCARD), summed
+    over all paths of the lattice, and its gradient times d_loss[b] (default: ones) with respect to x (ctc_amd_wildcard_loss_grad).
+    want_grad=False is the forward-only launch and returns None for the gradient.  An utterance whose loss is +inf gets a zero
+    gradient and its d_loss is not interpreted.  labels [B, W]; U bounds every label_length (default: W, or the maximum inside when
+    W is large).  Takes the logits as greedy_decode does (float32 / bfloat16 / float16, any batch and time strides, read in place);
+    grad has grad_dtype (default: the logits') and the logits' layout where that is dense, a contiguous one otherwise.  Does not
+    synchronise."""
+    if labels.dim() != 2 or label_length.dim() != 1:
+        raise ValueError(f"wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args("wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
+                                                                 logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if d_loss is not None:
+        if tuple(d_loss.shape) != (B,):
+            raise ValueError(f"wildcard_loss_grad: d_loss must be [B] = {(B,)}, got {tuple(d_loss.shape)}")
+        if not (d_loss.dtype == torch.float32 and d_loss.device == dev and d_loss.is_contiguous()):
+            d_loss = d_loss.to(device=dev, dtype=torch.float32).contiguous()
+    if grad_dtype is None:
+        grad_dtype = x.dtype
+    if grad_dtype not in _DTYPES:
+        raise ValueError(f"wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
+    with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
+    key = ("wildcard_loss_grad", kind, B, T, V, U, with_grad)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.wildcard_loss_workspace_bytes(kind, B, T, V, U, with_grad)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
+    if B == 0:
+        return loss, grad
+    ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None
+    gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
+    with _on_device(dev):
+        rc = lib.ctc_amd_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                            _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                                            _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None, _DTYPES[grad_dtype], gsb, gst,
+                                            _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_wildcard_loss_grad")
+    return loss, grad
+
+
 def nbest_best_path(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None):
     """(score[B, N] float32, tokens[B, N, T] int32, label_index[B, N, T] int32, first_frame[B, N, U] int32, last_frame[B, N, U] int32):
