@@ -788,6 +788,65 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt,
                                void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Label posteriors: the soft alignment of a transcript over all CTC paths (added under ABI v6: two new entry points, nothing
+ * existing changed).  What a forward-backward pass says most directly: with what probability frame t belongs to label position i,
+ * over all alignments -- per POSITION, not per token, so repeated labels and wildcards keep their own columns.  Forward only.
+ *
+ * Inputs, lattices, emissions, wildcard_log_weight, infeasible utterances, formats and strides are exactly those of
+ * ctc_amd_wildcard_loss_grad (a transcript without CTC_AMD_WILDCARD is the plain CTC lattice).  L = label_length[b], T_b =
+ * logit_length[b] clamped to [0, T].  The posterior of a state (classic) or of a step (simplified) at frame t is the share of Z that
+ * passes through it.  For a feasible utterance, t < T_b and i < L:
+ * Classic lattice.
+ *   label_posterior[b, t, i] = the posterior of the open state of position i after frame t (the state that emits label i, or e_w
+ *                              for a wildcard);
+ *   blank_posterior[b, t]    = the sum of the posteriors of all closed states and of the start state (all of which emit the blank).
+ * Simplified lattice.
+ *   label_posterior[b, t, i] = the posterior of entering position i at frame t; if position i is a wildcard, plus the posterior of
+ *                              staying in the state behind it at frame t (which emits e_w);
+ *   blank_posterior[b, t]    = the sum of the posteriors of all stays that emit the blank (behind an ordinary label, and in the
+ *                              start state).
+ * Both: sum_i label_posterior[b, t, i] + blank_posterior[b, t] = 1.
+ *   duration[b, i]       = sum_t label_posterior[b, t, i]: the expected number of frames of position i;
+ *   expected_frame[b, i] = sum_t t * label_posterior[b, t, i] / duration[b, i]: the soft timestamp.
+ * duration and expected_frame ARE DEFINED AS REDUCTIONS OF THE FLOAT32 label_posterior VALUES THE CALL RETURNS: both sums run in
+ * float64 over t < T_b in a fixed order (eight contiguous runs of frames, each in frame order, then the runs in frame order), the
+ * quotient is taken in float64 of the two unrounded sums, and each result is rounded once to float32.  A float64 host reduction of
+ * the returned matrix therefore reproduces them to the last float32 bit or two.
+ *   loss[b] = -ln Z[b]: the same bits as ctc_amd_wildcard_loss_grad returns forward-only on the same arguments.
+ * Every element of every output is written, so the caller never has to clear a buffer: frames t >= T_b get 0 in label_posterior and
+ * blank_posterior; positions L <= i < U get 0 in label_posterior and duration and -1 in expected_frame; an infeasible utterance gets
+ * loss +inf, zeros, and -1 in expected_frame, and changes nothing else in the batch.
+ * On every path each position holds at least one frame, so duration >= 1 for i < L of a feasible utterance (up to the rounding of
+ * the posteriors); it is 1 for an ordinary label on the simplified lattice, which is entered exactly once.  label_length == 0: the
+ * all-blank path, blank_posterior = 1 for t < T_b.  T_b == 0: loss 0 for an empty transcript, +inf otherwise; nothing to write for
+ * t.  NaN and +inf inputs: unspecified, the call completes.
+ *   loss[B], label_posterior[B][T][U], blank_posterior[B][T] float32, contiguous; duration[B][U], expected_frame[B][U] float32,
+ *   both given or both NULL (then no statistics work is done and the other outputs are the same bits).
+ * Validation in the order of ctc_amd_wildcard_loss_grad: common arguments, element type, B == 0 (CTC_AMD_OK without a launch),
+ * strides, wildcard_log_weight; then loss non-NULL, label_posterior non-NULL when T > 0 and U > 0, blank_posterior non-NULL when
+ * T > 0, duration and expected_frame both or neither; V <= CTC_AMD_MAX_V (U <= CTC_AMD_MAX_U is a common argument; no launch grid
+ * here depends on B * T) (CTC_AMD_EINVAL each); then the workspace (CTC_AMD_EWORKSPACE before any launch).
+ * Numerics: the sweeps of ctc_amd_wildcard_loss_grad -- the alpha sweep is its gradient path's, bit for bit; a posterior is the
+ * float32 exp2 of a float64 difference; blank_posterior is summed over the wavefront in a fixed order.  Every element has one
+ * writer, there are no atomics: the same bits on every run.
+ * Workspace (may hold anything on entry): that of ctc_amd_wildcard_loss_grad with a gradient,
+ *   ctc_amd_label_posterior_workspace_bytes = ctc_amd_wildcard_loss_workspace_bytes(want_grad = 1)
+ *                                           = r256(8 * B * T * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B)
+ * (section 7 names what would cut it).  Launches: the alpha sweep, the beta sweep (B workgroups each; T == 0:
+ * the first alone) and, when duration is given and U > 0, one launch of a workgroup per utterance and 64 positions.  No allocation, copy or
+ * synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_label_posterior(int kind, int wrt,
+                            const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride,
+                            const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                            float wildcard_log_weight, int B, int T, int V, int U,
+                            float *loss /* [B] */, float *label_posterior /* [B][T][U] */, float *blank_posterior /* [B][T] */,
+                            float *duration /* [B][U], may be NULL */, float *expected_frame /* [B][U], may be NULL */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

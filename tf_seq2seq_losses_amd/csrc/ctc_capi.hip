@@ -815,6 +815,37 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits
   return CTC_AMD_OK;
 }
 
+int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
+}
+
+// Checked in the order of ctc_amd_wildcard_loss_grad: common arguments, element type, B == 0, strides, the wildcard weight; then the
+// outputs, the vocabulary limit and the workspace.
+int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                            int blank_index, float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                            float *blank_posterior, float *duration, float *expected_frame, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
+  if (int rc = check_common(c)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
+    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
+  if (!loss || (T > 0 && U > 0 && !label_posterior) || (T > 0 && !blank_posterior))
+    return fail(CTC_AMD_EINVAL, "null loss / label_posterior / blank_posterior pointer");
+  if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the label posteriors", V, MAX_V_GRAD);
+  const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, true);
+  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_label_posterior(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream)), "label posterior launch");
+  return CTC_AMD_OK;
+}
+
 // what ctc_amd_edit_distance and its size query take as a shape
 int check_edit(int B, int N, int R) {
   if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);

@@ -11,5 +11,10 @@ constexpr int WILD_LOSS_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h
 size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad);
 // grad == nullptr: one launch, the loss alone.  Otherwise the alpha sweep, the beta sweep and the row stage (T == 0: the first alone).
 hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws, hipStream_t st);
+// ctc_amd_label_posterior: the alpha sweep of the gradient path (so `ws` is a workspace of wild_loss_workspace_bytes(want_grad = true)),
+// the beta sweep that writes label_posterior [B][T][U] and blank_posterior [B][T] (none when T == 0) and, when duration is given,
+// one launch for duration / expected_frame [B][U] (none when U == 0)
+hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+                               float *duration, float *expected_frame, char *ws, hipStream_t st);
 
 }  // namespace ctc

@@ -14,12 +14,18 @@
 //     S'[i] = lse(S[i] + (e_w if i is a wildcard else e[blank]), S[i-1] + e[i])
 // -- classic: two more sources of the `allow` bits, set once; simplified: one select per position for the horizontal weight.
 //
-// The kernel body runs in three modes (template parameter MODE), as ctc_nbest.hip's:
+// The kernel body runs in four modes (template parameter MODE), the first three as ctc_nbest.hip's:
 //   MODE 0  the loss alone;
 //   MODE 1  the same alpha sweep, bit for bit, that also stores the chain's state of every frame (float64), log2 Z and the row
 //           statistics to the workspace;
 //   MODE 2  the beta sweep, frames from T_b - 1 down: per frame the chain reads its saved row, forms the posteriors
 //           2^(alpha + beta - log2 Z) and writes them as float32 pairs over the slots it has just read, then steps beta back;
+//   MODE 3  the beta sweep of ctc_amd_label_posterior: the same recursion and the same posteriors, but the
+//           saved rows stay as they are; each label position's posterior goes straight to label_posterior[b, t, i] (a lane's NL
+//           positions are contiguous: a frame is one run of U floats) and the blank's share, summed over the wavefront in a fixed
+//           order, to blank_posterior[b, t].  Rows t >= T_b and whole infeasible utterances are zeroed by the same workgroup;
+//   label_stat_kernel  duration and expected_frame: one lane per label position, float64 sums over the frames of the matrix
+//           MODE 3 has just written;
 //   wild_grad_row_kernel  one wavefront per row (b, t): the posteriors of ordinary positions go into 64-bit fixed-point LDS bins by
 //           token (integer atomics: no arrival order in the sum), those of wildcard positions and of the blank into per-lane sums
 //           in a fixed order; the vocabulary in passes of 1024 columns; the row streams out as d_loss * (c * softmax - bins) with
@@ -31,6 +37,8 @@
 // and the start state's slot its blank posterior.  .x belongs to the token's column, or to Gamma_t for a wildcard; .y to the blank's
 // column, or (simplified, behind a wildcard) to Gamma_t.
 #include "ctc_wild_loss.h"
+
+#include <type_traits>
 
 namespace ctc {
 namespace {
@@ -80,13 +88,21 @@ struct WlWs {
   double *logp;  // [B] log2 Z, -inf for an infeasible utterance
 };
 constexpr int wl_row_doubles(int kind, int UP) { return (kind == 0 ? 2 : 1) * UP + 2; }
+// ... and what MODE 3 writes instead of the posteriors in the rows
+struct WlPostWs : WlWs {
+  float *post;  // [B][T][U] label_posterior
+  float *blk;   // [B][T] blank_posterior
+};
+template <int MODE> using WlArg = std::conditional_t<MODE == 3, WlPostWs, WlWs>;
 
 template <int KIND, int NL, int MODE>
-__global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss, const WlWs ws) {
+__global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss,
+                                                               const WlArg<MODE> ws) {
+  constexpr bool BACK = MODE >= 2;              // a beta sweep: frames from T_b - 1 down
   constexpr int UP = 64 * NL;
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
   constexpr int SRD = wl_row_doubles(KIND, UP);
-  constexpr bool PF = NL <= 4;                  // MODE 2: the next frame's saved row is requested one frame ahead
+  constexpr bool PF = NL <= 4;                  // beta sweeps: the next frame's saved row is requested one frame ahead
   constexpr int F = WL_RING / UP;               // frames per ring buffer: 64, 32, 16, 8, 4
   constexpr int RS = UP + 4;                    // ring row: UP label emissions, then x[blank], the row max, log2 sum exp(x - max)
   constexpr int FPW = F / WL_PW;                // frames per producer wavefront and block
@@ -107,10 +123,17 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   if (too_long) L = 0;  // (nothing of such an utterance is read; it is reported infeasible below)
 
   double lP = 0.0;
-  if constexpr (MODE == 2) {  // an infeasible utterance has no posteriors: the row stage writes its zeros without them
-    lP = ws.logp[b];
-    if (!(lP > NINF && lP < -NINF)) return;  // (the same in every thread)
+  if constexpr (BACK) lP = ws.logp[b];
+  const bool feasible = lP > NINF && lP < -NINF;  // (the same in every thread)
+  if constexpr (MODE == 3) {  // every element has a writer: frames from T_b on, and every frame of an infeasible utterance, are zero
+    const size_t z0 = (size_t)(feasible ? Tb : 0), nz = (size_t)p.T - z0;
+    float *const zp = ws.post + ((size_t)b * p.T + z0) * p.U;
+    for (size_t q = tid; q < nz * p.U; q += WL_THREADS) zp[q] = 0.f;
+    float *const zb = ws.blk + (size_t)b * p.T + z0;
+    for (size_t q = tid; q < nz; q += WL_THREADS) zb[q] = 0.f;
   }
+  // an infeasible utterance has no posteriors: the row stage (MODE 2) writes its zeros without them
+  if (BACK && !feasible) return;
 
   for (int i = tid; i < UP; i += WL_THREADS) {
     int tok = -1;
@@ -148,7 +171,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
     O[j] = NINF; C[j] = NINF;
     if (KIND == 0 && allowed(lane * NL + j)) allow |= 1u << j;
   }
-  if constexpr (MODE == 2) {  // behind the last frame only the end states have any mass
+  if constexpr (BACK) {  // behind the last frame only the end states have any mass
 #pragma unroll
     for (int j = 0; j < NL; ++j) O[j] = C[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
     cs = L == 0 ? 0.0 : NINF;
@@ -159,7 +182,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   // results are never stored
   auto real_t = [&](int q) {
     const int c = q < Tb ? q : Tb - 1;
-    return MODE == 2 ? Tb - 1 - c : c;
+    return BACK ? Tb - 1 - c : c;
   };
 
   auto produce = [&](int kb) {
@@ -280,7 +303,33 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
     }
   };
 
-  // MODE 2: block kb holds the frames T_b - 1 - kb F downwards
+  // MODE 3: a lane's NL label posteriors of frame t (positions from U on are not written) and its part of the blank's share.
+  // Vector stores where U and the base pointer keep every group of VW positions aligned and whole, element-wise otherwise
+  [[maybe_unused]] auto put_post = [&](int t, const float (&pl)[NL], float pb) {
+    if constexpr (MODE == 3) {
+      constexpr int VW = NL < 4 ? NL : 4;
+      float *const o = ws.post + ((size_t)b * p.T + t) * p.U;
+      const int i0 = lane * NL, U = p.U;
+      if (p.U % VW == 0 && (reinterpret_cast<uintptr_t>(ws.post) & (VW * 4 - 1)) == 0) {
+#pragma unroll
+        for (int j = 0; j < NL; j += VW) {
+          if (i0 + j < U) {
+            if constexpr (VW == 4) *reinterpret_cast<float4 *>(o + i0 + j) = make_float4(pl[j], pl[j + 1], pl[j + 2], pl[j + 3]);
+            else if constexpr (VW == 2) *reinterpret_cast<float2 *>(o + i0 + j) = make_float2(pl[j], pl[j + 1]);
+            else o[i0 + j] = pl[j];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+          if (i0 + j < U) o[i0 + j] = pl[j];
+      }
+      const float bs = wave_sum(pb);
+      if (lane == 0) ws.blk[(size_t)b * p.T + t] = bs;
+    }
+  };
+
+  // beta sweeps: block kb holds the frames T_b - 1 - kb F downwards
   double An[NS], Acsn = 0.0;
   auto consume_back = [&](int kb) {
     const int t0 = kb * F;
@@ -304,13 +353,23 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       } else {
         load_row(t, A, Acs);
       }
-      double *const r = myrows + (size_t)t * SRD;
+      [[maybe_unused]] double *const r = myrows + (size_t)t * SRD;
       auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
       if (KIND == 0) {
+        if constexpr (MODE == 3) {  // the open states are the labels', the closed ones and the start state the blank's
+          float pl[NL], pb = lane == 0 ? post(Acs + cs) : 0.f;
 #pragma unroll
-        for (int j = 0; j < NL; ++j)
-          *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(post(A[2 * j] + O[j]), post(A[2 * j + 1] + C[j]));
-        if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
+          for (int j = 0; j < NL; ++j) {
+            pl[j] = post(A[2 * j] + O[j]);
+            pb += post(A[2 * j + 1] + C[j]);
+          }
+          put_post(t, pl, pb);
+        } else {
+#pragma unroll
+          for (int j = 0; j < NL; ++j)
+            *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(post(A[2 * j] + O[j]), post(A[2 * j + 1] + C[j]));
+          if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
+        }
         // beta back over frame t: x = what entering O[i] with this frame is worth
         double x = O[0] + em(0);
         const double xl = from_next_lane(x, NINF);
@@ -326,13 +385,23 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         }
       } else {
         const double ap0 = from_prev_lane(A[NL - 1], Acs);
+        [[maybe_unused]] float pl[NL], pb = 0.f;
+        if (MODE == 3 && lane == 0) pb = post(Acs + eb + cs);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
           const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
-          const double h = ((wild >> j) & 1u) ? fr.ew : eb;
-          *reinterpret_cast<float2 *>(r + lane * NS + j) = make_float2(post(ap + em(j) + C[j]), post(A[j] + h + C[j]));
+          const bool wj = ((wild >> j) & 1u) != 0;
+          const double h = wj ? fr.ew : eb;
+          const float pe = post(ap + em(j) + C[j]), ps = post(A[j] + h + C[j]);
+          if constexpr (MODE == 3) {  // a stay emits the wildcard behind a wildcard, the blank otherwise
+            pl[j] = wj ? pe + ps : pe;
+            pb += wj ? 0.f : ps;
+          } else {
+            *reinterpret_cast<float2 *>(r + lane * NS + j) = make_float2(pe, ps);
+          }
         }
-        if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
+        if constexpr (MODE == 3) put_post(t, pl, pb);
+        else if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
         double x = C[0] + em(0);
         const double xl = from_next_lane(x, NINF);
         cs = wl_lse(cs + eb, x);
@@ -348,13 +417,13 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
 
   const int nb = (Tb + F - 1) / F;
   if (wave > 0 && nb > 0) produce(0);
-  if constexpr (MODE == 2 && PF) {
+  if constexpr (BACK && PF) {
     if (wave == 0 && Tb > 0) load_row(Tb - 1, An, Acsn);
   }
   __syncthreads();
   for (int kb = 0; kb < nb; ++kb) {
     if (wave == 0) {
-      if constexpr (MODE == 2) consume_back(kb);
+      if constexpr (BACK) consume_back(kb);
       else consume(kb);
     } else if (kb + 1 < nb) {
       produce(kb + 1);
@@ -363,7 +432,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   }
 
   // ---- the end state ----
-  if (MODE != 2 && wave == 0) {
+  if (!BACK && wave == 0) {
     const int i = L - 1, jj = i & (NL - 1);
     double cv = C[0], ov = O[0];
 #pragma unroll
@@ -487,15 +556,52 @@ __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Pro
   }
 }
 
+// ---- duration and expected_frame of ctc_amd_label_posterior: one workgroup per utterance and 64 label positions ----
+// A lane is a position (a frame's 64 posteriors are one 256-byte read), a wavefront one of LS_SLICES contiguous runs of frames; the
+// float64 partial sums meet in LDS and are added in the order of the frames: a fixed order, the same bits on every run.
+constexpr int LS_SLICES = 8;
+
+__global__ __launch_bounds__(64 * LS_SLICES) void label_stat_kernel(const Problem p, const double *__restrict__ logp,
+                                                                    const float *__restrict__ post, float *__restrict__ duration,
+                                                                    float *__restrict__ expected_frame) {
+  __shared__ double sd[LS_SLICES][64], sm[LS_SLICES][64];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  const int i = blockIdx.y * 64 + lane;
+  const double lp = logp[b];
+  const bool feasible = lp > -__builtin_inf() && lp < __builtin_inf();  // (then label_length <= U)
+  const int Tb = frame_count(p, b);
+  const int per = (Tb + LS_SLICES - 1) / LS_SLICES;
+  const int t0 = sl * per, t1 = t0 + per < Tb ? t0 + per : Tb;
+  double d = 0.0, m = 0.0;
+  if (feasible && i < p.U && i < label_count(p, b)) {
+    const float *const r = post + (size_t)b * p.T * p.U + i;
+#pragma unroll 8
+    for (int t = t0; t < t1; ++t) {
+      const double v = (double)r[(size_t)t * p.U];
+      d += v;
+      m += (double)t * v;
+    }
+  }
+  sd[sl][lane] = d;
+  sm[sl][lane] = m;
+  __syncthreads();
+  if (sl != 0 || i >= p.U) return;
+  d = 0.0; m = 0.0;
+#pragma unroll
+  for (int q = 0; q < LS_SLICES; ++q) { d += sd[q][lane]; m += sm[q][lane]; }
+  duration[(size_t)b * p.U + i] = (float)d;
+  expected_frame[(size_t)b * p.U + i] = d > 0.0 ? (float)(m / d) : -1.f;
+}
+
 template <int KIND, int NL, int MODE>
-hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlWs &ws, hipStream_t st) {
+hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, hipStream_t st) {
   hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws);
   return hipGetLastError();
 }
 
 template <int MODE>
-hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlWs &ws, hipStream_t st) {
-  typedef hipError_t Launch(const Problem &, double, float *, const WlWs &, hipStream_t);
+hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, hipStream_t st) {
+  typedef hipError_t Launch(const Problem &, double, float *, const WlArg<MODE> &, hipStream_t);
   static Launch *const table[2][5] = {
       {launch_wild_loss<0, 1, MODE>, launch_wild_loss<0, 2, MODE>, launch_wild_loss<0, 4, MODE>, launch_wild_loss<0, 8, MODE>,
        launch_wild_loss<0, 16, MODE>},
@@ -508,6 +614,13 @@ hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlWs &w
 }
 
 inline size_t wl_al(size_t x) { return (x + 255) & ~size_t(255); }
+
+// the three regions of a workspace of wild_loss_workspace_bytes(want_grad = true)
+WlWs wl_regions(const Problem &p, char *wsp) {
+  const size_t rows = wl_al((size_t)p.B * p.T * wl_row_doubles(p.kind, 64 * nl_for(p.U)) * 8);
+  return WlWs{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + rows),
+              reinterpret_cast<double *>(wsp + rows + wl_al((size_t)p.B * p.T * 16))};
+}
 
 }  // namespace
 
@@ -523,9 +636,7 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
   if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, st);
   const int UP = 64 * nl_for(p.U);
-  const size_t rows = wl_al((size_t)p.B * p.T * wl_row_doubles(p.kind, UP) * 8);
-  const WlWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + rows),
-                reinterpret_cast<double *>(wsp + rows + wl_al((size_t)p.B * p.T * 16))};
+  const WlWs ws = wl_regions(p, wsp);
   if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, st)) return e;
   if (p.T == 0) return hipSuccess;  // no rows
   if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, st)) return e;
@@ -533,6 +644,23 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
   if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
   else hipLaunchKernelGGL((wild_grad_row_kernel<1>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
   return hipGetLastError();
+}
+
+hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+                               float *duration, float *expected_frame, char *wsp, hipStream_t st) {
+  const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  WlPostWs ws;
+  static_cast<WlWs &>(ws) = wl_regions(p, wsp);
+  ws.post = label_posterior;
+  ws.blk = blank_posterior;
+  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, st)) return e;
+  if (p.T > 0)
+    if (hipError_t e = run_wild_mode<3>(p, w2, loss, ws, st)) return e;
+  if (duration && p.U > 0) {
+    hipLaunchKernelGGL(label_stat_kernel, dim3(p.B, (p.U + 63) / 64), dim3(64 * LS_SLICES), 0, st, p, ws.logp, label_posterior, duration, expected_frame);
+    return hipGetLastError();
+  }
+  return hipSuccess;
 }
 
 }  // namespace ctc

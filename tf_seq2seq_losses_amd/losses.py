@@ -408,6 +408,77 @@ def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_lengt
 
 
 # --------------------------------------------------------------------------------------------------
+# label posteriors (soft alignment over all paths): an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcLabelPosterior(NamedTuple):
+    """loss [batch] float32: -ln Z, the bits of the wildcard loss on the same arguments (+inf: no path);
+    label_posterior [batch, max_length, U] float32: the probability, over all alignments, that frame t belongs to label position i
+    (per position, not per token: a repeated label and every wildcard keep their own columns), U the bound on the label length
+    the call ran with (the width of `labels`, or max_label_length);
+    blank_posterior [batch, max_length] float32: the probability that frame t is a blank outside any label; each frame's
+    label_posterior and blank_posterior sum to 1;
+    duration [batch, U] float32: the expected number of frames of every position, the sum of its label_posterior column;
+    expected_frame [batch, U] float32: its soft timestamp, sum_t t * label_posterior / duration (-1 from label_length on).
+    Frames beyond logit_length and positions from label_length on are 0; an infeasible sample has loss +inf, zeros, and -1 in
+    expected_frame."""
+    loss: torch.Tensor
+    label_posterior: torch.Tensor
+    blank_posterior: torch.Tensor
+    duration: torch.Tensor
+    expected_frame: torch.Tensor
+
+
+def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
+                     max_label_length=None) -> CtcLabelPosterior:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    weight = float(wildcard_log_weight)
+    if not (weight <= 0.0) or weight == float("-inf"):
+        raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
+    U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    with torch.no_grad():  # forward only: the result is detached
+        return CtcLabelPosterior(*ops.label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
+                                                      _blank(blank_index), U, wildcard_log_weight=weight))
+
+
+def classic_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+    """The soft alignment of a transcript on the classic lattice: the occupancy matrix of a forward-backward pass, where
+    classic_ctc_alignment returns the single best path.  label_posterior[b, t, i] is the probability that frame t emits label
+    position i; a frame's remaining mass is blank_posterior[b, t].  Labels may contain WILDCARD (-2), with the lattice and
+    wildcard_log_weight of classic_ctc_wildcard_loss; without one this is plain CTC.  Arguments as classic_ctc_wildcard_loss
+    (float32 / bfloat16 / float16 logits, any batch / time strides, read in place); returns CtcLabelPosterior, float32 on the
+    logits' device, not differentiable.  check_labels keeps rejecting -2."""
+    return _label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                            max_label_length)
+
+
+def simplified_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                   blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                   max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+    """The same on the simplified lattice: label_posterior[b, t, i] is the probability that label i is emitted at frame t (so an
+    ordinary label's duration is 1 and expected_frame is its expected emission frame); a wildcard also owns the frames spent
+    behind it.  Same arguments and return value as classic_ctc_label_posterior."""
+    return _label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                            wildcard_log_weight, max_label_length)
+
+
+def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                      wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+    """The same for log-probabilities used as they stand (a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]));
+    ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                            wildcard_log_weight, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # greedy decoding: an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcDecoding(NamedTuple):

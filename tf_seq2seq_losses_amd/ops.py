@@ -659,6 +659,40 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
     return loss, grad
 
 
+def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+                    blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True):
+    """(loss[B], label_posterior[B, T, U], blank_posterior[B, T], duration[B, U], expected_frame[B, U]), all float32: with what
+    probability every frame belongs to every label position (or to the blank) over all paths of the lattice, and per position the
+    expected number of frames and the soft timestamp (ctc_amd_label_posterior).  Labels may be wildcards (_lib.WILDCARD); the loss
+    is wildcard_loss_grad's forward-only one, bit for bit.  want_stats=False skips the statistics launch and returns None for the
+    last two.  Arguments as wildcard_loss_grad; every element of every output is written.  Does not synchronise."""
+    if labels.dim() != 2 or label_length.dim() != 1:
+        raise ValueError(f"label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args("label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
+                                                                 logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    key = ("label_posterior", kind, B, T, V, U)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.label_posterior_workspace_bytes(kind, B, T, V, U)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    post = torch.empty((B, T, U), dtype=torch.float32, device=dev)
+    blk = torch.empty((B, T), dtype=torch.float32, device=dev)
+    dur = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    exf = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    if B == 0:
+        return loss, post, blk, dur, exf
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                         _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                                         _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_label_posterior")
+    return loss, post, blk, dur, exf
+
+
 def nbest_best_path(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None):
     """(score[B, N] float32, tokens[B, N, T] int32, label_index[B, N, T] int32, first_frame[B, N, U] int32, last_frame[B, N, U] int32):
