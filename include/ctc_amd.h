@@ -67,6 +67,7 @@ extern "C" {
  *   V <= CTC_AMD_MAX_V          tokens for loss / gradient / alpha-beta (one 64 KB LDS token row per wavefront)
  *   V <= CTC_AMD_MAX_V_HESSIAN  tokens for ctc_amd_hessian / ctc_amd_hvp (V + 4 floats of LDS per wavefront)
  * ctc_amd_best_path takes V <= CTC_AMD_MAX_V as well (it stages no row in LDS; the limit is the ABI's, kept uniform).
+ * ctc_amd_long_best_path alone takes U <= CTC_AMD_LONG_MAX_U (it spreads the label axis over workgroups, 1024 positions each).
  * ctc_amd_loss_grad* / ctc_amd_grad_resume / ctc_amd_alpha_beta: vector (16-byte / 8-byte) row accesses are used when V, the
  * strides AND the base pointers are aligned; any other alignment runs element-wise paths with identical results.
  * ctc_amd_hessian / ctc_amd_hvp require 16-byte aligned tensor pointers (CTC_AMD_EINVAL otherwise). */
@@ -719,6 +720,70 @@ int ctc_amd_wildcard_best_path(int kind, int wrt,
                                int32_t *first_frame /* [B][U], may be NULL */, int32_t *last_frame /* [B][U], may be NULL */,
                                float *label_score /* [B][U], may be NULL */,
                                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Long-form forced alignment: transcripts beyond CTC_AMD_MAX_U labels (added under ABI v6: two new entry points, nothing existing
+ * changed; CTC_AMD_MAX_U and every other call's validation stay as they are).  The best path of ctc_amd_best_path -- the same
+ * lattices, recursion, candidate order, strict comparisons and float64 state -- for U <= CTC_AMD_LONG_MAX_U label positions: a
+ * whole recording against its transcript (ten minutes at 20 ms frames and character labels: T = 30 000, U = 8 000).  The
+ * reference has no counterpart.
+ *
+ * Decomposition.  The lattice is tiled over label blocks of 1024 positions (16 per lane of one
+ * wavefront) and time blocks of frames_per_tile frames; K = max(1, ceil(U / 1024)) label blocks, J = max(1, ceil(T / TF)) time
+ * blocks.  Launch d = 0 .. K + J - 2 runs the tiles (k, j) with k + j = d of every utterance, one workgroup each; a tile takes its
+ * chain state from the row its predecessor in time left and its left edge from the column its left neighbour stored, both on
+ * launch d - 1, so the order of the launches on the stream is the only dependency: no workgroup waits for another.  One further
+ * launch traces the path back across the tiles, and one more derives first_frame / last_frame when either is asked for.
+ * K + J - 1 (+ 1 or 2) launches whatever the lengths are: asynchronous on `stream`, capturable, no allocation, copy or
+ * synchronisation.  Vector stores only, no atomics, one writer per element: the same bits on every run.  float64 max and add hand
+ * over exactly between tiles, so the path does not depend on frames_per_tile or on B; `score` may differ in its last bits between
+ * values of frames_per_tile (the float64 sum of the rows' log-sum-exps is taken per time block, then over the blocks).
+ *
+ * frames_per_tile: 0 selects CTC_AMD_LONG_FRAMES_DEFAULT; otherwise a positive multiple of CTC_AMD_LONG_FRAMES_MULTIPLE (the
+ * frames of one ring block at 16 positions per lane); anything else is CTC_AMD_EINVAL.  Smaller tiles put more workgroups on a
+ * diagonal and cost more launches.
+ *
+ *   score[B]            float32: as ctc_amd_best_path documents it; -inf when no path exists
+ *   tokens[B][T]        int32:   pi_t; -1 for t >= T_b
+ *   label_index[B][T]   int32:   as ctc_amd_best_path documents it.  May be NULL.
+ *   first_frame[B][U]   int32:   the first frame whose label_index is i, for i < label_length; -1 from label_length on (the
+ *   last_frame[B][U]    int32:   convention of ctc_amd_nbest_best_path).  ... and the last.  Each may be NULL.
+ * The input contract of the other entry points holds: too few frames, label_length > U, a label equal to
+ * the blank or outside [0, V) -- CTC_AMD_WILDCARD included: wildcards are not part of this call -- and a position beyond
+ * label_stride make the utterance infeasible: score = -inf and -1 everywhere else.  label_length == 0: the all-blank path.
+ * T_b == 0: score 0 for an empty label, -inf otherwise.  Ties: deterministic but unspecified, in the words of ctc_amd_best_path;
+ * in practice a call with U <= CTC_AMD_MAX_U (legal: one label block) returns the path of ctc_amd_best_path.
+ *
+ * Validation follows ctc_amd_best_path in its order and with its messages: common arguments (U <= CTC_AMD_LONG_MAX_U in place of
+ * CTC_AMD_MAX_U), element type, B == 0 (CTC_AMD_OK without a launch), strides, then score and tokens non-NULL, V <= CTC_AMD_MAX_V,
+ * frames_per_tile (also: B so large that a launch grid would pass 2^31 - 1 workgroups) -- CTC_AMD_EINVAL each -- then the
+ * workspace (CTC_AMD_EWORKSPACE before any launch).  Logits in the producer formats of ctc_amd_loss_grad_ex, read in place with
+ * both access paths (16-byte / 8-byte row accesses when V, the strides and the base pointer allow them, element-wise otherwise).
+ *
+ * Workspace (may hold anything on entry; every count is a size_t: B * K * T * 512 passes 2^31 at realistic sizes).  With
+ * TF = frames_per_tile or the default, K and J as above and r256(x) = x rounded up to a multiple of 256:
+ *   ctc_amd_long_best_path_workspace_bytes =
+ *       r256(B * K * T * 512)          back-pointers: one 8-byte word per lane, frame and label block
+ *     + r256(B * (K - 1) * T * 16)     columns: the float64 pair (open, closed) of a block's last position before every frame
+ *     + r256(B * K * 16448)            rows: the chain state of every label block, 2 * 1024 + 8 float64
+ *     + r256(B * J * 8)                the log-sum-exp partial sum of every time block
+ *     + r256(B * T * 4)                label_index when the caller passes none
+ *     + r256(B * 4)                    feasibility of every utterance
+ * B = 1, T = 30000, U = 8192, frames_per_tile = 0 (128): K = 8, J = 235:
+ *   122 880 000 + 3 360 000 + 131 584 + 2 048 + 120 064 + 256 = 126 493 952 bytes, 242 + 2 launches.
+ */
+#define CTC_AMD_LONG_MAX_U 65536
+#define CTC_AMD_LONG_FRAMES_MULTIPLE 4
+#define CTC_AMD_LONG_FRAMES_DEFAULT 128
+int ctc_amd_long_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes /*host*/);
+int ctc_amd_long_best_path(int kind, int wrt,
+                           const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride,
+                           const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                           int B, int T, int V, int U, int frames_per_tile,
+                           float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                           int32_t *first_frame /* [B][U], may be NULL */, int32_t *last_frame /* [B][U], may be NULL */,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * CTC loss and gradient with wildcard labels: training on partial transcripts (added under ABI v6: two new entry points, nothing

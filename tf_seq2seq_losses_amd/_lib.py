@@ -19,6 +19,7 @@ WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
 WILDCARD = -2  # CTC_AMD_WILDCARD: the label value of a wildcard position (ctc_amd_wildcard_best_path)
+LONG_MAX_U, LONG_FRAMES_MULTIPLE, LONG_FRAMES_DEFAULT = 65536, 4, 128  # CTC_AMD_LONG_*: ctc_amd_long_best_path
 PREFIX_MAX, PREFIX_GROUP = 64, 8  # CTC_AMD_PREFIX_MAX, CTC_AMD_PREFIX_GROUP
 NBEST_MAX, NBEST_GROUP = 64, 8  # CTC_AMD_NBEST_MAX, CTC_AMD_NBEST_GROUP: hypotheses per utterance, and per workgroup (one logits read)
 
@@ -90,6 +91,9 @@ SIGNATURES = {
     "ctc_amd_wildcard_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
     "ctc_amd_wildcard_best_path": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # score, tokens, label_index, first_frame, last_frame, label_score
                                                          _c_void_p, _c_size_t, _c_void_p]),                              # ws, bytes, stream
+    "ctc_amd_long_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
+    "ctc_amd_long_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, score, tokens, label_index, first_frame, last_frame
+                                                     _c_void_p, _c_size_t, _c_void_p]),                          # ws, bytes, stream
     "ctc_amd_wildcard_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
     "ctc_amd_wildcard_loss_grad": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +    # .. blank_index, wildcard_log_weight, B, T, V, U
                                    [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),     # d_loss, loss .. grad strides, ws, bytes, stream
@@ -219,6 +223,13 @@ def nbest_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N
 def wildcard_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_wildcard_best_path_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_wildcard_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def long_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_best_path_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_best_path_workspace_bytes")
     return int(out.value)
 
 

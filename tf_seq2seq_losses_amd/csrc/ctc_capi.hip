@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "ctc_align_long.h"
 #include "ctc_align_wild.h"
 #include "ctc_amd.h"
 #include "ctc_beam.h"
@@ -59,13 +60,13 @@ bool shape_ok(int kind, int B, int T, int V, int U) {
   return (kind == CTC_AMD_CLASSIC || kind == CTC_AMD_SIMPLIFIED) && B >= 0 && T >= 0 && V > 0 && U >= 0 && U <= MAX_U;
 }
 
-int check_common(const Common &c) {
+int check_common(const Common &c, int max_u = MAX_U) {  // (max_u: CTC_AMD_LONG_MAX_U for the tiled alignment, whose label axis spans workgroups)
   if (c.kind != CTC_AMD_CLASSIC && c.kind != CTC_AMD_SIMPLIFIED) return fail(CTC_AMD_EINVAL, "kind must be 0 (classic) or 1 (simplified), got %d", c.kind);
   if (c.wrt != CTC_AMD_WRT_LOGITS && c.wrt != CTC_AMD_WRT_LOGPROBS) return fail(CTC_AMD_EINVAL, "wrt must be 0 (logits) or 1 (logprobs), got %d", c.wrt);
   if (c.B < 0 || c.T < 0 || c.V <= 0 || c.U < 0 || c.label_stride < 0)
     return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d V=%d U=%d label_stride=%d", c.B, c.T, c.V, c.U, c.label_stride);
   if (c.blank < 0 || c.blank >= c.V) return fail(CTC_AMD_EINVAL, "blank_index %d outside [0, %d)", c.blank, c.V);
-  if (c.U > MAX_U) return fail(CTC_AMD_EINVAL, "U=%d exceeds the supported maximum %d", c.U, MAX_U);
+  if (c.U > max_u) return fail(CTC_AMD_EINVAL, "U=%d exceeds the supported maximum %d", c.U, max_u);
   if (c.B > 0 && (!c.label_length || !c.logit_length)) return fail(CTC_AMD_EINVAL, "null length pointer");
   if (c.B > 0 && c.T > 0 && !c.logits) return fail(CTC_AMD_EINVAL, "null logits pointer");
   if (c.B > 0 && c.label_stride > 0 && !c.labels) return fail(CTC_AMD_EINVAL, "null labels pointer");
@@ -775,6 +776,48 @@ int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_align_wild(p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
                               static_cast<hipStream_t>(stream)), "wildcard alignment launch");
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::LONG_MAX_U == CTC_AMD_LONG_MAX_U && ctc::LONG_RING_FRAMES == CTC_AMD_LONG_FRAMES_MULTIPLE &&
+              ctc::LONG_TF_DEFAULT == CTC_AMD_LONG_FRAMES_DEFAULT, "the tiled alignment's limits are the ABI's");
+
+int ctc_amd_long_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
+    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  ctc::LongPlan plan;
+  if (!ctc::long_plan(B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_best_path, with its messages and CTC_AMD_LONG_MAX_U in place of its limit on U: common arguments,
+// element type, B == 0, strides; then the two outputs that must exist, the vocabulary limit, frames_per_tile and the workspace.
+int ctc_amd_long_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                           int blank_index, int B, int T, int V, int U, int frames_per_tile, float *score, int32_t *tokens,
+                           int32_t *label_index, int32_t *first_frame, int32_t *last_frame, void *workspace, size_t workspace_bytes,
+                           void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
+  ctc::LongPlan plan;
+  if (!ctc::long_plan(B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_align_long(p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                              static_cast<hipStream_t>(stream)), "long alignment launch");
   return CTC_AMD_OK;
 }
 

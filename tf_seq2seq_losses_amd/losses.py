@@ -329,6 +329,71 @@ def ctc_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_
 
 
 # --------------------------------------------------------------------------------------------------
+# long-form forced alignment (a whole recording against its transcript): an extension, the reference has no counterpart
+# --------------------------------------------------------------------------------------------------
+class CtcLongAlignment(NamedTuple):
+    """score [batch] float32: log-probability of the best path (-inf: no path exists);
+    tokens [batch, max_length] int32: the token every frame emits on it (-1 beyond logit_length);
+    label_index [batch, max_length] int32: index into labels[b] of the label the frame emits or, on the classic lattice, continues
+    by repeating it; -1 on blank frames and beyond logit_length;
+    first_frame, last_frame [batch, U] int32: the first and last frame of every label (-1 from label_length on), U the bound on the
+    label length the call ran with (the width of `labels`, or max_label_length).
+    An infeasible sample has score = -inf and -1 in every frame and label."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    label_index: torch.Tensor
+    first_frame: torch.Tensor
+    last_frame: torch.Tensor
+
+
+def _long_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, frames_per_tile=None,
+                max_label_length=None) -> CtcLongAlignment:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    with torch.no_grad():  # a path is not differentiable: the result is detached
+        prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
+                            host_max_label_length=max_label_length)
+        return CtcLongAlignment(*ops.long_best_path(ops.KINDS[kind_name], wrt, prep, 0 if frames_per_tile is None else int(frames_per_tile)))
+
+
+def classic_ctc_long_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                               blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
+                               max_label_length: Optional[int] = None) -> CtcLongAlignment:
+    """Forced alignment of a long recording on the classic lattice: the path of classic_ctc_alignment for transcripts of up to
+    65536 labels (that call stops at 1024), with the first and last frame of every label.  The lattice is tiled over blocks of 1024
+    labels and of `frames_per_tile` frames (None: 128; otherwise a positive multiple of 4) and swept one anti-diagonal of tiles per
+    kernel launch, so that one long utterance spreads over many compute units; smaller tiles mean more of them side by side and
+    more launches.  The path does not depend on frames_per_tile.  Arguments otherwise as classic_ctc_alignment (float32 /
+    bfloat16 / float16 logits, any batch / time strides, read in place); wildcards are not supported here.  Returns
+    CtcLongAlignment, not differentiable."""
+    return _long_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, frames_per_tile,
+                       max_label_length)
+
+
+def simplified_ctc_long_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                  blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
+                                  max_label_length: Optional[int] = None) -> CtcLongAlignment:
+    """The same on the simplified lattice (every non-blank frame emits exactly one label).  Same arguments and return value as
+    classic_ctc_long_alignment."""
+    return _long_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, frames_per_tile,
+                       max_label_length)
+
+
+def ctc_long_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                     frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None) -> CtcLongAlignment:
+    """The same for log-probabilities used as they stand (the counterpart of ctc_alignment_from_logproba); ctc_loss_data_cls
+    selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index, frames_per_tile,
+                       max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # training on partial transcripts (wildcard labels): an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class _WildcardLossFn(torch.autograd.Function):
