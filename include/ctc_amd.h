@@ -67,7 +67,8 @@ extern "C" {
  *   V <= CTC_AMD_MAX_V          tokens for loss / gradient / alpha-beta (one 64 KB LDS token row per wavefront)
  *   V <= CTC_AMD_MAX_V_HESSIAN  tokens for ctc_amd_hessian / ctc_amd_hvp (V + 4 floats of LDS per wavefront)
  * ctc_amd_best_path takes V <= CTC_AMD_MAX_V as well (it stages no row in LDS; the limit is the ABI's, kept uniform).
- * ctc_amd_long_best_path alone takes U <= CTC_AMD_LONG_MAX_U (it spreads the label axis over workgroups, 1024 positions each).
+ * ctc_amd_long_best_path and ctc_amd_long_wildcard_best_path alone take U <= CTC_AMD_LONG_MAX_U (they spread the label axis over
+ * workgroups, 1024 positions each).
  * ctc_amd_loss_grad* / ctc_amd_grad_resume / ctc_amd_alpha_beta: vector (16-byte / 8-byte) row accesses are used when V, the
  * strides AND the base pointers are aligned; any other alignment runs element-wise paths with identical results.
  * ctc_amd_hessian / ctc_amd_hvp require 16-byte aligned tensor pointers (CTC_AMD_EINVAL otherwise). */
@@ -784,6 +785,73 @@ int ctc_amd_long_best_path(int kind, int wrt,
                            float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
                            int32_t *first_frame /* [B][U], may be NULL */, int32_t *last_frame /* [B][U], may be NULL */,
                            void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Long-form forced alignment of partial transcripts: wildcard labels and per-label scores beyond CTC_AMD_MAX_U labels (added under
+ * ABI v6: two new entry points, nothing existing changed).  ctc_amd_wildcard_best_path for U <= CTC_AMD_LONG_MAX_U label
+ * positions, computed by the decomposition of ctc_amd_long_best_path: a whole recording against a transcript that leaves out its
+ * preface, its applause or its advertisements.  The reference has no counterpart.
+ *
+ * Semantics are exactly those of ctc_amd_wildcard_best_path (above): a label equal to CTC_AMD_WILDCARD
+ * inside label_length is a wildcard position with the definition given there for both lattices; m_t and a_t with the tie rule of
+ * ctc_amd_greedy_decode; tokens is a_t on wildcard frames and label_index is i on every frame of wildcard i; label_score is the
+ * float64 sum of lp over a label's frames in time order, rounded to float32, and sum_i label_score + the lp of the blank frames
+ * outside any label = score; the same degenerate cases; an infeasible utterance (also: fewer frames than the positions need -- a
+ * wildcard needs a frame of its own; label_length > U; a label other than the wildcard outside [0, V) or equal to the blank)
+ * gives score -inf, -1 in tokens, label_index, first_frame and last_frame and -inf in label_score.  The one difference is
+ * U <= CTC_AMD_LONG_MAX_U in place of CTC_AMD_MAX_U.
+ *
+ *   score[B]            float32
+ *   tokens[B][T]        int32:   pi_t; -1 for t >= T_b
+ *   label_index[B][T]   int32:   as ctc_amd_wildcard_best_path documents it.  May be NULL.
+ *   first_frame[B][U]   int32:   the first frame whose label_index is i, for i < label_length; -1 from label_length on.
+ *   last_frame[B][U]    int32:   ... and the last.  Each may be NULL.
+ *   label_score[B][U]   float32: as ctc_amd_wildcard_best_path documents it; -inf from label_length on.  May be NULL.
+ *
+ * Decomposition and launch properties are those of ctc_amd_long_best_path (DESIGN.md sections 5.18, 5.19): label blocks of 1024
+ * positions x time blocks of frames_per_tile frames (0: CTC_AMD_LONG_FRAMES_DEFAULT; otherwise a positive multiple of
+ * CTC_AMD_LONG_FRAMES_MULTIPLE), K and J as there, one launch per anti-diagonal of tiles, the order of the launches on the stream
+ * the only dependency.  The row statistics (m_t, a_t, the log-sum-exp) are taken once, by label block 0, and kept per frame in the
+ * workspace for the tiles further right, which run on later launches.  Then one launch traces the path back, one derives
+ * first_frame / last_frame when either is asked for and one sums label_score when it is asked for: K + J - 1 (+ 1 .. 3) launches,
+ * a number that depends on (T, U, frames_per_tile) and on which outputs are passed, never on the lengths.  Asynchronous on
+ * `stream`, capturable, no allocation, copy or synchronisation.  Vector stores only, no atomics, one writer per element: the same
+ * bits on every run.  tokens, label_index, first_frame, last_frame and label_score do not depend on frames_per_tile or on B, bit
+ * for bit (float64 max and add hand over exactly between tiles; every log-sum-exp is one wavefront's row pass; every label_score
+ * is one thread's sum in time order); `score` may differ in its last bits between values of frames_per_tile, as in
+ * ctc_amd_long_best_path.
+ *
+ * Validation follows ctc_amd_long_best_path in its order and with its messages: common arguments (U <= CTC_AMD_LONG_MAX_U),
+ * element type, B == 0 (CTC_AMD_OK without a launch), strides, then score and tokens non-NULL, V <= CTC_AMD_MAX_V,
+ * frames_per_tile (also: B so large that a launch grid would pass 2^31 - 1 workgroups) -- CTC_AMD_EINVAL each -- then the
+ * workspace (CTC_AMD_EWORKSPACE before any launch).  Logits in the producer formats of ctc_amd_loss_grad_ex, read in place with
+ * both access paths (identical results).
+ *
+ * Workspace (may hold anything on entry; every count is a size_t).  The regions of ctc_amd_long_best_path at the same offsets,
+ * then three per-frame regions.  With TF, K, J and r256 as there:
+ *   ctc_amd_long_wildcard_best_path_workspace_bytes =
+ *       r256(B * K * T * 512)          back-pointers: one 8-byte word per lane, frame and label block
+ *     + r256(B * (K - 1) * T * 16)     columns: the float64 pair (open, closed) of a block's last position before every frame
+ *     + r256(B * K * 16448)            rows: the chain state of every label block, 2 * 1024 + 8 float64
+ *     + r256(B * J * 8)                the log-sum-exp partial sum of every time block
+ *     + r256(B * T * 4)                label_index when the caller passes none
+ *     + r256(B * 4)                    feasibility of every utterance
+ *     + r256(B * T * 8)                m_t of every frame, float64
+ *     + r256(B * T * 4)                a_t of every frame, int32
+ *     + r256(B * T * 8)                the log-sum-exp of every frame, then the log-probability of the path's token, float64
+ * B = 1, T = 30000, U = 8192, frames_per_tile = 0 (128): K = 8, J = 235:
+ *   122 880 000 + 3 360 000 + 131 584 + 2 048 + 120 064 + 256 + 240 128 + 120 064 + 240 128 = 127 094 272 bytes, 242 + 3 launches.
+ */
+int ctc_amd_long_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes /*host*/);
+int ctc_amd_long_wildcard_best_path(int kind, int wrt,
+                                    const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride,
+                                    const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                    int B, int T, int V, int U, int frames_per_tile,
+                                    float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                                    int32_t *first_frame /* [B][U], may be NULL */, int32_t *last_frame /* [B][U], may be NULL */,
+                                    float *label_score /* [B][U], may be NULL */,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * CTC loss and gradient with wildcard labels: training on partial transcripts (added under ABI v6: two new entry points, nothing

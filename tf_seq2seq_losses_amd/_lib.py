@@ -94,6 +94,9 @@ SIGNATURES = {
     "ctc_amd_long_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
     "ctc_amd_long_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, score, tokens, label_index, first_frame, last_frame
                                                      _c_void_p, _c_size_t, _c_void_p]),                          # ws, bytes, stream
+    "ctc_amd_long_wildcard_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
+    "ctc_amd_long_wildcard_best_path": (_c_int, _COMMON_EX + [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, score, tokens, label_index, first_frame, last_frame, label_score
+                                                              _c_void_p, _c_size_t, _c_void_p]),                                     # ws, bytes, stream
     "ctc_amd_wildcard_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
     "ctc_amd_wildcard_loss_grad": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +    # .. blank_index, wildcard_log_weight, B, T, V, U
                                    [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),     # d_loss, loss .. grad strides, ws, bytes, stream
@@ -230,6 +233,13 @@ def long_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, fr
     out = _c_size_t(0)
     check(load().ctc_amd_long_best_path_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
           "ctc_amd_long_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def long_wildcard_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_wildcard_best_path_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_wildcard_best_path_workspace_bytes")
     return int(out.value)
 
 

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "ctc_align_long.h"
+#include "ctc_align_long_wild.h"
 #include "ctc_align_wild.h"
 #include "ctc_amd.h"
 #include "ctc_beam.h"
@@ -818,6 +819,44 @@ int ctc_amd_long_best_path(int kind, int wrt, const void *logits, int logits_dty
   const Problem p = f.applied(make_problem(c));
   CTC_TRY(ctc::run_align_long(p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
                               static_cast<hipStream_t>(stream)), "long alignment launch");
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_long_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
+    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  ctc::LongWildPlan plan;
+  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_long_best_path, with its messages; label_score, like the other per-label outputs, may be null.
+int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                    const int32_t *logit_length, int blank_index, int B, int T, int V, int U, int frames_per_tile,
+                                    float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
+                                    float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
+  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
+  ctc::LongWildPlan plan;
+  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_align_long_wild(p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                                   label_score, static_cast<hipStream_t>(stream)), "long wildcard alignment launch");
   return CTC_AMD_OK;
 }
 

@@ -394,6 +394,68 @@ def ctc_long_alignment_from_logproba(labels, logprobas, label_length, logit_leng
 
 
 # --------------------------------------------------------------------------------------------------
+# long-form forced alignment of partial transcripts (wildcard labels beyond 1024 labels): an extension, no counterpart in the reference
+# --------------------------------------------------------------------------------------------------
+class CtcLongWildcardAlignment(NamedTuple):
+    """The fields of CtcWildcardAlignment, with their meaning, for transcripts of up to 65536 labels:
+    score [batch] float32; tokens, label_index [batch, max_length] int32; first_frame, last_frame [batch, U] int32;
+    label_score [batch, U] float32.  An infeasible sample has score = -inf, -1 in every frame and label and -inf in label_score."""
+    score: torch.Tensor
+    tokens: torch.Tensor
+    label_index: torch.Tensor
+    first_frame: torch.Tensor
+    last_frame: torch.Tensor
+    label_score: torch.Tensor
+
+
+def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, frames_per_tile=None,
+                         max_label_length=None) -> CtcLongWildcardAlignment:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    with torch.no_grad():  # a path is not differentiable: the result is detached
+        prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
+                            host_max_label_length=max_label_length)
+        return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep,
+                                                                     0 if frames_per_tile is None else int(frames_per_tile)))
+
+
+def classic_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                        blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
+                                        max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+    """Forced alignment of a long recording against a partial transcript, on the classic lattice: classic_ctc_wildcard_alignment
+    (a label equal to WILDCARD, -2, stands for any non-empty run of frames with any tokens on them; every label gets its first and
+    last frame and a label_score) for transcripts of up to 65536 labels, computed on the tiled lattice of
+    classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4).  The path and the per-label
+    outputs do not depend on frames_per_tile.  Returns CtcLongWildcardAlignment, not differentiable.  check_labels keeps rejecting
+    -2: it validates transcripts for the loss functions."""
+    return _long_wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, frames_per_tile,
+                                max_label_length)
+
+
+def simplified_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                           blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
+                                           max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+    """The same on the simplified lattice (a wildcard owns every frame from its entry until the next label's frame).  Same arguments
+    and return value as classic_ctc_long_wildcard_alignment."""
+    return _long_wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                frames_per_tile, max_label_length)
+
+
+def ctc_long_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                              frames_per_tile: Optional[int] = None,
+                                              max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                                frames_per_tile, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # training on partial transcripts (wildcard labels): an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class _WildcardLossFn(torch.autograd.Function):

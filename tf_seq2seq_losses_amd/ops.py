@@ -481,6 +481,36 @@ def long_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0):
     return out
 
 
+def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0):
+    """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
+    label_score[B,U] float32): wildcard_best_path for up to _lib.LONG_MAX_U label positions, on the tiled lattice of long_best_path
+    (ctc_amd_long_wildcard_best_path).  Reads the logits in the format `p` holds them in; the workspace is the stream's cached
+    one, as in long_best_path."""
+    lib = _lib.load()
+    score = torch.empty(p.B, dtype=torch.float32, device=p.device)
+    tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    label_index = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
+    first_frame = torch.empty((p.B, p.U), dtype=torch.int32, device=p.device)
+    last_frame = torch.empty((p.B, p.U), dtype=torch.int32, device=p.device)
+    label_score = torch.empty((p.B, p.U), dtype=torch.float32, device=p.device)
+    out = (score, tokens, label_index, first_frame, last_frame, label_score)
+    if p.B == 0:
+        return out
+    key = ("long_wildcard_best_path", kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
+    n = _WS_BYTES.get(key)
+    if n is None:
+        n = _WS_BYTES[key] = _lib.long_wildcard_best_path_workspace_bytes(kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
+    ck = (p.device, _stream(p.device))
+    ws = _WS_CACHE.get(ck)
+    if ws is None or ws.numel() < n:
+        ws = _WS_CACHE[ck] = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    with _on_device(p.device):
+        rc = lib.ctc_amd_long_wildcard_best_path(*p.common_ex(kind, wrt), int(frames_per_tile), *(_ptr(t) for t in out),
+                                                 ws.data_ptr(), ws.numel(), _stream(p.device))
+    _lib.check(rc, "ctc_amd_long_wildcard_best_path")
+    return out
+
+
 def greedy_decode(kind: int, wrt: int, x: torch.Tensor, logit_length: torch.Tensor, blank: int):
     """(score[B] float32, tokens[B,T] int32, labels[B,T] int32, label_length[B] int32, frames[B,T] int32, label_score[B,T] float32):
     the frame-wise argmax path and the labels it collapses to (ctc_amd_greedy_decode).  Takes the logits as they stand -- float32 /
