@@ -67,8 +67,8 @@ extern "C" {
  *   V <= CTC_AMD_MAX_V          tokens for loss / gradient / alpha-beta (one 64 KB LDS token row per wavefront)
  *   V <= CTC_AMD_MAX_V_HESSIAN  tokens for ctc_amd_hessian / ctc_amd_hvp (V + 4 floats of LDS per wavefront)
  * ctc_amd_best_path takes V <= CTC_AMD_MAX_V as well (it stages no row in LDS; the limit is the ABI's, kept uniform).
- * ctc_amd_long_best_path and ctc_amd_long_wildcard_best_path alone take U <= CTC_AMD_LONG_MAX_U (they spread the label axis over
- * workgroups, 1024 positions each).
+ * ctc_amd_long_best_path, ctc_amd_long_wildcard_best_path and ctc_amd_long_wildcard_loss_grad alone take U <= CTC_AMD_LONG_MAX_U
+ * (they spread the label axis over workgroups, 1024 positions each).
  * ctc_amd_loss_grad* / ctc_amd_grad_resume / ctc_amd_alpha_beta: vector (16-byte / 8-byte) row accesses are used when V, the
  * strides AND the base pointers are aligned; any other alignment runs element-wise paths with identical results.
  * ctc_amd_hessian / ctc_amd_hvp require 16-byte aligned tensor pointers (CTC_AMD_EINVAL otherwise). */
@@ -920,6 +920,58 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt,
                                const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
                                void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
                                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Long-form CTC loss and gradient: ctc_amd_wildcard_loss_grad for U <= CTC_AMD_LONG_MAX_U label positions (added under ABI v6: two
+ * new entry points, nothing existing changed).  The confidence -ln P(transcript | recording) of a recording aligned with
+ * ctc_amd_long_wildcard_best_path, and training on it without cutting it up.
+ *
+ * Labels, lengths, blank, formats, lattices, emissions, wildcard_log_weight, the loss, the gradient with respect to logits or
+ * log-probabilities, d_loss, infeasible utterances (loss +inf, an exactly zero gradient, d_loss[b] not interpreted), every degenerate
+ * case and what is written (every gradient row t < T of every utterance, nothing between V and a larger stride) are those of
+ * ctc_amd_wildcard_loss_grad; a transcript without CTC_AMD_WILDCARD is the plain CTC loss.  First derivatives only.
+ * The lattice is tiled as in ctc_amd_long_best_path: K = max(1, ceil(U / 1024)) label blocks x J = max(1, ceil(T / TF)) time blocks
+ * of TF = frames_per_tile frames (0: CTC_AMD_LONG_FRAMES_DEFAULT; otherwise a positive multiple of CTC_AMD_LONG_FRAMES_MULTIPLE).
+ * The alpha sweep runs one launch per anti-diagonal of tiles (K + J - 1), a finish kernel takes log2 Z; with a gradient the beta
+ * sweep runs the anti-diagonals in reverse and one wavefront per row (b, t) writes the gradient.  The order of the launches on the
+ * stream is the only dependency: no workgroup waits for another.  Tiles wholly beyond an utterance's frames or labels, or wholly
+ * before the first frame their positions can be reached in, do not run.
+ * Numerics: those of ctc_amd_wildcard_loss_grad (float64 base-2 logarithms with a true -inf in both sweeps and in everything handed
+ * from tile to tile, float32 row statistics taken once per frame, integer sums of the posteriors).  The same bits on every run, for
+ * every frames_per_tile and for every batch composition; no floating-point atomics.
+ * Validation follows ctc_amd_wildcard_loss_grad in its order and with its messages: common arguments (U <= CTC_AMD_LONG_MAX_U in
+ * place of CTC_AMD_MAX_U), element types, B == 0 (CTC_AMD_OK without a launch), strides (the gradient's only when grad != NULL),
+ * wildcard_log_weight, loss non-NULL, V <= CTC_AMD_MAX_V, B * T < 2^33 when grad != NULL; then frames_per_tile and the tile grid
+ * (B * min(K, J) <= 2^31 - 1 workgroups) as in ctc_amd_long_best_path (CTC_AMD_EINVAL each); then the workspace
+ * (CTC_AMD_EWORKSPACE before any launch).
+ * Workspace (may hold anything on entry; needed without a gradient too), every term a size_t, r256(x) = x rounded up to a multiple
+ * of 256, S = 2 (classic) or 1 (simplified):
+ *   ctc_amd_long_wildcard_loss_workspace_bytes =
+ *       r256(16 * B * (K - 1) * T)          alpha columns: the pair (O, C) of a block's last position before every frame, float64
+ *     + r256(8 * B * K * 2056)              alpha row buffers: the chain state between the time blocks of a label block, float64
+ *     + r256(16 * B * T)                    row statistics of every frame: x[blank], max, log2 sum exp, float32
+ *     + r256(8 * B)                         log2 Z, float64
+ *     + r256(4 * B)                         feasible, int32
+ *   and, with want_grad != 0 (grad != NULL),
+ *     + r256(8 * B * (K - 1) * T)           beta columns: the worth of entering a block's first position with every frame, float64
+ *     + r256(8 * B * K * 2056)              beta row buffers
+ *     + r256(8 * B * K * T * (S * 1024 + 2))  the chain's float64 state of every frame and label block (overwritten by the posteriors)
+ * The last term is all that matters: B = 1, T = 30 000, U = 8 192 takes 3 941 783 808 bytes classic and 1 975 703 808 simplified with
+ * a gradient and 3 972 096 without one; an hour of audio (T = 180 000, U = 50 000) 144.9 GB with a gradient, which fits no card, and
+ * 141.9 MB without one (section 7 names what would cut it).  A call with grad == NULL accepts the want_grad
+ * size too.  No allocation, copy or synchronisation; asynchronous on `stream`, capturable; the number of launches depends on T, U
+ * and frames_per_tile alone.
+ */
+int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                               size_t *out_bytes /*host*/);
+int ctc_amd_long_wildcard_loss_grad(int kind, int wrt,
+                                    const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride,
+                                    const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                    float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                    const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
+                                    void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Label posteriors: the soft alignment of a transcript over all CTC paths (added under ABI v6: two new entry points, nothing

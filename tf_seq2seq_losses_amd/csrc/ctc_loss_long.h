@@ -1,0 +1,18 @@
+// Host launcher of ctc_loss_long.hip (long-form CTC loss and gradient with wildcard labels: the sum-product lattice of
+// ctc_wild_loss.hip on the tiles of ctc_align_long.hip), for that unit and ctc_capi.hip.  Host declarations only; the plan is
+// ctc_loss_long_plan.h.
+#pragma once
+#include "ctc_common.h"
+#include "ctc_loss_long_plan.h"
+
+namespace ctc {
+
+constexpr int LONG_LOSS_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h): the label value of a wildcard position
+
+// grad == nullptr (a plan with want_grad == 0 suffices): P.launches alpha tile launches and the finish kernel.  Otherwise (want_grad
+// == 1) the same, bit for bit, then P.launches beta tile launches and the row stage.  T == 0: the finish kernel alone.  `ws` holds
+// P.total bytes and may hold anything.
+hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
+                         char *ws, hipStream_t st);
+
+}  // namespace ctc

@@ -1,0 +1,634 @@
+// Long-form CTC loss and gradient with wildcard labels on both lattices: ctc_amd_long_wildcard_loss_grad (include/ctc_amd.h),
+// DESIGN.md section 5.20.  The contract of ctc_amd_wildcard_loss_grad for U <= CTC_AMD_LONG_MAX_U label positions.
+//
+// The sum-product lattice of ctc_wild_loss.hip (float64 base-2 log state with a true -inf, the same chain step, posteriors and row
+// stage) on the tiles of ctc_align_long_wild.hip (label blocks of UB = 1024 positions x time blocks of TF frames, one launch per
+// anti-diagonal of tiles, the order of the launches on the stream the only dependency).  Both units stay as they are: what is
+// file-local there is repeated here.
+//   alpha tile   <KIND, MODE>; wave 0 the chain at NL = 16, waves 1..4 the producers, one frame each through a ring of 4 frames.
+//                Row in / row out per (utterance, label block); column in / column out the pair (O, C) (simplified: S) of position
+//                k * UB - 1 BEFORE every frame, stored per frame by the left neighbour.  The `allow` bit of position k * UB sees
+//                label[k * UB - 1].  Label block 0 takes the row statistics (x[blank], max, log2 sum exp) once per frame and keeps
+//                them per frame for the blocks to its right, which run on later launches.  MODE 1 also stores the chain's state of
+//                every frame per (b, k, t): the saved row of ctc_wild_loss.hip, one per label block (classic AFTER the frame,
+//                simplified BEFORE it, the start state in block 0).
+//   finish       log2 Z from the row buffer of block (L - 1) / UB (L = 0: the start state): loss[b], log2 Z, a feasibility word.
+//   beta tile    the reverse anti-diagonals: tile (k, j) after (k + 1, j) and (k, j + 1).  What MODE 2 of wild_loss_kernel gets
+//                from the next lane comes across the block boundary per frame through a column: the worth of entering position
+//                (k + 1) * UB with that frame (beta plus the emission), stored by lane 0 of the right neighbour and staged through
+//                LDS by the producers; the `allow` bit of the skip into it is read off the labels.  Beta rows go back in time
+//                through a row buffer.  Per frame the chain reads the saved alpha row, forms 2^(alpha + beta - log2 Z) and writes
+//                the posteriors as float32 pairs over the slots it has read (MODE 2's slot convention).  Simplified: alpha of
+//                position k * UB - 1 before the frame is the alpha column of the forward sweep.
+//   row stage    one wavefront per (b, t) looping over the label blocks of that frame: wild_grad_row_kernel.
+// Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all three; nothing unwritten is read.  No workgroup
+// waits for another: no flags, no cooperative launch, no floating-point atomics, vector stores only, one writer per element.
+#include "ctc_loss_long.h"
+
+namespace ctc {
+namespace {
+
+constexpr int NL = LONG_NL, UB = LONG_UB, RW = LONG_ROW_DOUBLES;
+constexpr int LL_PW = 4;                      // producer wavefronts
+constexpr int LL_THREADS = 64 * (1 + LL_PW);  // + the chain
+constexpr int F = 4096 / UB;                  // frames per ring block
+static_assert(F == LONG_RING_FRAMES && F == LL_PW, "one frame per producer wavefront and ring block");
+constexpr int RS = UB + 4;  // ring row: UB label emissions, then x[blank], the row max, log2 sum exp(x - max)
+constexpr double LOG2E_D = 1.44269504088896340736;
+
+__device__ __forceinline__ float4 ll_row_load4(const char *row, int k, int dt) {
+  if (dt == 0) return *reinterpret_cast<const float4 *>(row + (size_t)k * 4);
+  const uint2 u = *reinterpret_cast<const uint2 *>(row + (size_t)k * 2);
+  return make_float4(h16_to_f32((unsigned short)(u.x & 0xffffu), dt), h16_to_f32((unsigned short)(u.x >> 16), dt),
+                     h16_to_f32((unsigned short)(u.y & 0xffffu), dt), h16_to_f32((unsigned short)(u.y >> 16), dt));
+}
+// the same four elements one by one (unaligned rows, V no multiple of 4): -inf past the row, which adds nothing to either statistic
+__device__ __forceinline__ float4 ll_row_load4_elem(const char *row, int k, int V, int dt) {
+  const float ninf = -__builtin_inff();
+  return make_float4(row_load1(row, k, dt), k + 1 < V ? row_load1(row, k + 1, dt) : ninf, k + 2 < V ? row_load1(row, k + 2, dt) : ninf,
+                     k + 3 < V ? row_load1(row, k + 3, dt) : ninf);
+}
+// running (max, sum of exp(x - max)) of one lane: four more elements (both access paths end here: identical bits)
+__device__ __forceinline__ void ll_stat_add4(float &m, float &s, const float4 v) {
+  const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+  s = s * fexp2((m - mn) * LOG2E) +
+      ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
+  m = mn;
+}
+
+// base-2 log(2^a + 2^b [+ 2^c]) of float64 operands that may be -inf (log 0): differences against the maximum, or against 0
+// when every operand is -inf
+__device__ __forceinline__ double ll_lse(double a, double b) {
+  const double m = fmax(a, b);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2(fexp2((float)(a - mm)) + fexp2((float)(b - mm)));
+}
+__device__ __forceinline__ double ll_lse(double a, double b, double c) {
+  const double m = fmax(fmax(a, b), c);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm)));
+}
+
+struct LongLossWs {  // device pointers into the workspace (LongLossPlan offsets)
+  double *col, *row;
+  float *stat;
+  double *logp;
+  int *flag;
+  double *colb, *rowb, *rows;
+};
+
+// what a ring row says about its frame, in the lattice's units (base-2 logarithms of lp)
+struct LlFrame {
+  double Md, nl2s, eb, ew;
+};
+__device__ __forceinline__ LlFrame ll_frame_of(const float *r, bool lpin, double w2) {
+  const float4 sv = *reinterpret_cast<const float4 *>(r + UB);
+  LlFrame fr;
+  // logits: lp = x - max - ln sum; log-probabilities: lp = x
+  fr.Md = lpin ? 0.0 : (double)sv.y;
+  fr.nl2s = lpin ? 0.0 : -(double)sv.z;
+  fr.eb = fma((double)sv.x - fr.Md, LOG2E_D, fr.nl2s);
+  // e_w = w + ln sum_k exp(lp[t, k]): w for logits, w + LSE_t for log-probabilities; a row of -inf emits nothing
+  fr.ew = sv.z == __builtin_inff() ? -__builtin_inf() : lpin ? w2 + fma((double)sv.y, LOG2E_D, (double)sv.z) : w2;
+  return fr;
+}
+
+// the validated labels of positions k * UB - 1 .. k * UB + n - 2 into lab_s[0 .. n - 1] (-1: no emission)
+__device__ __forceinline__ void ll_labels(const Problem &p, int b, int k, int L, int n, int *lab_s) {
+  for (int i = threadIdx.x; i < n; i += LL_THREADS) {
+    const int g = k * UB + i - 1;
+    int tok = -1;
+    if (g >= 0 && g < L) tok = label_at(p, label_row(p, b), g);
+    lab_s[i] = tok == LONG_LOSS_WILDCARD ? LONG_LOSS_WILDCARD : emits(p, tok) ? tok : -1;
+  }
+}
+
+template <int KIND, int MODE>
+__global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Problem p, const double w2, const LongLossWs w, int K, int TF,
+                                                                     int d, int k_lo, int count) {
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
+  constexpr int SRD = long_loss_row_doubles(KIND);
+  const double NINF = -__builtin_inf();
+  __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
+  __shared__ int lab_s[UB + 1];  // positions k * UB - 1 .. k * UB + UB - 1
+  __shared__ double col_s[2][F][2];
+
+  const int b = blockIdx.x / count, k = k_lo + blockIdx.x % count, j = d - k;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int T = p.T, V = p.V, blank = p.blank, dt = p.xdtype;
+  const bool lpin = p.wrt != 0;  // log-probability input
+  const int Tb = frame_count(p, b);
+  const int L = label_count(p, b);
+  if (too_many_labels(p, L) || !long_loss_tile_active(Tb, L, k, j, TF)) return;
+  const int t_lo = j * TF;                           // (J * TF < T + TF: no overflow)
+  const int t_hi = Tb - t_lo < TF ? Tb : t_lo + TF;  // one past the tile's last frame
+  const bool fresh = long_loss_alpha_fresh(k, j, TF);
+  const bool has_right = long_loss_has_right(L, k);
+
+  ll_labels(p, b, k, L, UB + 1, lab_s);
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0;  // bit q = position k * UB + lane * NL + q is a wildcard
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    lab[q] = lab_s[1 + lane * NL + q];
+    if (lab[q] == LONG_LOSS_WILDCARD) wild |= 1u << q;
+  }
+
+  const int esz = dt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  // vector row accesses (16 bytes of float32, 8 bytes of 16-bit elements) need aligned rows; element-wise otherwise
+  const bool vec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
+  double *const row = w.row + ((size_t)b * K + k) * RW;
+  const double *const col_in = k > 0 ? w.col + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T * 2 : nullptr;
+  double *const col_out = has_right ? w.col + ((size_t)b * (K - 1) + k) * (size_t)T * 2 : nullptr;
+  float *const statw = w.stat + (size_t)b * T * 4;
+  double *const myrows = MODE == 1 ? w.rows + ((size_t)b * K + k) * (size_t)T * SRD : nullptr;
+
+  // chain state (wave 0): row in
+  double O[NL], C[NL];  // simplified: C is S, O unused
+  unsigned allow = 0;   // classic: bit q = label[i] differs from label[i-1], or one of the two is a wildcard
+  double cs = 0.0;      // the start state (label block 0): blank so far
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    O[q] = NINF; C[q] = NINF;
+    const int i = lane * NL + q;
+    if (KIND == 0 && k * UB + i > 0) {
+      const int prev = lab_s[i];
+      if (lab[q] != prev || lab[q] == LONG_LOSS_WILDCARD || prev == LONG_LOSS_WILDCARD) allow |= 1u << q;
+    }
+  }
+  if (wave == 0 && !fresh) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      if (KIND == 0) O[q] = row[q * 64 + lane];
+      C[q] = row[(NL + q) * 64 + lane];
+    }
+    if (k == 0) cs = row[2 * UB];
+  }
+
+  auto produce = [&](int kb) {  // one frame per producer wavefront
+    const int f = wave - 1, t = t_lo + kb * F + f;
+    if (t >= t_hi) return;
+    const char *const xr = xb + (size_t)((long)t * p.xst) * esz;
+    float e[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
+      e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+    }
+    float4 sv;
+    if (k == 0) {
+      // the row pass.  Both access paths give a lane the same elements in the same order: identical bits
+      const float eb = row_load1(xr, blank, dt);
+      float m = -3.402823466e38f, s = 0.f;
+      for (int c = lane * 4; c < V; c += 256) ll_stat_add4(m, s, vec ? ll_row_load4(xr, c, dt) : ll_row_load4_elem(xr, c, V, dt));
+      float M = wave_max(m);
+      const float S = wave_sum(s * fexp2((m - M) * LOG2E));
+      float l2s = flog2(S);
+      if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+      sv = make_float4(eb, M, l2s, 0.f);
+      if (lane == 0) *reinterpret_cast<float4 *>(statw + (size_t)t * 4) = sv;
+    } else {
+      sv = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (tile (0, j) stored it on an earlier launch)
+    }
+    float *const r = ring + ((kb & 1) * F + f) * RS;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) r[lane * NL + q] = e[q];
+    if (lane == 0) *reinterpret_cast<float4 *>(r + UB) = sv;
+    if (k > 0 && lane < 2) col_s[kb & 1][f][lane] = col_in[(size_t)t * 2 + lane];
+  };
+
+  auto consume = [&](int kb) {
+    const int t0 = t_lo + kb * F;
+    const int nf = t_hi - t0 < F ? t_hi - t0 : F;
+    const float *const rb = ring + (kb & 1) * F * RS;
+    for (int f = 0; f < nf; ++f) {
+      const float *const rr = rb + f * RS;
+      float e[NL];
+#pragma unroll
+      for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
+      const LlFrame fr = ll_frame_of(rr, lpin, w2);
+      const double eb = fr.eb;
+      auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
+      double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
+      if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
+#pragma unroll
+        for (int q = 0; q < NL; ++q) r[lane * NS + q] = C[q];
+        if (k == 0 && lane == 0) r[SRD - 2] = cs;
+      }
+      if (col_out && lane == 63) {  // column out: the last position before this frame
+        col_out[(size_t)(t0 + f) * 2] = O[NL - 1];
+        col_out[(size_t)(t0 + f) * 2 + 1] = C[NL - 1];
+      }
+      const double fillO = k > 0 ? col_s[kb & 1][f][0] : NINF;
+      const double fillC = k > 0 ? col_s[kb & 1][f][1] : cs;
+      if (KIND == 0) {
+        const double pO = from_prev_lane(O[NL - 1], fillO);
+        const double pC = from_prev_lane(C[NL - 1], fillC);
+#pragma unroll
+        for (int q = NL - 1; q >= 0; --q) {
+          const double qO = q > 0 ? O[q > 0 ? q - 1 : 0] : pO;
+          const double qC = q > 0 ? C[q > 0 ? q - 1 : 0] : pC;
+          const double a2 = ((allow >> q) & 1u) ? qO : NINF;
+          const double o = ll_lse(O[q], qC, a2) + em(q);
+          C[q] = ll_lse(C[q], O[q]) + eb;
+          O[q] = o;
+        }
+      } else {
+        const double pS = from_prev_lane(C[NL - 1], fillC);
+#pragma unroll
+        for (int q = NL - 1; q >= 0; --q) {
+          const double s = q > 0 ? C[q > 0 ? q - 1 : 0] : pS;
+          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? fr.ew : eb), s + em(q));
+        }
+      }
+      cs += eb;
+      if (MODE == 1 && KIND == 0) {  // the state AFTER the frame
+#pragma unroll
+        for (int q = 0; q < NL; ++q) *reinterpret_cast<double2 *>(r + lane * NS + 2 * q) = make_double2(O[q], C[q]);
+        if (k == 0 && lane == 0) r[SRD - 2] = cs;
+      }
+    }
+  };
+
+  const int nb = (t_hi - t_lo + F - 1) / F;
+  if (wave > 0) produce(0);
+  __syncthreads();
+  for (int kb = 0; kb < nb; ++kb) {
+    if (wave == 0) consume(kb);
+    else if (kb + 1 < nb) produce(kb + 1);
+    __syncthreads();
+  }
+
+  // row out
+  if (wave == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      row[q * 64 + lane] = O[q];
+      row[(NL + q) * 64 + lane] = C[q];
+    }
+    if (k == 0 && lane == 0) row[2 * UB] = cs;
+  }
+}
+
+// log2 Z of every utterance from the row buffers: one thread per utterance
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_long_finish_kernel(const Problem p, const LongLossWs w, int K, float *__restrict__ loss) {
+  const double NINF = -__builtin_inf();
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= p.B) return;
+  const int Tb = frame_count(p, b);
+  const int L = label_count(p, b);
+  double v = NINF;
+  if (too_many_labels(p, L) || L > Tb) {
+    // infeasible by the count: no tile ran
+  } else if (L == 0) {
+    v = Tb == 0 ? 0.0 : w.row[(size_t)b * K * RW + 2 * UB];
+  } else {  // (L <= Tb: block (L - 1) / UB ran at least one tile)
+    const int i = L - 1, r = i % UB;
+    const double *const row = w.row + ((size_t)b * K + i / UB) * RW;
+    const double ov = row[(r % NL) * 64 + r / NL], cv = row[(NL + r % NL) * 64 + r / NL];
+    v = KIND == 0 ? ll_lse(ov, cv) : cv;
+  }
+  loss[b] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
+  w.logp[b] = v;
+  w.flag[b] = v > NINF && v < -NINF ? 1 : 0;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Problem p, const double w2, const LongLossWs w, int K, int TF,
+                                                                    int d, int k_lo, int count) {
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
+  constexpr int SRD = long_loss_row_doubles(KIND);
+  const double NINF = -__builtin_inf();
+  __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
+  __shared__ int lab_s[UB + 2];  // positions k * UB - 1 .. k * UB + UB
+  __shared__ double col_s[2][F][2];  // [0]: the worth of entering position (k + 1) * UB with the frame; [1]: simplified, alpha of k * UB - 1 before it
+
+  const int b = blockIdx.x / count, k = k_lo + blockIdx.x % count, j = d - k;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int T = p.T, blank = p.blank, dt = p.xdtype;
+  const bool lpin = p.wrt != 0;
+  const int Tb = frame_count(p, b);
+  const int L = label_count(p, b);
+  // an infeasible utterance has no posteriors: the row stage writes its zeros without them
+  if (too_many_labels(p, L) || !long_loss_tile_active(Tb, L, k, j, TF) || w.flag[b] == 0) return;
+  const double lP = w.logp[b];
+  const int t_lo = j * TF;
+  const int t_hi = Tb - t_lo < TF ? Tb : t_lo + TF;
+  const bool fresh = long_loss_beta_fresh(Tb, j, TF);
+  const bool right = long_loss_beta_has_right(Tb, L, k, j, TF);
+
+  ll_labels(p, b, k, L, UB + 2, lab_s);
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    lab[q] = lab_s[1 + lane * NL + q];
+    if (lab[q] == LONG_LOSS_WILDCARD) wild |= 1u << q;
+  }
+
+  const int esz = dt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  double *const row = w.rowb + ((size_t)b * K + k) * RW;
+  const double *const colb_in = right ? w.colb + ((size_t)b * (K - 1) + k) * (size_t)T : nullptr;
+  double *const colb_out = k > 0 ? w.colb + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T : nullptr;
+  const double *const cola_in = KIND == 1 && k > 0 ? w.col + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T * 2 : nullptr;
+  const float *const statw = w.stat + (size_t)b * T * 4;
+  double *const myrows = w.rows + ((size_t)b * K + k) * (size_t)T * SRD;
+
+  // chain state (wave 0): beta, the mass of the frames still to come
+  double O[NL], C[NL];
+  unsigned allow = 0;
+  int allow_nx = 0;  // ... of the next lane's first position (lane 63: position (k + 1) * UB)
+  double cs = NINF;
+  auto allowed = [&](int i) {  // position k * UB + i, 0 <= i <= UB
+    if (k * UB + i <= 0) return false;
+    const int a = lab_s[1 + i], q = lab_s[i];
+    return a != q || a == LONG_LOSS_WILDCARD || q == LONG_LOSS_WILDCARD;
+  };
+#pragma unroll
+  for (int q = 0; q < NL; ++q)
+    if (KIND == 0 && allowed(lane * NL + q)) allow |= 1u << q;
+  if (KIND == 0) allow_nx = allowed((lane + 1) * NL) ? 1 : 0;
+  if (fresh) {  // behind the last frame only the end states have any mass
+#pragma unroll
+    for (int q = 0; q < NL; ++q) O[q] = C[q] = (k * UB + lane * NL + q == L - 1) ? 0.0 : NINF;
+    if (k == 0 && L == 0) cs = 0.0;
+  } else {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      O[q] = row[q * 64 + lane];
+      C[q] = row[(NL + q) * 64 + lane];
+    }
+    if (k == 0) cs = row[2 * UB];
+  }
+
+  // ring position q of the tile stands for frame t_hi - 1 - q
+  auto produce = [&](int kb) {
+    const int f = wave - 1, t = t_hi - 1 - (kb * F + f);
+    if (t < t_lo) return;
+    const char *const xr = xb + (size_t)((long)t * p.xst) * esz;
+    float e[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
+      e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+    }
+    float *const r = ring + ((kb & 1) * F + f) * RS;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) r[lane * NL + q] = e[q];
+    if (lane == 0) {
+      *reinterpret_cast<float4 *>(r + UB) = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (the alpha sweep stored it)
+      col_s[kb & 1][f][0] = colb_in ? colb_in[t] : NINF;
+    } else if (lane == 1) {
+      col_s[kb & 1][f][1] = cola_in ? cola_in[(size_t)t * 2 + 1] : NINF;
+    }
+  };
+
+  auto consume = [&](int kb) {
+    const int q0 = kb * F;
+    const int nf = t_hi - t_lo - q0 < F ? t_hi - t_lo - q0 : F;
+    const float *const rb = ring + (kb & 1) * F * RS;
+    for (int f = 0; f < nf; ++f) {
+      const int t = t_hi - 1 - (q0 + f);
+      const float *const rr = rb + f * RS;
+      float e[NL];
+#pragma unroll
+      for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
+      const LlFrame fr = ll_frame_of(rr, lpin, w2);
+      const double eb = fr.eb;
+      auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
+      double *const r = myrows + (size_t)t * SRD;
+      double A[NS], Acs = NINF;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) A[q] = r[lane * NS + q];
+      if (k == 0) Acs = r[SRD - 2];
+      const double fillR = col_s[kb & 1][f][0];
+      auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+      if (KIND == 0) {
+#pragma unroll
+        for (int q = 0; q < NL; ++q)
+          *reinterpret_cast<float2 *>(r + lane * NS + 2 * q) = make_float2(post(A[2 * q] + O[q]), post(A[2 * q + 1] + C[q]));
+        if (k == 0 && lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
+        // beta back over frame t: x = what entering O[i] with this frame is worth
+        double x = O[0] + em(0);
+        if (colb_out && lane == 0) colb_out[t] = x;
+        const double xl = from_next_lane(x, fillR);
+        cs = ll_lse(cs + eb, x);
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+          const double xn = q + 1 < NL ? O[q + 1 < NL ? q + 1 : 0] + em(q + 1 < NL ? q + 1 : 0) : xl;
+          const bool al = q + 1 < NL ? ((allow >> (q + 1)) & 1u) != 0 : allow_nx != 0;
+          const double cb = C[q] + eb;
+          O[q] = ll_lse(x, cb, al ? xn : NINF);
+          C[q] = ll_lse(cb, xn);
+          x = xn;
+        }
+      } else {
+        const double ap0 = from_prev_lane(A[NL - 1], k > 0 ? col_s[kb & 1][f][1] : Acs);
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+          const double ap = q > 0 ? A[q > 0 ? q - 1 : 0] : ap0;
+          const double h = ((wild >> q) & 1u) ? fr.ew : eb;
+          *reinterpret_cast<float2 *>(r + lane * NS + q) = make_float2(post(ap + em(q) + C[q]), post(A[q] + h + C[q]));
+        }
+        if (k == 0 && lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
+        double x = C[0] + em(0);
+        if (colb_out && lane == 0) colb_out[t] = x;
+        const double xl = from_next_lane(x, fillR);
+        cs = ll_lse(cs + eb, x);
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+          const double xn = q + 1 < NL ? C[q + 1 < NL ? q + 1 : 0] + em(q + 1 < NL ? q + 1 : 0) : xl;
+          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? fr.ew : eb), xn);
+          x = xn;
+        }
+      }
+    }
+  };
+
+  const int nb = (t_hi - t_lo + F - 1) / F;
+  if (wave > 0) produce(0);
+  __syncthreads();
+  for (int kb = 0; kb < nb; ++kb) {
+    if (wave == 0) consume(kb);
+    else if (kb + 1 < nb) produce(kb + 1);
+    __syncthreads();
+  }
+
+  // row out: beta before the tile's first frame, for the tile before it in time
+  if (wave == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      row[q * 64 + lane] = O[q];
+      row[(NL + q) * 64 + lane] = C[q];
+    }
+    if (k == 0 && lane == 0) row[2 * UB] = cs;
+  }
+}
+
+// ---- the gradient's row stage: one wavefront per row (b, t), four per workgroup ----
+constexpr int LLG_WAVES = 4;
+constexpr int LLG_CH = 1024;  // columns per pass
+constexpr int LLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units of 2^-40, so |bin| < U 2^40 <= 2^56
+
+template <int KIND>
+__global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Problem p, const LongLossWs w, int K, int TF,
+                                                                       const float *__restrict__ d_loss, void *__restrict__ grad) {
+  constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
+  constexpr size_t ROWB = (size_t)long_loss_row_doubles(KIND) * 8;
+  __shared__ unsigned long long bins_all[LLG_WAVES][LLG_CH];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long rowi = (long)blockIdx.x * LLG_WAVES + wv;
+  if (rowi >= (long)p.B * p.T) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
+  unsigned long long *const bins = bins_all[wv];
+  const int b = (int)(rowi / p.T), t = (int)(rowi % p.T);
+  const int V = p.V, blank = p.blank, xdt = p.xdtype, gdt = p.gdtype;
+  const int Tb = frame_count(p, b);
+  const int xesz = xdt == 0 ? 4 : 2, gesz = gdt == 0 ? 4 : 2;
+  const char *const x = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb + (long)t * p.xst) * xesz;
+  char *const g = reinterpret_cast<char *>(grad) + (size_t)((long)b * p.gsb + (long)t * p.gst) * gesz;
+  const bool xvec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (xdt == 0 ? 15 : 7)) == 0;
+  const bool gvec = ((V | p.gsb | p.gst) & 3) == 0 && (reinterpret_cast<uintptr_t>(grad) & (gdt == 0 ? 15 : 7)) == 0;
+
+  // four consecutive elements of the gradient row from column c (c + 3 < V on the vector path; both paths convert alike)
+  auto gput4 = [&](int c, const float4 r) {
+    if (gdt == 0) {
+      if (gvec) { *reinterpret_cast<float4 *>(g + (size_t)c * 4) = r; return; }
+      float *const o = reinterpret_cast<float *>(g);
+      o[c] = r.x;
+      if (c + 1 < V) o[c + 1] = r.y;
+      if (c + 2 < V) o[c + 2] = r.z;
+      if (c + 3 < V) o[c + 3] = r.w;
+      return;
+    }
+    auto cv = [&](float f) { return gdt == 1 ? f32_to_bf16(f) : f32_to_f16(f); };
+    const unsigned short h0 = cv(r.x), h1 = cv(r.y), h2 = cv(r.z), h3 = cv(r.w);
+    if (gvec) {
+      *reinterpret_cast<uint2 *>(g + (size_t)c * 2) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
+      return;
+    }
+    unsigned short *const o = reinterpret_cast<unsigned short *>(g);
+    o[c] = h0;
+    if (c + 1 < V) o[c + 1] = h1;
+    if (c + 2 < V) o[c + 2] = h2;
+    if (c + 3 < V) o[c + 3] = h3;
+  };
+
+  // an infinite loss contributes nothing and its d_loss is not interpreted
+  if (!(t < Tb) || w.flag[b] == 0) {  // a padded frame, an infeasible utterance: exactly zero
+    for (int c = lane * 4; c < V; c += 256) gput4(c, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  const float dl = d_loss ? d_loss[b] : 1.f;
+  const float4 sv = *reinterpret_cast<const float4 *>(w.stat + ((size_t)b * p.T + t) * 4);
+  const float mx = sv.y, l2s = sv.z;
+  const int L = label_count(p, b);  // (feasible: L <= U)
+  const int j = t / TF;
+  const char *const rows = reinterpret_cast<const char *>(w.rows) + ((size_t)b * K * (size_t)p.T + t) * ROWB;
+  const int32_t *const lab = label_row(p, b);
+
+  float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
+  for (int c0 = 0; c0 < V; c0 += LLG_CH) {
+#pragma unroll
+    for (int q = 0; q < LLG_CH / 64; ++q) bins[lane + 64 * q] = 0ull;
+    wave_lds_fence();
+    for (int k = 0; k < K && (k == 0 || k * UB < L); ++k) {
+      // a tile that did not run has no posteriors: they are exactly zero, and adding them would change no bit
+      if (!long_loss_tile_active(Tb, L, k, j, TF)) continue;
+      const char *const r = rows + (size_t)k * p.T * ROWB;
+      const int n = L - k * UB < UB ? L - k * UB : UB;
+      for (int i = lane; i < n; i += 64) {
+        const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+        const int tok = label_at(p, lab, k * UB + i);
+        const bool wc = tok == LONG_LOSS_WILDCARD;
+        const unsigned rel = (unsigned)(tok - c0);
+        if (!wc && emits(p, tok) && rel < (unsigned)LLG_CH)
+          atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, LLG_FIX)));
+        if (c0 == 0) {
+          if (wc) gam += pq.x;
+          if (KIND == 1 && wc) gam += pq.y;
+          else blk += pq.y;
+        }
+      }
+      if (c0 == 0 && k == 0 && lane == 0) blk += *reinterpret_cast<const float *>(r + (size_t)UB * SLOT);  // the start state
+    }
+    if (c0 == 0) {
+      blk = wave_sum(blk);
+      gam = wave_sum(gam);
+    }
+    wave_lds_fence();
+    // logits: (1 - Gamma) softmax - gamma;  log-probabilities: -Gamma exp(x - LSE) - gamma
+    const float c = p.wrt == 0 ? 1.f - gam : -gam;
+#pragma unroll
+    for (int q = 0; q < LLG_CH / 256; ++q) {
+      const int col = c0 + lane * 4 + 256 * q;
+      if (col < V) {
+        const float4 xv = xvec ? ll_row_load4(x, col, xdt) : ll_row_load4_elem(x, col, V, xdt);
+        float o[4];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[col - c0 + cc]), -LLG_FIX) + (col + cc == blank ? blk : 0.f);
+          const float sm = c == 0.f ? 0.f : c * fexp2((xs[cc] - mx) * LOG2E - l2s);
+          o[cc] = dl * (sm - bin);
+        }
+        gput4(col, make_float4(o[0], o[1], o[2], o[3]));
+      }
+    }
+    wave_lds_fence();
+  }
+}
+
+template <int KIND>
+hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
+                    const LongLossWs &w, hipStream_t st) {
+  if (p.T > 0) {
+    for (int d = 0; d < P.launches; ++d) {
+      int k_lo, count;
+      long_loss_forward_diagonal(P, d, &k_lo, &count);
+      const dim3 grid((unsigned)((size_t)p.B * count));
+      if (grad) hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 1>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+      else hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 0>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+    }
+  }
+  hipLaunchKernelGGL(loss_long_finish_kernel<KIND>, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, st, p, w, P.K, loss);
+  if (!grad || p.T == 0) return hipGetLastError();
+  for (int e = 0; e < P.launches; ++e) {
+    int d, k_lo, count;
+    long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
+    hipLaunchKernelGGL(loss_long_beta_kernel<KIND>, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d,
+                       k_lo, count);
+  }
+  const unsigned blocks = (unsigned)(((long)p.B * p.T + LLG_WAVES - 1) / LLG_WAVES);
+  hipLaunchKernelGGL(loss_long_row_kernel<KIND>, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, d_loss, grad);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
+                         char *ws, hipStream_t st) {
+  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad)) return hipErrorInvalidValue;
+  LongLossWs w;
+  w.col = reinterpret_cast<double *>(ws + P.off_col);
+  w.row = reinterpret_cast<double *>(ws + P.off_row);
+  w.stat = reinterpret_cast<float *>(ws + P.off_stat);
+  w.logp = reinterpret_cast<double *>(ws + P.off_logp);
+  w.flag = reinterpret_cast<int *>(ws + P.off_flag);
+  w.colb = reinterpret_cast<double *>(ws + P.off_colb);
+  w.rowb = reinterpret_cast<double *>(ws + P.off_rowb);
+  w.rows = reinterpret_cast<double *>(ws + P.off_rows);
+  const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, st);
+}
+
+}  // namespace ctc

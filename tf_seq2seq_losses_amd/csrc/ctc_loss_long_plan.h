@@ -1,0 +1,103 @@
+// Host-side plan of the tiled CTC loss and gradient (ctc_loss_long.hip, ctc_amd_long_wildcard_loss_grad): the tile grid of
+// ctc_align_long_plan.h, the forward and backward launch schedules, the one predicate that says which tiles run, and the workspace
+// offsets.  Plain C++ with no HIP in it, so that tests/tools/long_loss_plan_check.cpp can run it under the host sanitizers; the
+// predicates are compiled for the device too (the kernels call the same functions).  Every byte count is a size_t: the saved rows
+// take 8 * B * K * T * (S * 1024 + 2) bytes and pass 2^32 at realistic sizes.
+#pragma once
+#include <stddef.h>
+
+#include "ctc_align_long_plan.h"
+
+#if defined(__HIPCC__)
+#define CTC_LL_HD __host__ __device__ inline
+#else
+#define CTC_LL_HD inline
+#endif
+
+namespace ctc {
+
+// doubles of a saved row of one (utterance, label block, frame): per position the pair (O, C) (classic) or S (simplified), then the
+// start state (block 0 only) and one double of padding -- the row of ctc_wild_loss.hip at UP = LONG_UB
+constexpr int long_loss_row_doubles(int kind) { return (kind == 0 ? 2 : 1) * LONG_UB + 2; }
+
+// ---- which tiles run ----
+// Tile (k, j) holds the label positions k * UB .. k * UB + UB - 1 and the frames j * TF .. j * TF + TF - 1 of an utterance of Tb
+// frames and L labels (L <= U: an utterance with more labels runs no tile at all).  A tile that does not run writes nothing, and
+// nothing of it is ever read: every reader below asks the same function.
+//   L > Tb                       infeasible by the count (every position takes a frame of its own): no tile runs
+//   j * TF >= Tb                 beyond the frames
+//   k > 0 and k * UB >= L        beyond the labels (block 0 runs for an empty transcript too: the start state lives there)
+//   j * TF + TF - 1 < k * UB     alpha of position i is log 0 before frame i: the whole tile is, and so are its posteriors
+// The beta sweep needs nothing more: a tile that the last test drops would hand beta to paths that no alpha reaches, whose
+// posteriors are exactly 0 whatever beta is, so its left neighbour takes log 0 in its place.
+CTC_LL_HD bool long_loss_tile_active(int Tb, int L, int k, int j, int TF, int UB = LONG_UB) {
+  if (L > Tb) return false;
+  if ((long long)j * TF >= Tb) return false;
+  if (k > 0 && (long long)k * UB >= L) return false;
+  if ((long long)j * TF + TF - 1 < (long long)k * UB) return false;
+  return true;
+}
+// (all four for a tile that runs)
+// alpha: the block's first tile starts from log 0 (block 0, tile 0: from the start state); every other reads the row buffer
+CTC_LL_HD bool long_loss_alpha_fresh(int k, int j, int TF, int UB = LONG_UB) { return (long long)j * TF <= (long long)k * UB; }
+// alpha: block k + 1 has labels, so this tile stores the column (its last position before every frame); the tile to the right then
+// runs for every frame range in which it could read it
+CTC_LL_HD bool long_loss_has_right(int L, int k, int UB = LONG_UB) { return (long long)(k + 1) * UB < L; }
+// beta: the block's last tile in time starts from the end state; every other reads the beta row buffer
+CTC_LL_HD bool long_loss_beta_fresh(int Tb, int j, int TF) { return (long long)(j + 1) * TF >= Tb; }
+// beta: the tile to the right ran on an earlier launch and stored its column (else: log 0)
+CTC_LL_HD bool long_loss_beta_has_right(int Tb, int L, int k, int j, int TF, int UB = LONG_UB) {
+  return long_loss_has_right(L, k, UB) && long_loss_tile_active(Tb, L, k + 1, j, TF, UB);
+}
+
+struct LongLossPlan {
+  int kind, B, T, U, want_grad;
+  int K, J, TF;   // label blocks, time blocks, frames per tile
+  int launches;   // K + J - 1 anti-diagonals of tiles per sweep (none when T == 0)
+  size_t off_col, off_row, off_stat, off_logp, off_flag;  // both paths
+  size_t off_colb, off_rowb, off_rows;                    // the gradient's (want_grad == 0: all equal to total)
+  size_t total;
+};
+
+// false: what long_plan refuses (frames_per_tile, sizes, the tile grid), or, with a gradient, a row stage of more than 2^31 - 1
+// workgroups (four rows (b, t) each)
+inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out) {
+  LongPlan A;
+  if (kind < 0 || kind > 1 || !long_plan(B, T, U, frames_per_tile, &A)) return false;
+  if (want_grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return false;
+  LongLossPlan P;
+  P.kind = kind; P.B = B; P.T = T; P.U = U; P.want_grad = want_grad ? 1 : 0;
+  P.K = A.K; P.J = A.J; P.TF = A.TF; P.launches = A.launches;
+  const size_t b = (size_t)B, t = (size_t)T, k = (size_t)P.K;
+  size_t o = 0;
+  P.off_col = o;  o = long_r256(o + b * (k - 1) * t * 16);          // alpha columns: [B][K - 1][T] pairs (O, C) of float64
+  P.off_row = o;  o = long_r256(o + b * k * LONG_ROW_DOUBLES * 8);  // alpha row buffers: [B][K] chain states
+  P.off_stat = o; o = long_r256(o + b * t * 16);                    // row statistics: [B][T] x[blank], max, log2 sum exp, 0 (float32)
+  P.off_logp = o; o = long_r256(o + b * 8);                         // log2 Z: [B] float64
+  P.off_flag = o; o = long_r256(o + b * 4);                         // feasible: [B] int32
+  P.off_colb = o;
+  if (want_grad) o = long_r256(o + b * (k - 1) * t * 8);            // beta columns: [B][K - 1][T] float64
+  P.off_rowb = o;
+  if (want_grad) o = long_r256(o + b * k * LONG_ROW_DOUBLES * 8);   // beta row buffers: [B][K] chain states
+  P.off_rows = o;
+  if (want_grad) o = long_r256(o + b * k * t * (size_t)long_loss_row_doubles(kind) * 8);  // saved rows: [B][K][T][S * 1024 + 2] float64
+  P.total = o;
+  *out = P;
+  return true;
+}
+
+// forward launch d of 0 .. launches - 1 runs the tiles (k, d - k), k = *k_lo .. *k_lo + *count - 1, of every utterance: tile (k, j)
+// after (k - 1, j), (k, j - 1) and (0, j)
+inline void long_loss_forward_diagonal(const LongLossPlan &P, int d, int *k_lo, int *count) {
+  const int lo = d - (P.J - 1) > 0 ? d - (P.J - 1) : 0, hi = d < P.K - 1 ? d : P.K - 1;
+  *k_lo = lo;
+  *count = hi - lo + 1;
+}
+// backward launch e of 0 .. launches - 1 runs the tiles of the forward diagonal launches - 1 - e: tile (k, j) after (k + 1, j) and
+// (k, j + 1)
+inline void long_loss_backward_diagonal(const LongLossPlan &P, int e, int *d, int *k_lo, int *count) {
+  *d = P.launches - 1 - e;
+  long_loss_forward_diagonal(P, *d, k_lo, count);
+}
+
+}  // namespace ctc

@@ -535,6 +535,85 @@ def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_lengt
 
 
 # --------------------------------------------------------------------------------------------------
+# long-form loss and gradient (transcripts beyond 1024 labels, wildcards included): an extension, no counterpart in the reference
+# --------------------------------------------------------------------------------------------------
+class _LongLossFn(torch.autograd.Function):
+    """_WildcardLossFn on ops.long_wildcard_loss_grad: forward is the forward-only call and keeps nothing but the inputs; backward is
+    ONE call with d_loss.  Backward is not itself differentiable: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf):
+        ctx.save_for_backward(x, labels, label_length, logit_length)
+        ctx.call = (kind, wrt, blank, U, weight, tf)
+        return ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
+                                           wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss):
+        x, labels, label_length, logit_length = ctx.saved_tensors
+        kind, wrt, blank, U, weight, tf = ctx.call
+        _, grad = ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
+                                              wildcard_log_weight=weight, frames_per_tile=tf)
+        return grad, None, None, None, None, None, None, None, None, None
+
+
+def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
+               frames_per_tile=None, max_label_length=None) -> torch.Tensor:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    weight = float(wildcard_log_weight)
+    if not (weight <= 0.0) or weight == float("-inf"):
+        raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
+    U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    kind = ops.KINDS[kind_name]
+    tf = 0 if frames_per_tile is None else int(frames_per_tile)
+    if x.requires_grad and torch.is_grad_enabled():
+        return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf)
+    with torch.no_grad():  # forward only: the result is detached
+        return ops.long_wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
+                                           wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
+
+
+def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                          blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                          frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None) -> torch.Tensor:
+    """CTC loss of a long recording on the classic lattice: classic_ctc_wildcard_loss (without a WILDCARD label, -2, the plain CTC
+    loss; with one, the loss of a partial transcript) for transcripts of up to 65536 labels, computed on the tiled lattice of
+    classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4; the loss and the gradient do not
+    depend on it).  Returns loss [batch] float32 = -ln Z with a first-order gradient when the logits require one (float32 / bfloat16
+    / float16 logits, any batch / time strides, read in place; the gradient comes back in the logits' dtype and layout; a second
+    derivative raises).  An infeasible sample has loss +inf and a zero gradient.  Backward holds the lattice's float64 state of
+    every frame: 8 * batch * ceil(U / 1024) * max_length * 2050 bytes (half of that on the simplified lattice); forward alone holds
+    no per-frame state.  check_labels keeps rejecting -2."""
+    return _long_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                      frames_per_tile, max_label_length)
+
+
+def simplified_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                             blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                             frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same on the simplified lattice.  Same arguments and return value as classic_ctc_long_loss."""
+    return _long_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                      frames_per_tile, max_label_length)
+
+
+def ctc_long_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The
+    gradient is with respect to logprobas."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index, wildcard_log_weight,
+                      frames_per_tile, max_label_length)
+
+
+# --------------------------------------------------------------------------------------------------
 # label posteriors (soft alignment over all paths): an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcLabelPosterior(NamedTuple):

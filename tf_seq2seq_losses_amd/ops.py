@@ -718,6 +718,51 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
     return loss, grad
 
 
+def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                            logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
+                            grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0, want_grad: bool = True,
+                            frames_per_tile: int = 0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(loss[B] float32, grad[B, T, V] or None): wildcard_loss_grad for up to _lib.LONG_MAX_U label positions, on the tiled lattice
+    of long_wildcard_best_path (ctc_amd_long_wildcard_loss_grad).  frames_per_tile: 0 is the default tile, otherwise a positive
+    multiple of _lib.LONG_FRAMES_MULTIPLE; the result does not depend on it.  Every other argument and the return value as
+    wildcard_loss_grad.  The workspace is allocated per call: with a gradient it holds the lattice's float64 state of every frame
+    (8 * B * ceil(U / 1024) * T * (S * 1024 + 2) bytes, S = 2 classic / 1 simplified).  Does not synchronise."""
+    if labels.dim() != 2 or label_length.dim() != 1:
+        raise ValueError(f"long_wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args("long_wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
+                                                                 logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    if d_loss is not None:
+        if tuple(d_loss.shape) != (B,):
+            raise ValueError(f"long_wildcard_loss_grad: d_loss must be [B] = {(B,)}, got {tuple(d_loss.shape)}")
+        if not (d_loss.dtype == torch.float32 and d_loss.device == dev and d_loss.is_contiguous()):
+            d_loss = d_loss.to(device=dev, dtype=torch.float32).contiguous()
+    if grad_dtype is None:
+        grad_dtype = x.dtype
+    if grad_dtype not in _DTYPES:
+        raise ValueError(f"long_wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
+    with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
+    key = ("long_wildcard_loss_grad", kind, B, T, V, U, int(frames_per_tile), with_grad)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.long_wildcard_loss_workspace_bytes(kind, B, T, V, U, int(frames_per_tile), with_grad)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
+    if B == 0:
+        return loss, grad
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
+    with _on_device(dev):
+        rc = lib.ctc_amd_long_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                 _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                                                 int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
+                                                 _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_long_wildcard_loss_grad")
+    return loss, grad
+
+
 def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True):
     """(loss[B], label_posterior[B, T, U], blank_posterior[B, T], duration[B, U], expected_frame[B, U]), all float32: with what
