@@ -974,6 +974,57 @@ int ctc_amd_long_wildcard_loss_grad(int kind, int wrt,
                                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Long-form CTC loss and gradient from tile checkpoints: ctc_amd_long_wildcard_loss_grad with a workspace that keeps no per-frame
+ * chain rows for the whole recording, so that an hour of audio fits one card with its gradient (added under ABI v6: two new entry
+ * points, nothing existing changed).
+ *
+ * Contract: every word of ctc_amd_long_wildcard_loss_grad's -- arguments, lattices, formats, degenerate cases, what is written --
+ * and the same bits in loss and gradient for the same inputs and any frames_per_tile: the chain step, the posteriors and the row
+ * stage are the same code, and what a tile starts from is the same float64 state.  With grad == NULL the call IS
+ * ctc_amd_long_wildcard_loss_grad (same launches, same workspace size).
+ * Schedule, with K, J, TF as there and R = min(K, J):
+ *   forward   the alpha tiles on the K + J - 1 anti-diagonals, keeping no per-frame rows; the chain row that leaves tile (k, j) goes
+ *             to a checkpoint of its own, [b][k][j], and tile (k, j + 1) starts from it.  The finish kernel takes log2 Z from the
+ *             checkpoint of the last tile in time of block (L - 1) / 1024.  K + J launches.
+ *   backward  per reverse anti-diagonal d = K + J - 2 .. 0: the alpha tiles (k, d - k) run again from their checkpoints (and the
+ *             alpha columns and row statistics the forward sweep left) and save their per-frame rows into slot j mod R of a ring
+ *             per (utterance, label block); the beta tiles of the diagonal turn those rows into posteriors, as in the existing
+ *             call; then, tile (0, d) having been the last of time block d, the row stage writes the gradient rows of frames
+ *             d * TF .. min(T, d * TF + TF) - 1 of every utterance (d < J).  2 (K + J - 1) + J launches.
+ *   The time blocks in flight on diagonal d are d - K + 1 .. d, K consecutive ones, so distinct modulo R; slot (d - R) mod R is next
+ *   written on diagonal d - 1, behind the row stage of time block d on the stream.  J < K: every time block has a slot of its own.
+ *   Every gradient row (b, t) is written exactly once.  The order of the launches on the stream is the only dependency.
+ * Validation: that of ctc_amd_long_wildcard_loss_grad, in its order and with its messages (B * T < 2^33 with a gradient included:
+ * it is not relaxed, although the row stage's grids are B * TF rows here).
+ * Workspace (may hold anything on entry), in the terms of ctc_amd_long_wildcard_loss_workspace_bytes.  want_grad == 0: that
+ * function's value.  want_grad != 0:
+ *   ctc_amd_long_wildcard_loss_ckpt_workspace_bytes =
+ *       r256(16 * B * (K - 1) * T)                 alpha columns                        (as there)
+ *     + r256(8 * B * K * J * 2056)                 alpha checkpoints                    (there: 8 * B * K * 2056)
+ *     + r256(16 * B * T) + r256(8 * B) + r256(4 * B)   row statistics, log2 Z, feasible (as there)
+ *     + r256(8 * B * (K - 1) * T)                  beta columns                         (as there)
+ *     + r256(8 * B * K * 2056)                     beta row buffers                     (as there)
+ *     + r256(8 * B * K * min(R * TF, T) * (S * 1024 + 2))   the ring of saved rows      (there: 8 * B * K * T * (S * 1024 + 2))
+ *   (J = max(1, ceil(T / TF)) as above.  min(R * TF, T): with R = J the last time block is short and the slots are the T per-frame
+ *   rows themselves, so the ring never exceeds the term it replaces; T = 0: no rows.)
+ * B = 1, T = 30 000, U = 8 192: 170 923 264 bytes classic (3 941 783 808 there, 23 x), 103 814 400 simplified.  An hour of audio
+ * (T = 180 000, U = 50 000; K = 49, J = 1407): 6 385 200 384 bytes classic, 3 867 569 408 simplified, against 144.9 / 72.6 GB.
+ * frames_per_tile trades memory here: the ring grows with TF, the checkpoints with 1 / TF (the hour at TF = 32: 6.0 GB, at TF = 512:
+ * 20.7 GB).  The price is one more alpha sweep.  No allocation, copy or synchronisation; asynchronous on
+ * `stream`, capturable; the number of launches depends on T, U and frames_per_tile alone.
+ */
+int ctc_amd_long_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                    size_t *out_bytes /*host*/);
+int ctc_amd_long_wildcard_loss_grad_ckpt(int kind, int wrt,
+                                         const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                         const int32_t *labels, int label_stride,
+                                         const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                         float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                         const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
+                                         void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Label posteriors: the soft alignment of a transcript over all CTC paths (added under ABI v6: two new entry points, nothing
  * existing changed).  What a forward-backward pass says most directly: with what probability frame t belongs to label position i,
  * over all alignments -- per POSITION, not per token, so repeated labels and wildcards keep their own columns.  Forward only.

@@ -103,6 +103,9 @@ SIGNATURES = {
     "ctc_amd_long_wildcard_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile, want_grad
     "ctc_amd_long_wildcard_loss_grad": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, wildcard_log_weight, B, T, V, U
                                         [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),  # frames_per_tile, d_loss, loss .. grad strides, ws, bytes, stream
+    "ctc_amd_long_wildcard_loss_ckpt_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile, want_grad
+    "ctc_amd_long_wildcard_loss_grad_ckpt": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, wildcard_log_weight, B, T, V, U
+                                             [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),  # frames_per_tile, d_loss, loss .. grad strides, ws, bytes, stream
     "ctc_amd_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
     "ctc_amd_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +       # .. blank_index, wildcard_log_weight, B, T, V, U
                                 [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,             # loss, label_posterior, blank_posterior, duration, expected_frame
@@ -256,6 +259,13 @@ def long_wildcard_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int
     out = _c_size_t(0)
     check(load().ctc_amd_long_wildcard_loss_workspace_bytes(kind, B, T, V, U, frames_per_tile, int(want_grad), ctypes.byref(out)),
           "ctc_amd_long_wildcard_loss_workspace_bytes")
+    return int(out.value)
+
+
+def long_wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0, want_grad: bool = True) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_wildcard_loss_ckpt_workspace_bytes(kind, B, T, V, U, frames_per_tile, int(want_grad), ctypes.byref(out)),
+          "ctc_amd_long_wildcard_loss_ckpt_workspace_bytes")
     return int(out.value)
 
 

@@ -942,6 +942,50 @@ int ctc_amd_long_wildcard_loss_grad(int kind, int wrt, const void *logits, int l
   return CTC_AMD_OK;
 }
 
+// The checkpointed gradient: the checks of the two entries above, word for word, on long_loss_ckpt_plan (which refuses what
+// long_loss_plan refuses, and is long_loss_plan without a gradient).
+int ctc_amd_long_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                    size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
+    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  ctc::LongLossPlan plan;
+  if (!ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, want_grad != 0, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_long_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                         int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                         const int32_t *logit_length, int blank_index, float wildcard_log_weight, int B, int T, int V,
+                                         int U, int frames_per_tile, const float *d_loss, float *loss, void *grad, int grad_dtype,
+                                         int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes,
+                                         void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
+  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
+    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
+  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
+  if (grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  ctc::LongLossPlan plan;
+  if (!ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, grad != nullptr, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_loss_long(p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
+                             static_cast<hipStream_t>(stream)), "long wildcard loss launch");
+  return CTC_AMD_OK;
+}
+
 int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
   return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
 }

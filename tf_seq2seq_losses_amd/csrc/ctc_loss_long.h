@@ -11,7 +11,9 @@ constexpr int LONG_LOSS_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h
 
 // grad == nullptr (a plan with want_grad == 0 suffices): P.launches alpha tile launches and the finish kernel.  Otherwise (want_grad
 // == 1) the same, bit for bit, then P.launches beta tile launches and the row stage.  T == 0: the finish kernel alone.  `ws` holds
-// P.total bytes and may hold anything.
+// P.total bytes and may hold anything.  A plan of long_loss_ckpt_plan with a gradient (P.ckpt; grad != nullptr) runs the
+// checkpointed schedule instead: the alpha tiles that keep a checkpoint per tile and the finish kernel, then per reverse
+// anti-diagonal the alpha tiles again, the beta tiles and, for d < P.J, the row stage of time block d.  The same bits.
 hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
                          char *ws, hipStream_t st);
 

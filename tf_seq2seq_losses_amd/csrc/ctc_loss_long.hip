@@ -21,6 +21,10 @@
 //                the posteriors as float32 pairs over the slots it has read (MODE 2's slot convention).  Simplified: alpha of
 //                position k * UB - 1 before the frame is the alpha column of the forward sweep.
 //   row stage    one wavefront per (b, t) looping over the label blocks of that frame: wild_grad_row_kernel.
+// ctc_amd_long_wildcard_loss_grad_ckpt is the same kernels on another workspace: alpha MODE 2 is MODE 0 with
+// a row buffer per tile (the checkpoints), MODE 3 runs a tile again from its checkpoint on the backward sweep and saves its rows into
+// a ring of min(K, J) time blocks, the beta tile and the row stage read the ring, and the row stage runs per time block.  Where a
+// checkpoint and a saved row live is long_loss_ckpt_index / long_loss_row_index (ctc_loss_long_plan.h) in both layouts.
 // Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all three; nothing unwritten is read.  No workgroup
 // waits for another: no flags, no cooperative launch, no floating-point atomics, vector stores only, one writer per element.
 #include "ctc_loss_long.h"
@@ -108,6 +112,9 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
                                                                      int d, int k_lo, int count) {
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
   constexpr int SRD = long_loss_row_doubles(KIND);
+  constexpr bool CKPT = MODE >= 2;               // row in / row out: the checkpoints of tiles (k, j - 1) / (k, j)
+  constexpr bool SAVE = MODE == 1 || MODE == 3;  // the chain's state of every frame is stored
+  constexpr bool REDO = MODE == 3;               // the forward sweep has run: nothing but the saved rows is written
   const double NINF = -__builtin_inf();
   __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
   __shared__ int lab_s[UB + 1];  // positions k * UB - 1 .. k * UB + UB - 1
@@ -121,6 +128,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   const int Tb = frame_count(p, b);
   const int L = label_count(p, b);
   if (too_many_labels(p, L) || !long_loss_tile_active(Tb, L, k, j, TF)) return;
+  if (REDO && w.flag[b] == 0) return;  // (as the beta tile: an infeasible utterance has no posteriors, and nothing reads its rows)
   const int t_lo = j * TF;                           // (J * TF < T + TF: no overflow)
   const int t_hi = Tb - t_lo < TF ? Tb : t_lo + TF;  // one past the tile's last frame
   const bool fresh = long_loss_alpha_fresh(k, j, TF);
@@ -141,11 +149,14 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
   // vector row accesses (16 bytes of float32, 8 bytes of 16-bit elements) need aligned rows; element-wise otherwise
   const bool vec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
-  double *const row = w.row + ((size_t)b * K + k) * RW;
+  double *const row = w.row + (CKPT ? long_loss_ckpt_index(b, K, k, T, TF, j) : (size_t)b * K + k) * RW;  // row out
+  const double *const row_in = CKPT && !fresh ? row - RW : row;  // (not fresh: j > 0, and tile (k, j - 1) ran)
   const double *const col_in = k > 0 ? w.col + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T * 2 : nullptr;
-  double *const col_out = has_right ? w.col + ((size_t)b * (K - 1) + k) * (size_t)T * 2 : nullptr;
+  double *const col_out = has_right && !REDO ? w.col + ((size_t)b * (K - 1) + k) * (size_t)T * 2 : nullptr;
   float *const statw = w.stat + (size_t)b * T * 4;
-  double *const myrows = MODE == 1 ? w.rows + ((size_t)b * K + k) * (size_t)T * SRD : nullptr;
+  // the saved row of frame t_base; the rows of a tile are consecutive (without checkpoints: so are all rows of the label block)
+  const int t_base = REDO ? t_lo : 0;
+  double *const myrows = SAVE ? w.rows + long_loss_row_index(REDO, b, K, k, T, t_base, TF) * SRD : nullptr;
 
   // chain state (wave 0): row in
   double O[NL], C[NL];  // simplified: C is S, O unused
@@ -163,10 +174,10 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   if (wave == 0 && !fresh) {
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
-      if (KIND == 0) O[q] = row[q * 64 + lane];
-      C[q] = row[(NL + q) * 64 + lane];
+      if (KIND == 0) O[q] = row_in[q * 64 + lane];
+      C[q] = row_in[(NL + q) * 64 + lane];
     }
-    if (k == 0) cs = row[2 * UB];
+    if (k == 0) cs = row_in[2 * UB];
   }
 
   auto produce = [&](int kb) {  // one frame per producer wavefront
@@ -180,7 +191,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       e[q] = lab[q] >= 0 ? v : -__builtin_inff();
     }
     float4 sv;
-    if (k == 0) {
+    if (k == 0 && !REDO) {
       // the row pass.  Both access paths give a lane the same elements in the same order: identical bits
       const float eb = row_load1(xr, blank, dt);
       float m = -3.402823466e38f, s = 0.f;
@@ -192,7 +203,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       sv = make_float4(eb, M, l2s, 0.f);
       if (lane == 0) *reinterpret_cast<float4 *>(statw + (size_t)t * 4) = sv;
     } else {
-      sv = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (tile (0, j) stored it on an earlier launch)
+      sv = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (tile (0, j) stored it on an earlier launch: the same bits)
     }
     float *const r = ring + ((kb & 1) * F + f) * RS;
 #pragma unroll
@@ -213,8 +224,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
       auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
-      double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
-      if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
+      double *const r = SAVE ? myrows + (size_t)(t0 + f - t_base) * SRD : nullptr;
+      if (SAVE && KIND == 1) {  // the state BEFORE the frame
 #pragma unroll
         for (int q = 0; q < NL; ++q) r[lane * NS + q] = C[q];
         if (k == 0 && lane == 0) r[SRD - 2] = cs;
@@ -246,7 +257,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
         }
       }
       cs += eb;
-      if (MODE == 1 && KIND == 0) {  // the state AFTER the frame
+      if (SAVE && KIND == 0) {  // the state AFTER the frame
 #pragma unroll
         for (int q = 0; q < NL; ++q) *reinterpret_cast<double2 *>(r + lane * NS + 2 * q) = make_double2(O[q], C[q]);
         if (k == 0 && lane == 0) r[SRD - 2] = cs;
@@ -264,7 +275,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   }
 
   // row out
-  if (wave == 0) {
+  if (wave == 0 && !REDO) {
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
       row[q * 64 + lane] = O[q];
@@ -274,22 +285,24 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   }
 }
 
-// log2 Z of every utterance from the row buffers: one thread per utterance
-template <int KIND>
-__global__ __launch_bounds__(256) void loss_long_finish_kernel(const Problem p, const LongLossWs w, int K, float *__restrict__ loss) {
+// log2 Z of every utterance from the row buffers: one thread per utterance.  CKPT: from the checkpoint that the block's last tile
+// in time, (k, (Tb - 1) / TF), wrote (it ran: 0 < L <= Tb, or block 0 of an empty transcript with Tb > 0)
+template <int KIND, bool CKPT>
+__device__ __forceinline__ void loss_long_finish(const Problem &p, const LongLossWs &w, int K, int TF, float *__restrict__ loss) {
   const double NINF = -__builtin_inf();
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= p.B) return;
   const int Tb = frame_count(p, b);
   const int L = label_count(p, b);
+  auto row_of = [&](int k) { return w.row + (CKPT ? long_loss_ckpt_index(b, K, k, p.T, TF, (Tb - 1) / TF) : (size_t)b * K + k) * RW; };
   double v = NINF;
   if (too_many_labels(p, L) || L > Tb) {
     // infeasible by the count: no tile ran
   } else if (L == 0) {
-    v = Tb == 0 ? 0.0 : w.row[(size_t)b * K * RW + 2 * UB];
+    v = Tb == 0 ? 0.0 : row_of(0)[2 * UB];
   } else {  // (L <= Tb: block (L - 1) / UB ran at least one tile)
     const int i = L - 1, r = i % UB;
-    const double *const row = w.row + ((size_t)b * K + i / UB) * RW;
+    const double *const row = row_of(i / UB);
     const double ov = row[(r % NL) * 64 + r / NL], cv = row[(NL + r % NL) * 64 + r / NL];
     v = KIND == 0 ? ll_lse(ov, cv) : cv;
   }
@@ -297,8 +310,18 @@ __global__ __launch_bounds__(256) void loss_long_finish_kernel(const Problem p, 
   w.logp[b] = v;
   w.flag[b] = v > NINF && v < -NINF ? 1 : 0;
 }
-
 template <int KIND>
+__global__ __launch_bounds__(256) void loss_long_finish_kernel(const Problem p, const LongLossWs w, int K, float *__restrict__ loss) {
+  loss_long_finish<KIND, false>(p, w, K, 0, loss);
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void loss_long_finish_ckpt_kernel(const Problem p, const LongLossWs w, int K, int TF,
+                                                                    float *__restrict__ loss) {
+  loss_long_finish<KIND, true>(p, w, K, TF, loss);
+}
+
+// CKPT: the saved rows are the ring's (long_loss_row_index), written by alpha MODE 3 on the launch before this one
+template <int KIND, bool CKPT>
 __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Problem p, const double w2, const LongLossWs w, int K, int TF,
                                                                     int d, int k_lo, int count) {
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
@@ -341,7 +364,9 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
   double *const colb_out = k > 0 ? w.colb + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T : nullptr;
   const double *const cola_in = KIND == 1 && k > 0 ? w.col + ((size_t)b * (K - 1) + (k - 1)) * (size_t)T * 2 : nullptr;
   const float *const statw = w.stat + (size_t)b * T * 4;
-  double *const myrows = w.rows + ((size_t)b * K + k) * (size_t)T * SRD;
+  // the saved row of frame t_base; the rows of a tile are consecutive (without checkpoints: so are all rows of the label block)
+  const int t_base = CKPT ? t_lo : 0;
+  double *const myrows = w.rows + long_loss_row_index(CKPT, b, K, k, T, t_base, TF) * SRD;
 
   // chain state (wave 0): beta, the mass of the frames still to come
   double O[NL], C[NL];
@@ -405,7 +430,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
       auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
-      double *const r = myrows + (size_t)t * SRD;
+      double *const r = myrows + (size_t)(t - t_base) * SRD;
       double A[NS], Acs = NINF;
 #pragma unroll
       for (int q = 0; q < NS; ++q) A[q] = r[lane * NS + q];
@@ -479,18 +504,19 @@ constexpr int LLG_WAVES = 4;
 constexpr int LLG_CH = 1024;  // columns per pass
 constexpr int LLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units of 2^-40, so |bin| < U 2^40 <= 2^56
 
-template <int KIND>
-__global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Problem p, const LongLossWs w, int K, int TF,
-                                                                       const float *__restrict__ d_loss, void *__restrict__ grad) {
+// CKPT: the rows (b, t) of one time block, t = t0 .. t0 + nt - 1, from the ring; otherwise all of them (t0 = 0, nt = T)
+template <int KIND, bool CKPT>
+__device__ __forceinline__ void loss_long_row(const Problem &p, const LongLossWs &w, int K, int TF, int t0, int nt,
+                                              const float *__restrict__ d_loss, void *__restrict__ grad) {
   constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
   constexpr size_t ROWB = (size_t)long_loss_row_doubles(KIND) * 8;
   __shared__ unsigned long long bins_all[LLG_WAVES][LLG_CH];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long rowi = (long)blockIdx.x * LLG_WAVES + wv;
-  if (rowi >= (long)p.B * p.T) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
+  if (rowi >= (long)p.B * nt) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
   unsigned long long *const bins = bins_all[wv];
-  const int b = (int)(rowi / p.T), t = (int)(rowi % p.T);
+  const int b = (int)(rowi / nt), t = t0 + (int)(rowi % nt);
   const int V = p.V, blank = p.blank, xdt = p.xdtype, gdt = p.gdtype;
   const int Tb = frame_count(p, b);
   const int xesz = xdt == 0 ? 4 : 2, gesz = gdt == 0 ? 4 : 2;
@@ -533,7 +559,9 @@ __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Pro
   const float mx = sv.y, l2s = sv.z;
   const int L = label_count(p, b);  // (feasible: L <= U)
   const int j = t / TF;
-  const char *const rows = reinterpret_cast<const char *>(w.rows) + ((size_t)b * K * (size_t)p.T + t) * ROWB;
+  // the saved row of (b, 0, t); those of the other label blocks lie long_loss_row_stride rows apart
+  const char *const rows = reinterpret_cast<const char *>(w.rows) + long_loss_row_index(CKPT, b, K, 0, p.T, t, TF) * ROWB;
+  const size_t kstride = long_loss_row_stride(CKPT, K, p.T, TF);
   const int32_t *const lab = label_row(p, b);
 
   float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
@@ -544,7 +572,7 @@ __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Pro
     for (int k = 0; k < K && (k == 0 || k * UB < L); ++k) {
       // a tile that did not run has no posteriors: they are exactly zero, and adding them would change no bit
       if (!long_loss_tile_active(Tb, L, k, j, TF)) continue;
-      const char *const r = rows + (size_t)k * p.T * ROWB;
+      const char *const r = rows + (size_t)k * kstride * ROWB;
       const int n = L - k * UB < UB ? L - k * UB : UB;
       for (int i = lane; i < n; i += 64) {
         const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
@@ -587,6 +615,16 @@ __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Pro
     wave_lds_fence();
   }
 }
+template <int KIND>
+__global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Problem p, const LongLossWs w, int K, int TF,
+                                                                       const float *__restrict__ d_loss, void *__restrict__ grad) {
+  loss_long_row<KIND, false>(p, w, K, TF, 0, p.T, d_loss, grad);
+}
+template <int KIND>
+__global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_ckpt_kernel(const Problem p, const LongLossWs w, int K, int TF, int t0, int nt,
+                                                                            const float *__restrict__ d_loss, void *__restrict__ grad) {
+  loss_long_row<KIND, true>(p, w, K, TF, t0, nt, d_loss, grad);
+}
 
 template <int KIND>
 hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
@@ -605,7 +643,7 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
   for (int e = 0; e < P.launches; ++e) {
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
-    hipLaunchKernelGGL(loss_long_beta_kernel<KIND>, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d,
+    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, false>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d,
                        k_lo, count);
   }
   const unsigned blocks = (unsigned)(((long)p.B * p.T + LLG_WAVES - 1) / LLG_WAVES);
@@ -613,11 +651,44 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
   return hipGetLastError();
 }
 
+// The checkpointed gradient (P.ckpt, grad != nullptr).  Forward: the alpha tiles keep no per-frame rows and
+// leave their row out in the checkpoint of the tile.  Backward, per reverse anti-diagonal d: the alpha tiles of the diagonal run
+// again from their checkpoints and save their rows into the ring, the beta tiles turn them into posteriors, and tile (0, d) having
+// been the last of time block d, the row stage takes that block's frames.  The ring slot of time block d is next written on
+// diagonal d - 1 (ctc_loss_long_plan.h), behind this row stage on the stream.
+template <int KIND>
+hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
+                         const LongLossWs &w, hipStream_t st) {
+  if (p.T > 0) {
+    for (int d = 0; d < P.launches; ++d) {
+      int k_lo, count;
+      long_loss_forward_diagonal(P, d, &k_lo, &count);
+      hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 2>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K,
+                         P.TF, d, k_lo, count);
+    }
+  }
+  hipLaunchKernelGGL(loss_long_finish_ckpt_kernel<KIND>, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, st, p, w, P.K, P.TF, loss);
+  if (p.T == 0) return hipGetLastError();
+  for (int e = 0; e < P.launches; ++e) {
+    int d, k_lo, count;
+    long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
+    const dim3 grid((unsigned)((size_t)p.B * count));
+    hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 3>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, true>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+    if (d < P.J) {
+      const int t0 = d * P.TF, nt = p.T - t0 < P.TF ? p.T - t0 : P.TF;
+      const unsigned blocks = (unsigned)(((long)p.B * nt + LLG_WAVES - 1) / LLG_WAVES);
+      hipLaunchKernelGGL(loss_long_row_ckpt_kernel<KIND>, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, t0, nt, d_loss, grad);
+    }
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
                          char *ws, hipStream_t st) {
-  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad)) return hipErrorInvalidValue;
+  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad)) return hipErrorInvalidValue;
   LongLossWs w;
   w.col = reinterpret_cast<double *>(ws + P.off_col);
   w.row = reinterpret_cast<double *>(ws + P.off_row);
@@ -628,6 +699,7 @@ hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard
   w.rowb = reinterpret_cast<double *>(ws + P.off_rowb);
   w.rows = reinterpret_cast<double *>(ws + P.off_rows);
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  if (P.ckpt) return p.kind == 0 ? run_kind_ckpt<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind_ckpt<1>(p, P, w2, d_loss, loss, grad, w, st);
   return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, st);
 }
 

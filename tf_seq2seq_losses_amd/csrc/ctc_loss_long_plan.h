@@ -50,10 +50,41 @@ CTC_LL_HD bool long_loss_beta_has_right(int Tb, int L, int k, int j, int TF, int
   return long_loss_has_right(L, k, UB) && long_loss_tile_active(Tb, L, k + 1, j, TF, UB);
 }
 
+// ---- where things live ----
+// The checkpointed gradient (ctc_amd_long_wildcard_loss_grad_ckpt) keeps the chain row that leaves tile (k, j) in a slot of its own,
+// [b][k][j] of [B][K][Jc], Jc = max(J, 1) time blocks, and the saved rows of a tile only while its time block is in flight: a ring
+// of R = min(K, Jc) time blocks per (utterance, label block).
+CTC_LL_HD int long_loss_ckpt_cols(int T, int TF) { return T > 0 ? (int)(((long long)T + TF - 1) / TF) : 1; }
+CTC_LL_HD int long_loss_ring_cols(int K, int T, int TF) {
+  const int Jc = long_loss_ckpt_cols(T, TF);
+  return K < Jc ? K : Jc;
+}
+// frames of the ring of one (utterance, label block): R * TF, and no more than T (R == Jc: every time block has its own slot, the
+// last one is T - (Jc - 1) * TF frames long, and the slots are the per-frame rows themselves)
+CTC_LL_HD size_t long_loss_ring_frames(int K, int T, int TF) {
+  const size_t rt = (size_t)long_loss_ring_cols(K, T, TF) * (size_t)TF;
+  return rt < (size_t)T ? rt : (size_t)T;
+}
+// index of the checkpoint of tile (k, j) of utterance b, in chain states of LONG_ROW_DOUBLES doubles
+CTC_LL_HD size_t long_loss_ckpt_index(int b, int K, int k, int T, int TF, int j) {
+  return ((size_t)b * K + k) * (size_t)long_loss_ckpt_cols(T, TF) + (size_t)j;
+}
+// index of the saved row of (b, k, t), in rows of long_loss_row_doubles(kind) doubles: the one function that the alpha tile that
+// saves rows, the beta tile, the row stage and the plan checkers ask.  ckpt == 0: [B][K][T].  ckpt != 0: the ring
+// [B][K][(t / TF) mod R][t mod TF], whose time blocks lie TF rows apart (the rows of one tile are consecutive in both).
+// long_loss_row_stride: the rows between one label block and the next, index(k) = index(0) + k * stride (the row stage walks that).
+CTC_LL_HD size_t long_loss_row_stride(int ckpt, int K, int T, int TF) { return ckpt ? long_loss_ring_frames(K, T, TF) : (size_t)T; }
+CTC_LL_HD size_t long_loss_row_index(int ckpt, int b, int K, int k, int T, int t, int TF) {
+  if (!ckpt) return ((size_t)b * K + k) * (size_t)T + (size_t)t;
+  const int j = t / TF, R = long_loss_ring_cols(K, T, TF);
+  return ((size_t)b * K + k) * long_loss_ring_frames(K, T, TF) + (size_t)(j % R) * TF + (size_t)(t - j * TF);
+}
+
 struct LongLossPlan {
   int kind, B, T, U, want_grad;
   int K, J, TF;   // label blocks, time blocks, frames per tile
   int launches;   // K + J - 1 anti-diagonals of tiles per sweep (none when T == 0)
+  int ckpt;       // 1: the checkpointed layout (long_loss_ckpt_plan with a gradient); off_row is then [B][K][Jc], off_rows the ring
   size_t off_col, off_row, off_stat, off_logp, off_flag;  // both paths
   size_t off_colb, off_rowb, off_rows;                    // the gradient's (want_grad == 0: all equal to total)
   size_t total;
@@ -67,7 +98,7 @@ inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, i
   if (want_grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return false;
   LongLossPlan P;
   P.kind = kind; P.B = B; P.T = T; P.U = U; P.want_grad = want_grad ? 1 : 0;
-  P.K = A.K; P.J = A.J; P.TF = A.TF; P.launches = A.launches;
+  P.K = A.K; P.J = A.J; P.TF = A.TF; P.launches = A.launches; P.ckpt = 0;
   const size_t b = (size_t)B, t = (size_t)T, k = (size_t)P.K;
   size_t o = 0;
   P.off_col = o;  o = long_r256(o + b * (k - 1) * t * 16);          // alpha columns: [B][K - 1][T] pairs (O, C) of float64
@@ -81,6 +112,28 @@ inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, i
   if (want_grad) o = long_r256(o + b * k * LONG_ROW_DOUBLES * 8);   // beta row buffers: [B][K] chain states
   P.off_rows = o;
   if (want_grad) o = long_r256(o + b * k * t * (size_t)long_loss_row_doubles(kind) * 8);  // saved rows: [B][K][T][S * 1024 + 2] float64
+  P.total = o;
+  *out = P;
+  return true;
+}
+
+// The checkpointed call's plan.  Without a gradient it is long_loss_plan's (the call runs the existing forward).  With one, two terms
+// differ: the alpha row buffers become the checkpoints [B][K][Jc], and the saved rows become the ring [B][K][min(R * TF, T)] rows,
+// never more than the T rows it replaces.  Refuses what long_loss_plan refuses.
+inline bool long_loss_ckpt_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out) {
+  LongLossPlan P;
+  if (!long_loss_plan(kind, B, T, U, frames_per_tile, want_grad, &P)) return false;
+  if (!want_grad) { *out = P; return true; }
+  P.ckpt = 1;
+  const size_t b = (size_t)P.B, t = (size_t)P.T, k = (size_t)P.K;
+  size_t o = P.off_row;  // (the alpha columns before it: as they are)
+  o = long_r256(o + b * k * (size_t)long_loss_ckpt_cols(P.T, P.TF) * LONG_ROW_DOUBLES * 8);  // alpha checkpoints: [B][K][Jc] chain states
+  P.off_stat = o; o = long_r256(o + b * t * 16);
+  P.off_logp = o; o = long_r256(o + b * 8);
+  P.off_flag = o; o = long_r256(o + b * 4);
+  P.off_colb = o; o = long_r256(o + b * (k - 1) * t * 8);
+  P.off_rowb = o; o = long_r256(o + b * k * LONG_ROW_DOUBLES * 8);
+  P.off_rows = o; o = long_r256(o + b * k * long_loss_ring_frames(P.K, P.T, P.TF) * (size_t)long_loss_row_doubles(kind) * 8);  // the ring
   P.total = o;
   *out = P;
   return true;

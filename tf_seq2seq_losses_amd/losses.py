@@ -542,9 +542,9 @@ class _LongLossFn(torch.autograd.Function):
     ONE call with d_loss.  Backward is not itself differentiable: a second derivative raises."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf, checkpoint):
         ctx.save_for_backward(x, labels, label_length, logit_length)
-        ctx.call = (kind, wrt, blank, U, weight, tf)
+        ctx.call = (kind, wrt, blank, U, weight, tf, checkpoint)
         return ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
                                            wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
 
@@ -552,14 +552,14 @@ class _LongLossFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_loss):
         x, labels, label_length, logit_length = ctx.saved_tensors
-        kind, wrt, blank, U, weight, tf = ctx.call
+        kind, wrt, blank, U, weight, tf, checkpoint = ctx.call
         _, grad = ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
-                                              wildcard_log_weight=weight, frames_per_tile=tf)
-        return grad, None, None, None, None, None, None, None, None, None
+                                              wildcard_log_weight=weight, frames_per_tile=tf, checkpoint=checkpoint)
+        return grad, None, None, None, None, None, None, None, None, None, None
 
 
 def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-               frames_per_tile=None, max_label_length=None) -> torch.Tensor:
+               frames_per_tile=None, max_label_length=None, checkpoint=False) -> torch.Tensor:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -574,7 +574,7 @@ def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, 
     kind = ops.KINDS[kind_name]
     tf = 0 if frames_per_tile is None else int(frames_per_tile)
     if x.requires_grad and torch.is_grad_enabled():
-        return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf)
+        return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf, bool(checkpoint))
     with torch.no_grad():  # forward only: the result is detached
         return ops.long_wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
                                            wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
@@ -582,7 +582,8 @@ def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, 
 
 def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                           blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                          frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None) -> torch.Tensor:
+                          frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
+                          checkpoint: bool = False) -> torch.Tensor:
     """CTC loss of a long recording on the classic lattice: classic_ctc_wildcard_loss (without a WILDCARD label, -2, the plain CTC
     loss; with one, the loss of a partial transcript) for transcripts of up to 65536 labels, computed on the tiled lattice of
     classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4; the loss and the gradient do not
@@ -590,27 +591,35 @@ def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: 
     / float16 logits, any batch / time strides, read in place; the gradient comes back in the logits' dtype and layout; a second
     derivative raises).  An infeasible sample has loss +inf and a zero gradient.  Backward holds the lattice's float64 state of
     every frame: 8 * batch * ceil(U / 1024) * max_length * 2050 bytes (half of that on the simplified lattice); forward alone holds
-    no per-frame state.  check_labels keeps rejecting -2."""
+    no per-frame state.  checkpoint=True gives the same bits in loss and gradient from a backward that keeps one chain row per tile
+    and the per-frame state of min(K, J) time blocks only (K = ceil(U / 1024), J = ceil(max_length / TF), TF = frames_per_tile):
+    8 * batch * K * (J * 2056 + min(K, J) * TF * 2050) bytes in place of the term above (1026 for 2050 on the simplified lattice),
+    23 times less at ten minutes of audio, and an hour (180 000 frames, 50 000 labels) takes 6.4 GB in place of 144.9 GB; it costs
+    one more forward sweep, and frames_per_tile then trades memory: the ring grows with it, the checkpoints shrink.  Forward is the
+    same call either way.  check_labels keeps rejecting -2."""
     return _long_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length)
+                      frames_per_tile, max_label_length, checkpoint)
 
 
 def simplified_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                              blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                             frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None) -> torch.Tensor:
-    """The same on the simplified lattice.  Same arguments and return value as classic_ctc_long_loss."""
+                             frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
+                             checkpoint: bool = False) -> torch.Tensor:
+    """The same on the simplified lattice.  Same arguments and return value as classic_ctc_long_loss; backward holds
+    8 * batch * K * max_length * 1026 bytes, with checkpoint=True 8 * batch * K * (J * 2056 + min(K, J) * TF * 1026), the same bits."""
     return _long_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length)
+                      frames_per_tile, max_label_length, checkpoint)
 
 
 def ctc_long_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                 wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
-                                max_label_length: Optional[int] = None) -> torch.Tensor:
+                                max_label_length: Optional[int] = None, checkpoint: bool = False) -> torch.Tensor:
     """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The
-    gradient is with respect to logprobas."""
+    gradient is with respect to logprobas.  checkpoint and both workspace formulas as in classic_ctc_long_loss /
+    simplified_ctc_long_loss: the same bits from the smaller workspace."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length)
+                      frames_per_tile, max_label_length, checkpoint)
 
 
 # --------------------------------------------------------------------------------------------------

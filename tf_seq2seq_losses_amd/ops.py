@@ -721,12 +721,15 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
 def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
                             logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
                             grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0, want_grad: bool = True,
-                            frames_per_tile: int = 0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                            frames_per_tile: int = 0, checkpoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(loss[B] float32, grad[B, T, V] or None): wildcard_loss_grad for up to _lib.LONG_MAX_U label positions, on the tiled lattice
     of long_wildcard_best_path (ctc_amd_long_wildcard_loss_grad).  frames_per_tile: 0 is the default tile, otherwise a positive
     multiple of _lib.LONG_FRAMES_MULTIPLE; the result does not depend on it.  Every other argument and the return value as
     wildcard_loss_grad.  The workspace is allocated per call: with a gradient it holds the lattice's float64 state of every frame
-    (8 * B * ceil(U / 1024) * T * (S * 1024 + 2) bytes, S = 2 classic / 1 simplified).  Does not synchronise."""
+    (8 * B * ceil(U / 1024) * T * (S * 1024 + 2) bytes, S = 2 classic / 1 simplified).  checkpoint=True is
+    ctc_amd_long_wildcard_loss_grad_ckpt: the same bits from a workspace of one checkpoint per tile and a ring of
+    min(K, J) * frames_per_tile frames of that state (K = ceil(U / 1024), J = ceil(T / frames_per_tile)) in place of T frames, for
+    one more alpha sweep; frames_per_tile then trades memory (the ring grows with it, the checkpoints shrink).  Does not synchronise."""
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"long_wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("long_wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -744,10 +747,12 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
     if grad_dtype not in _DTYPES:
         raise ValueError(f"long_wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
     with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
-    key = ("long_wildcard_loss_grad", kind, B, T, V, U, int(frames_per_tile), with_grad)
+    name = "long_wildcard_loss_grad_ckpt" if checkpoint else "long_wildcard_loss_grad"
+    key = (name, kind, B, T, V, U, int(frames_per_tile), with_grad)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = _lib.long_wildcard_loss_workspace_bytes(kind, B, T, V, U, int(frames_per_tile), with_grad)
+        size = _lib.long_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_wildcard_loss_workspace_bytes
+        n = _WS_BYTES[key] = size(kind, B, T, V, U, int(frames_per_tile), with_grad)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
     if B == 0:
@@ -755,11 +760,12 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
     with _on_device(dev):
-        rc = lib.ctc_amd_long_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
-                                                 _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
-                                                 int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
-                                                 _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
-    _lib.check(rc, "ctc_amd_long_wildcard_loss_grad")
+        call = lib.ctc_amd_long_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_wildcard_loss_grad
+        rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                  _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                  int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
+                  _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_" + name)
     return loss, grad
 
 
