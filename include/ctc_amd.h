@@ -1083,6 +1083,68 @@ int ctc_amd_label_posterior(int kind, int wrt,
                             float *duration /* [B][U], may be NULL */, float *expected_frame /* [B][U], may be NULL */,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Long-form label posteriors: ctc_amd_label_posterior for U <= CTC_AMD_LONG_MAX_U label positions, and a per-label confidence that
+ * needs no [B][T][U] matrix (added under ABI v6: two new entry points, nothing existing changed).  Which stretches of a ten-minute
+ * or one-hour alignment to trust: the best path of ctc_amd_long_wildcard_best_path cannot say, the posteriors can.
+ *
+ * Inputs, lattices, emissions, wildcard_log_weight, infeasible utterances, formats (float32 / bfloat16 / float16) and strides
+ * (logits read in place) are those of ctc_amd_long_wildcard_loss_grad; the meaning of label_posterior, blank_posterior, duration
+ * and expected_frame is that of ctc_amd_label_posterior.  Forward only.  L = label_length[b], T_b = logit_length[b] clamped to
+ * [0, T].  The outputs, all contiguous:
+ *   loss[B]                  the bits of ctc_amd_long_wildcard_loss_grad.
+ *   label_posterior[B][T][U] MAY BE NULL (T = 180 000, U = 50 000 would be 36 GB): then it is not written and every other output
+ *                            keeps its bits.  Otherwise, for t < T_b and i < L of a feasible utterance, the float32 posterior the
+ *                            beta sweep forms -- classic: of the open state of position i after frame t; simplified: of entering
+ *                            position i at frame t, plus (added in float32) that of staying behind it when it is a wildcard -- the
+ *                            values ctc_amd_label_posterior returns; exactly 0 in a tile that does not run (wholly before the
+ *                            first frame its positions can be reached in).
+ *   blank_posterior[B][T]    the closed states' (classic) or the blank-emitting stays' (simplified) posteriors plus the start
+ *                            state's, summed in float32 in one fixed order that depends on neither frames_per_tile nor the batch:
+ *                            lane l of a wavefront takes positions l, l + 64, ... of label block 0, then of block 1, and so on
+ *                            (lane 0 the start state behind block 0), then the 64 lanes are summed.
+ *   duration[B][U], expected_frame[B][U]   both or neither.  REDUCTIONS OF THE FLOAT32 label_posterior VALUES (returned or not):
+ *                            sum_t p and sum_t t * p run in float64, STRICTLY SEQUENTIALLY IN DESCENDING FRAME ORDER, from T_b - 1
+ *                            to 0 (the backward sweep meets the time blocks in that order, and a sequential sum carried from block
+ *                            to block is the same sequence whatever frames_per_tile is; t * p is exact in float64); the quotient
+ *                            is taken in float64 and each result is rounded once.  A float64 host reduction of the returned matrix
+ *                            in that order reproduces them bit for bit.
+ *   peak_posterior[B][U] float32, peak_frame[B][U] int32   both or neither.  max_t label_posterior[b, t, i] and the lowest t that
+ *                            attains it: the per-label confidence when the dense matrix does not fit.
+ * Every element of every given output is written: frames t >= T_b get 0 in label_posterior and blank_posterior; positions
+ * L <= i < U get 0 in label_posterior, duration and peak_posterior and -1 in expected_frame and peak_frame; an infeasible utterance
+ * gets loss +inf, zeros and -1 and changes nothing else in the batch.  T == 0 still writes the [B][U] outputs (0 / -1).
+ * Schedule: that of ctc_amd_long_wildcard_loss_grad_ckpt, with a posterior stage in the row stage's place: after the beta tiles of
+ * reverse anti-diagonal d < J one launch reads the ring rows of time block d -- a wavefront per row (b, t) writes the dense run and
+ * blank_posterior[b, t]; a wavefront per (b, 64 positions) walks the block's frames downwards and carries sum p, sum t p, the peak
+ * and its frame in the workspace (the stage of block J - 1 starts them, that of block 0 rounds and writes).  No workgroup waits for
+ * another; vector stores only, one writer per element, no atomics: the same bits on every run, for every frames_per_tile and every
+ * batch composition.  K + J launches forward and 2 (K + J - 1) + J backward, as there (T == 0: 1 or 2).
+ * Validation: that of ctc_amd_long_wildcard_loss_grad_ckpt with a gradient, in its order and with its messages -- common arguments
+ * (U <= CTC_AMD_LONG_MAX_U), element type, B == 0 (CTC_AMD_OK without a launch), strides, wildcard_log_weight, loss non-NULL,
+ * V <= CTC_AMD_MAX_V, B * T < 2^33 --; then blank_posterior non-NULL when T > 0, duration / expected_frame both or neither,
+ * peak_posterior / peak_frame both or neither; then frames_per_tile and the launch grids (CTC_AMD_EINVAL each); then the workspace
+ * (CTC_AMD_EWORKSPACE before any launch).
+ * Workspace (may hold anything on entry):
+ *   ctc_amd_long_label_posterior_workspace_bytes = ctc_amd_long_wildcard_loss_ckpt_workspace_bytes(want_grad = 1)
+ *     + r256(16 * B * U)                    sum p and sum t p of every position, float64
+ *     + r256(8 * B * U)                     the running peak (float32) and its frame (int32)
+ * B = 1, T = 30 000, U = 8 192: 171 119 872 bytes classic; the hour (T = 180 000, U = 50 000): 6 386 400 512 classic.  No
+ * allocation, copy or synchronisation; asynchronous on `stream`, capturable; the number of launches depends on T, U and
+ * frames_per_tile alone.
+ */
+int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes /*host*/);
+int ctc_amd_long_label_posterior(int kind, int wrt,
+                                 const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride,
+                                 const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                 float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                 float *loss /* [B] */, float *label_posterior /* [B][T][U], may be NULL */,
+                                 float *blank_posterior /* [B][T] */,
+                                 float *duration /* [B][U], may be NULL */, float *expected_frame /* [B][U], may be NULL */,
+                                 float *peak_posterior /* [B][U], may be NULL */, int32_t *peak_frame /* [B][U], may be NULL */,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,10 @@ SIGNATURES = {
     "ctc_amd_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +       # .. blank_index, wildcard_log_weight, B, T, V, U
                                 [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,             # loss, label_posterior, blank_posterior, duration, expected_frame
                                  _c_void_p, _c_size_t, _c_void_p]),                                 # ws, bytes, stream
+    "ctc_amd_long_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
+    "ctc_amd_long_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, wildcard_log_weight, B, T, V, U
+                                     [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame
+                                      _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),       # peak_posterior, peak_frame, ws, bytes, stream
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
@@ -272,6 +276,13 @@ def long_wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U
 def label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_label_posterior_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_label_posterior_workspace_bytes")
+    return int(out.value)
+
+
+def long_label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_label_posterior_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_label_posterior_workspace_bytes")
     return int(out.value)
 
 

@@ -1017,6 +1017,52 @@ int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dt
   return CTC_AMD_OK;
 }
 
+int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
+    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  ctc::LongPostPlan plan;
+  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+// Checked in the order of ctc_amd_long_wildcard_loss_grad_ckpt with a gradient, with its messages; then the outputs as in
+// ctc_amd_label_posterior; then frames_per_tile and the launch grids, then the workspace.
+int ctc_amd_long_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                 int blank_index, float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile, float *loss,
+                                 float *label_posterior, float *blank_posterior, float *duration, float *expected_frame,
+                                 float *peak_posterior, int32_t *peak_frame, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
+  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
+  if (int rc = f.check_dtypes()) return rc;
+  if (B == 0) return CTC_AMD_OK;
+  if (int rc = f.check_strides(V, false)) return rc;
+  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
+    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
+  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
+  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  if (T > 0 && !blank_posterior) return fail(CTC_AMD_EINVAL, "null blank_posterior pointer");
+  if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
+  if (!peak_posterior != !peak_frame) return fail(CTC_AMD_EINVAL, "peak_posterior and peak_frame must both be given or both be NULL");
+  ctc::LongPostPlan plan;
+  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan))
+    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  const Problem p = f.applied(make_problem(c));
+  CTC_TRY(ctc::run_long_label_posterior(p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+                                        peak_posterior, peak_frame, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+          "long label posterior launch");
+  return CTC_AMD_OK;
+}
+
 // what ctc_amd_edit_distance and its size query take as a shape
 int check_edit(int B, int N, int R) {
   if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);

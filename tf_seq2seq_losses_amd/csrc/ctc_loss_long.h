@@ -17,4 +17,13 @@ constexpr int LONG_LOSS_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h
 hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
                          char *ws, hipStream_t st);
 
+// ctc_amd_long_label_posterior: the checkpointed schedule above (P.L) with the posterior stage in the row stage's place.  Per time
+// block d < P.L.J one launch writes label_posterior (nullptr: not wanted) and blank_posterior of the block's frames and carries the
+// per-position sums and the peak in the workspace; the stage of block 0 writes duration / expected_frame and peak_posterior /
+// peak_frame (each pair both or neither).  T == 0: the finish kernel and, for the [B][U] outputs, one launch.  `ws` holds P.total
+// bytes and may hold anything.
+hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss, float *label_posterior,
+                                    float *blank_posterior, float *duration, float *expected_frame, float *peak_posterior,
+                                    int *peak_frame, char *ws, hipStream_t st);
+
 }  // namespace ctc

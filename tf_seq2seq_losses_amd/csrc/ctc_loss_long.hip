@@ -25,7 +25,9 @@
 // a row buffer per tile (the checkpoints), MODE 3 runs a tile again from its checkpoint on the backward sweep and saves its rows into
 // a ring of min(K, J) time blocks, the beta tile and the row stage read the ring, and the row stage runs per time block.  Where a
 // checkpoint and a saved row live is long_loss_ckpt_index / long_loss_row_index (ctc_loss_long_plan.h) in both layouts.
-// Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all three; nothing unwritten is read.  No workgroup
+// ctc_amd_long_label_posterior is that schedule with the posterior stage in the row stage's place: the ring
+// rows of a time block become label_posterior / blank_posterior rows and, carried from block to block, the per-position sums and peaks.
+// Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all of them; nothing unwritten is read.  No workgroup
 // waits for another: no flags, no cooperative launch, no floating-point atomics, vector stores only, one writer per element.
 #include "ctc_loss_long.h"
 
@@ -626,6 +628,148 @@ __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_ckpt_kernel(cons
   loss_long_row<KIND, true>(p, w, K, TF, t0, nt, d_loss, grad);
 }
 
+// ---- the posterior stage of ctc_amd_long_label_posterior: the ring rows of one time block, read a second
+// way.  One launch, two kinds of wavefront, LONG_POST_WAVES to a workgroup; neither waits for the other, both only read the ring ----
+struct LongPostOut {
+  float *post, *blk;       // label_posterior [B][T][U] (nullptr: not wanted), blank_posterior [B][T]
+  float *dur, *exf, *peak; // [B][U] each; dur and exf both or neither, peak and peak_frame both or neither
+  int *peak_frame;
+  double2 *acc;            // workspace, [B][U]: (sum p, sum t p) over the frames met so far, descending
+  float2 *pk;              // workspace, [B][U]: the running peak and (as an int's bits) its frame
+};
+
+// what a position's slot of a ring row says: the value label_posterior[b, t, i] takes
+template <int KIND>
+__device__ __forceinline__ float ll_post_value(const float2 pq, bool wc) {
+  return KIND == 1 && wc ? pq.x + pq.y : pq.x;
+}
+
+// Workgroups 0 .. row_groups - 1, one wavefront per row (b, t) of time block d (t = d * TF .. d * TF + nt - 1): the dense run of U
+// floats (when wanted) and blank_posterior[b, t], the blank's share summed in the row stage's order.  The workgroups behind them,
+// one wavefront per (b, 64 positions), a lane a position: the block's frames downwards into (sum p, sum t p, peak, its frame),
+// carried in the workspace from the stage of time block J - 1 (`first`: starts from nothing) to that of block 0 (`last`: rounds and
+// writes the four [B][U] outputs).  nt == 0 (T == 0): nothing but that.
+template <int KIND>
+__global__ __launch_bounds__(64 * LONG_POST_WAVES) void loss_long_post_kernel(const Problem p, const LongLossWs w, const LongPostOut o, int K, int TF,
+                                                                              int d, int nt, unsigned row_groups, int first, int last) {
+  constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
+  constexpr size_t ROWB = (size_t)long_loss_row_doubles(KIND) * 8;
+  __shared__ __attribute__((aligned(16))) float stage_all[LONG_POST_WAVES][UB];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int U = p.U, t0 = d * TF;
+  const size_t kstride = long_loss_row_stride(1, K, p.T, TF);
+
+  if (blockIdx.x < row_groups) {
+    const long rowi = (long)blockIdx.x * LONG_POST_WAVES + wv;
+    if (rowi >= (long)p.B * nt) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
+    float *const st = stage_all[wv];
+    const int b = (int)(rowi / nt), t = t0 + (int)(rowi % nt);
+    const int Tb = frame_count(p, b);
+    const int L = label_count(p, b);
+    const bool live = t < Tb && w.flag[b] != 0;  // (feasible: L <= U)
+    float *const out = o.post ? o.post + ((size_t)b * p.T + t) * (size_t)U : nullptr;
+    const bool vec = (U & 3) == 0 && (reinterpret_cast<uintptr_t>(o.post) & 15) == 0;
+    const char *const rows = reinterpret_cast<const char *>(w.rows) + long_loss_row_index(1, b, K, 0, p.T, t, TF) * ROWB;
+    const int32_t *const lab = label_row(p, b);
+    float blk = 0.f;  // the blank's share, lane-wise partial sums in a fixed order
+    for (int k = 0; k < K; ++k) {
+      const int u0 = k * UB;
+      const int nu = U - u0 < UB ? U - u0 : UB;  // positions of the block that have a column
+      // a padded frame, an infeasible utterance, a block beyond the labels, a tile that did not run: exactly zero
+      int n = 0;
+      const bool ran = live && (k == 0 || u0 < L) && long_loss_tile_active(Tb, L, k, d, TF);
+      if (ran) n = L - u0 < UB ? L - u0 : UB;
+      const char *const r = rows + (size_t)k * kstride * ROWB;
+      for (int i = lane; i < n; i += 64) {
+        const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+        const bool wc = label_at(p, lab, u0 + i) == LONG_LOSS_WILDCARD;
+        if (!(KIND == 1 && wc)) blk += pq.y;
+        if (out) st[i] = ll_post_value<KIND>(pq, wc);
+      }
+      if (ran && k == 0 && lane == 0) blk += *reinterpret_cast<const float *>(r + (size_t)UB * SLOT);  // the start state
+      if (out) {
+        wave_lds_fence();
+        if (vec) {  // (U and u0 multiples of 4: so is nu)
+          for (int c = lane * 4; c < nu; c += 256) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c + 3 < n) {
+              v = *reinterpret_cast<const float4 *>(st + c);
+            } else if (c < n) {
+              v.x = st[c];
+              if (c + 1 < n) v.y = st[c + 1];
+              if (c + 2 < n) v.z = st[c + 2];
+            }
+            *reinterpret_cast<float4 *>(out + u0 + c) = v;
+          }
+        } else {
+          for (int i = lane; i < nu; i += 64) out[u0 + i] = i < n ? st[i] : 0.f;
+        }
+        wave_lds_fence();
+      }
+    }
+    blk = wave_sum(blk);
+    if (lane == 0) o.blk[(size_t)b * p.T + t] = blk;
+    return;
+  }
+
+  // the per-position statistics
+  const int groups = (U + 63) / 64;
+  const long wi = (long)(blockIdx.x - row_groups) * LONG_POST_WAVES + wv;
+  if (wi >= (long)p.B * groups) return;
+  const int b = (int)(wi / groups), i = (int)(wi % groups) * 64 + lane;
+  if (i >= U) return;
+  const int Tb = frame_count(p, b);
+  const int L = label_count(p, b);
+  const bool mine = w.flag[b] != 0 && i < L;  // (feasible: L <= U)
+  const size_t at = (size_t)b * U + i;
+  const bool stats = o.dur != nullptr, peaks = o.peak != nullptr;
+  double sd = 0.0, sm = 0.0;
+  float pk = -1.f;  // (below every posterior)
+  int pf = -1;
+  if (!first) {
+    if (stats) { const double2 a = o.acc[at]; sd = a.x; sm = a.y; }
+    if (peaks) { const float2 q = o.pk[at]; pk = q.x; pf = __float_as_int(q.y); }
+  }
+  const int k = i / UB;
+  // (a tile that did not run: its posteriors are exactly zero; the sums keep their bits, and a peak of zero is settled below)
+  if (mine && nt > 0 && long_loss_tile_active(Tb, L, k, d, TF)) {
+    const bool wc = label_at(p, label_row(p, b), i) == LONG_LOSS_WILDCARD;
+    const int t_hi = Tb - t0 < nt ? Tb : t0 + nt;  // one past the block's last frame of this utterance (> t0: the tile runs)
+    const char *const r = reinterpret_cast<const char *>(w.rows) + long_loss_row_index(1, b, K, k, p.T, t0, TF) * ROWB + (size_t)(i - k * UB) * SLOT;
+    auto take = [&](int t, const float2 pq) {  // strictly in descending frame order
+      const float v = ll_post_value<KIND>(pq, wc);
+      sd += (double)v;
+      sm += (double)t * (double)v;  // (exact in float64: fused or not, the same bits)
+      if (v >= pk) { pk = v; pf = t; }  // (descending: the lowest frame that attains the peak stays)
+    };
+    int t = t_hi - 1;
+    for (; t - 7 >= t0; t -= 8) {  // eight loads in flight, the adds in order
+      float2 q[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) q[u] = *reinterpret_cast<const float2 *>(r + (size_t)(t - u - t0) * ROWB);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) take(t - u, q[u]);
+    }
+    for (; t >= t0; --t) take(t, *reinterpret_cast<const float2 *>(r + (size_t)(t - t0) * ROWB));
+  }
+  if (!last) {
+    if (stats) o.acc[at] = make_double2(sd, sm);
+    if (peaks) o.pk[at] = make_float2(pk, __int_as_float(pf));
+    return;
+  }
+  if (stats) {
+    o.dur[at] = mine ? (float)sd : 0.f;
+    o.exf[at] = mine && sd > 0.0 ? (float)(sm / sd) : -1.f;
+  }
+  if (peaks) {
+    // every posterior of a position zero (or none above it in a tile that ran): the peak is 0, first attained at frame 0
+    if (mine && !(pk > 0.f)) { pk = 0.f; pf = Tb > 0 ? 0 : -1; }
+    o.peak[at] = mine ? pk : 0.f;
+    o.peak_frame[at] = mine ? pf : -1;
+  }
+}
+
 template <int KIND>
 hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
                     const LongLossWs &w, hipStream_t st) {
@@ -658,7 +802,16 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
 // diagonal d - 1 (ctc_loss_long_plan.h), behind this row stage on the stream.
 template <int KIND>
 hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
-                         const LongLossWs &w, hipStream_t st) {
+                         const LongLossWs &w, hipStream_t st, const LongPostOut *post = nullptr) {
+  // post: ctc_amd_long_label_posterior, the posterior stage in the row stage's place (grad is nullptr)
+  const bool per_label = post && p.U > 0 && (post->dur || post->peak);
+  const unsigned stat_groups = per_label ? (unsigned)long_post_stat_groups(p.B, p.U) : 0u;
+  auto post_stage = [&](int d, int nt) {
+    const unsigned row_groups = (unsigned)long_post_row_groups(p.B, nt);
+    if (row_groups + stat_groups == 0) return;
+    hipLaunchKernelGGL(loss_long_post_kernel<KIND>, dim3(row_groups + stat_groups), dim3(64 * LONG_POST_WAVES), 0, st, p, w, *post, P.K, P.TF, d,
+                       nt, row_groups, d == P.J - 1 ? 1 : 0, d == 0 ? 1 : 0);
+  };
   if (p.T > 0) {
     for (int d = 0; d < P.launches; ++d) {
       int k_lo, count;
@@ -668,7 +821,10 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
     }
   }
   hipLaunchKernelGGL(loss_long_finish_ckpt_kernel<KIND>, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, st, p, w, P.K, P.TF, loss);
-  if (p.T == 0) return hipGetLastError();
+  if (p.T == 0) {
+    if (post) post_stage(0, 0);  // (J == 1: the first and the last stage; nothing but the [B][U] outputs)
+    return hipGetLastError();
+  }
   for (int e = 0; e < P.launches; ++e) {
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
@@ -677,6 +833,7 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
     hipLaunchKernelGGL((loss_long_beta_kernel<KIND, true>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
     if (d < P.J) {
       const int t0 = d * P.TF, nt = p.T - t0 < P.TF ? p.T - t0 : P.TF;
+      if (post) { post_stage(d, nt); continue; }
       const unsigned blocks = (unsigned)(((long)p.B * nt + LLG_WAVES - 1) / LLG_WAVES);
       hipLaunchKernelGGL(loss_long_row_ckpt_kernel<KIND>, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, t0, nt, d_loss, grad);
     }
@@ -684,11 +841,7 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
   return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
-                         char *ws, hipStream_t st) {
-  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad)) return hipErrorInvalidValue;
+LongLossWs long_loss_ws(char *ws, const LongLossPlan &P) {
   LongLossWs w;
   w.col = reinterpret_cast<double *>(ws + P.off_col);
   w.row = reinterpret_cast<double *>(ws + P.off_row);
@@ -698,9 +851,32 @@ hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard
   w.colb = reinterpret_cast<double *>(ws + P.off_colb);
   w.rowb = reinterpret_cast<double *>(ws + P.off_rowb);
   w.rows = reinterpret_cast<double *>(ws + P.off_rows);
+  return w;
+}
+
+}  // namespace
+
+hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
+                         char *ws, hipStream_t st) {
+  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad)) return hipErrorInvalidValue;
+  const LongLossWs w = long_loss_ws(ws, P);
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
   if (P.ckpt) return p.kind == 0 ? run_kind_ckpt<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind_ckpt<1>(p, P, w2, d_loss, loss, grad, w, st);
   return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, st);
+}
+
+hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss, float *label_posterior,
+                                    float *blank_posterior, float *duration, float *expected_frame, float *peak_posterior,
+                                    int *peak_frame, char *ws, hipStream_t st) {
+  if (p.kind < 0 || p.kind > 1 || !P.L.ckpt || !duration != !expected_frame || !peak_posterior != !peak_frame) return hipErrorInvalidValue;
+  const LongLossWs w = long_loss_ws(ws, P.L);
+  LongPostOut o;
+  o.post = label_posterior; o.blk = blank_posterior;
+  o.dur = duration; o.exf = expected_frame; o.peak = peak_posterior; o.peak_frame = peak_frame;
+  o.acc = reinterpret_cast<double2 *>(ws + P.off_acc);
+  o.pk = reinterpret_cast<float2 *>(ws + P.off_peak);
+  const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  return p.kind == 0 ? run_kind_ckpt<0>(p, P.L, w2, nullptr, loss, nullptr, w, st, &o) : run_kind_ckpt<1>(p, P.L, w2, nullptr, loss, nullptr, w, st, &o);
 }
 
 }  // namespace ctc

@@ -139,6 +139,32 @@ inline bool long_loss_ckpt_plan(int kind, int B, int T, int U, int frames_per_ti
   return true;
 }
 
+// The plan of the long-form label posteriors (ctc_amd_long_label_posterior): the checkpointed gradient's,
+// schedule and all, with the posterior stage in the row stage's place, and behind it what that stage carries from time block to time
+// block per (utterance, label position): the float64 sums (sum p, sum t p) and the running peak with its frame.
+struct LongPostPlan {
+  LongLossPlan L;            // long_loss_ckpt_plan(want_grad = 1)
+  size_t off_acc, off_peak;  // [B][U] pairs of float64; [B][U] pairs (float32 peak, int32 frame)
+  size_t total;
+};
+// wavefronts of one launch of the posterior stage: first one per row (b, t) of a time block of nt frames, then one per (utterance,
+// 64 label positions); LONG_POST_WAVES to a workgroup, each part rounded up to whole workgroups
+constexpr int LONG_POST_WAVES = 4;
+CTC_LL_HD size_t long_post_row_groups(int B, int nt) { return ((size_t)B * (size_t)nt + LONG_POST_WAVES - 1) / LONG_POST_WAVES; }
+CTC_LL_HD size_t long_post_stat_groups(int B, int U) { return ((size_t)B * (((size_t)U + 63) / 64) + LONG_POST_WAVES - 1) / LONG_POST_WAVES; }
+// false: what long_loss_ckpt_plan refuses with a gradient, or a posterior stage of more than 2^31 - 1 workgroups
+inline bool long_post_plan(int kind, int B, int T, int U, int frames_per_tile, LongPostPlan *out) {
+  LongPostPlan P;
+  if (!long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, 1, &P.L)) return false;
+  if (long_post_row_groups(B, T < P.L.TF ? T : P.L.TF) + long_post_stat_groups(B, U) > 2147483647u) return false;
+  size_t o = P.L.total;
+  P.off_acc = o;  o = long_r256(o + (size_t)B * (size_t)U * 16);
+  P.off_peak = o; o = long_r256(o + (size_t)B * (size_t)U * 8);
+  P.total = o;
+  *out = P;
+  return true;
+}
+
 // forward launch d of 0 .. launches - 1 runs the tiles (k, d - k), k = *k_lo .. *k_lo + *count - 1, of every utterance: tile (k, j)
 // after (k - 1, j), (k, j - 1) and (0, j)
 inline void long_loss_forward_diagonal(const LongLossPlan &P, int d, int *k_lo, int *count) {

@@ -694,6 +694,81 @@ def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_len
 
 
 # --------------------------------------------------------------------------------------------------
+# long-form label posteriors (soft timestamps of transcripts beyond 1024 labels): an extension, no counterpart in the reference
+# --------------------------------------------------------------------------------------------------
+class CtcLongLabelPosterior(NamedTuple):
+    """loss, label_posterior, blank_posterior, duration, expected_frame: as CtcLabelPosterior, for up to 65536 label positions;
+    label_posterior is None when the call ran with dense=False (the [batch, max_length, U] matrix is then never allocated).
+    duration and expected_frame are float64 reductions of the float32 label_posterior values, summed sequentially from the last
+    frame down to frame 0 and rounded once: a host reduction of the dense matrix in that order gives the same bits;
+    peak_posterior [batch, U] float32: the largest label_posterior of every position over the frames, the per-label confidence that
+    needs no dense matrix; peak_frame [batch, U] int32: the lowest frame that attains it.  Positions from label_length on and
+    infeasible samples have 0 in peak_posterior and -1 in peak_frame."""
+    loss: torch.Tensor
+    label_posterior: Optional[torch.Tensor]
+    blank_posterior: torch.Tensor
+    duration: torch.Tensor
+    expected_frame: torch.Tensor
+    peak_posterior: torch.Tensor
+    peak_frame: torch.Tensor
+
+
+def _long_label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
+                          frames_per_tile=None, max_label_length=None, dense=True) -> CtcLongLabelPosterior:
+    x = _as_tensor(x)
+    labels = _as_tensor(labels, torch.int32)
+    if max_label_length is None:
+        max_label_length = _host_max(label_length)
+    label_length = _as_tensor(label_length, torch.int32)
+    logit_length = _as_tensor(logit_length, torch.int32)
+    _verify_inputs(labels, x, label_length, logit_length)
+    weight = float(wildcard_log_weight)
+    if not (weight <= 0.0) or weight == float("-inf"):
+        raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
+    U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    tf = 0 if frames_per_tile is None else int(frames_per_tile)
+    with torch.no_grad():  # forward only: the result is detached
+        return CtcLongLabelPosterior(*ops.long_label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
+                                                               _blank(blank_index), U, wildcard_log_weight=weight, frames_per_tile=tf,
+                                                               dense=bool(dense)))
+
+
+def classic_ctc_long_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                     blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                     frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
+                                     dense: bool = True) -> CtcLongLabelPosterior:
+    """The soft alignment of a long recording on the classic lattice: classic_ctc_label_posterior for transcripts of up to 65536
+    labels, on the tiled lattice and from the workspace of classic_ctc_long_loss(checkpoint=True) (`frames_per_tile`: None for 128,
+    otherwise a positive multiple of 4; no output depends on it).  Which stretches of a long alignment to trust: where
+    classic_ctc_long_alignment gives the single best path, this gives per label position the probability of every frame, the
+    expected duration, the soft timestamp, and the peak posterior with its frame.  dense=False leaves the
+    [batch, max_length, U] float32 matrix out (36 GB for an hour of audio with 50 000 labels) and returns None in its place; every
+    other output keeps its bits, the per-label statistics coming straight from the sweep.  Labels may contain WILDCARD (-2).
+    Arguments as classic_ctc_long_loss; returns CtcLongLabelPosterior on the logits' device, not differentiable."""
+    return _long_label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense)
+
+
+def simplified_ctc_long_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                        blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                        frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
+                                        dense: bool = True) -> CtcLongLabelPosterior:
+    """The same on the simplified lattice (label_posterior as in simplified_ctc_label_posterior).  Same arguments and return value
+    as classic_ctc_long_label_posterior."""
+    return _long_label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense)
+
+
+def ctc_long_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                           wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                           max_label_length: Optional[int] = None, dense: bool = True) -> CtcLongLabelPosterior:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense)
+
+
+# --------------------------------------------------------------------------------------------------
 # greedy decoding: an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 class CtcDecoding(NamedTuple):

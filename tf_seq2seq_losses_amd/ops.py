@@ -803,6 +803,46 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     return loss, post, blk, dur, exf
 
 
+def long_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                         logit_length: torch.Tensor, blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0,
+                         frames_per_tile: int = 0, dense: bool = True, want_stats: bool = True, want_peak: bool = True):
+    """(loss[B], label_posterior[B, T, U] or None, blank_posterior[B, T], duration[B, U], expected_frame[B, U], peak_posterior[B, U]
+    float32, peak_frame[B, U] int32): label_posterior for up to _lib.LONG_MAX_U label positions, on the tiled lattice and from the
+    workspace of long_wildcard_loss_grad(checkpoint=True) (ctc_amd_long_label_posterior).  dense=False returns None for the
+    [B, T, U] matrix, which is then neither allocated nor written; every other output keeps its bits.  peak_posterior is
+    max_t label_posterior and peak_frame the lowest frame that attains it (0 / -1 from label_length on).  want_stats=False /
+    want_peak=False return None for the pair.  frames_per_tile as in long_wildcard_loss_grad; no output depends on it.  Every element
+    of every output is written.  Does not synchronise."""
+    if labels.dim() != 2 or label_length.dim() != 1:
+        raise ValueError(f"long_label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args("long_label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
+                                                                 logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    key = ("long_label_posterior", kind, B, T, V, U, int(frames_per_tile))
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.long_label_posterior_workspace_bytes(kind, B, T, V, U, int(frames_per_tile))
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    post = torch.empty((B, T, U), dtype=torch.float32, device=dev) if dense else None
+    blk = torch.empty((B, T), dtype=torch.float32, device=dev)
+    dur = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    exf = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    peak = torch.empty((B, U), dtype=torch.float32, device=dev) if want_peak else None
+    pfr = torch.empty((B, U), dtype=torch.int32, device=dev) if want_peak else None
+    if B == 0:
+        return loss, post, blk, dur, exf, peak, pfr
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_long_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                              _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                                              int(frames_per_tile), _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(peak),
+                                              _ptr(pfr), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_long_label_posterior")
+    return loss, post, blk, dur, exf, peak, pfr
+
+
 def nbest_best_path(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None):
     """(score[B, N] float32, tokens[B, N, T] int32, label_index[B, N, T] int32, first_frame[B, N, U] int32, last_frame[B, N, U] int32):
