@@ -1145,6 +1145,50 @@ int ctc_amd_long_label_posterior(int kind, int wrt,
                                  float *peak_posterior /* [B][U], may be NULL */, int32_t *peak_frame /* [B][U], may be NULL */,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Edit counts (added under ABI v6: two new entry points, nothing existing changed): what an error-rate report prints -- distance,
+ * substitutions, insertions, deletions -- of every hypothesis against its utterance's reference, for references of up to
+ * CTC_AMD_LONG_MAX_U tokens.  ctc_amd_edit_distance keeps its limit of CTC_AMD_MAX_U and its single number.
+ * Rows of the table are hypothesis tokens (i = 0 .. h), columns reference tokens (j = 0 .. r).  A move up, (i - 1, j) -> (i, j), is
+ * an insertion (a hypothesis token with no reference token); a move left, (i, j - 1) -> (i, j), a deletion; a diagonal move a hit
+ * if the two tokens are equal and a substitution otherwise.  Every cell carries the triple (d, S, I) -- distance, substitutions,
+ * insertions --, a move adds (1, 0, 1), (1, 0, 0), (0, 0, 0) or (1, 1, 0), and a cell keeps the LEXICOGRAPHIC MINIMUM of its three
+ * candidates; the boundaries are (j, 0, 0) in row 0 and (i, 0, i) in column 0.  Addition is monotone in that order, so the result is
+ * the lexicographic minimum of (d, S, I) over all alignments: among the alignments of minimum distance the one with the fewest
+ * substitutions (the most hits), then the fewest insertions.  It names no path, so it depends on no tie rule of a back-trace.
+ *   counts[b, n] = (d, S, I, d - S - I)                                          int32 [B][N][4], exact
+ *   hits = h - S - I = r - S - deletions.   hyp (0, 1) against ref (1, 0): (2, 0, 1, 1), one hit.
+ * Layouts, length clamping and token semantics are those of ctc_amd_edit_distance: tokens at and beyond the lengths are not read;
+ * h == 0 gives (r, 0, 0, r) and r == 0 gives (h, 0, h, 0).
+ * R bounds every reference length, 0 <= R <= CTC_AMD_LONG_MAX_U: an utterance with r > R gets -1 four times for all its hypotheses
+ * and changes nothing else.  0 <= hyp_stride <= CTC_AMD_EDIT_COUNTS_MAX_STRIDE.  rows_per_tile is 0 (the default, 256) or a
+ * positive multiple of CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE: a tile of the table is 1024 reference tokens x rows_per_tile hypothesis
+ * tokens, and the result does not depend on it.  N >= 1, B * N < 2^31, and no launch grid beyond 2^31 - 1 workgroups
+ * (B * N * min(K, J) / 4).  B == 0 returns CTC_AMD_OK without a launch.
+ * Validation before any launch (CTC_AMD_EINVAL, ctc_amd_last_error), in the order of ctc_amd_edit_distance: negative B or R, R
+ * beyond its limit, N < 1, the product limit, negative strides, hyp_stride beyond its limit, rows_per_tile, the launch grid, null
+ * lengths, null hyp / ref (allowed when their stride is 0), null counts; then a null or too small workspace (CTC_AMD_EWORKSPACE).
+ * Every element of `counts` has one writer; counts[b, n] is the same whatever N, rows_per_tile and the other hypotheses are, wherever
+ * in the list it stands, and on every run.
+ * Workspace (8-byte aligned; may hold anything on entry), with K = max(1, ceil(R / 1024)):
+ *   ctc_amd_edit_counts_workspace_bytes = r256(8 * B * N * (K - 1) * hyp_stride)   the last column of every column block but the last
+ *                                       + r256(8 * B * N * K * 1024)               the bottom row of the tile above, per column block
+ * in packed words d * 2^42 + S * 2^21 + I, r256 rounding up to a multiple of 256.  B = 1, N = 1, R = hyp_stride = 65 536: 33 554 432
+ * bytes.
+ * K + J - 1 launches, J = max(1, ceil(hyp_stride / rows_per_tile)): one per anti-diagonal of tiles, one wavefront per tile, tiles
+ * wholly beyond a pair's own (h, r) return at once; R <= 512 runs one column block with 1, 2, 4 or 8 reference tokens per lane in
+ * place of 16.  Asynchronous on `stream`, capturable (a serial chain of launches), no allocation, copy or synchronisation; the
+ * number of launches depends on R, hyp_stride and rows_per_tile alone.
+ */
+#define CTC_AMD_EDIT_COUNTS_MAX_STRIDE 1048576  /* 2^20: d, S, I each fit 21 bits */
+#define CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE 64
+int ctc_amd_edit_counts_workspace_bytes(int B, int N, int R, int hyp_stride, int rows_per_tile, size_t *out_bytes /*host*/);
+int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length /* [B][N] */,
+                        const int32_t *ref, int ref_stride, const int32_t *ref_length /* [B] */,
+                        int B, int N, int R, int rows_per_tile /* 0: default */,
+                        int32_t *counts /* [B][N][4]: distance, substitutions, insertions, deletions */,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

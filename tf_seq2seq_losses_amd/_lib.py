@@ -118,6 +118,10 @@ SIGNATURES = {
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
                                        _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
+    "ctc_amd_edit_counts_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R, hyp_stride, rows_per_tile
+    "ctc_amd_edit_counts": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
+                                     _c_int, _c_int, _c_int, _c_int, _c_void_p,                   # B, N, R, rows_per_tile, counts
+                                     _c_void_p, _c_size_t, _c_void_p]),                           # ws, bytes, stream
     "ctc_amd_prefix_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t), ctypes.POINTER(_c_size_t)]),  # B, T, V, N, rows, state
     "ctc_amd_prefix_rows": (_c_int, [_c_void_p, _c_int, _c_int64, _c_int64, _c_void_p, _c_int, _c_int, _c_int,  # logits, dtype, stride_b, stride_t, logit_length, B, T, V
                                      _c_void_p, _c_size_t, _c_void_p]),                                      # rows, bytes, stream
@@ -289,6 +293,12 @@ def long_label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: i
 def edit_distance_workspace_bytes(B: int, N: int, R: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_edit_distance_workspace_bytes(B, N, R, ctypes.byref(out)), "ctc_amd_edit_distance_workspace_bytes")
+    return int(out.value)
+
+
+def edit_counts_workspace_bytes(B: int, N: int, R: int, hyp_stride: int, rows_per_tile: int = 0) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_edit_counts_workspace_bytes(B, N, R, hyp_stride, rows_per_tile, ctypes.byref(out)), "ctc_amd_edit_counts_workspace_bytes")
     return int(out.value)
 
 

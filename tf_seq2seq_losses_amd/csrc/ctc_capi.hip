@@ -10,6 +10,7 @@
 #include "ctc_amd.h"
 #include "ctc_beam.h"
 #include "ctc_common.h"
+#include "ctc_edit_long_plan.h"
 #include "ctc_hvp_fused.h"
 #include "ctc_launch.h"
 #include "ctc_loss_long.h"
@@ -1098,6 +1099,57 @@ int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp
   if (!distance) return fail(CTC_AMD_EINVAL, "null distance pointer");
   CTC_TRY(ctc::run_edit_distance(hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length, B, N, R, distance,
                                  static_cast<hipStream_t>(stream)), "edit distance launch");
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::EDIT_LONG_MAX_R == CTC_AMD_LONG_MAX_U && ctc::EDIT_LONG_MAX_STRIDE == CTC_AMD_EDIT_COUNTS_MAX_STRIDE &&
+              ctc::EDIT_LONG_ROWS_MULTIPLE == CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE, "include/ctc_amd.h and ctc_edit_long_plan.h disagree");
+
+// what ctc_amd_edit_counts and its size query take as a shape, and the plan of a valid one
+int check_edit_counts(int B, int N, int R, int hyp_stride, int rows_per_tile, ctc::EditCountsPlan *plan) {
+  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
+  if (R > CTC_AMD_LONG_MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, CTC_AMD_LONG_MAX_U);
+  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
+  if (hyp_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d", hyp_stride);
+  if (hyp_stride > CTC_AMD_EDIT_COUNTS_MAX_STRIDE)
+    return fail(CTC_AMD_EINVAL, "hyp_stride=%d exceeds the supported maximum %d", hyp_stride, CTC_AMD_EDIT_COUNTS_MAX_STRIDE);
+  if (rows_per_tile < 0 || rows_per_tile % CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE != 0)
+    return fail(CTC_AMD_EINVAL, "rows_per_tile=%d is neither 0 nor a positive multiple of %d", rows_per_tile, CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE);
+  if (!ctc::edit_counts_plan(B, N, R, hyp_stride, rows_per_tile, plan))
+    return fail(CTC_AMD_EINVAL, "B * N = %lld pairs are too many for the launch grid at R=%d hyp_stride=%d rows_per_tile=%d", (long long)B * N,
+                R, hyp_stride, rows_per_tile);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_edit_counts_workspace_bytes(int B, int N, int R, int hyp_stride, int rows_per_tile, size_t *out_bytes) {
+  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  ctc::EditCountsPlan plan;
+  if (int rc = check_edit_counts(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+// Checked before any launch, in the order of ctc_amd_edit_distance: the sizes and R, B == 0, then N and the number of pairs, the
+// strides, rows_per_tile and the launch grid, the pointers, the workspace.
+int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length, const int32_t *ref, int ref_stride,
+                        const int32_t *ref_length, int B, int N, int R, int rows_per_tile, int32_t *counts, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
+  if (R > CTC_AMD_LONG_MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, CTC_AMD_LONG_MAX_U);
+  if (B == 0) return CTC_AMD_OK;
+  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
+  if (hyp_stride < 0 || ref_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d ref_stride=%d", hyp_stride, ref_stride);
+  ctc::EditCountsPlan plan;
+  if (int rc = check_edit_counts(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
+  if (!hyp_length || !ref_length) return fail(CTC_AMD_EINVAL, "null length pointer");
+  if (hyp_stride > 0 && !hyp) return fail(CTC_AMD_EINVAL, "null hyp pointer");
+  if (ref_stride > 0 && !ref) return fail(CTC_AMD_EINVAL, "null ref pointer");
+  if (!counts) return fail(CTC_AMD_EINVAL, "null counts pointer");
+  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  CTC_TRY(ctc::run_edit_counts(hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length, N, plan, counts, static_cast<char *>(workspace),
+                               static_cast<hipStream_t>(stream)), "edit counts launch");
   return CTC_AMD_OK;
 }
 

@@ -60,6 +60,13 @@ hipError_t run_nbest_grad(const Problem &p, int N, const float *weight, float *l
 hipError_t run_edit_distance(const int *hyp, int hyp_stride, const int *hyp_length, const int *ref, int ref_stride, const int *ref_length,
                              int B, int N, int R, int *distance, hipStream_t st);
 
+// ctc_edit_long.hip: (distance, substitutions, insertions, deletions) of every pair for references of up to 65536 tokens; the table
+// is tiled over blocks of 1024 reference tokens x plan.RT hypothesis tokens, one launch per anti-diagonal of tiles; the workspace
+// holds the tiles' boundary rows and columns (ctc_edit_long_plan.h)
+struct EditCountsPlan;
+hipError_t run_edit_counts(const int *hyp, int hyp_stride, const int *hyp_length, const int *ref, int ref_stride, const int *ref_length,
+                           int N, const EditCountsPlan &plan, int *counts, char *ws, hipStream_t st);
+
 #ifdef CTC_WIDE_EXPERIMENT
 // experiments/wide/ctc_wide.hip: parked outside the product tree, built by experiments/wide/build_wide_variant.sh only
 extern int g_wide_diag;  // timing diagnostics (results are then meaningless)

@@ -1234,6 +1234,79 @@ def ctc_edit_distance(hypotheses: TensorLike, hypothesis_length: TensorLike, ref
         return CtcEditDistance(distance, rate)
 
 
+class CtcEditCounts(NamedTuple):
+    """distance, substitutions, insertions, deletions, hits [batch, nbest] int32: the lexicographic minimum of (distance,
+    substitutions, insertions) over all alignments of a hypothesis with its utterance's reference -- among the alignments of
+    minimum distance the one with the most hits, then the fewest insertions --, deletions = distance - substitutions - insertions
+    and hits = hypothesis length - substitutions - insertions; all -1 where masked or where the reference is longer than the
+    reference tensor is wide;
+    error_rate [batch, nbest] float32: distance / max(reference_length, 1), NaN where masked.
+    All are [batch] when the hypotheses were passed as [batch, width]."""
+    distance: torch.Tensor
+    substitutions: torch.Tensor
+    insertions: torch.Tensor
+    deletions: torch.Tensor
+    hits: torch.Tensor
+    error_rate: torch.Tensor
+
+
+def ctc_edit_counts(hypotheses: TensorLike, hypothesis_length: TensorLike, references: TensorLike, reference_length: TensorLike, *,
+                    hypothesis_mask: Optional[TensorLike] = None, rows_per_tile: Optional[int] = None) -> CtcEditCounts:
+    """What an error-rate report prints: distance, substitutions, insertions, deletions and hits of every hypothesis against the
+    reference transcript of its utterance, on the device and without a synchronisation, for references of up to 65536 tokens and
+    hypotheses of up to 2^20 (ctc_edit_distance stops at 1024 and returns the distance alone).  Tokens are any int32 values
+    compared for equality.
+
+    Args:
+        hypotheses:        [batch, nbest, width] int32 -- a CtcBeamDecoding's `labels` as it stands (padding is not read) -- or
+                           [batch, width] with a [batch] length: one hypothesis per utterance, e.g. a CtcDecoding's `labels`; the
+                           result is then [batch].
+        hypothesis_length: [batch, nbest] (or [batch]) int32
+        references:        [batch, max_label_length] int32, at most 65536 wide
+        reference_length:  [batch] int32
+        hypothesis_mask:   (keyword only) [batch, nbest] (or [batch]) bool; where False the five counts are -1 and the error rate
+                           NaN -- pass `isfinite(score)` for the missing hypotheses of a CtcBeamDecoding.
+        rows_per_tile:     (keyword only) hypothesis tokens per tile of the table, a multiple of 64 (None: the library's default);
+                           the result does not depend on it.
+    Returns: CtcEditCounts(distance, substitutions, insertions, deletions, hits, error_rate), not differentiable."""
+    hyp = _as_tensor(hypotheses, torch.int32)
+    hyp_length = _as_tensor(hypothesis_length, torch.int32)
+    ref = _as_tensor(references, torch.int32)
+    ref_length = _as_tensor(reference_length, torch.int32)
+    single = hyp.dim() == 2
+    if single:
+        assert hyp_length.dim() == 1
+        hyp, hyp_length = hyp[:, None, :], hyp_length[:, None]
+    assert hyp.dim() == 3
+    assert hyp_length.dim() == 2
+    assert ref.dim() == 2
+    assert ref_length.dim() == 1
+    assert hyp.shape[0] == hyp_length.shape[0] == ref.shape[0] == ref_length.shape[0]
+    assert hyp.shape[1] == hyp_length.shape[1]
+    with torch.no_grad():
+        counts = ops.edit_counts(hyp, hyp_length, ref, ref_length, rows_per_tile=rows_per_tile)
+        dev = counts.device
+        distance, subs, ins, dels = counts.unbind(-1)
+        # (the lengths as the kernel reads them: clamped to the tensors' widths)
+        h = hyp_length.to(device=dev).clamp(0, int(hyp.shape[2]))
+        ref_length = ref_length.to(device=dev)
+        valid = distance >= 0
+        hits = torch.where(valid, h - subs - ins, torch.full_like(distance, -1))
+        rate = distance.to(torch.float32) / ref_length.clamp(1, max(int(ref.shape[1]), 1)).to(torch.float32)[:, None]
+        fields = [distance, subs, ins, dels, hits]
+        if hypothesis_mask is not None:
+            mask = _as_tensor(hypothesis_mask).to(device=dev, dtype=torch.bool)
+            if single:
+                mask = mask[:, None]
+            assert tuple(mask.shape) == tuple(distance.shape)
+            fields = [torch.where(mask, f, torch.full_like(f, -1)) for f in fields]
+            rate = torch.where(mask, rate, torch.full_like(rate, float("nan")))
+        fields = [f.contiguous() for f in fields]
+        if single:
+            fields, rate = [f[:, 0] for f in fields], rate[:, 0]
+        return CtcEditCounts(*fields, rate)
+
+
 class CtcMwerLoss(NamedTuple):
     """loss [batch] float32: the expected risk of the N-best list relative to its mean risk (differentiable);
     risk [batch, nbest] float32: the edit distance of every hypothesis to the labels (a constant);

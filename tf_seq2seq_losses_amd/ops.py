@@ -906,6 +906,44 @@ def edit_distance(hyp: torch.Tensor, hyp_length: torch.Tensor, ref: torch.Tensor
     return distance
 
 
+def edit_counts(hyp: torch.Tensor, hyp_length: torch.Tensor, ref: torch.Tensor, ref_length: torch.Tensor,
+                R: Optional[int] = None, rows_per_tile: Optional[int] = None) -> torch.Tensor:
+    """counts[B, N, 4] int32: (distance, substitutions, insertions, deletions) of every hypothesis hyp[b, n, :hyp_length[b, n]]
+    against its utterance's reference ref[b, :ref_length[b]] (ctc_amd_edit_counts): the lexicographic minimum of (distance,
+    substitutions, insertions) over all alignments.  The tensors are those of edit_distance; the reference may be up to 65536
+    tokens long and the hypotheses up to 2^20.  R bounds every ref_length (an utterance with a longer reference gets -1
+    throughout; default: the reference tensor's width Wr).  rows_per_tile (None: the library's default) is the number of
+    hypothesis tokens per tile; the result does not depend on it.  Does not synchronise."""
+    _require_gpu(hyp)
+    dev = hyp.device
+    if (hyp.dim() != 3 or hyp_length.dim() != 2 or ref.dim() != 2 or ref_length.dim() != 1
+            or tuple(hyp_length.shape) != tuple(hyp.shape[:2]) or int(ref.shape[0]) != int(hyp.shape[0])
+            or int(ref_length.shape[0]) != int(hyp.shape[0])):
+        raise ValueError(f"edit_counts: hyp must be [B, N, W], hyp_length [B, N], ref [B, Wr] and ref_length [B], got "
+                         f"{tuple(hyp.shape)}, {tuple(hyp_length.shape)}, {tuple(ref.shape)} and {tuple(ref_length.shape)}")
+    B, N, W = (int(s) for s in hyp.shape)
+    Wr = int(ref.shape[1])
+    R = Wr if R is None else int(R)
+    rt = 0 if rows_per_tile is None else int(rows_per_tile)
+    key = ("edit_counts", B, N, R, W, rt)
+    if key not in _WS_BYTES:  # (also the check of the shape, which an empty batch would otherwise skip)
+        _WS_BYTES[key] = _lib.edit_counts_workspace_bytes(B, N, R, W, rt)
+    n = _WS_BYTES[key]
+
+    def i32(t):
+        return t if (t.dtype == torch.int32 and t.device == dev and t.is_contiguous()) else t.to(device=dev, dtype=torch.int32).contiguous()
+    hyp, hyp_length, ref, ref_length = i32(hyp), i32(hyp_length), i32(ref), i32(ref_length)
+    counts = torch.empty((B, N, 4), dtype=torch.int32, device=dev)
+    if B == 0:
+        return counts
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = _lib.load().ctc_amd_edit_counts(_ptr(hyp), W, _ptr(hyp_length), _ptr(ref), Wr, _ptr(ref_length), B, N, R, rt,
+                                             _ptr(counts), ws.data_ptr(), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_edit_counts")
+    return counts
+
+
 def prefix_prepare(wrt: int, x: torch.Tensor, logit_length: torch.Tensor):
     """(x, logit_length, rows) of a prefix scorer: the logits as greedy_decode takes them and, for logits, the row statistics
     (ctc_amd_prefix_rows: one launch, once per scorer); rows is None for log-probabilities."""
