@@ -58,9 +58,9 @@ struct Common {  // what every compute entry point takes first
   int blank, B, T, V, U;
 };
 
-// the guard of the query functions, which take a shape and no tensors
-bool shape_ok(int kind, int B, int T, int V, int U) {
-  return (kind == CTC_AMD_CLASSIC || kind == CTC_AMD_SIMPLIFIED) && B >= 0 && T >= 0 && V > 0 && U >= 0 && U <= MAX_U;
+// the guard of the query functions, which take a shape and no tensors (max_u: as in check_common)
+bool shape_ok(int kind, int B, int T, int V, int U, int max_u = MAX_U) {
+  return (kind == CTC_AMD_CLASSIC || kind == CTC_AMD_SIMPLIFIED) && B >= 0 && T >= 0 && V > 0 && U >= 0 && U <= max_u;
 }
 
 int check_common(const Common &c, int max_u = MAX_U) {  // (max_u: CTC_AMD_LONG_MAX_U for the tiled alignment, whose label axis spans workgroups)
@@ -97,19 +97,24 @@ Problem shape_problem(int kind, int wrt, int B, int T, int V, int U) {  // what 
 }
 
 // Producer formats (ctc_amd_loss_grad_ex and its kin): element types and element strides of the batch and time axes of the
-// logits (x) and of the gradient (g); the token axis is contiguous.  Packed batches have rows and no batch stride (sb = 0).
+// logits (x) and of the gradient (g); the token axis is contiguous.  Packed batches have rows and no batch stride (sb = 0):
+// utterance b starts at row row0[b].
 struct Format {
   int xdtype;
   int64_t xsb, xst;
   int gdtype;
   int64_t gsb, gst;
+  bool packed = false;
+  const int64_t *row0 = nullptr;
+  // a call without a gradient of its own: the pipeline is chosen as for a gradient in the logits' format
+  static Format of_logits(int dtype, int64_t sb, int64_t st) { return {dtype, sb, st, dtype, sb, st}; }
   int check_dtypes() const {
     if (xdtype < CTC_AMD_F32 || xdtype > CTC_AMD_F16 || gdtype < CTC_AMD_F32 || gdtype > CTC_AMD_F16)
       return fail(CTC_AMD_EINVAL, "dtype must be CTC_AMD_F32, CTC_AMD_BF16 or CTC_AMD_F16 (logits %d, grad %d)", xdtype, gdtype);
     return CTC_AMD_OK;
   }
   // rows must not overlap: stride_t >= V, and the batch stride must step over whole rows in either nesting order
-  int check_strides(int V, bool with_grad, bool packed = false) const {
+  int check_strides(int V, bool with_grad) const {
     if (xst < V || (!packed && xsb < V) || (with_grad && (gst < V || (!packed && gsb < V))))
       return fail(CTC_AMD_EINVAL, "%sstrides smaller than a row of V=%d elements (logits %lld/%lld, grad %lld/%lld)", packed ? "row " : "", V,
                   (long long)xsb, (long long)xst, (long long)gsb, (long long)gst);
@@ -117,9 +122,160 @@ struct Format {
   }
   Problem applied(Problem p) const {
     p.xsb = xsb; p.xst = xst; p.xdtype = xdtype; p.gsb = gsb; p.gst = gst; p.gdtype = gdtype;
+    if (packed) p.row0 = reinterpret_cast<const long long *>(row0);
     return p;
   }
 };
+
+// What every producer-format entry point does first, in this order: the common arguments, the element types, B == 0 (CTC_AMD_OK
+// and nothing further), a packed batch's row offsets, the strides.  `go`: the call goes on, with `p`; otherwise `rc` is its answer.
+struct Prelude { bool go; int rc; Problem p; };
+Prelude prelude(const Common &c, const Format &f, bool with_grad, int max_u = MAX_U) {
+  if (int rc = check_common(c, max_u)) return {false, rc, {}};
+  if (int rc = f.check_dtypes()) return {false, rc, {}};
+  if (c.B == 0) return {false, CTC_AMD_OK, {}};
+  if (f.packed && !f.row0) return {false, fail(CTC_AMD_EINVAL, "null row_offsets pointer"), {}};
+  if (int rc = f.check_strides(c.V, with_grad)) return {false, rc, {}};
+  return {true, CTC_AMD_OK, f.applied(make_problem(c))};
+}
+
+// ---- checks that several entry points make ----
+
+// everything that stages a token row in LDS; `of_what` ends the message (" of the alignment"; nothing in the size queries)
+int check_vocab(int V, const char *of_what = "") {
+  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d%s", V, MAX_V_GRAD, of_what);
+  return CTC_AMD_OK;
+}
+
+// the alignments behind the prelude: the two outputs that must exist, then the vocabulary limit
+int check_alignment(const float *score, const int32_t *tokens, int T, int V) {
+  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
+  return check_vocab(V, " of the alignment");
+}
+
+// the row stages run one workgroup per `rows_per_group` (4 or 16) of the B * T rows
+int check_row_grid(int B, int T, int rows_per_group) {
+  if (((long long)B * T + rows_per_group - 1) / rows_per_group > 0x7fffffffLL)
+    return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  return CTC_AMD_OK;
+}
+
+int check_wildcard_weight(float w) {
+  if (!(w <= 0.f) || w < -3.402823466e38f) return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)w);
+  return CTC_AMD_OK;
+}
+
+// what the wildcard loss and the entries built on it take behind the prelude; the row stage runs only for a gradient
+int check_wildcard_loss(float w, const float *loss, int B, int T, int V, bool row_stage) {
+  if (int rc = check_wildcard_weight(w)) return rc;
+  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
+  if (int rc = check_vocab(V, " of the wildcard loss")) return rc;
+  return row_stage ? check_row_grid(B, T, 4) : CTC_AMD_OK;
+}
+
+// the answer to a long-form plan function that refused
+int bad_tiling(int frames_per_tile, int B, int T, int U) {
+  return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
+              frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
+}
+
+// A null workspace: refused even where no byte is needed, or taken where none is.  Which of the two an entry point has is part of
+// its contract.
+enum class NullWs { Refused, TakenIfUnneeded };
+int check_workspace(const void *ws, size_t bytes, size_t need, NullWs rule) {
+  if (bytes < need || (!ws && (rule == NullWs::Refused || need > 0)))
+    return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", bytes, need);
+  return CTC_AMD_OK;
+}
+
+// every size query looks at its result pointer first
+int check_out_bytes(const size_t *out_bytes) { return out_bytes ? CTC_AMD_OK : fail(CTC_AMD_EINVAL, "out_bytes is null"); }
+
+// ... and those that take a lattice shape then at the shape
+int check_query_shape(int kind, int B, int T, int V, int U, const size_t *out_bytes, int max_u = MAX_U) {
+  if (int rc = check_out_bytes(out_bytes)) return rc;
+  if (!shape_ok(kind, B, T, V, U, max_u)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  return CTC_AMD_OK;
+}
+
+// ... and then the vocabulary limit
+int check_query(int kind, int B, int T, int V, int U, const size_t *out_bytes, int max_u = MAX_U) {
+  if (int rc = check_query_shape(kind, B, T, V, U, out_bytes, max_u)) return rc;
+  return check_vocab(V);
+}
+
+// a long-form size query: make_plan(&plan) is the entry point's plan function on the query's arguments
+template <class Plan, class MakePlan>
+int long_query(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes, MakePlan make_plan) {
+  if (int rc = check_query(kind, B, T, V, U, out_bytes, CTC_AMD_LONG_MAX_U)) return rc;
+  Plan plan;
+  if (!make_plan(&plan)) return bad_tiling(frames_per_tile, B, T, U);
+  *out_bytes = plan.total;
+  return CTC_AMD_OK;
+}
+
+// what ctc_amd_beam_search and its size query take beyond a shape
+int check_beam(int V, int beam_width, int top_k) {
+  if (int rc = check_vocab(V, " of the beam search")) return rc;
+  if (beam_width < 1 || beam_width > CTC_AMD_BEAM_MAX_WIDTH) return fail(CTC_AMD_EINVAL, "beam_width %d outside [1, %d]", beam_width, CTC_AMD_BEAM_MAX_WIDTH);
+  if (top_k < 1 || top_k > CTC_AMD_BEAM_MAX_TOP_K) return fail(CTC_AMD_EINVAL, "top_k %d outside [1, %d]", top_k, CTC_AMD_BEAM_MAX_TOP_K);
+  return CTC_AMD_OK;
+}
+
+// what the N-best entry points (max_n = CTC_AMD_NBEST_MAX) and the prefix scorer's (CTC_AMD_PREFIX_MAX) take beyond a shape
+int check_hypotheses(int B, int V, int N, int max_n, const char *of_what) {
+  if (int rc = check_vocab(V, of_what)) return rc;
+  if (N < 1 || N > max_n) return fail(CTC_AMD_EINVAL, "N %d outside [1, %d]", N, max_n);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld hypotheses exceed 2^31", (long long)B * N);
+  return CTC_AMD_OK;
+}
+int check_nbest(int B, int V, int N) { return check_hypotheses(B, V, N, CTC_AMD_NBEST_MAX, " of the N-best loss"); }
+int check_prefix(int B, int V, int N) { return check_hypotheses(B, V, N, CTC_AMD_PREFIX_MAX, " of the prefix scorer"); }
+
+// what the two step calls of the prefix scorer share behind the prelude; only logits need the row statistics
+int check_prefix_step(const Problem &p, int N, const void *rows, size_t rows_bytes) {
+  if (int rc = check_prefix(p.B, p.V, N)) return rc;
+  if (p.wrt == CTC_AMD_WRT_LOGITS && p.T > 0) {
+    if (!rows) return fail(CTC_AMD_EINVAL, "null rows pointer (ctc_amd_prefix_rows fills it once per logits tensor)");
+    const size_t need = ctc::prefix_rows_bytes(p.B, p.T);
+    if (rows_bytes < need) return fail(CTC_AMD_EWORKSPACE, "rows buffer too small: %zu < %zu", rows_bytes, need);
+  }
+  return CTC_AMD_OK;
+}
+
+// The edit-distance entry points and their size queries (max_r: CTC_AMD_MAX_U, or CTC_AMD_LONG_MAX_U for the tiled counts): the
+// sizes, which the compute calls check before B == 0, and the pairs, which they check behind it.
+int check_edit_sizes(int B, int R, int max_r) {
+  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
+  if (R > max_r) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, max_r);
+  return CTC_AMD_OK;
+}
+int check_edit_pairs(int B, int N) {
+  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
+  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
+  return CTC_AMD_OK;
+}
+int check_edit_strides(int hyp_stride, int ref_stride) {
+  if (hyp_stride < 0 || ref_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d ref_stride=%d", hyp_stride, ref_stride);
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::EDIT_LONG_MAX_R == CTC_AMD_LONG_MAX_U && ctc::EDIT_LONG_MAX_STRIDE == CTC_AMD_EDIT_COUNTS_MAX_STRIDE &&
+              ctc::EDIT_LONG_ROWS_MULTIPLE == CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE, "include/ctc_amd.h and ctc_edit_long_plan.h disagree");
+
+// the tiling of ctc_amd_edit_counts and its size query, and the plan of a valid one (the size query has no ref_stride: only here
+// can its hyp_stride be found negative)
+int check_edit_counts_tiling(int B, int N, int R, int hyp_stride, int rows_per_tile, ctc::EditCountsPlan *plan) {
+  if (hyp_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d", hyp_stride);
+  if (hyp_stride > CTC_AMD_EDIT_COUNTS_MAX_STRIDE)
+    return fail(CTC_AMD_EINVAL, "hyp_stride=%d exceeds the supported maximum %d", hyp_stride, CTC_AMD_EDIT_COUNTS_MAX_STRIDE);
+  if (rows_per_tile < 0 || rows_per_tile % CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE != 0)
+    return fail(CTC_AMD_EINVAL, "rows_per_tile=%d is neither 0 nor a positive multiple of %d", rows_per_tile, CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE);
+  if (!ctc::edit_counts_plan(B, N, R, hyp_stride, rows_per_tile, plan))
+    return fail(CTC_AMD_EINVAL, "B * N = %lld pairs are too many for the launch grid at R=%d hyp_stride=%d rows_per_tile=%d", (long long)B * N,
+                R, hyp_stride, rows_per_tile);
+  return CTC_AMD_OK;
+}
 
 // ---- tier selection ----
 
@@ -203,7 +359,7 @@ int add_loss_sum(const float *loss, int B, long long *sum2, long long *zero_next
 
 int loss_grad_impl(Problem p, float *loss, void *grad, const float *d_loss, void *workspace, size_t workspace_bytes, void *stream) {
   if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  if (grad && p.V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d for the gradient", p.V, MAX_V_GRAD);
+  if (int rc = grad ? check_vocab(p.V, " for the gradient") : CTC_AMD_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float *gradf = static_cast<float *>(grad);  // element-typed inside the kernels (Problem::gdtype)
   p.align_bits = low_bits(p.logits, grad);
@@ -236,10 +392,28 @@ int loss_grad_impl(Problem p, float *loss, void *grad, const float *d_loss, void
 struct LogDomain { Layout L; Problem p; char *ws; hipStream_t st; };
 int log_domain_setup(const Common &c, size_t extra, void *workspace, size_t workspace_bytes, void *stream, LogDomain &d) {
   d.L = ctc::make_layout(c.kind, c.B, c.T, c.U, extra);
-  if (!workspace || workspace_bytes < d.L.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, d.L.total);
+  if (int rc = check_workspace(workspace, workspace_bytes, d.L.total, NullWs::Refused)) return rc;
   d.p = make_problem(c);
   d.ws = static_cast<char *>(workspace);
   d.st = static_cast<hipStream_t>(stream);
+  return CTC_AMD_OK;
+}
+
+static_assert(ctc::LONG_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the tiled loss kernel's wildcard label is the ABI's");
+
+// ctc_amd_long_wildcard_loss_grad and its checkpointed twin, which differ in the plan function alone (long_loss_ckpt_plan refuses
+// what long_loss_plan refuses, and is long_loss_plan without a gradient)
+using LongLossPlanFn = bool(int, int, int, int, int, int, ctc::LongLossPlan *);
+int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, const Common &c, const Format &f, float wildcard_log_weight, int frames_per_tile,
+                                 const float *d_loss, float *loss, void *grad, void *workspace, size_t workspace_bytes, void *stream) {
+  const Prelude pre = prelude(c, f, grad != nullptr, CTC_AMD_LONG_MAX_U);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_wildcard_loss(wildcard_log_weight, loss, c.B, c.T, c.V, grad != nullptr)) return rc;
+  ctc::LongLossPlan plan;
+  if (!plan_fn(c.kind, c.B, c.T, c.U, frames_per_tile, grad != nullptr, &plan)) return bad_tiling(frames_per_tile, c.B, c.T, c.U);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_loss_long(pre.p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
+                             static_cast<hipStream_t>(stream)), "long wildcard loss launch");
   return CTC_AMD_OK;
 }
 
@@ -352,8 +526,7 @@ int ctc_amd_check_labels(const int32_t *labels, int label_stride, const int32_t 
 }
 
 int ctc_amd_workspace_bytes(int what, int kind, int B, int T, int V, int U, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_query_shape(kind, B, T, V, U, out_bytes)) return rc;  // (no vocabulary limit: the loss alone has none)
   size_t extra = 0;
   if (what == CTC_AMD_WS_LOSS_GRAD_LOGITS) {
     // the pipeline a float32 / aligned bfloat16 logits call of this shape selects; its own (smaller) layout when that is a fused tier
@@ -378,9 +551,10 @@ int ctc_amd_loss_grad(int kind, int wrt, const float *logits, const int32_t *lab
   return loss_grad_impl(make_problem(c), loss, grad, d_loss, workspace, workspace_bytes, stream);
 }
 
-// The five producer-format entry points check in the same order: common arguments, what only they take, element types,
-// B == 0, strides.  (Two historical exceptions are part of the contract: ctc_amd_loss_grad_sum looks at its strides before
-// B == 0, ctc_amd_grad_resume at its gradient pointer.)
+// Every entry point from here on that takes a producer format begins with prelude() and goes on with what only it takes; the
+// order of those checks is part of the contract (tests/golden/cabi_fault_matrix.json).  Two historical exceptions are part of it
+// too and make the prelude's steps by hand: ctc_amd_loss_grad_sum looks at sum2 before the element types and at its strides before
+// B == 0 (an empty batch still clears the next step's buffer), ctc_amd_grad_resume at its gradient pointer before B == 0.
 
 int ctc_amd_loss_grad_ex(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                          int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
@@ -389,11 +563,9 @@ int ctc_amd_loss_grad_ex(int kind, int wrt, const void *logits, int logits_dtype
                          size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
-  return loss_grad_impl(f.applied(make_problem(c)), loss, grad, d_loss, workspace, workspace_bytes, stream);
+  const Prelude pre = prelude(c, f, grad != nullptr);
+  if (!pre.go) return pre.rc;
+  return loss_grad_impl(pre.p, loss, grad, d_loss, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_loss_grad_packed(int kind, int wrt, const void *logits, int logits_dtype, const int64_t *row_offsets, int64_t row_stride,
@@ -401,15 +573,10 @@ int ctc_amd_loss_grad_packed(int kind, int wrt, const void *logits, int logits_d
                              int blank_index, int B, int T, int V, int U, float *loss, void *grad, int grad_dtype,
                              int64_t grad_row_stride, const float *d_loss, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, 0, row_stride, grad_dtype, 0, grad ? grad_row_stride : V};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (!row_offsets) return fail(CTC_AMD_EINVAL, "null row_offsets pointer");
-  if (int rc = f.check_strides(V, grad != nullptr, true)) return rc;
-  Problem p = f.applied(make_problem(c));
-  p.row0 = reinterpret_cast<const long long *>(row_offsets);
-  return loss_grad_impl(p, loss, grad, d_loss, workspace, workspace_bytes, stream);
+  const Format f{logits_dtype, 0, row_stride, grad_dtype, 0, grad ? grad_row_stride : V, true, row_offsets};
+  const Prelude pre = prelude(c, f, grad != nullptr);
+  if (!pre.go) return pre.rc;
+  return loss_grad_impl(pre.p, loss, grad, d_loss, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_loss_grad_sum(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
@@ -437,12 +604,9 @@ int ctc_amd_loss_forward(int kind, int wrt, const void *logits, int logits_dtype
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   // (no gradient in this half: the pipeline is chosen as for a gradient in the logits' own format, which is what the front ends ask
   // ctc_amd_grad_resume for)
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  Problem p = f.applied(make_problem(c));
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  Problem p = pre.p;
   // (Problem::resume: 0 = a call of its own, 1 = second half of a pair, 2 = first half of a pair -- the linear-domain kernel then
   // honours its conservative loss-only signs for binding alignments only, ctc_fused6.hip; other pipelines do not look at it)
   p.resume = 2;
@@ -552,151 +716,104 @@ int ctc_amd_hvp(int kind, int wrt, const float *logits, const int32_t *labels, i
 }
 
 int ctc_amd_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
   *out_bytes = ctc::align_workspace_bytes(B, T, U);
   return CTC_AMD_OK;
 }
 
-// Checked like the producer-format entry points: common arguments, element type, B == 0, strides; then what only it takes.
 int ctc_amd_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                       const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                       int blank_index, int B, int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index,
                       void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
-  const size_t need = ctc::align_workspace_bytes(B, T, U);
-  if (!workspace || workspace_bytes < need) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_align(p, static_cast<char *>(workspace), score, tokens, label_index, static_cast<hipStream_t>(stream)), "alignment launch");
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align(pre.p, static_cast<char *>(workspace), score, tokens, label_index, static_cast<hipStream_t>(stream)), "alignment launch");
   return CTC_AMD_OK;
 }
 
 int ctc_amd_greedy_decode_workspace_bytes(int B, int T, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (int rc = check_out_bytes(out_bytes)) return rc;
   if (B < 0 || T < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d", B, T);
   *out_bytes = ctc::decode_workspace_bytes(B, T);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_best_path: common arguments (it takes no labels: an empty label tensor stands in for them),
-// element type, B == 0, strides; then the outputs and the workspace.  No vocabulary limit: no row is staged in LDS.
+// It takes no labels: an empty label tensor stands in for them.  No vocabulary limit: no row is staged in LDS.
 int ctc_amd_greedy_decode(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                           const int32_t *logit_length, int blank_index, int B, int T, int V, float *score, int32_t *tokens,
                           int32_t *decoded, int32_t *decoded_length, int32_t *frames, float *label_score, void *workspace,
                           size_t workspace_bytes, void *stream) {
   // (label_length: only its null check applies, and logit_length answers it)
   const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
   if (!score || !decoded_length || (T > 0 && (!tokens || !decoded)))
     return fail(CTC_AMD_EINVAL, "null score / tokens / decoded / decoded_length pointer");
-  if (((long long)B * T + 15) / 16 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
-  const size_t need = ctc::decode_workspace_bytes(B, T);
-  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_decode(p, static_cast<char *>(workspace), score, tokens, decoded, decoded_length, frames, label_score,
+  if (int rc = check_row_grid(B, T, 16)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::decode_workspace_bytes(B, T), NullWs::TakenIfUnneeded)) return rc;
+  CTC_TRY(ctc::run_decode(pre.p, static_cast<char *>(workspace), score, tokens, decoded, decoded_length, frames, label_score,
                           static_cast<hipStream_t>(stream)), "greedy decode launch");
   return CTC_AMD_OK;
 }
 
-// what ctc_amd_beam_search and its size query take beyond a shape
-int check_beam(int V, int beam_width, int top_k) {
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the beam search", V, MAX_V_GRAD);
-  if (beam_width < 1 || beam_width > CTC_AMD_BEAM_MAX_WIDTH) return fail(CTC_AMD_EINVAL, "beam_width %d outside [1, %d]", beam_width, CTC_AMD_BEAM_MAX_WIDTH);
-  if (top_k < 1 || top_k > CTC_AMD_BEAM_MAX_TOP_K) return fail(CTC_AMD_EINVAL, "top_k %d outside [1, %d]", top_k, CTC_AMD_BEAM_MAX_TOP_K);
-  return CTC_AMD_OK;
-}
-
 int ctc_amd_beam_search_workspace_bytes(int B, int T, int V, int beam_width, int top_k, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (int rc = check_out_bytes(out_bytes)) return rc;
   if (B < 0 || T < 0 || V <= 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d T=%d V=%d", B, T, V);
   if (int rc = check_beam(V, beam_width, top_k)) return rc;
   *out_bytes = ctc::beam_workspace_bytes(B, T, V, beam_width, top_k);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_greedy_decode: common arguments, element type, B == 0, strides; then what only it takes (the
-// vocabulary limit, beam_width, top_k, nbest), the outputs and the workspace.
+// No labels, as in ctc_amd_greedy_decode.
 int ctc_amd_beam_search(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                         const int32_t *logit_length, int blank_index, int B, int T, int V, int beam_width, int top_k, int nbest,
                         float *score, int32_t *decoded, int32_t *decoded_length, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
   if (int rc = check_beam(V, beam_width, top_k)) return rc;
   if (nbest < 1 || nbest > beam_width) return fail(CTC_AMD_EINVAL, "nbest %d outside [1, beam_width = %d]", nbest, beam_width);
   if (!score || !decoded_length || (T > 0 && !decoded)) return fail(CTC_AMD_EINVAL, "null score / decoded / decoded_length pointer");
-  if (((long long)B * T + 15) / 16 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  if (int rc = check_row_grid(B, T, 16)) return rc;
   if ((long long)beam_width * T + 1 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "beam_width * T = %lld prefix nodes exceed 2^31", (long long)beam_width * T);
-  const size_t need = ctc::beam_workspace_bytes(B, T, V, beam_width, top_k);
-  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_beam(p, beam_width, top_k, nbest, static_cast<char *>(workspace), score, decoded, decoded_length,
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::beam_workspace_bytes(B, T, V, beam_width, top_k), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_beam(pre.p, beam_width, top_k, nbest, static_cast<char *>(workspace), score, decoded, decoded_length,
                         static_cast<hipStream_t>(stream)), "beam search launch");
   return CTC_AMD_OK;
 }
 
-// what ctc_amd_nbest_loss and its size query take beyond a shape
-int check_nbest(int B, int V, int N) {
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the N-best loss", V, MAX_V_GRAD);
-  if (N < 1 || N > CTC_AMD_NBEST_MAX) return fail(CTC_AMD_EINVAL, "N %d outside [1, %d]", N, CTC_AMD_NBEST_MAX);
-  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld hypotheses exceed 2^31", (long long)B * N);
-  return CTC_AMD_OK;
-}
-
 int ctc_amd_nbest_loss_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_query_shape(kind, B, T, V, U, out_bytes)) return rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   *out_bytes = ctc::nbest_workspace_bytes(kind, B, T, V, U, N);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_best_path: common arguments, element type, B == 0, strides; then what only it takes (the
-// vocabulary limit, N) and the output.  No workspace: the pointer may be null.
+// It needs no workspace today, so a null one passes.
 int ctc_amd_nbest_loss(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                        const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                        int blank_index, int B, int T, int V, int U, int N, float *loss, void *workspace, size_t workspace_bytes,
                        void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  const size_t need = ctc::nbest_workspace_bytes(kind, B, T, V, U, N);
-  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_nbest(p, N, loss, static_cast<hipStream_t>(stream)), "N-best loss launch");
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::nbest_workspace_bytes(kind, B, T, V, U, N), NullWs::TakenIfUnneeded)) return rc;
+  CTC_TRY(ctc::run_nbest(pre.p, N, loss, static_cast<hipStream_t>(stream)), "N-best loss launch");
   return CTC_AMD_OK;
 }
 
 int ctc_amd_nbest_loss_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_query_shape(kind, B, T, V, U, out_bytes)) return rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   *out_bytes = ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_nbest_loss (both element types with the logits', the gradient's strides with the logits'); then
-// the three tensors only this call takes, the row stage's launch grid and the workspace.
 int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                             const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                             int blank_index, int B, int T, int V, int U, int N, const float *weight, float *loss, void *grad,
@@ -704,47 +821,35 @@ int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dt
                             void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, true)) return rc;
+  const Prelude pre = prelude(c, f, true);  // (the gradient's strides are looked at before its pointer)
+  if (!pre.go) return pre.rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   if (!weight || !loss || !grad) return fail(CTC_AMD_EINVAL, "null weight / loss / grad pointer");
-  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
-  const size_t need = ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
-  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_nbest_grad(p, N, weight, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+  if (int rc = check_row_grid(B, T, 4)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_nbest_grad(pre.p, N, weight, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
           "N-best loss gradient launch");
   return CTC_AMD_OK;
 }
 
 int ctc_amd_nbest_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
+  if (int rc = check_query_shape(kind, B, T, V, U, out_bytes)) return rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   *out_bytes = ctc::nbest_align_workspace_bytes(B, T, U, N);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_nbest_loss: common arguments, element type, B == 0, strides, the vocabulary limit and N; then the
-// two outputs that must exist and the workspace.
 int ctc_amd_nbest_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                             const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                             int blank_index, int B, int T, int V, int U, int N, float *score, int32_t *tokens, int32_t *label_index,
                             int32_t *first_frame, int32_t *last_frame, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
   if (int rc = check_nbest(B, V, N)) return rc;
   if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
-  const size_t need = ctc::nbest_align_workspace_bytes(B, T, U, N);
-  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_nbest_align(p, N, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::nbest_align_workspace_bytes(B, T, U, N), NullWs::TakenIfUnneeded)) return rc;
+  CTC_TRY(ctc::run_nbest_align(pre.p, N, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
                                static_cast<hipStream_t>(stream)), "N-best alignment launch");
   return CTC_AMD_OK;
 }
@@ -752,32 +857,22 @@ int ctc_amd_nbest_best_path(int kind, int wrt, const void *logits, int logits_dt
 static_assert(ctc::ALIGN_WILDCARD == CTC_AMD_WILDCARD, "the kernel's wildcard label is the ABI's");
 
 int ctc_amd_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
   *out_bytes = ctc::align_wild_workspace_bytes(B, T, U);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_best_path, with its messages: common arguments, element type, B == 0, strides; then the two outputs
-// that must exist, the vocabulary limit and the workspace.
 int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                                int blank_index, int B, int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index,
                                int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace, size_t workspace_bytes,
                                void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
-  const size_t need = ctc::align_wild_workspace_bytes(B, T, U);
-  if (!workspace || workspace_bytes < need) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_align_wild(p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
                               static_cast<hipStream_t>(stream)), "wildcard alignment launch");
   return CTC_AMD_OK;
 }
@@ -786,78 +881,47 @@ static_assert(ctc::LONG_MAX_U == CTC_AMD_LONG_MAX_U && ctc::LONG_RING_FRAMES == 
               ctc::LONG_TF_DEFAULT == CTC_AMD_LONG_FRAMES_DEFAULT, "the tiled alignment's limits are the ABI's");
 
 int ctc_amd_long_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
-    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
-  ctc::LongPlan plan;
-  if (!ctc::long_plan(B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  *out_bytes = plan.total;
-  return CTC_AMD_OK;
+  return long_query<ctc::LongPlan>(kind, B, T, V, U, frames_per_tile, out_bytes,
+                                   [=](ctc::LongPlan *plan) { return ctc::long_plan(B, T, U, frames_per_tile, plan); });
 }
 
-// Checked in the order of ctc_amd_best_path, with its messages and CTC_AMD_LONG_MAX_U in place of its limit on U: common arguments,
-// element type, B == 0, strides; then the two outputs that must exist, the vocabulary limit, frames_per_tile and the workspace.
+// The long-form entry points take CTC_AMD_LONG_MAX_U label positions: the label axis spans workgroups.
 int ctc_amd_long_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                            int blank_index, int B, int T, int V, int U, int frames_per_tile, float *score, int32_t *tokens,
                            int32_t *label_index, int32_t *first_frame, int32_t *last_frame, void *workspace, size_t workspace_bytes,
                            void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false, CTC_AMD_LONG_MAX_U);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
   ctc::LongPlan plan;
-  if (!ctc::long_plan(B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_align_long(p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+  if (!ctc::long_plan(B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_long(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
                               static_cast<hipStream_t>(stream)), "long alignment launch");
   return CTC_AMD_OK;
 }
 
 int ctc_amd_long_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
-    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
-  ctc::LongWildPlan plan;
-  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  *out_bytes = plan.total;
-  return CTC_AMD_OK;
+  return long_query<ctc::LongWildPlan>(kind, B, T, V, U, frames_per_tile, out_bytes,
+                                       [=](ctc::LongWildPlan *plan) { return ctc::long_wild_plan(B, T, U, frames_per_tile, plan); });
 }
 
-// Checked in the order of ctc_amd_long_best_path, with its messages; label_score, like the other per-label outputs, may be null.
+// label_score, like the other per-label outputs, may be null.
 int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                     const int32_t *logit_length, int blank_index, int B, int T, int V, int U, int frames_per_tile,
                                     float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
                                     float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!score || (T > 0 && !tokens)) return fail(CTC_AMD_EINVAL, "null score / tokens pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the alignment", V, MAX_V_GRAD);
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false, CTC_AMD_LONG_MAX_U);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
   ctc::LongWildPlan plan;
-  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_align_long_wild(p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_long_wild(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
                                    label_score, static_cast<hipStream_t>(stream)), "long wildcard alignment launch");
   return CTC_AMD_OK;
 }
@@ -865,16 +929,12 @@ int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int l
 static_assert(ctc::WILD_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the loss kernel's wildcard label is the ABI's");
 
 int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (!shape_ok(kind, B, T, V, U)) return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
+  if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
   *out_bytes = ctc::wild_loss_workspace_bytes(kind, B, T, U, want_grad != 0);
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_nbest_loss_grad: common arguments, element types, B == 0, strides (the gradient's only when there
-// is one); then what only this call takes (the wildcard weight), the output, the vocabulary limit, the row stage's launch grid and
-// the workspace.
+// The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
 int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                                int blank_index, float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss,
@@ -882,40 +942,22 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits
                                size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
-  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
-    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
-  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
-  if (grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const Prelude pre = prelude(c, f, grad != nullptr);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_wildcard_loss(wildcard_log_weight, loss, B, T, V, grad != nullptr)) return rc;
   const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
-  if (workspace_bytes < need || (need > 0 && !workspace)) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_wild_loss(p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+  if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
+  CTC_TRY(ctc::run_wild_loss(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
           "wildcard loss launch");
   return CTC_AMD_OK;
 }
 
-static_assert(ctc::LONG_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the tiled loss kernel's wildcard label is the ABI's");
-
 int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
-    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
-  ctc::LongLossPlan plan;
-  if (!ctc::long_loss_plan(kind, B, T, U, frames_per_tile, want_grad != 0, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  *out_bytes = plan.total;
-  return CTC_AMD_OK;
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan);
+  });
 }
 
-// Checked in the order of ctc_amd_wildcard_loss_grad, with its messages and CTC_AMD_LONG_MAX_U in place of its limit on U; then
-// frames_per_tile and the launch grids as in ctc_amd_long_best_path, then the workspace.
 int ctc_amd_long_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                     const int32_t *logit_length, int blank_index, float wildcard_log_weight, int B, int T, int V, int U,
@@ -923,40 +965,15 @@ int ctc_amd_long_wildcard_loss_grad(int kind, int wrt, const void *logits, int l
                                     int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
-  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
-    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
-  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
-  if (grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
-  ctc::LongLossPlan plan;
-  if (!ctc::long_loss_plan(kind, B, T, U, frames_per_tile, grad != nullptr, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_loss_long(p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
-                             static_cast<hipStream_t>(stream)), "long wildcard loss launch");
-  return CTC_AMD_OK;
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, c, f, wildcard_log_weight, frames_per_tile, d_loss, loss, grad, workspace,
+                                      workspace_bytes, stream);
 }
 
-// The checkpointed gradient: the checks of the two entries above, word for word, on long_loss_ckpt_plan (which refuses what
-// long_loss_plan refuses, and is long_loss_plan without a gradient).
 int ctc_amd_long_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
                                                     size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
-    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
-  ctc::LongLossPlan plan;
-  if (!ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, want_grad != 0, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  *out_bytes = plan.total;
-  return CTC_AMD_OK;
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan);
+  });
 }
 
 int ctc_amd_long_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
@@ -967,32 +984,14 @@ int ctc_amd_long_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, 
                                          void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, grad != nullptr)) return rc;
-  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
-    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
-  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
-  if (grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
-  ctc::LongLossPlan plan;
-  if (!ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, grad != nullptr, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_loss_long(p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
-                             static_cast<hipStream_t>(stream)), "long wildcard loss launch");
-  return CTC_AMD_OK;
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, c, f, wildcard_log_weight, frames_per_tile, d_loss, loss, grad, workspace,
+                                      workspace_bytes, stream);
 }
 
 int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
   return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
 }
 
-// Checked in the order of ctc_amd_wildcard_loss_grad: common arguments, element type, B == 0, strides, the wildcard weight; then the
-// outputs, the vocabulary limit and the workspace.
 int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                             const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                             int blank_index, float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
@@ -1000,39 +999,26 @@ int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dt
                             void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
-    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
+  const Prelude pre = prelude(c, f, false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_wildcard_weight(wildcard_log_weight)) return rc;
   if (!loss || (T > 0 && U > 0 && !label_posterior) || (T > 0 && !blank_posterior))
     return fail(CTC_AMD_EINVAL, "null loss / label_posterior / blank_posterior pointer");
   if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the label posteriors", V, MAX_V_GRAD);
-  const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, true);
-  if (workspace_bytes < need || !workspace) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_label_posterior(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+  if (int rc = check_vocab(V, " of the label posteriors")) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::wild_loss_workspace_bytes(kind, B, T, U, true), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_label_posterior(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
                                    static_cast<char *>(workspace), static_cast<hipStream_t>(stream)), "label posterior launch");
   return CTC_AMD_OK;
 }
 
 int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if ((kind != CTC_AMD_CLASSIC && kind != CTC_AMD_SIMPLIFIED) || B < 0 || T < 0 || V <= 0 || U < 0 || U > CTC_AMD_LONG_MAX_U)
-    return fail(CTC_AMD_EINVAL, "bad kind or shape: kind=%d B=%d T=%d V=%d U=%d", kind, B, T, V, U);
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d", V, MAX_V_GRAD);
-  ctc::LongPostPlan plan;
-  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  *out_bytes = plan.total;
-  return CTC_AMD_OK;
+  return long_query<ctc::LongPostPlan>(kind, B, T, V, U, frames_per_tile, out_bytes,
+                                       [=](ctc::LongPostPlan *plan) { return ctc::long_post_plan(kind, B, T, U, frames_per_tile, plan); });
 }
 
-// Checked in the order of ctc_amd_long_wildcard_loss_grad_ckpt with a gradient, with its messages; then the outputs as in
-// ctc_amd_label_posterior; then frames_per_tile and the launch grids, then the workspace.
+// It begins like ctc_amd_long_wildcard_loss_grad with a gradient, whose messages it gives (the row stage always runs); its own
+// outputs come behind that.
 int ctc_amd_long_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                  const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                                  int blank_index, float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile, float *loss,
@@ -1040,58 +1026,40 @@ int ctc_amd_long_label_posterior(int kind, int wrt, const void *logits, int logi
                                  float *peak_posterior, int32_t *peak_frame, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
-  if (int rc = check_common(c, CTC_AMD_LONG_MAX_U)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
-  if (!(wildcard_log_weight <= 0.f) || wildcard_log_weight < -3.402823466e38f)
-    return fail(CTC_AMD_EINVAL, "wildcard_log_weight must be finite and <= 0, got %g", (double)wildcard_log_weight);
-  if (!loss) return fail(CTC_AMD_EINVAL, "null loss pointer");
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the wildcard loss", V, MAX_V_GRAD);
-  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  const Prelude pre = prelude(c, f, false, CTC_AMD_LONG_MAX_U);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_wildcard_loss(wildcard_log_weight, loss, B, T, V, true)) return rc;
   if (T > 0 && !blank_posterior) return fail(CTC_AMD_EINVAL, "null blank_posterior pointer");
   if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
   if (!peak_posterior != !peak_frame) return fail(CTC_AMD_EINVAL, "peak_posterior and peak_frame must both be given or both be NULL");
   ctc::LongPostPlan plan;
-  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan))
-    return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
-                frames_per_tile, CTC_AMD_LONG_FRAMES_MULTIPLE, B, T, U);
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_long_label_posterior(p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_long_label_posterior(pre.p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
                                         peak_posterior, peak_frame, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
           "long label posterior launch");
   return CTC_AMD_OK;
 }
 
-// what ctc_amd_edit_distance and its size query take as a shape
-int check_edit(int B, int N, int R) {
-  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
-  if (R > MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, MAX_U);
-  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
-  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
-  return CTC_AMD_OK;
-}
-
 int ctc_amd_edit_distance_workspace_bytes(int B, int N, int R, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
-  if (int rc = check_edit(B, N, R)) return rc;
+  if (int rc = check_out_bytes(out_bytes)) return rc;
+  if (int rc = check_edit_sizes(B, R, MAX_U)) return rc;
+  if (int rc = check_edit_pairs(B, N)) return rc;
   *out_bytes = 0;
   return CTC_AMD_OK;
 }
 
-// Checked before any launch: the sizes and R, B == 0, then N and the number of pairs, the strides, the pointers.  No workspace: the
+// No logits, so no prelude: the sizes, B == 0, then N and the number of pairs, the strides, the pointers.  No workspace: the
 // pointer may be null.
 int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length, const int32_t *ref, int ref_stride,
                           const int32_t *ref_length, int B, int N, int R, int32_t *distance, void *workspace, size_t workspace_bytes,
                           void *stream) {
   (void)workspace;
   (void)workspace_bytes;
-  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
-  if (R > MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, MAX_U);
+  if (int rc = check_edit_sizes(B, R, MAX_U)) return rc;
   if (B == 0) return CTC_AMD_OK;
-  if (int rc = check_edit(B, N, R)) return rc;
-  if (hyp_stride < 0 || ref_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d ref_stride=%d", hyp_stride, ref_stride);
+  if (int rc = check_edit_pairs(B, N)) return rc;
+  if (int rc = check_edit_strides(hyp_stride, ref_stride)) return rc;
   if (hyp_stride > CTC_AMD_EDIT_MAX_STRIDE) return fail(CTC_AMD_EINVAL, "hyp_stride=%d exceeds the supported maximum %d", hyp_stride, CTC_AMD_EDIT_MAX_STRIDE);
   if (!hyp_length || !ref_length) return fail(CTC_AMD_EINVAL, "null length pointer");
   if (hyp_stride > 0 && !hyp) return fail(CTC_AMD_EINVAL, "null hyp pointer");
@@ -1102,62 +1070,33 @@ int ctc_amd_edit_distance(const int32_t *hyp, int hyp_stride, const int32_t *hyp
   return CTC_AMD_OK;
 }
 
-static_assert(ctc::EDIT_LONG_MAX_R == CTC_AMD_LONG_MAX_U && ctc::EDIT_LONG_MAX_STRIDE == CTC_AMD_EDIT_COUNTS_MAX_STRIDE &&
-              ctc::EDIT_LONG_ROWS_MULTIPLE == CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE, "include/ctc_amd.h and ctc_edit_long_plan.h disagree");
-
-// what ctc_amd_edit_counts and its size query take as a shape, and the plan of a valid one
-int check_edit_counts(int B, int N, int R, int hyp_stride, int rows_per_tile, ctc::EditCountsPlan *plan) {
-  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
-  if (R > CTC_AMD_LONG_MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, CTC_AMD_LONG_MAX_U);
-  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
-  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
-  if (hyp_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d", hyp_stride);
-  if (hyp_stride > CTC_AMD_EDIT_COUNTS_MAX_STRIDE)
-    return fail(CTC_AMD_EINVAL, "hyp_stride=%d exceeds the supported maximum %d", hyp_stride, CTC_AMD_EDIT_COUNTS_MAX_STRIDE);
-  if (rows_per_tile < 0 || rows_per_tile % CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE != 0)
-    return fail(CTC_AMD_EINVAL, "rows_per_tile=%d is neither 0 nor a positive multiple of %d", rows_per_tile, CTC_AMD_EDIT_COUNTS_ROWS_MULTIPLE);
-  if (!ctc::edit_counts_plan(B, N, R, hyp_stride, rows_per_tile, plan))
-    return fail(CTC_AMD_EINVAL, "B * N = %lld pairs are too many for the launch grid at R=%d hyp_stride=%d rows_per_tile=%d", (long long)B * N,
-                R, hyp_stride, rows_per_tile);
-  return CTC_AMD_OK;
-}
-
 int ctc_amd_edit_counts_workspace_bytes(int B, int N, int R, int hyp_stride, int rows_per_tile, size_t *out_bytes) {
-  if (!out_bytes) return fail(CTC_AMD_EINVAL, "out_bytes is null");
+  if (int rc = check_out_bytes(out_bytes)) return rc;
+  if (int rc = check_edit_sizes(B, R, CTC_AMD_LONG_MAX_U)) return rc;
+  if (int rc = check_edit_pairs(B, N)) return rc;
   ctc::EditCountsPlan plan;
-  if (int rc = check_edit_counts(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
+  if (int rc = check_edit_counts_tiling(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
   *out_bytes = plan.total;
   return CTC_AMD_OK;
 }
 
-// Checked before any launch, in the order of ctc_amd_edit_distance: the sizes and R, B == 0, then N and the number of pairs, the
-// strides, rows_per_tile and the launch grid, the pointers, the workspace.
+// As ctc_amd_edit_distance, with rows_per_tile and the launch grid behind the strides, and a workspace.
 int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_length, const int32_t *ref, int ref_stride,
                         const int32_t *ref_length, int B, int N, int R, int rows_per_tile, int32_t *counts, void *workspace,
                         size_t workspace_bytes, void *stream) {
-  if (B < 0 || R < 0) return fail(CTC_AMD_EINVAL, "negative size: B=%d R=%d", B, R);
-  if (R > CTC_AMD_LONG_MAX_U) return fail(CTC_AMD_EINVAL, "R=%d exceeds the supported maximum %d", R, CTC_AMD_LONG_MAX_U);
+  if (int rc = check_edit_sizes(B, R, CTC_AMD_LONG_MAX_U)) return rc;
   if (B == 0) return CTC_AMD_OK;
-  if (N < 1) return fail(CTC_AMD_EINVAL, "N %d below 1", N);
-  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld pairs exceed 2^31", (long long)B * N);
-  if (hyp_stride < 0 || ref_stride < 0) return fail(CTC_AMD_EINVAL, "negative stride: hyp_stride=%d ref_stride=%d", hyp_stride, ref_stride);
+  if (int rc = check_edit_pairs(B, N)) return rc;
+  if (int rc = check_edit_strides(hyp_stride, ref_stride)) return rc;
   ctc::EditCountsPlan plan;
-  if (int rc = check_edit_counts(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
+  if (int rc = check_edit_counts_tiling(B, N, R, hyp_stride, rows_per_tile, &plan)) return rc;
   if (!hyp_length || !ref_length) return fail(CTC_AMD_EINVAL, "null length pointer");
   if (hyp_stride > 0 && !hyp) return fail(CTC_AMD_EINVAL, "null hyp pointer");
   if (ref_stride > 0 && !ref) return fail(CTC_AMD_EINVAL, "null ref pointer");
   if (!counts) return fail(CTC_AMD_EINVAL, "null counts pointer");
-  if (!workspace || workspace_bytes < plan.total) return fail(CTC_AMD_EWORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, plan.total);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
   CTC_TRY(ctc::run_edit_counts(hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length, N, plan, counts, static_cast<char *>(workspace),
                                static_cast<hipStream_t>(stream)), "edit counts launch");
-  return CTC_AMD_OK;
-}
-
-// what the prefix scorer's entry points take beyond a shape
-int check_prefix(int B, int V, int N) {
-  if (V > MAX_V_GRAD) return fail(CTC_AMD_EINVAL, "V=%d exceeds the supported maximum %d of the prefix scorer", V, MAX_V_GRAD);
-  if (N < 1 || N > CTC_AMD_PREFIX_MAX) return fail(CTC_AMD_EINVAL, "N %d outside [1, %d]", N, CTC_AMD_PREFIX_MAX);
-  if ((long long)B * N > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * N = %lld hypotheses exceed 2^31", (long long)B * N);
   return CTC_AMD_OK;
 }
 
@@ -1170,34 +1109,17 @@ int ctc_amd_prefix_workspace_bytes(int B, int T, int V, int N, size_t *rows_byte
   return CTC_AMD_OK;
 }
 
-// Checked in the order of ctc_amd_greedy_decode: common arguments (no labels, no blank: column 0 stands in), element type, B == 0,
-// strides; then the vocabulary limit, the launch grid and the buffer.
+// No labels, as in ctc_amd_greedy_decode, and no blank: column 0 stands in.  Its buffer has a message of its own.
 int ctc_amd_prefix_rows(const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                         const int32_t *logit_length, int B, int T, int V, void *rows, size_t rows_bytes, void *stream) {
   const Common c{CTC_AMD_CLASSIC, CTC_AMD_WRT_LOGITS, logits, nullptr, 0, logit_length, logit_length, 0, B, T, V, 0};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = f.check_strides(V, false)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
   if (int rc = check_prefix(B, V, 1)) return rc;
-  if (((long long)B * T + 3) / 4 > 0x7fffffffLL) return fail(CTC_AMD_EINVAL, "B * T = %lld rows exceed the launch grid", (long long)B * T);
+  if (int rc = check_row_grid(B, T, 4)) return rc;
   const size_t need = ctc::prefix_rows_bytes(B, T);
   if (rows_bytes < need || (need > 0 && !rows)) return fail(CTC_AMD_EWORKSPACE, "rows buffer too small: %zu < %zu", rows_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_prefix_rows(p, rows, static_cast<hipStream_t>(stream)), "prefix rows launch");
-  return CTC_AMD_OK;
-}
-
-// the checks the two step calls share, in the order of ctc_amd_nbest_loss; then the row statistics, which only logits need
-int check_prefix_step(const Common &c, const Format &f, int N, const void *rows, size_t rows_bytes) {
-  if (int rc = f.check_strides(c.V, false)) return rc;
-  if (int rc = check_prefix(c.B, c.V, N)) return rc;
-  if (c.wrt == CTC_AMD_WRT_LOGITS && c.T > 0) {
-    if (!rows) return fail(CTC_AMD_EINVAL, "null rows pointer (ctc_amd_prefix_rows fills it once per logits tensor)");
-    const size_t need = ctc::prefix_rows_bytes(c.B, c.T);
-    if (rows_bytes < need) return fail(CTC_AMD_EWORKSPACE, "rows buffer too small: %zu < %zu", rows_bytes, need);
-  }
+  CTC_TRY(ctc::run_prefix_rows(pre.p, rows, static_cast<hipStream_t>(stream)), "prefix rows launch");
   return CTC_AMD_OK;
 }
 
@@ -1207,19 +1129,16 @@ int ctc_amd_prefix_extend(int kind, int wrt, const void *logits, int logits_dtyp
                           const int32_t *token, void *state_out, size_t state_bytes, int32_t *last_token_out, int32_t *length_out,
                           float *full_score, void *stream) {
   const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = check_prefix_step(c, f, N, rows, rows_bytes)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_prefix_step(pre.p, N, rows, rows_bytes)) return rc;
   if (!parent || !token || !state_out || !last_token_out || !length_out || !full_score)
     return fail(CTC_AMD_EINVAL, "null parent / token / state_out / last_token_out / length_out / full_score pointer");
   if (state_in && (!last_token_in || !length_in)) return fail(CTC_AMD_EINVAL, "state_in without last_token_in / length_in");
   if (state_in == state_out) return fail(CTC_AMD_EINVAL, "state_out must not be state_in");
   const size_t need = ctc::prefix_state_bytes(B, T, N);
   if (state_bytes < need) return fail(CTC_AMD_EWORKSPACE, "state buffer too small: %zu < %zu", state_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_prefix_extend(p, N, rows, static_cast<const double *>(state_in), last_token_in, length_in, parent, token,
+  CTC_TRY(ctc::run_prefix_extend(pre.p, N, rows, static_cast<const double *>(state_in), last_token_in, length_in, parent, token,
                                  static_cast<double *>(state_out), last_token_out, length_out, full_score,
                                  static_cast<hipStream_t>(stream)), "prefix extend launch");
   return CTC_AMD_OK;
@@ -1230,16 +1149,13 @@ int ctc_amd_prefix_score(int kind, int wrt, const void *logits, int logits_dtype
                          const void *state, size_t state_bytes, const int32_t *last_token, const int32_t *length, float *score,
                          void *stream) {
   const Common c{kind, wrt, logits, nullptr, 0, logit_length, logit_length, blank_index, B, T, V, 0};
-  const Format f{logits_dtype, logits_stride_b, logits_stride_t, logits_dtype, logits_stride_b, logits_stride_t};
-  if (int rc = check_common(c)) return rc;
-  if (int rc = f.check_dtypes()) return rc;
-  if (B == 0) return CTC_AMD_OK;
-  if (int rc = check_prefix_step(c, f, N, rows, rows_bytes)) return rc;
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_prefix_step(pre.p, N, rows, rows_bytes)) return rc;
   if (!state || !last_token || !length || !score) return fail(CTC_AMD_EINVAL, "null state / last_token / length / score pointer");
   const size_t need = ctc::prefix_state_bytes(B, T, N);
   if (state_bytes < need) return fail(CTC_AMD_EWORKSPACE, "state buffer too small: %zu < %zu", state_bytes, need);
-  const Problem p = f.applied(make_problem(c));
-  CTC_TRY(ctc::run_prefix_score(p, N, rows, static_cast<const double *>(state), last_token, length, score,
+  CTC_TRY(ctc::run_prefix_score(pre.p, N, rows, static_cast<const double *>(state), last_token, length, score,
                                 static_cast<hipStream_t>(stream)), "prefix score launch");
   return CTC_AMD_OK;
 }
