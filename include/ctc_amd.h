@@ -1189,6 +1189,80 @@ int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_l
                         int32_t *counts /* [B][N][4]: distance, substitutions, insertions, deletions */,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Frame windows per label: time-constrained CTC loss, posteriors and forced alignment (added under ABI v6: four new entry points,
+ * nothing existing changed).  A caller who knows roughly where every label belongs -- a reference alignment and a tolerance
+ * (alignment-restricted training), subtitles or a coarse first pass, another model's first_frame / last_frame or expected_frame --
+ * says so per label POSITION.  A mask on the logits cannot: it is per token, and the same token at two positions needs two masks.
+ *
+ * Each entry point is its counterpart with two more arguments behind blank_index, and is otherwise its counterpart in every
+ * respect: inputs, formats, strides, outputs, limits, validation order and messages, workspace (the counterpart's size query; a
+ * window needs none), launches, capture.
+ *   ctc_amd_windowed_loss_grad         ctc_amd_wildcard_loss_grad        (the loss alone, or the loss and its gradient)
+ *   ctc_amd_windowed_label_posterior   ctc_amd_label_posterior
+ *   ctc_amd_windowed_best_path         ctc_amd_wildcard_best_path
+ *   ctc_amd_long_windowed_best_path    ctc_amd_long_wildcard_best_path   (U <= CTC_AMD_LONG_MAX_U)
+ *   frame_window   int32 [B][window_stride] device memory: (first, last) = frame_window[b * window_stride + 2 i], [.. + 2 i + 1]
+ *                  for label position i, BOTH INCLUSIVE -- the convention of the first_frame / last_frame outputs, which can be
+ *                  fed back in.  NULL: the unwindowed call, bit for bit, whatever window_stride holds.
+ *   window_stride  int32 elements between utterances, >= 2 * U when frame_window is given (CTC_AMD_EINVAL otherwise; checked
+ *                  behind the counterpart's own argument checks and before the workspace).
+ * Position i of utterance b may OWN frame t only if first <= t <= last.  To own a frame is what the alignment calls report as
+ * label_index[b, t] == i:
+ *   classic lattice     the frames spent in the open state of position i (for a wildcard: its open state, which emits m_t / e_w);
+ *   simplified lattice  the frame of the diagonal step into position i; for a wildcard also every frame of a horizontal step
+ *                       behind it, for which it pays m_t / e_w.
+ * Frames that emit the blank are never constrained (closed states and the start state; simplified: horizontal steps behind an
+ * ordinary label and in the start state).  A wildcard position obeys its window like any other.
+ * Outside its window the emission of a position is -inf.  The summed lattice (loss, gradient, posteriors) and the maximised one
+ * (alignment) are otherwise those of the counterparts, with their tie rules: the recursions read
+ *     e[i](t) = -inf when t < first_i or t > last_i, else the counterpart's e[i](t)
+ * in every place where position i emits, the horizontal m_t / e_w of a simplified wildcard included.
+ *   - The values are read on the device only and are not validated: first < 0 and last >= T_b act as clipped to [0, T_b - 1].
+ *   - first > last is an empty window: the position cannot emit, so the utterance is infeasible exactly as the counterpart's
+ *     infeasible utterances are -- loss +inf, a zero gradient, zero posteriors, score -inf and the documented degenerate outputs --
+ *     and changes nothing else in the batch.  So is every utterance whose windows admit no path.
+ *   - Positions at or beyond label_length[b] are ignored (their pairs may hold anything, but the memory must be there).
+ *   - label_posterior is exactly 0 outside a position's window; every frame's posteriors still sum to 1.
+ * Windows that cover every frame return the bits of the unwindowed call for every output.  Long-form: frames are absolute; no
+ * output depends on where a window's edges fall relative to time blocks or label blocks, on frames_per_tile or on the batch, as for
+ * the counterpart.  Tiles that no window reaches still run.
+ * Numerics, determinism and cost are the counterparts': the producers compare the frame with the two bounds as they gather the
+ * emissions, one block ahead of the chain.
+ */
+int ctc_amd_windowed_loss_grad(int kind, int wrt,
+                               const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride,
+                               const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                               const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                               float wildcard_log_weight, int B, int T, int V, int U,
+                               const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                               int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_windowed_label_posterior(int kind, int wrt,
+                                     const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                     const int32_t *labels, int label_stride,
+                                     const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                     const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                                     float wildcard_log_weight, int B, int T, int V, int U,
+                                     float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                     float *expected_frame, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_windowed_best_path(int kind, int wrt,
+                               const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride,
+                               const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                               const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                               int B, int T, int V, int U,
+                               float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
+                               float *label_score, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_windowed_best_path(int kind, int wrt,
+                                    const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride,
+                                    const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                    const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                                    int B, int T, int V, int U, int frames_per_tile,
+                                    float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
+                                    float *label_score, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

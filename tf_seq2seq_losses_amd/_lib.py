@@ -114,6 +114,16 @@ SIGNATURES = {
     "ctc_amd_long_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, wildcard_log_weight, B, T, V, U
                                      [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame
                                       _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),       # peak_posterior, peak_frame, ws, bytes, stream
+    # the four windowed entry points: their counterparts with (frame_window, window_stride) behind blank_index
+    "ctc_amd_windowed_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                   [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_windowed_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                         [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_windowed_best_path": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int] + _COMMON_EX[11:] +
+                                   [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_windowed_best_path": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int] + _COMMON_EX[11:] +
+                                        [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance

@@ -19,6 +19,11 @@
 //                    horizontal step behind it (simplified), is the wildcard's: token a_t.  LSE_t becomes lp[t, pi_t] in place.
 //   per label        first_frame / last_frame: the frame-parallel scheme of ctc_align_long.hip.  label_score: the thread that sees
 //                    a label's first frame is its one writer and sums the label's contiguous frames in time order in float64.
+//   windows          WIN (ctc_amd_long_windowed_best_path): every lane holds the (first, last) frames of its
+//                    own NL positions of the tile's label block; the producers compare them with the absolute frame and write -inf
+//                    outside, a wildcard's m_t included, so the horizontal step behind a wildcard costs its ring slot.  A window
+//                    knows nothing of tiles: it acts the same on either side of a time-block or label-block boundary.  The three
+//                    skip tests stay true (a window only takes frames away), and nothing behind the ring knows of windows.
 // Vector stores only, no atomics, one writer per element: the same bits on every run, and -- score's last bits apart -- for every
 // frames_per_tile and batch composition.
 #include "ctc_align_long_wild.h"
@@ -75,7 +80,7 @@ __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
 
 // One frame of the chain: classic, align_chain_step as it stands (a wildcard shows in `allow` and in its emission only); simplified,
 // the step of ctc_align_wild.hip: the horizontal step of a wildcard position costs the row maximum emd instead of the blank's ebd.
-template <int KIND>
+template <int KIND, bool WIN>
 __device__ __forceinline__ Bits wild_chain_step(double (&O)[NL], double (&C)[NL], unsigned allow, unsigned wild, double fillO,
                                                 double fillC, const float (&e)[NL], double ebd, double emd) {
   if (KIND == 0) return align_chain_step<0, NL>(O, C, allow, fillO, fillC, e, ebd);
@@ -84,7 +89,7 @@ __device__ __forceinline__ Bits wild_chain_step(double (&O)[NL], double (&C)[NL]
 #pragma unroll
   for (int j = NL - 1; j >= 0; --j) {
     const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
-    const double dg = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? emd : ebd);
+    const double dg = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? (WIN ? (double)e[j] : emd) : ebd);
     const unsigned sd = dg > h ? 1u : 0u;
     C[j] = sd ? dg : h;
     bits |= (Bits)sd << j;
@@ -92,9 +97,10 @@ __device__ __forceinline__ Bits wild_chain_step(double (&O)[NL], double (&C)[NL]
   return bits;
 }
 
-template <int KIND>
+template <int KIND, bool WIN>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_long_wild_tile_kernel(const Problem p, const LongWildWs w, int K, int J, int TF,
-                                                                             int d, int k_lo, int count) {
+                                                                             int d, int k_lo, int count,
+                                                                             const int32_t *__restrict__ win, int wstride) {
   const double NINF = -__builtin_inf();
   __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
   __shared__ int lab_s[UB + 1];  // validated labels (-1: no emission, ALIGN_WILDCARD: a wildcard) of positions k * UB - 1 .. k * UB + UB - 1
@@ -129,6 +135,16 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_long_wild_tile_kernel(con
   for (int q = 0; q < NL; ++q) {
     lab[q] = lab_s[1 + lane * NL + q];
     if (lab[q] == ALIGN_WILDCARD) wild |= 1u << q;
+  }
+  [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position k * UB + lane * NL + q may own (from label_length on: never read, empty)
+  if constexpr (WIN) {
+    const int32_t *const wb = win + (size_t)b * wstride;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const int g = k * UB + lane * NL + q;
+      wf[q] = g < L ? wb[2 * (size_t)g] : 0;
+      wl[q] = g < L ? wb[2 * (size_t)g + 1] : -1;
+    }
   }
 
   const int esz = dt == 0 ? 4 : 2;
@@ -218,7 +234,13 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_long_wild_tile_kernel(con
     }
     float *const r = ring + ((kb & 1) * F + f) * RS;
 #pragma unroll
-    for (int q = 0; q < NL; ++q) r[lane * NL + q] = ((wild >> q) & 1u) ? M : e[q];
+    for (int q = 0; q < NL; ++q) {
+      float v = ((wild >> q) & 1u) ? M : e[q];
+      if constexpr (WIN) {
+        if (t < wf[q] || t > wl[q]) v = -__builtin_inff();
+      }
+      r[lane * NL + q] = v;
+    }
     if (lane == 0) { r[UB] = eb; r[UB + 1] = M; }
     if (k > 0 && lane < 2) col_s[kb & 1][f][lane] = col_in[(size_t)t * 2 + lane];
   };
@@ -250,7 +272,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_long_wild_tile_kernel(con
       }
       const double fillO = k > 0 ? col_s[kb & 1][f][0] : NINF;
       const double fillC = k > 0 ? col_s[kb & 1][f][1] : cs;
-      const Bits bits = wild_chain_step<KIND>(O, C, allow, wild, fillO, fillC, e, ebd, (double)em);
+      const Bits bits = wild_chain_step<KIND, WIN>(O, C, allow, wild, fillO, fillC, e, ebd, (double)em);
       cs += ebd;
       bp[(size_t)(t0 + f) * 64 + lane] = (Word)bits;
     }
@@ -496,7 +518,8 @@ __global__ __launch_bounds__(256) void align_long_wild_score_kernel(const Proble
 }  // namespace
 
 hipError_t run_align_long_wild(const Problem &p, const LongWildPlan &W, char *ws, float *score, int *tokens, int *label_index,
-                               int *first_frame, int *last_frame, float *label_score, hipStream_t st) {
+                               int *first_frame, int *last_frame, float *label_score, hipStream_t st, const int32_t *frame_window,
+                               int window_stride) {
   if (p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
   const LongPlan &P = W.base;
   LongWildWs w;
@@ -514,8 +537,9 @@ hipError_t run_align_long_wild(const Problem &p, const LongWildPlan &W, char *ws
       int k_lo, count;
       long_diagonal(P, d, &k_lo, &count);
       const dim3 grid((unsigned)((size_t)p.B * count));
-      if (p.kind == 0) hipLaunchKernelGGL(align_long_wild_tile_kernel<0>, grid, dim3(ALIGN_THREADS), 0, st, p, w, P.K, P.J, P.TF, d, k_lo, count);
-      else hipLaunchKernelGGL(align_long_wild_tile_kernel<1>, grid, dim3(ALIGN_THREADS), 0, st, p, w, P.K, P.J, P.TF, d, k_lo, count);
+      const auto tile = frame_window ? (p.kind == 0 ? align_long_wild_tile_kernel<0, true> : align_long_wild_tile_kernel<1, true>)
+                                     : (p.kind == 0 ? align_long_wild_tile_kernel<0, false> : align_long_wild_tile_kernel<1, false>);
+      hipLaunchKernelGGL(tile, grid, dim3(ALIGN_THREADS), 0, st, p, w, P.K, P.J, P.TF, d, k_lo, count, frame_window, window_stride);
     }
   }
   if (p.kind == 0) hipLaunchKernelGGL(align_long_wild_trace_kernel<0>, dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, w, P.K, P.J, P.TF, score, tokens, label_index);

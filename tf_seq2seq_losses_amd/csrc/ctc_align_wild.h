@@ -10,7 +10,9 @@ constexpr int ALIGN_WILDCARD = -2;  // = CTC_AMD_WILDCARD (include/ctc_amd.h): t
 // words of 1 .. 8 bytes), the float64 log-probability of the path's token on every frame ([B][T]; during the sweep: the frame's
 // log-sum-exp) and the int32 argmax token of every frame ([B][T])
 size_t align_wild_workspace_bytes(int B, int T, int U);
+// frame_window (ctc_amd_windowed_best_path): int32 [B][window_stride >= 2 U] device memory, (first, last) inclusive per label position;
+// nullptr runs the kernels of the unwindowed call
 hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
-                          float *label_score, hipStream_t st);
+                          float *label_score, hipStream_t st, const int32_t *frame_window = nullptr, int window_stride = 0);
 
 }  // namespace ctc

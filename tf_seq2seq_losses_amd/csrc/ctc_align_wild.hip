@@ -19,6 +19,9 @@
 //               step behind it), turns the workspace's log-sum-exp of every frame into the log-probability of the path's token
 //               and notes the first and last frame of every label in LDS.  Each label's frames are contiguous on both lattices:
 //               afterwards one lane per label sums its own range in time order in float64.
+// WIN (ctc_amd_windowed_best_path): every lane holds the (first, last) frames of its own NL positions and the
+// producers write -inf for a position whose frame lies outside them -- a wildcard's m_t included, so on the simplified lattice the
+// horizontal step behind a wildcard costs its ring slot instead of the wave-uniform m_t.  Nothing behind the ring knows of windows.
 // Every output element has one writer, no atomics: the same bits on every run.
 #include <type_traits>
 
@@ -76,11 +79,12 @@ __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-template <int KIND, int NL>
+template <int KIND, int NL, bool WIN>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem p, char *__restrict__ ws, size_t off_lp, size_t off_at,
                                                                    float *__restrict__ score, int *__restrict__ tokens,
                                                                    int *__restrict__ label_index, int *__restrict__ first_frame,
-                                                                   int *__restrict__ last_frame, float *__restrict__ label_score) {
+                                                                   int *__restrict__ last_frame, float *__restrict__ label_score,
+                                                                   const int32_t *__restrict__ win, int wstride) {
   typedef typename BpWord<NL>::type Word;
   typedef typename std::conditional<NL == 16, unsigned long long, unsigned int>::type Bits;
   constexpr int UP = 64 * NL;
@@ -124,6 +128,16 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   for (int j = 0; j < NL; ++j) {
     lab[j] = lab_s[lane * NL + j];
     if (lab[j] == ALIGN_WILDCARD) wild |= 1u << j;
+  }
+  [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position lane * NL + j may own (from label_length on: never read, empty)
+  if constexpr (WIN) {
+    const int32_t *const wb = win + (size_t)b * wstride;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = lane * NL + j;
+      wf[j] = i < L ? wb[2 * i] : 0;
+      wl[j] = i < L ? wb[2 * i + 1] : -1;
+    }
   }
 
   const int esz = dt == 0 ? 4 : 2;
@@ -222,7 +236,13 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
         if (t0 + f0 + g < Tb) {
           float *const r = rb + (f0 + g) * RS;
 #pragma unroll
-          for (int j = 0; j < NL; ++j) r[lane * NL + j] = ((wild >> j) & 1u) ? M[g] : e[g][j];
+          for (int j = 0; j < NL; ++j) {
+            float v = ((wild >> j) & 1u) ? M[g] : e[g][j];
+            if constexpr (WIN) {
+              if (t0 + f0 + g < wf[j] || t0 + f0 + g > wl[j]) v = -__builtin_inff();
+            }
+            r[lane * NL + j] = v;
+          }
           if (lane == 0) { r[UP] = eb[g]; r[UP + 1] = M[g]; }
         }
       }
@@ -275,7 +295,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
-          const double d = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? emd : ebd);
+          const double d = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? (WIN ? (double)e[j] : emd) : ebd);
           const unsigned sd = d > h ? 1u : 0u;
           C[j] = sd ? d : h;
           bits |= (Bits)sd << j;
@@ -421,11 +441,11 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   }
 }
 
-template <int KIND, int NL>
+template <int KIND, int NL, bool WIN>
 hipError_t launch_align_wild(const Problem &p, char *ws, size_t off_lp, size_t off_at, float *score, int *tokens, int *label_index,
-                             int *first_frame, int *last_frame, float *label_score, hipStream_t st) {
-  hipLaunchKernelGGL((align_wild_kernel<KIND, NL>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
-                     label_index, first_frame, last_frame, label_score);
+                             int *first_frame, int *last_frame, float *label_score, const int32_t *win, int wstride, hipStream_t st) {
+  hipLaunchKernelGGL((align_wild_kernel<KIND, NL, WIN>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
+                     label_index, first_frame, last_frame, label_score, win, wstride);
   return hipGetLastError();
 }
 
@@ -435,18 +455,23 @@ size_t align_wild_workspace_bytes(int B, int T, int U) {
   return r256((size_t)B * T * 64 * bp_word_bytes(nl_for(U))) + r256((size_t)B * T * 8) + r256((size_t)B * T * 4);
 }
 
+#define CTC_ALIGN_WILD_ROW(KIND, WIN)                                                                                  \
+  {launch_align_wild<KIND, 1, WIN>, launch_align_wild<KIND, 2, WIN>, launch_align_wild<KIND, 4, WIN>, launch_align_wild<KIND, 8, WIN>, \
+   launch_align_wild<KIND, 16, WIN>}
+
 hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
-                          float *label_score, hipStream_t st) {
-  typedef hipError_t Launch(const Problem &, char *, size_t, size_t, float *, int *, int *, int *, int *, float *, hipStream_t);
-  static Launch *const table[2][5] = {
-      {launch_align_wild<0, 1>, launch_align_wild<0, 2>, launch_align_wild<0, 4>, launch_align_wild<0, 8>, launch_align_wild<0, 16>},
-      {launch_align_wild<1, 1>, launch_align_wild<1, 2>, launch_align_wild<1, 4>, launch_align_wild<1, 8>, launch_align_wild<1, 16>}};
+                          float *label_score, hipStream_t st, const int32_t *frame_window, int window_stride) {
+  typedef hipError_t Launch(const Problem &, char *, size_t, size_t, float *, int *, int *, int *, int *, float *, const int32_t *, int,
+                            hipStream_t);
+  static Launch *const table[2][2][5] = {{CTC_ALIGN_WILD_ROW(0, false), CTC_ALIGN_WILD_ROW(1, false)},
+                                         {CTC_ALIGN_WILD_ROW(0, true), CTC_ALIGN_WILD_ROW(1, true)}};
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
   if (lg < 0 || p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
   const size_t off_lp = r256((size_t)p.B * p.T * 64 * bp_word_bytes(NL));
   const size_t off_at = off_lp + r256((size_t)p.B * p.T * 8);
-  return table[p.kind][lg](p, ws, off_lp, off_at, score, tokens, label_index, first_frame, last_frame, label_score, st);
+  return table[frame_window ? 1 : 0][p.kind][lg](p, ws, off_lp, off_at, score, tokens, label_index, first_frame, last_frame, label_score,
+                                                 frame_window, window_stride, st);
 }
 
 }  // namespace ctc

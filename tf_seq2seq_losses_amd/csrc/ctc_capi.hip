@@ -173,6 +173,14 @@ int check_wildcard_loss(float w, const float *loss, int B, int T, int V, bool ro
   return row_stage ? check_row_grid(B, T, 4) : CTC_AMD_OK;
 }
 
+// the frame windows of the windowed entry points: [B][window_stride] int32 with (first, last) of U label positions per utterance.
+// A null pointer is the unwindowed call, whatever the stride says.
+int check_window(const int32_t *frame_window, int window_stride, int U) {
+  if (frame_window && (long long)window_stride < 2LL * U)
+    return fail(CTC_AMD_EINVAL, "window_stride=%d is smaller than 2 * U = %lld", window_stride, 2LL * U);
+  return CTC_AMD_OK;
+}
+
 // the answer to a long-form plan function that refused
 int bad_tiling(int frames_per_tile, int B, int T, int U) {
   return fail(CTC_AMD_EINVAL, "frames_per_tile=%d is neither 0 nor a positive multiple of %d, or B=%d is too large for T=%d U=%d",
@@ -862,19 +870,31 @@ int ctc_amd_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, in
   return CTC_AMD_OK;
 }
 
+// The four windowed entry points are their counterparts with a frame window; the counterparts are they with none.
+int ctc_amd_windowed_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                               int blank_index, const int32_t *frame_window, int window_stride, int B, int T, int V, int U, float *score,
+                               int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame, float *label_score,
+                               void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
+  if (int rc = check_window(frame_window, window_stride, U)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
+                              static_cast<hipStream_t>(stream), frame_window, window_stride), "wildcard alignment launch");
+  return CTC_AMD_OK;
+}
+
 int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                                int blank_index, int B, int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index,
                                int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace, size_t workspace_bytes,
                                void *stream) {
-  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
-  if (!pre.go) return pre.rc;
-  if (int rc = check_alignment(score, tokens, T, V)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
-                              static_cast<hipStream_t>(stream)), "wildcard alignment launch");
-  return CTC_AMD_OK;
+  return ctc_amd_windowed_best_path(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                                    logit_length, blank_index, nullptr, 0, B, T, V, U, score, tokens, label_index, first_frame, last_frame,
+                                    label_score, workspace, workspace_bytes, stream);
 }
 
 static_assert(ctc::LONG_MAX_U == CTC_AMD_LONG_MAX_U && ctc::LONG_RING_FRAMES == CTC_AMD_LONG_FRAMES_MULTIPLE &&
@@ -909,21 +929,34 @@ int ctc_amd_long_wildcard_best_path_workspace_bytes(int kind, int B, int T, int 
 }
 
 // label_score, like the other per-label outputs, may be null.
+int ctc_amd_long_windowed_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride, int B,
+                                    int T, int V, int U, int frames_per_tile, float *score, int32_t *tokens, int32_t *label_index,
+                                    int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false, CTC_AMD_LONG_MAX_U);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
+  if (int rc = check_window(frame_window, window_stride, U)) return rc;
+  ctc::LongWildPlan plan;
+  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_long_wild(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                                   label_score, static_cast<hipStream_t>(stream), frame_window, window_stride),
+          "long wildcard alignment launch");
+  return CTC_AMD_OK;
+}
+
 int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                     const int32_t *logit_length, int blank_index, int B, int T, int V, int U, int frames_per_tile,
                                     float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
                                     float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
-  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false, CTC_AMD_LONG_MAX_U);
-  if (!pre.go) return pre.rc;
-  if (int rc = check_alignment(score, tokens, T, V)) return rc;
-  ctc::LongWildPlan plan;
-  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
-  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_align_long_wild(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
-                                   label_score, static_cast<hipStream_t>(stream)), "long wildcard alignment launch");
-  return CTC_AMD_OK;
+  return ctc_amd_long_windowed_best_path(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                         label_length, logit_length, blank_index, nullptr, 0, B, T, V, U, frames_per_tile, score, tokens,
+                                         label_index, first_frame, last_frame, label_score, workspace, workspace_bytes, stream);
 }
 
 static_assert(ctc::WILD_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the loss kernel's wildcard label is the ABI's");
@@ -935,21 +968,32 @@ int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, 
 }
 
 // The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
-int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
-                               int blank_index, float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss,
-                               void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
-                               size_t workspace_bytes, void *stream) {
+                               int blank_index, const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T,
+                               int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                               int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
   const Prelude pre = prelude(c, f, grad != nullptr);
   if (!pre.go) return pre.rc;
   if (int rc = check_wildcard_loss(wildcard_log_weight, loss, B, T, V, grad != nullptr)) return rc;
+  if (int rc = check_window(frame_window, window_stride, U)) return rc;
   const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
-  CTC_TRY(ctc::run_wild_loss(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
-          "wildcard loss launch");
+  CTC_TRY(ctc::run_wild_loss(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
+                             frame_window, window_stride), "wildcard loss launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                               int blank_index, float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss,
+                               void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+  return ctc_amd_windowed_loss_grad(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                                    logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad, grad_dtype,
+                                    grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad, size_t *out_bytes) {
@@ -992,11 +1036,12 @@ int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U
   return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
 }
 
-int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
-                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
-                            int blank_index, float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
-                            float *blank_posterior, float *duration, float *expected_frame, void *workspace, size_t workspace_bytes,
-                            void *stream) {
+int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                     const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
+                                     float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                     float *blank_posterior, float *duration, float *expected_frame, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
   const Prelude pre = prelude(c, f, false);
@@ -1006,10 +1051,22 @@ int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dt
     return fail(CTC_AMD_EINVAL, "null loss / label_posterior / blank_posterior pointer");
   if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
   if (int rc = check_vocab(V, " of the label posteriors")) return rc;
+  if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, ctc::wild_loss_workspace_bytes(kind, B, T, U, true), NullWs::Refused)) return rc;
   CTC_TRY(ctc::run_label_posterior(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
-                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream)), "label posterior launch");
+                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream), frame_window, window_stride),
+          "label posterior launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                            int blank_index, float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                            float *blank_posterior, float *duration, float *expected_frame, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+  return ctc_amd_windowed_label_posterior(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                          label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss,
+                                          label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {

@@ -30,6 +30,10 @@
 //           token (integer atomics: no arrival order in the sum), those of wildcard positions and of the blank into per-lane sums
 //           in a fixed order; the vocabulary in passes of 1024 columns; the row streams out as d_loss * (c * softmax - bins) with
 //           c = 1 - Gamma_t (logits) or -Gamma_t (log-probabilities; softmax is then exp(x - LSE_t)).
+// WIN (ctc_amd_windowed_loss_grad / _label_posterior): every lane holds the (first, last) frames of its own
+// NL positions; the producers write -inf for an ordinary position whose frame lies outside them and, into the ring slot of a wildcard
+// position (which holds -inf otherwise and is never read), the gate 0 / -inf that the chain adds to the wave-uniform e_w.  The row
+// stage and the statistics know nothing of windows.
 // A saved row of frame t: per position i the pair (O, C) (classic, AFTER frame t) or S (simplified, BEFORE frame t), then the start
 // state: (2 or 1) * UP + 2 doubles.  After the beta sweep the first 8 bytes of position i hold
 //   classic:    (posterior of O[i] after frame t,  posterior of C[i] = a blank behind label i)
@@ -95,9 +99,9 @@ struct WlPostWs : WlWs {
 };
 template <int MODE> using WlArg = std::conditional_t<MODE == 3, WlPostWs, WlWs>;
 
-template <int KIND, int NL, int MODE>
+template <int KIND, int NL, int MODE, bool WIN>
 __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss,
-                                                               const WlArg<MODE> ws) {
+                                                               const WlArg<MODE> ws, const int32_t *__restrict__ win, int wstride) {
   constexpr bool BACK = MODE >= 2;              // a beta sweep: frames from T_b - 1 down
   constexpr int UP = 64 * NL;
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
@@ -148,6 +152,16 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   for (int j = 0; j < NL; ++j) {
     lab[j] = lab_s[lane * NL + j];
     if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+  }
+  [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position lane * NL + j may own (from label_length on: never read, empty)
+  if constexpr (WIN) {
+    const int32_t *const wb = win + (size_t)b * wstride;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = lane * NL + j;
+      wf[j] = i < L ? wb[2 * i] : 0;
+      wl[j] = i < L ? wb[2 * i + 1] : -1;
+    }
   }
 
   const int esz = dt == 0 ? 4 : 2;
@@ -223,7 +237,15 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         if (q0 + f0 + g < Tb) {
           float *const r = rb + (f0 + g) * RS;
 #pragma unroll
-          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          for (int j = 0; j < NL; ++j) {
+            float v = e[g][j];
+            if constexpr (WIN) {
+              const int t = real_t(q0 + f0 + g);
+              if ((wild >> j) & 1u) v = 0.f;  // the gate of e_w
+              if (t < wf[j] || t > wl[j]) v = -__builtin_inff();
+            }
+            r[lane * NL + j] = v;
+          }
           if (lane == 0) {
             *reinterpret_cast<float4 *>(r + UP) = make_float4(eb[g], M, l2s, 0.f);
             if (MODE == 1) *reinterpret_cast<float4 *>(ws.stat + ((size_t)b * p.T + real_t(q0 + f0 + g)) * 4) = make_float4(eb[g], M, l2s, 0.f);
@@ -267,7 +289,8 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
       const Frame fr = frame_of(rr);
       const double eb = fr.eb;
-      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      auto ewj = [&](int j) { return WIN ? fr.ew + (double)e[j] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? ewj(j) : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
       if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
 #pragma unroll
@@ -291,7 +314,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
-          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? fr.ew : eb), q + em(j));
+          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), q + em(j));
         }
       }
       cs += eb;
@@ -343,7 +366,8 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
       const Frame fr = frame_of(rr);
       const double eb = fr.eb;
-      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      auto ewj = [&](int j) { return WIN ? fr.ew + (double)e[j] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? ewj(j) : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
       double A[NS], Acs;
       if constexpr (PF) {
 #pragma unroll
@@ -391,7 +415,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         for (int j = 0; j < NL; ++j) {
           const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
           const bool wj = ((wild >> j) & 1u) != 0;
-          const double h = wj ? fr.ew : eb;
+          const double h = wj ? ewj(j) : eb;
           const float pe = post(ap + em(j) + C[j]), ps = post(A[j] + h + C[j]);
           if constexpr (MODE == 3) {  // a stay emits the wildcard behind a wildcard, the blank otherwise
             pl[j] = wj ? pe + ps : pe;
@@ -408,7 +432,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
           const double xn = j + 1 < NL ? C[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
-          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? fr.ew : eb), xn);
+          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), xn);
           x = xn;
         }
       }
@@ -593,24 +617,31 @@ __global__ __launch_bounds__(64 * LS_SLICES) void label_stat_kernel(const Proble
   expected_frame[(size_t)b * p.U + i] = d > 0.0 ? (float)(m / d) : -1.f;
 }
 
-template <int KIND, int NL, int MODE>
-hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, hipStream_t st) {
-  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws);
+template <int KIND, int NL, int MODE, bool WIN>
+hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const int32_t *win, int wstride, hipStream_t st) {
+  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE, WIN>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws, win, wstride);
   return hipGetLastError();
 }
 
+// the window of a call: nullptr runs the WIN = false kernels
+struct WlWindow {
+  const int32_t *ptr;
+  int stride;
+};
+
+#define CTC_WILD_LOSS_ROW(KIND, WIN)                                                                                     \
+  {launch_wild_loss<KIND, 1, MODE, WIN>, launch_wild_loss<KIND, 2, MODE, WIN>, launch_wild_loss<KIND, 4, MODE, WIN>, \
+   launch_wild_loss<KIND, 8, MODE, WIN>, launch_wild_loss<KIND, 16, MODE, WIN>}
+
 template <int MODE>
-hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, hipStream_t st) {
-  typedef hipError_t Launch(const Problem &, double, float *, const WlArg<MODE> &, hipStream_t);
-  static Launch *const table[2][5] = {
-      {launch_wild_loss<0, 1, MODE>, launch_wild_loss<0, 2, MODE>, launch_wild_loss<0, 4, MODE>, launch_wild_loss<0, 8, MODE>,
-       launch_wild_loss<0, 16, MODE>},
-      {launch_wild_loss<1, 1, MODE>, launch_wild_loss<1, 2, MODE>, launch_wild_loss<1, 4, MODE>, launch_wild_loss<1, 8, MODE>,
-       launch_wild_loss<1, 16, MODE>}};
+hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const WlWindow &fw, hipStream_t st) {
+  typedef hipError_t Launch(const Problem &, double, float *, const WlArg<MODE> &, const int32_t *, int, hipStream_t);
+  static Launch *const table[2][2][5] = {{CTC_WILD_LOSS_ROW(0, false), CTC_WILD_LOSS_ROW(1, false)},
+                                         {CTC_WILD_LOSS_ROW(0, true), CTC_WILD_LOSS_ROW(1, true)}};
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
   if (lg < 0 || p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
-  return table[p.kind][lg](p, w2, loss, ws, st);
+  return table[fw.ptr ? 1 : 0][p.kind][lg](p, w2, loss, ws, fw.ptr, fw.stride, st);
 }
 
 inline size_t wl_al(size_t x) { return (x + 255) & ~size_t(255); }
@@ -632,14 +663,15 @@ size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad) 
 }
 
 hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
-                         hipStream_t st) {
+                         hipStream_t st, const int32_t *frame_window, int window_stride) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
-  if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, st);
+  const WlWindow fw{frame_window, window_stride};
+  if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, fw, st);
   const int UP = 64 * nl_for(p.U);
   const WlWs ws = wl_regions(p, wsp);
-  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, st)) return e;
+  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, fw, st)) return e;
   if (p.T == 0) return hipSuccess;  // no rows
-  if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, st)) return e;
+  if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, fw, st)) return e;
   const unsigned blocks = (unsigned)(((long)p.B * p.T + WLG_WAVES - 1) / WLG_WAVES);
   if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
   else hipLaunchKernelGGL((wild_grad_row_kernel<1>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
@@ -647,15 +679,17 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
 }
 
 hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
-                               float *duration, float *expected_frame, char *wsp, hipStream_t st) {
+                               float *duration, float *expected_frame, char *wsp, hipStream_t st, const int32_t *frame_window,
+                               int window_stride) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
+  const WlWindow fw{frame_window, window_stride};
   WlPostWs ws;
   static_cast<WlWs &>(ws) = wl_regions(p, wsp);
   ws.post = label_posterior;
   ws.blk = blank_posterior;
-  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, st)) return e;
+  if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, fw, st)) return e;
   if (p.T > 0)
-    if (hipError_t e = run_wild_mode<3>(p, w2, loss, ws, st)) return e;
+    if (hipError_t e = run_wild_mode<3>(p, w2, loss, ws, fw, st)) return e;
   if (duration && p.U > 0) {
     hipLaunchKernelGGL(label_stat_kernel, dim3(p.B, (p.U + 63) / 64), dim3(64 * LS_SLICES), 0, st, p, ws.logp, label_posterior, duration, expected_frame);
     return hipGetLastError();

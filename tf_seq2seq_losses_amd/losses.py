@@ -265,6 +265,25 @@ def ctc_alignment_from_logproba(labels, logprobas, label_length, logit_length, b
 WILDCARD = _lib.WILDCARD  # -2: the label value of a wildcard position
 
 
+def ctc_frame_window(first_frame: TensorLike, last_frame: TensorLike, logit_length: TensorLike, *, before: int = 0,
+                     after: int = 0) -> torch.Tensor:
+    """frame_window [batch, U, 2] int32 for the `frame_window` argument of the wildcard loss, label posterior and (long) wildcard
+    alignment functions: (first_frame - before, last_frame + after), clipped to [0, logit_length - 1], on the device of
+    first_frame and without a synchronisation.  first_frame / last_frame [batch, U] are an alignment's (CtcWildcardAlignment and
+    its long-form twin), or a rounded CtcLabelPosterior.expected_frame given twice; `before` / `after` are the tolerance in frames.
+    Positions from label_length on (-1 in both) come out as some clipped pair and are ignored by the calls."""
+    first = _as_tensor(first_frame)
+    last = _as_tensor(last_frame).to(first.device)
+    if first.dim() != 2 or first.shape != last.shape:
+        raise ValueError(f"first_frame and last_frame must both be [batch, U], got {tuple(first.shape)} and {tuple(last.shape)}")
+    top = (_as_tensor(logit_length).to(device=first.device, dtype=torch.int64) - 1).clamp_min(0).unsqueeze(1)
+    if top.shape[0] != first.shape[0]:
+        raise ValueError(f"logit_length must be [batch] = {(int(first.shape[0]),)}, got {tuple(top.shape[:1])}")
+    lo = torch.minimum((first.to(torch.int64) - int(before)).clamp_min(0), top)
+    hi = torch.minimum((last.to(torch.int64) + int(after)).clamp_min(0), top)
+    return torch.stack([lo, hi], dim=-1).to(torch.int32)
+
+
 class CtcWildcardAlignment(NamedTuple):
     """score [batch] float32: log-probability of the best path, the frame-wise best token on wildcard frames (-inf: no path);
     tokens [batch, max_length] int32: the token of every frame on it -- on the frames of a wildcard the frame's argmax, ties to the
@@ -284,7 +303,7 @@ class CtcWildcardAlignment(NamedTuple):
 
 
 def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index,
-                    max_label_length=None) -> CtcWildcardAlignment:
+                    max_label_length=None, frame_window=None) -> CtcWildcardAlignment:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -295,37 +314,45 @@ def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_len
     with torch.no_grad():  # a path is not differentiable: the result is detached
         prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
                             host_max_label_length=max_label_length)
-        return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep))
+        if frame_window is None:
+            return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep))
+        return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep, _as_tensor(frame_window)))
 
 
 def classic_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                    blank_index: Union[int, torch.Tensor] = 0, *,
-                                   max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+                                   max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
     """Forced alignment of a partial transcript on the classic lattice.  As classic_ctc_alignment, but a label equal to WILDCARD
     (-2) stands for any non-empty run of frames with any tokens on them: untranscribed speech before, after or inside the known
     words (free start and end are a wildcard as the first and last label).  A wildcard's frames score their best token and report
     it in `tokens`; adjacent wildcards take at least one frame each.  Arguments as classic_ctc_alignment (float32 / bfloat16 /
     float16 logits, any batch / time strides, read in place); returns CtcWildcardAlignment, not differentiable.
-    check_labels keeps rejecting -2: it validates transcripts for the loss functions, where a wildcard is an impossible emission."""
-    return _wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+    check_labels keeps rejecting -2: it validates transcripts for the loss functions, where a wildcard is an impossible emission.
+    frame_window [batch, U, 2] int32 / int64 on the logits' device, (first, last) inclusive per
+    label position -- the convention of first_frame / last_frame; see ctc_frame_window -- lets position i own frame t only if
+    first <= t <= last (label_index[b, t] == i only inside it; blank frames are free; a wildcard obeys
+    its window like any label).  An empty window (first > last), or windows that admit no path, make the sample infeasible."""
+    return _wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length,
+                           frame_window)
 
 
 def simplified_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                       blank_index: Union[int, torch.Tensor] = 0, *,
-                                      max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+                                      max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
     """The same on the simplified lattice (every other non-blank frame emits exactly one label): a wildcard owns every frame from
     its entry until the next label's frame.  Same arguments and return value as classic_ctc_wildcard_alignment; check_labels keeps
-    rejecting -2 here as well."""
-    return _wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length)
+    rejecting -2 here as well.  frame_window constrains the frame at which a label is emitted, and every frame a wildcard owns."""
+    return _wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length,
+                           frame_window)
 
 
 def ctc_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
-                                         max_label_length: Optional[int] = None) -> CtcWildcardAlignment:
+                                         max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
     """The same for log-probabilities used as they stand (the counterpart of ctc_alignment_from_logproba); ctc_loss_data_cls
     selects the lattice (default: ClassicCtcLossData).  check_labels keeps rejecting -2 here as well."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                           max_label_length)
+                           max_label_length, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -409,7 +436,7 @@ class CtcLongWildcardAlignment(NamedTuple):
 
 
 def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, frames_per_tile=None,
-                         max_label_length=None) -> CtcLongWildcardAlignment:
+                         max_label_length=None, frame_window=None) -> CtcLongWildcardAlignment:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -420,39 +447,43 @@ def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logi
     with torch.no_grad():  # a path is not differentiable: the result is detached
         prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
                             host_max_label_length=max_label_length)
-        return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep,
-                                                                     0 if frames_per_tile is None else int(frames_per_tile)))
+        fpt = 0 if frames_per_tile is None else int(frames_per_tile)
+        if frame_window is None:
+            return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep, fpt))
+        return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep, fpt, _as_tensor(frame_window)))
 
 
 def classic_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                         blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
-                                        max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+                                        max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
     """Forced alignment of a long recording against a partial transcript, on the classic lattice: classic_ctc_wildcard_alignment
     (a label equal to WILDCARD, -2, stands for any non-empty run of frames with any tokens on them; every label gets its first and
     last frame and a label_score) for transcripts of up to 65536 labels, computed on the tiled lattice of
     classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4).  The path and the per-label
     outputs do not depend on frames_per_tile.  Returns CtcLongWildcardAlignment, not differentiable.  check_labels keeps rejecting
-    -2: it validates transcripts for the loss functions."""
+    -2: it validates transcripts for the loss functions.  frame_window as in classic_ctc_wildcard_alignment, in absolute frames:
+    approximate timestamps (subtitles, a coarse first pass) pin every label so the path cannot drift into a repeated phrase; every
+    tile of the lattice still runs."""
     return _long_wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, frames_per_tile,
-                                max_label_length)
+                                max_label_length, frame_window)
 
 
 def simplified_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                            blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
-                                           max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+                                           max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
     """The same on the simplified lattice (a wildcard owns every frame from its entry until the next label's frame).  Same arguments
     and return value as classic_ctc_long_wildcard_alignment."""
     return _long_wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
-                                frames_per_tile, max_label_length)
+                                frames_per_tile, max_label_length, frame_window)
 
 
 def ctc_long_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                               frames_per_tile: Optional[int] = None,
-                                              max_label_length: Optional[int] = None) -> CtcLongWildcardAlignment:
+                                              max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
     """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                                frames_per_tile, max_label_length)
+                                frames_per_tile, max_label_length, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -464,11 +495,12 @@ class _WildcardLossFn(torch.autograd.Function):
     interpreted).  Backward is not itself differentiable: a second derivative raises."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, frame_window):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U, weight)
+        ctx.window = {} if frame_window is None else {"frame_window": frame_window}  # (no window: the call as it always was)
         return ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
-                                      wildcard_log_weight=weight, want_grad=False)[0]
+                                      wildcard_log_weight=weight, want_grad=False, **ctx.window)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -476,12 +508,12 @@ class _WildcardLossFn(torch.autograd.Function):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U, weight = ctx.call
         _, grad = ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
-                                         wildcard_log_weight=weight)
-        return grad, None, None, None, None, None, None, None, None
+                                         wildcard_log_weight=weight, **ctx.window)
+        return grad, None, None, None, None, None, None, None, None, None
 
 
 def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                   max_label_length=None) -> torch.Tensor:
+                   max_label_length=None, frame_window=None) -> torch.Tensor:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -494,16 +526,17 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
         raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
     kind = ops.KINDS[kind_name]
+    window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
     if x.requires_grad and torch.is_grad_enabled():
-        return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight)
+        return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, window.get("frame_window"))
     with torch.no_grad():  # forward only: the result is detached
         return ops.wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
-                                      wildcard_log_weight=weight, want_grad=False)[0]
+                                      wildcard_log_weight=weight, want_grad=False, **window)[0]
 
 
 def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                               blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                              max_label_length: Optional[int] = None) -> torch.Tensor:
+                              max_label_length: Optional[int] = None, frame_window=None) -> torch.Tensor:
     """CTC loss of a partial transcript on the classic lattice (wildcard CTC / star temporal classification).  As classic_ctc_loss,
     but a label equal to WILDCARD (-2) stands for any non-empty run of frames with any tokens on them: the lattice of
     classic_ctc_wildcard_alignment, summed over all its paths instead of maximised.  Returns loss [batch] float32 = -ln Z, with a
@@ -511,27 +544,33 @@ def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_leng
     the gradient comes back in the logits' dtype and layout; a second derivative raises).  Z is a sum over lattice paths, NOT a
     probability: one token sequence can match under several segmentations, so the loss may be negative.  wildcard_log_weight <= 0
     is added to the log-emission of every wildcard frame (STC's per-frame penalty against that).  An infeasible sample (too few
-    frames -- every wildcard needs one --, a malformed label) has loss +inf and a zero gradient.  check_labels keeps rejecting -2."""
+    frames -- every wildcard needs one --, a malformed label) has loss +inf and a zero gradient.  check_labels keeps rejecting -2.
+    frame_window [batch, U, 2] int32 / int64 on the logits' device, (first, last) inclusive per
+    label position -- the convention of first_frame / last_frame; see ctc_frame_window -- lets position i own frame t only if
+    first <= t <= last: the time-restricted loss of latency-controlled training (every token within a
+    tolerance of a reference alignment).  Paths outside the windows are left out of Z, so the loss is at least the unconstrained
+    one; windows that admit no path give +inf and a zero gradient.  A transcript without wildcards is plain CTC with windows."""
     return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length)
+                          max_label_length, frame_window)
 
 
 def simplified_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                  blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                 max_label_length: Optional[int] = None) -> torch.Tensor:
+                                 max_label_length: Optional[int] = None, frame_window=None) -> torch.Tensor:
     """The same on the simplified lattice: entering a wildcard and every stay behind it emit the wildcard's weight instead of a
     token's or the blank's probability.  Same arguments and return value as classic_ctc_wildcard_loss."""
     return _wildcard_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length)
+                          max_label_length, frame_window)
 
 
 def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
-                                    wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None) -> torch.Tensor:
+                                    wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
+                                    frame_window=None) -> torch.Tensor:
     """The same for log-probabilities used as they stand: a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]);
     ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                          wildcard_log_weight, max_label_length)
+                          wildcard_log_weight, max_label_length, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -644,7 +683,7 @@ class CtcLabelPosterior(NamedTuple):
 
 
 def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                     max_label_length=None) -> CtcLabelPosterior:
+                     max_label_length=None, frame_window=None) -> CtcLabelPosterior:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -656,41 +695,44 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
     if not (weight <= 0.0) or weight == float("-inf"):
         raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
     with torch.no_grad():  # forward only: the result is detached
         return CtcLabelPosterior(*ops.label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
-                                                      _blank(blank_index), U, wildcard_log_weight=weight))
+                                                      _blank(blank_index), U, wildcard_log_weight=weight, **window))
 
 
 def classic_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                 blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+                                max_label_length: Optional[int] = None, frame_window=None) -> CtcLabelPosterior:
     """The soft alignment of a transcript on the classic lattice: the occupancy matrix of a forward-backward pass, where
     classic_ctc_alignment returns the single best path.  label_posterior[b, t, i] is the probability that frame t emits label
     position i; a frame's remaining mass is blank_posterior[b, t].  Labels may contain WILDCARD (-2), with the lattice and
     wildcard_log_weight of classic_ctc_wildcard_loss; without one this is plain CTC.  Arguments as classic_ctc_wildcard_loss
     (float32 / bfloat16 / float16 logits, any batch / time strides, read in place); returns CtcLabelPosterior, float32 on the
-    logits' device, not differentiable.  check_labels keeps rejecting -2."""
+    logits' device, not differentiable.  check_labels keeps rejecting -2.  frame_window as in classic_ctc_wildcard_loss:
+    label_posterior is exactly 0 outside a position's window and every frame still sums to 1."""
     return _label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                            max_label_length)
+                            max_label_length, frame_window)
 
 
 def simplified_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                    blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                   max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+                                   max_label_length: Optional[int] = None, frame_window=None) -> CtcLabelPosterior:
     """The same on the simplified lattice: label_posterior[b, t, i] is the probability that label i is emitted at frame t (so an
     ordinary label's duration is 1 and expected_frame is its expected emission frame); a wildcard also owns the frames spent
     behind it.  Same arguments and return value as classic_ctc_label_posterior."""
     return _label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length)
+                            wildcard_log_weight, max_label_length, frame_window)
 
 
 def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
-                                      wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None) -> CtcLabelPosterior:
+                                      wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
+                                      frame_window=None) -> CtcLabelPosterior:
     """The same for log-probabilities used as they stand (a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]));
     ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length)
+                            wildcard_log_weight, max_label_length, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -426,10 +426,26 @@ def best_path(kind: int, wrt: int, p: Prepared) -> Tuple[torch.Tensor, torch.Ten
     return score, tokens, label_index
 
 
-def wildcard_best_path(kind: int, wrt: int, p: Prepared):
+def _frame_window(what: str, frame_window: torch.Tensor, B: int, U: int, dev) -> Tuple[torch.Tensor, int]:
+    """(int32 contiguous tensor, window_stride) of a [B, >= U, 2] frame window as the windowed entry points take it: (first, last)
+    inclusive per label position.  int64 values are narrowed on the device; nothing is looked at on the host."""
+    if frame_window.dim() != 3 or int(frame_window.shape[0]) != B or int(frame_window.shape[1]) < U or int(frame_window.shape[2]) != 2:
+        raise ValueError(f"{what}: frame_window must be [B, U, 2] with B = {B} and U >= {U}, got {tuple(frame_window.shape)}")
+    if frame_window.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: frame_window must be int32 or int64, got {frame_window.dtype}")
+    if frame_window.device != dev:
+        raise ValueError(f"{what}: frame_window must be on the logits' device {dev}, got {frame_window.device}")
+    if frame_window.dtype == torch.int64:  # (frames beyond int32 do not exist: clamping keeps "before everything" / "behind everything")
+        frame_window = frame_window.clamp(-2**31, 2**31 - 1).to(torch.int32)
+    frame_window = frame_window.contiguous()
+    return frame_window, 2 * int(frame_window.shape[1])
+
+
+def wildcard_best_path(kind: int, wrt: int, p: Prepared, frame_window: Optional[torch.Tensor] = None):
     """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
     label_score[B,U] float32): the best path of the lattice whose labels may be wildcards (_lib.WILDCARD), and where every label
-    lies on it (ctc_amd_wildcard_best_path).  Reads the logits in the format `p` holds them in, as best_path does."""
+    lies on it (ctc_amd_wildcard_best_path).  Reads the logits in the format `p` holds them in, as best_path does.  frame_window
+    [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_best_path."""
     lib = _lib.load()
     score = torch.empty(p.B, dtype=torch.float32, device=p.device)
     tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
@@ -445,6 +461,13 @@ def wildcard_best_path(kind: int, wrt: int, p: Prepared):
     if n is None:
         n = _WS_BYTES[key] = _lib.wildcard_best_path_workspace_bytes(kind, p.B, p.T, p.V, p.U)
     ws = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    if frame_window is not None:
+        fw, fws = _frame_window("wildcard_best_path", frame_window, p.B, p.U, p.device)
+        with _on_device(p.device):
+            rc = lib.ctc_amd_windowed_best_path(*p.common_ex(kind, wrt)[:11], _ptr(fw), fws, p.B, p.T, p.V, p.U, *(_ptr(t) for t in out),
+                                                ws.data_ptr(), ws.numel(), _stream(p.device))
+        _lib.check(rc, "ctc_amd_windowed_best_path")
+        return out
     with _on_device(p.device):
         rc = lib.ctc_amd_wildcard_best_path(*p.common_ex(kind, wrt), *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(),
                                             _stream(p.device))
@@ -481,11 +504,11 @@ def long_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0):
     return out
 
 
-def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0):
+def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0, frame_window: Optional[torch.Tensor] = None):
     """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
     label_score[B,U] float32): wildcard_best_path for up to _lib.LONG_MAX_U label positions, on the tiled lattice of long_best_path
     (ctc_amd_long_wildcard_best_path).  Reads the logits in the format `p` holds them in; the workspace is the stream's cached
-    one, as in long_best_path."""
+    one, as in long_best_path.  frame_window as in wildcard_best_path, frames absolute: ctc_amd_long_windowed_best_path."""
     lib = _lib.load()
     score = torch.empty(p.B, dtype=torch.float32, device=p.device)
     tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
@@ -504,6 +527,13 @@ def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: i
     ws = _WS_CACHE.get(ck)
     if ws is None or ws.numel() < n:
         ws = _WS_CACHE[ck] = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    if frame_window is not None:
+        fw, fws = _frame_window("long_wildcard_best_path", frame_window, p.B, p.U, p.device)
+        with _on_device(p.device):
+            rc = lib.ctc_amd_long_windowed_best_path(*p.common_ex(kind, wrt)[:11], _ptr(fw), fws, p.B, p.T, p.V, p.U, int(frames_per_tile),
+                                                     *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(), _stream(p.device))
+        _lib.check(rc, "ctc_amd_long_windowed_best_path")
+        return out
     with _on_device(p.device):
         rc = lib.ctc_amd_long_wildcard_best_path(*p.common_ex(kind, wrt), int(frames_per_tile), *(_ptr(t) for t in out),
                                                  ws.data_ptr(), ws.numel(), _stream(p.device))
@@ -674,14 +704,14 @@ def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
 def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                        blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
                        grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
-                       want_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       want_grad: bool = True, frame_window: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(loss[B] float32, grad[B, T, V] or None): the CTC loss of transcripts whose labels may be wildcards (_lib.WILDCARD), summed
     over all paths of the lattice, and its gradient times d_loss[b] (default: ones) with respect to x (ctc_amd_wildcard_loss_grad).
     want_grad=False is the forward-only launch and returns None for the gradient.  An utterance whose loss is +inf gets a zero
     gradient and its d_loss is not interpreted.  labels [B, W]; U bounds every label_length (default: W, or the maximum inside when
     W is large).  Takes the logits as greedy_decode does (float32 / bfloat16 / float16, any batch and time strides, read in place);
-    grad has grad_dtype (default: the logits') and the logits' layout where that is dense, a contiguous one otherwise.  Does not
-    synchronise."""
+    grad has grad_dtype (default: the logits') and the logits' layout where that is dense, a contiguous one otherwise.
+    frame_window [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_loss_grad.  Does not synchronise."""
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -709,6 +739,15 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
         return loss, grad
     ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None
     gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
+    if frame_window is not None:
+        fw, fws = _frame_window("wildcard_loss_grad", frame_window, B, U, dev)
+        with _on_device(dev):
+            rc = lib.ctc_amd_windowed_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                _ptr(label_length), _ptr(logit_length), int(blank), _ptr(fw), fws,
+                                                float(wildcard_log_weight), B, T, V, U, _ptr(d_loss), _ptr(loss),
+                                                _ptr(grad) if with_grad else None, _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_windowed_loss_grad")
+        return loss, grad
     with _on_device(dev):
         rc = lib.ctc_amd_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
                                             _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
@@ -770,12 +809,14 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
 
 
 def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
-                    blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True):
+                    blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True,
+                    frame_window: Optional[torch.Tensor] = None):
     """(loss[B], label_posterior[B, T, U], blank_posterior[B, T], duration[B, U], expected_frame[B, U]), all float32: with what
     probability every frame belongs to every label position (or to the blank) over all paths of the lattice, and per position the
     expected number of frames and the soft timestamp (ctc_amd_label_posterior).  Labels may be wildcards (_lib.WILDCARD); the loss
     is wildcard_loss_grad's forward-only one, bit for bit.  want_stats=False skips the statistics launch and returns None for the
-    last two.  Arguments as wildcard_loss_grad; every element of every output is written.  Does not synchronise."""
+    last two.  Arguments as wildcard_loss_grad (frame_window: ctc_amd_windowed_label_posterior); every element of every output is
+    written.  Does not synchronise."""
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -795,6 +836,15 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     if B == 0:
         return loss, post, blk, dur, exf
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    if frame_window is not None:
+        fw, fws = _frame_window("label_posterior", frame_window, B, U, dev)
+        with _on_device(dev):
+            rc = lib.ctc_amd_windowed_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                      _ptr(label_length), _ptr(logit_length), int(blank), _ptr(fw), fws,
+                                                      float(wildcard_log_weight), B, T, V, U, _ptr(loss), _ptr(post), _ptr(blk),
+                                                      _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_windowed_label_posterior")
+        return loss, post, blk, dur, exf
     with _on_device(dev):
         rc = lib.ctc_amd_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
                                          _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
