@@ -1191,7 +1191,7 @@ int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_l
 
 /*
  * Frame windows per label: time-constrained CTC loss, posteriors and forced alignment (added under ABI v6: four new entry points,
- * nothing existing changed).  A caller who knows roughly where every label belongs -- a reference alignment and a tolerance
+ * then the three long-form ones of the loss, its checkpointed twin and the label posteriors; nothing existing changed).  A caller who knows roughly where every label belongs -- a reference alignment and a tolerance
  * (alignment-restricted training), subtitles or a coarse first pass, another model's first_frame / last_frame or expected_frame --
  * says so per label POSITION.  A mask on the logits cannot: it is per token, and the same token at two positions needs two masks.
  *
@@ -1202,6 +1202,10 @@ int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_l
  *   ctc_amd_windowed_label_posterior   ctc_amd_label_posterior
  *   ctc_amd_windowed_best_path         ctc_amd_wildcard_best_path
  *   ctc_amd_long_windowed_best_path    ctc_amd_long_wildcard_best_path   (U <= CTC_AMD_LONG_MAX_U)
+ *   ctc_amd_long_windowed_loss_grad        ctc_amd_long_wildcard_loss_grad        (U <= CTC_AMD_LONG_MAX_U; the loss alone, or with
+ *                                                                                  its gradient from the per-frame workspace)
+ *   ctc_amd_long_windowed_loss_grad_ckpt   ctc_amd_long_wildcard_loss_grad_ckpt   (the same bits from tile checkpoints)
+ *   ctc_amd_long_windowed_label_posterior  ctc_amd_long_label_posterior           (label_posterior may be NULL, as there)
  *   frame_window   int32 [B][window_stride] device memory: (first, last) = frame_window[b * window_stride + 2 i], [.. + 2 i + 1]
  *                  for label position i, BOTH INCLUSIVE -- the convention of the first_frame / last_frame outputs, which can be
  *                  fed back in.  NULL: the unwindowed call, bit for bit, whatever window_stride holds.
@@ -1226,7 +1230,12 @@ int ctc_amd_edit_counts(const int32_t *hyp, int hyp_stride, const int32_t *hyp_l
  *   - label_posterior is exactly 0 outside a position's window; every frame's posteriors still sum to 1.
  * Windows that cover every frame return the bits of the unwindowed call for every output.  Long-form: frames are absolute; no
  * output depends on where a window's edges fall relative to time blocks or label blocks, on frames_per_tile or on the batch, as for
- * the counterpart.  Tiles that no window reaches still run.
+ * the counterpart.  Tiles that no window reaches still run.  That holds for the three long-form calls of the
+ * summed lattice as for the alignment: the pair of position i is frame_window[b * window_stride + 2 i], [.. + 2 i + 1] for every
+ * i < label_length[b] <= CTC_AMD_LONG_MAX_U, whichever label block i falls into; ctc_amd_long_windowed_loss_grad_ckpt returns the
+ * bits of ctc_amd_long_windowed_loss_grad and the loss of ctc_amd_long_windowed_label_posterior is theirs; an hour aligned with
+ * ctc_amd_long_windowed_best_path (or unconstrained) and widened by a tolerance is a valid window for all three (DESIGN.md
+ * section 5.25).
  * Numerics, determinism and cost are the counterparts': the producers compare the frame with the two bounds as they gather the
  * emissions, one block ahead of the chain.
  */
@@ -1262,6 +1271,31 @@ int ctc_amd_long_windowed_best_path(int kind, int wrt,
                                     int B, int T, int V, int U, int frames_per_tile,
                                     float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
                                     float *label_score, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_windowed_loss_grad(int kind, int wrt,
+                                    const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride,
+                                    const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                    const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                                    float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                    const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                    int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_windowed_loss_grad_ckpt(int kind, int wrt,
+                                         const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                         const int32_t *labels, int label_stride,
+                                         const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                         const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                                         float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                         const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                         int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_windowed_label_posterior(int kind, int wrt,
+                                          const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                          const int32_t *labels, int label_stride,
+                                          const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                          const int32_t *frame_window /* [B][window_stride], may be NULL */, int window_stride,
+                                          float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                          float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                          float *expected_frame, float *peak_posterior, int32_t *peak_frame,
+                                          void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,12 @@
 // checkpoint and a saved row live is long_loss_ckpt_index / long_loss_row_index (ctc_loss_long_plan.h) in both layouts.
 // ctc_amd_long_label_posterior is that schedule with the posterior stage in the row stage's place: the ring
 // rows of a time block become label_posterior / blank_posterior rows and, carried from block to block, the per-position sums and peaks.
+// Frame windows (WIN; ctc_amd_long_windowed_loss_grad / _grad_ckpt / _label_posterior): every lane holds the
+// (first, last) frames of its own NL positions, and the producers of both tiles store -inf for a position's slot at an absolute frame
+// outside its pair -- in a wildcard's slot (which holds -inf otherwise and is never read) the gate 0 / -inf that the chain adds to the
+// wave-uniform e_w.  MODE 3 carries the gate of the forward sweep, so its saved rows are that sweep's bits.  Nothing behind the ring
+// knows of windows: the row statistics, columns, rows, checkpoints, the skip tests (a window only takes frames away), the finish
+// kernels, the row stage and the posterior stage are those of the unwindowed call.
 // Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all of them; nothing unwritten is read.  No workgroup
 // waits for another: no flags, no cooperative launch, no floating-point atomics, vector stores only, one writer per element.
 #include "ctc_loss_long.h"
@@ -109,9 +115,10 @@ __device__ __forceinline__ void ll_labels(const Problem &p, int b, int k, int L,
   }
 }
 
-template <int KIND, int MODE>
+template <int KIND, int MODE, bool WIN>
 __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Problem p, const double w2, const LongLossWs w, int K, int TF,
-                                                                     int d, int k_lo, int count) {
+                                                                     int d, int k_lo, int count, const int32_t *__restrict__ win,
+                                                                     int wstride) {
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
   constexpr int SRD = long_loss_row_doubles(KIND);
   constexpr bool CKPT = MODE >= 2;               // row in / row out: the checkpoints of tiles (k, j - 1) / (k, j)
@@ -145,6 +152,16 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   for (int q = 0; q < NL; ++q) {
     lab[q] = lab_s[1 + lane * NL + q];
     if (lab[q] == LONG_LOSS_WILDCARD) wild |= 1u << q;
+  }
+  [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position k * UB + lane * NL + q may own (from label_length on: never read, empty)
+  if constexpr (WIN) {
+    const int32_t *const wb = win + (size_t)b * wstride;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const int g = k * UB + lane * NL + q;
+      wf[q] = g < L ? wb[2 * (size_t)g] : 0;
+      wl[q] = g < L ? wb[2 * (size_t)g + 1] : -1;
+    }
   }
 
   const int esz = dt == 0 ? 4 : 2;
@@ -209,7 +226,14 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
     }
     float *const r = ring + ((kb & 1) * F + f) * RS;
 #pragma unroll
-    for (int q = 0; q < NL; ++q) r[lane * NL + q] = e[q];
+    for (int q = 0; q < NL; ++q) {
+      float v = e[q];
+      if constexpr (WIN) {
+        if ((wild >> q) & 1u) v = 0.f;  // the gate of e_w
+        if (t < wf[q] || t > wl[q]) v = -__builtin_inff();  // (t: the absolute frame, in the beta tile too)
+      }
+      r[lane * NL + q] = v;
+    }
     if (lane == 0) *reinterpret_cast<float4 *>(r + UB) = sv;
     if (k > 0 && lane < 2) col_s[kb & 1][f][lane] = col_in[(size_t)t * 2 + lane];
   };
@@ -225,7 +249,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
-      auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
+      auto ewq = [&](int q) { return WIN ? fr.ew + (double)e[q] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      auto em = [&](int q) { return ((wild >> q) & 1u) ? ewq(q) : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = SAVE ? myrows + (size_t)(t0 + f - t_base) * SRD : nullptr;
       if (SAVE && KIND == 1) {  // the state BEFORE the frame
 #pragma unroll
@@ -255,7 +280,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
 #pragma unroll
         for (int q = NL - 1; q >= 0; --q) {
           const double s = q > 0 ? C[q > 0 ? q - 1 : 0] : pS;
-          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? fr.ew : eb), s + em(q));
+          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? ewq(q) : eb), s + em(q));
         }
       }
       cs += eb;
@@ -323,9 +348,10 @@ __global__ __launch_bounds__(256) void loss_long_finish_ckpt_kernel(const Proble
 }
 
 // CKPT: the saved rows are the ring's (long_loss_row_index), written by alpha MODE 3 on the launch before this one
-template <int KIND, bool CKPT>
+template <int KIND, bool CKPT, bool WIN>
 __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Problem p, const double w2, const LongLossWs w, int K, int TF,
-                                                                    int d, int k_lo, int count) {
+                                                                    int d, int k_lo, int count, const int32_t *__restrict__ win,
+                                                                    int wstride) {
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
   constexpr int SRD = long_loss_row_doubles(KIND);
   const double NINF = -__builtin_inf();
@@ -357,6 +383,16 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
   for (int q = 0; q < NL; ++q) {
     lab[q] = lab_s[1 + lane * NL + q];
     if (lab[q] == LONG_LOSS_WILDCARD) wild |= 1u << q;
+  }
+  [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position k * UB + lane * NL + q may own (from label_length on: never read, empty)
+  if constexpr (WIN) {
+    const int32_t *const wb = win + (size_t)b * wstride;
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      const int g = k * UB + lane * NL + q;
+      wf[q] = g < L ? wb[2 * (size_t)g] : 0;
+      wl[q] = g < L ? wb[2 * (size_t)g + 1] : -1;
+    }
   }
 
   const int esz = dt == 0 ? 4 : 2;
@@ -410,7 +446,14 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
     }
     float *const r = ring + ((kb & 1) * F + f) * RS;
 #pragma unroll
-    for (int q = 0; q < NL; ++q) r[lane * NL + q] = e[q];
+    for (int q = 0; q < NL; ++q) {
+      float v = e[q];
+      if constexpr (WIN) {
+        if ((wild >> q) & 1u) v = 0.f;  // the gate of e_w
+        if (t < wf[q] || t > wl[q]) v = -__builtin_inff();  // (t: the absolute frame, in the beta tile too)
+      }
+      r[lane * NL + q] = v;
+    }
     if (lane == 0) {
       *reinterpret_cast<float4 *>(r + UB) = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (the alpha sweep stored it)
       col_s[kb & 1][f][0] = colb_in ? colb_in[t] : NINF;
@@ -431,7 +474,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
       for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
-      auto em = [&](int q) { return ((wild >> q) & 1u) ? fr.ew : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
+      auto ewq = [&](int q) { return WIN ? fr.ew + (double)e[q] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      auto em = [&](int q) { return ((wild >> q) & 1u) ? ewq(q) : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = myrows + (size_t)(t - t_base) * SRD;
       double A[NS], Acs = NINF;
 #pragma unroll
@@ -463,7 +507,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
           const double ap = q > 0 ? A[q > 0 ? q - 1 : 0] : ap0;
-          const double h = ((wild >> q) & 1u) ? fr.ew : eb;
+          const double h = ((wild >> q) & 1u) ? ewq(q) : eb;
           *reinterpret_cast<float2 *>(r + lane * NS + q) = make_float2(post(ap + em(q) + C[q]), post(A[q] + h + C[q]));
         }
         if (k == 0 && lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
@@ -474,7 +518,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
           const double xn = q + 1 < NL ? C[q + 1 < NL ? q + 1 : 0] + em(q + 1 < NL ? q + 1 : 0) : xl;
-          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? fr.ew : eb), xn);
+          C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? ewq(q) : eb), xn);
           x = xn;
         }
       }
@@ -770,16 +814,34 @@ __global__ __launch_bounds__(64 * LONG_POST_WAVES) void loss_long_post_kernel(co
   }
 }
 
+// the window of a call: nullptr runs the WIN = false kernels
+struct LlWindow {
+  const int32_t *win;
+  int stride;
+};
+
+template <int KIND, int MODE>
+void launch_alpha(const Problem &p, const LongLossPlan &P, double w2, const LongLossWs &w, const LlWindow &fw, int d, int k_lo, int count,
+                  hipStream_t st) {
+  const auto tile = fw.win ? loss_long_alpha_kernel<KIND, MODE, true> : loss_long_alpha_kernel<KIND, MODE, false>;
+  hipLaunchKernelGGL(tile, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
+}
+template <int KIND, bool CKPT>
+void launch_beta(const Problem &p, const LongLossPlan &P, double w2, const LongLossWs &w, const LlWindow &fw, int d, int k_lo, int count,
+                 hipStream_t st) {
+  const auto tile = fw.win ? loss_long_beta_kernel<KIND, CKPT, true> : loss_long_beta_kernel<KIND, CKPT, false>;
+  hipLaunchKernelGGL(tile, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
+}
+
 template <int KIND>
 hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
-                    const LongLossWs &w, hipStream_t st) {
+                    const LongLossWs &w, const LlWindow &fw, hipStream_t st) {
   if (p.T > 0) {
     for (int d = 0; d < P.launches; ++d) {
       int k_lo, count;
       long_loss_forward_diagonal(P, d, &k_lo, &count);
-      const dim3 grid((unsigned)((size_t)p.B * count));
-      if (grad) hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 1>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
-      else hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 0>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+      if (grad) launch_alpha<KIND, 1>(p, P, w2, w, fw, d, k_lo, count, st);
+      else launch_alpha<KIND, 0>(p, P, w2, w, fw, d, k_lo, count, st);
     }
   }
   hipLaunchKernelGGL(loss_long_finish_kernel<KIND>, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, st, p, w, P.K, loss);
@@ -787,8 +849,7 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
   for (int e = 0; e < P.launches; ++e) {
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
-    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, false>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d,
-                       k_lo, count);
+    launch_beta<KIND, false>(p, P, w2, w, fw, d, k_lo, count, st);
   }
   const unsigned blocks = (unsigned)(((long)p.B * p.T + LLG_WAVES - 1) / LLG_WAVES);
   hipLaunchKernelGGL(loss_long_row_kernel<KIND>, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, d_loss, grad);
@@ -802,7 +863,7 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
 // diagonal d - 1 (ctc_loss_long_plan.h), behind this row stage on the stream.
 template <int KIND>
 hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, const float *d_loss, float *loss, void *grad,
-                         const LongLossWs &w, hipStream_t st, const LongPostOut *post = nullptr) {
+                         const LongLossWs &w, const LlWindow &fw, hipStream_t st, const LongPostOut *post = nullptr) {
   // post: ctc_amd_long_label_posterior, the posterior stage in the row stage's place (grad is nullptr)
   const bool per_label = post && p.U > 0 && (post->dur || post->peak);
   const unsigned stat_groups = per_label ? (unsigned)long_post_stat_groups(p.B, p.U) : 0u;
@@ -816,8 +877,7 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
     for (int d = 0; d < P.launches; ++d) {
       int k_lo, count;
       long_loss_forward_diagonal(P, d, &k_lo, &count);
-      hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 2>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K,
-                         P.TF, d, k_lo, count);
+      launch_alpha<KIND, 2>(p, P, w2, w, fw, d, k_lo, count, st);
     }
   }
   hipLaunchKernelGGL(loss_long_finish_ckpt_kernel<KIND>, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0, st, p, w, P.K, P.TF, loss);
@@ -828,9 +888,8 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
   for (int e = 0; e < P.launches; ++e) {
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
-    const dim3 grid((unsigned)((size_t)p.B * count));
-    hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, 3>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
-    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, true>), grid, dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count);
+    launch_alpha<KIND, 3>(p, P, w2, w, fw, d, k_lo, count, st);
+    launch_beta<KIND, true>(p, P, w2, w, fw, d, k_lo, count, st);
     if (d < P.J) {
       const int t0 = d * P.TF, nt = p.T - t0 < P.TF ? p.T - t0 : P.TF;
       if (post) { post_stage(d, nt); continue; }
@@ -857,17 +916,19 @@ LongLossWs long_loss_ws(char *ws, const LongLossPlan &P) {
 }  // namespace
 
 hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
-                         char *ws, hipStream_t st) {
+                         char *ws, hipStream_t st, const int32_t *frame_window, int window_stride) {
   if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad)) return hipErrorInvalidValue;
   const LongLossWs w = long_loss_ws(ws, P);
+  const LlWindow fw{frame_window, window_stride};
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
-  if (P.ckpt) return p.kind == 0 ? run_kind_ckpt<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind_ckpt<1>(p, P, w2, d_loss, loss, grad, w, st);
-  return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, st);
+  if (P.ckpt)
+    return p.kind == 0 ? run_kind_ckpt<0>(p, P, w2, d_loss, loss, grad, w, fw, st) : run_kind_ckpt<1>(p, P, w2, d_loss, loss, grad, w, fw, st);
+  return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, fw, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, fw, st);
 }
 
 hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss, float *label_posterior,
                                     float *blank_posterior, float *duration, float *expected_frame, float *peak_posterior,
-                                    int *peak_frame, char *ws, hipStream_t st) {
+                                    int *peak_frame, char *ws, hipStream_t st, const int32_t *frame_window, int window_stride) {
   if (p.kind < 0 || p.kind > 1 || !P.L.ckpt || !duration != !expected_frame || !peak_posterior != !peak_frame) return hipErrorInvalidValue;
   const LongLossWs w = long_loss_ws(ws, P.L);
   LongPostOut o;
@@ -875,8 +936,10 @@ hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, flo
   o.dur = duration; o.exf = expected_frame; o.peak = peak_posterior; o.peak_frame = peak_frame;
   o.acc = reinterpret_cast<double2 *>(ws + P.off_acc);
   o.pk = reinterpret_cast<float2 *>(ws + P.off_peak);
+  const LlWindow fw{frame_window, window_stride};
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
-  return p.kind == 0 ? run_kind_ckpt<0>(p, P.L, w2, nullptr, loss, nullptr, w, st, &o) : run_kind_ckpt<1>(p, P.L, w2, nullptr, loss, nullptr, w, st, &o);
+  return p.kind == 0 ? run_kind_ckpt<0>(p, P.L, w2, nullptr, loss, nullptr, w, fw, st, &o)
+                     : run_kind_ckpt<1>(p, P.L, w2, nullptr, loss, nullptr, w, fw, st, &o);
 }
 
 }  // namespace ctc

@@ -18,7 +18,7 @@ All arithmetic is done by the HIP kernels behind the C ABI (include/ctc_amd.h); 
 """
 from __future__ import annotations
 
-from functools import cached_property
+from functools import cached_property, partial
 from typing import NamedTuple, Optional, Union
 
 import numpy as np
@@ -267,8 +267,8 @@ WILDCARD = _lib.WILDCARD  # -2: the label value of a wildcard position
 
 def ctc_frame_window(first_frame: TensorLike, last_frame: TensorLike, logit_length: TensorLike, *, before: int = 0,
                      after: int = 0) -> torch.Tensor:
-    """frame_window [batch, U, 2] int32 for the `frame_window` argument of the wildcard loss, label posterior and (long) wildcard
-    alignment functions: (first_frame - before, last_frame + after), clipped to [0, logit_length - 1], on the device of
+    """frame_window [batch, U, 2] int32 for the `frame_window` argument of the (long) wildcard loss, (long) label posterior and
+    (long) wildcard alignment functions: (first_frame - before, last_frame + after), clipped to [0, logit_length - 1], on the device of
     first_frame and without a synchronisation.  first_frame / last_frame [batch, U] are an alignment's (CtcWildcardAlignment and
     its long-form twin), or a rounded CtcLabelPosterior.expected_frame given twice; `before` / `after` are the tolerance in frames.
     Positions from label_length on (-1 in both) come out as some clipped pair and are ignored by the calls."""
@@ -576,29 +576,37 @@ def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_lengt
 # --------------------------------------------------------------------------------------------------
 # long-form loss and gradient (transcripts beyond 1024 labels, wildcards included): an extension, no counterpart in the reference
 # --------------------------------------------------------------------------------------------------
+def _long_loss_call(frame_window):
+    """ops.long_wildcard_loss_grad, or with a window ops.long_windowed_loss_grad bound to it (no window: the call as it always was)."""
+    if frame_window is None:
+        return ops.long_wildcard_loss_grad
+    return partial(ops.long_windowed_loss_grad, frame_window)
+
+
 class _LongLossFn(torch.autograd.Function):
     """_WildcardLossFn on ops.long_wildcard_loss_grad: forward is the forward-only call and keeps nothing but the inputs; backward is
     ONE call with d_loss.  Backward is not itself differentiable: a second derivative raises."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf, checkpoint):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf, checkpoint, frame_window):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U, weight, tf, checkpoint)
-        return ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
-                                           wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
+        ctx.window = frame_window
+        return _long_loss_call(frame_window)(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
+                                             wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_loss):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U, weight, tf, checkpoint = ctx.call
-        _, grad = ops.long_wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
+        _, grad = _long_loss_call(ctx.window)(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
                                               wildcard_log_weight=weight, frames_per_tile=tf, checkpoint=checkpoint)
-        return grad, None, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-               frames_per_tile=None, max_label_length=None, checkpoint=False) -> torch.Tensor:
+               frames_per_tile=None, max_label_length=None, checkpoint=False, frame_window=None) -> torch.Tensor:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -612,17 +620,19 @@ def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, 
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
     kind = ops.KINDS[kind_name]
     tf = 0 if frames_per_tile is None else int(frames_per_tile)
+    window = None if frame_window is None else _as_tensor(frame_window)
     if x.requires_grad and torch.is_grad_enabled():
-        return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf, bool(checkpoint))
+        return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf, bool(checkpoint),
+                                 window)
     with torch.no_grad():  # forward only: the result is detached
-        return ops.long_wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
-                                           wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
+        return _long_loss_call(window)(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
+                                       wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
 
 
 def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                           blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                           frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
-                          checkpoint: bool = False) -> torch.Tensor:
+                          checkpoint: bool = False, frame_window=None) -> torch.Tensor:
     """CTC loss of a long recording on the classic lattice: classic_ctc_wildcard_loss (without a WILDCARD label, -2, the plain CTC
     loss; with one, the loss of a partial transcript) for transcripts of up to 65536 labels, computed on the tiled lattice of
     classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4; the loss and the gradient do not
@@ -635,30 +645,34 @@ def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: 
     8 * batch * K * (J * 2056 + min(K, J) * TF * 2050) bytes in place of the term above (1026 for 2050 on the simplified lattice),
     23 times less at ten minutes of audio, and an hour (180 000 frames, 50 000 labels) takes 6.4 GB in place of 144.9 GB; it costs
     one more forward sweep, and frames_per_tile then trades memory: the ring grows with it, the checkpoints shrink.  Forward is the
-    same call either way.  check_labels keeps rejecting -2."""
+    same call either way.  check_labels keeps rejecting -2.  frame_window [batch, U, 2] as in classic_ctc_wildcard_loss, in absolute
+    frames and for every label block: the windows ctc_frame_window makes of a classic_ctc_long_wildcard_alignment hold every token of
+    the recording within a tolerance of that alignment, with either `checkpoint` setting and the same bits from both; no result
+    depends on where a window's edges fall relative to tiles.  The workspaces are those of the unwindowed call."""
     return _long_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint)
+                      frames_per_tile, max_label_length, checkpoint, frame_window)
 
 
 def simplified_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                              blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                              frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
-                             checkpoint: bool = False) -> torch.Tensor:
+                             checkpoint: bool = False, frame_window=None) -> torch.Tensor:
     """The same on the simplified lattice.  Same arguments and return value as classic_ctc_long_loss; backward holds
-    8 * batch * K * max_length * 1026 bytes, with checkpoint=True 8 * batch * K * (J * 2056 + min(K, J) * TF * 1026), the same bits."""
+    8 * batch * K * max_length * 1026 bytes, with checkpoint=True 8 * batch * K * (J * 2056 + min(K, J) * TF * 1026), the same bits.
+    frame_window as in classic_ctc_long_loss: a wildcard's horizontal frames obey its window too."""
     return _long_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint)
+                      frames_per_tile, max_label_length, checkpoint, frame_window)
 
 
 def ctc_long_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                 wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
-                                max_label_length: Optional[int] = None, checkpoint: bool = False) -> torch.Tensor:
+                                max_label_length: Optional[int] = None, checkpoint: bool = False, frame_window=None) -> torch.Tensor:
     """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The
     gradient is with respect to logprobas.  checkpoint and both workspace formulas as in classic_ctc_long_loss /
-    simplified_ctc_long_loss: the same bits from the smaller workspace."""
+    simplified_ctc_long_loss: the same bits from the smaller workspace.  frame_window as in classic_ctc_long_loss."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint)
+                      frames_per_tile, max_label_length, checkpoint, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -756,7 +770,7 @@ class CtcLongLabelPosterior(NamedTuple):
 
 
 def _long_label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                          frames_per_tile=None, max_label_length=None, dense=True) -> CtcLongLabelPosterior:
+                          frames_per_tile=None, max_label_length=None, dense=True, frame_window=None) -> CtcLongLabelPosterior:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -769,10 +783,11 @@ def _long_label_posterior(kind_name: str, wrt: int, labels, x, label_length, log
         raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
     tf = 0 if frames_per_tile is None else int(frames_per_tile)
+    window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
     with torch.no_grad():  # forward only: the result is detached
         return CtcLongLabelPosterior(*ops.long_label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
                                                                _blank(blank_index), U, wildcard_log_weight=weight, frames_per_tile=tf,
-                                                               dense=bool(dense)))
+                                                               dense=bool(dense), **window))
 
 
 def classic_ctc_long_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
@@ -786,7 +801,8 @@ def classic_ctc_long_label_posterior(labels: TensorLike, logits: TensorLike, lab
     expected duration, the soft timestamp, and the peak posterior with its frame.  dense=False leaves the
     [batch, max_length, U] float32 matrix out (36 GB for an hour of audio with 50 000 labels) and returns None in its place; every
     other output keeps its bits, the per-label statistics coming straight from the sweep.  Labels may contain WILDCARD (-2).
-    Arguments as classic_ctc_long_loss; returns CtcLongLabelPosterior on the logits' device, not differentiable."""
+    Arguments as classic_ctc_long_loss; returns CtcLongLabelPosterior on the logits' device, not differentiable.  With frame
+    windows: classic_ctc_long_windowed_label_posterior."""
     return _long_label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
                                  wildcard_log_weight, frames_per_tile, max_label_length, dense)
 
@@ -808,6 +824,40 @@ def ctc_long_label_posterior_from_logproba(labels, logprobas, label_length, logi
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
                                  wildcard_log_weight, frames_per_tile, max_label_length, dense)
+
+
+def classic_ctc_long_windowed_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                              blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                              frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
+                                              dense: bool = True, frame_window=None) -> CtcLongLabelPosterior:
+    """classic_ctc_long_label_posterior with frame windows: frame_window [batch, U, 2] as in classic_ctc_long_loss, in absolute
+    frames and for every label block (see ctc_frame_window).  The loss is the windowed long loss's, label_posterior is exactly 0
+    outside a position's window and every frame still sums to 1; dense=False works with windows.  frame_window=None is
+    classic_ctc_long_label_posterior, bit for bit.  (A function of its own because the signature of the unwindowed one is kept as it
+    is.)  Returns CtcLongLabelPosterior on the logits' device, not differentiable."""
+    return _long_label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, frame_window)
+
+
+def simplified_ctc_long_windowed_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike,
+                                                 logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                                                 wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                                 max_label_length: Optional[int] = None, dense: bool = True,
+                                                 frame_window=None) -> CtcLongLabelPosterior:
+    """The same on the simplified lattice: simplified_ctc_long_label_posterior with frame windows.  Same arguments and return value
+    as classic_ctc_long_windowed_label_posterior."""
+    return _long_label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, frame_window)
+
+
+def ctc_long_windowed_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None,
+                                                    *, wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                                    max_label_length: Optional[int] = None, dense: bool = True,
+                                                    frame_window=None) -> CtcLongLabelPosterior:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, frame_window)
 
 
 # --------------------------------------------------------------------------------------------------

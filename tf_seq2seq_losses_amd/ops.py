@@ -768,7 +768,28 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
     (8 * B * ceil(U / 1024) * T * (S * 1024 + 2) bytes, S = 2 classic / 1 simplified).  checkpoint=True is
     ctc_amd_long_wildcard_loss_grad_ckpt: the same bits from a workspace of one checkpoint per tile and a ring of
     min(K, J) * frames_per_tile frames of that state (K = ceil(U / 1024), J = ceil(T / frames_per_tile)) in place of T frames, for
-    one more alpha sweep; frames_per_tile then trades memory (the ring grows with it, the checkpoints shrink).  Does not synchronise."""
+    one more alpha sweep; frames_per_tile then trades memory (the ring grows with it, the checkpoints shrink).  With frame windows:
+    long_windowed_loss_grad.  Does not synchronise."""
+    return _long_loss_grad(None, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                           want_grad, frames_per_tile, checkpoint)
+
+
+def long_windowed_loss_grad(frame_window: torch.Tensor, kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor,
+                            label_length: torch.Tensor, logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None,
+                            U: Optional[int] = None, grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
+                            want_grad: bool = True, frames_per_tile: int = 0,
+                            checkpoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """long_wildcard_loss_grad with frame_window [B, U, 2] in front of its arguments, as in wildcard_loss_grad and in absolute
+    frames: ctc_amd_long_windowed_loss_grad / _grad_ckpt, on the same workspaces.  Every other argument and the return value as
+    long_wildcard_loss_grad, whose signature stays as it is.  Does not synchronise."""
+    if frame_window is None:
+        raise ValueError("long_windowed_loss_grad: frame_window is required (without one: long_wildcard_loss_grad)")
+    return _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype,
+                           wildcard_log_weight, want_grad, frames_per_tile, checkpoint)
+
+
+def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                    want_grad, frames_per_tile, checkpoint):
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"long_wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("long_wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -798,6 +819,17 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
         return loss, grad
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
+    if frame_window is not None:
+        fw, fws = _frame_window("long_windowed_loss_grad", frame_window, B, U, dev)
+        wname = "long_windowed_loss_grad_ckpt" if checkpoint else "long_windowed_loss_grad"
+        with _on_device(dev):
+            call = lib.ctc_amd_long_windowed_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_windowed_loss_grad
+            rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                      _ptr(label_length), _ptr(logit_length), int(blank), _ptr(fw), fws, float(wildcard_log_weight), B, T, V, U,
+                      int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
+                      _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_" + wname)
+        return loss, grad
     with _on_device(dev):
         call = lib.ctc_amd_long_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_wildcard_loss_grad
         rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
@@ -855,14 +887,16 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
 
 def long_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
                          logit_length: torch.Tensor, blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0,
-                         frames_per_tile: int = 0, dense: bool = True, want_stats: bool = True, want_peak: bool = True):
+                         frames_per_tile: int = 0, dense: bool = True, want_stats: bool = True, want_peak: bool = True,
+                         frame_window: Optional[torch.Tensor] = None):
     """(loss[B], label_posterior[B, T, U] or None, blank_posterior[B, T], duration[B, U], expected_frame[B, U], peak_posterior[B, U]
     float32, peak_frame[B, U] int32): label_posterior for up to _lib.LONG_MAX_U label positions, on the tiled lattice and from the
     workspace of long_wildcard_loss_grad(checkpoint=True) (ctc_amd_long_label_posterior).  dense=False returns None for the
     [B, T, U] matrix, which is then neither allocated nor written; every other output keeps its bits.  peak_posterior is
     max_t label_posterior and peak_frame the lowest frame that attains it (0 / -1 from label_length on).  want_stats=False /
-    want_peak=False return None for the pair.  frames_per_tile as in long_wildcard_loss_grad; no output depends on it.  Every element
-    of every output is written.  Does not synchronise."""
+    want_peak=False return None for the pair.  frames_per_tile as in long_wildcard_loss_grad; no output depends on it.  frame_window
+    as in label_posterior, frames absolute: ctc_amd_long_windowed_label_posterior.  Every element of every output is written.  Does
+    not synchronise."""
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"long_label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("long_label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -884,6 +918,16 @@ def long_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Ten
     if B == 0:
         return loss, post, blk, dur, exf, peak, pfr
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    if frame_window is not None:
+        fw, fws = _frame_window("long_label_posterior", frame_window, B, U, dev)
+        with _on_device(dev):
+            rc = lib.ctc_amd_long_windowed_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                           _ptr(label_length), _ptr(logit_length), int(blank), _ptr(fw), fws,
+                                                           float(wildcard_log_weight), B, T, V, U, int(frames_per_tile), _ptr(loss),
+                                                           _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(peak), _ptr(pfr), _ptr(ws), n,
+                                                           _stream(dev))
+        _lib.check(rc, "ctc_amd_long_windowed_label_posterior")
+        return loss, post, blk, dur, exf, peak, pfr
     with _on_device(dev):
         rc = lib.ctc_amd_long_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
                                               _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
