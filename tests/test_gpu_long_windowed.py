@@ -48,9 +48,11 @@ def short_fns(kind):
             ctc.classic_ctc_label_posterior if c else ctc.simplified_ctc_label_posterior)
 
 
-def run_long(kind, wrt, x, labels, ll, tl, window, weight=WEIGHT, checkpoint=False, dense=True, post=True, short=False, **kw):
+def run_long(kind, wrt, x, labels, ll, tl, window, weight=WEIGHT, checkpoint=False, dense=True, post=True, short=False, blank=0,
+             d_loss=None, **kw):
     """The windowed long-form loss + gradient (one `checkpoint` setting) and, with `post`, the label posteriors, as a dict of CPU
-    tensors.  window=None passes no frame_window at all.  short: the short-form calls on the same arguments instead."""
+    tensors.  window=None passes no frame_window at all.  short: the short-form calls on the same arguments instead.  d_loss: the
+    grad_outputs of the loss (default: its sum, that is ones)."""
     loss_fn, post_fn = short_fns(kind) if short else fns(kind, wrt)[:2]
     if window is None and not short:
         post_fn = fns(kind, wrt)[3]  # no window: the function that has no such keyword
@@ -58,12 +60,12 @@ def run_long(kind, wrt, x, labels, ll, tl, window, weight=WEIGHT, checkpoint=Fal
     lab, l1, l2 = dev(labels), dev(ll), dev(tl)
     xt = dev(x).clone().requires_grad_(True)
     ck = {} if short else {"checkpoint": checkpoint}
-    loss = loss_fn(lab, xt, l1, l2, 0, wildcard_log_weight=weight, **ck, **wk, **kw)
-    (grad,) = torch.autograd.grad(loss.sum(), xt)
+    loss = loss_fn(lab, xt, l1, l2, blank, wildcard_log_weight=weight, **ck, **wk, **kw)
+    (grad,) = torch.autograd.grad(loss.sum(), xt) if d_loss is None else torch.autograd.grad(loss, xt, dev(d_loss))
     out = dict(loss=loss.detach(), grad=grad)
     if post:
         dk = {} if short else {"dense": dense}
-        p = post_fn(lab, dev(x), l1, l2, 0, wildcard_log_weight=weight, **dk, **wk, **kw)
+        p = post_fn(lab, dev(x), l1, l2, blank, wildcard_log_weight=weight, **dk, **wk, **kw)
         out.update({"p_" + k: v for k, v in p._asdict().items() if v is not None})
     torch.cuda.synchronize()
     return {k: v.cpu() for k, v in out.items()}
@@ -72,16 +74,20 @@ def run_long(kind, wrt, x, labels, ll, tl, window, weight=WEIGHT, checkpoint=Fal
 _ORACLE = {}
 
 
-def oracle(key, kind, wrt, x64, labels, ll, tl, window, weight=WEIGHT):
-    """The float64 results for an input, computed once per `key` and not changed by anybody."""
-    k = (key, kind, wrt, weight)
+def oracle(key, kind, wrt, x64, labels, ll, tl, window, weight=WEIGHT, blank=0, d_loss=None, post=True):
+    """The float64 results for an input, computed once per `key` and not changed by anybody.  d_loss: the weights of the gradient
+    (part of the key); post=False: the loss and the gradient alone."""
+    k = (key, kind, wrt, weight) if (blank == 0 and d_loss is None and post) else \
+        (key, kind, wrt, weight, blank, None if d_loss is None else tuple(np.asarray(d_loss, np.float64).tolist()), post)
     if k not in _ORACLE:
-        loss, grad = WO.loss_and_grad(kind, wrt, labels, x64, ll, tl, window, 0, weight)
-        loss2, post, blk, dur, _ = WO.label_posterior(kind, wrt, labels, x64, ll, tl, window, 0, weight)
-        assert np.array_equal(loss, loss2)
-        for a in (loss, grad, post, blk, dur):
+        loss, grad = WO.loss_and_grad(kind, wrt, labels, x64, ll, tl, window, blank, weight, d_loss)
+        res = dict(loss=loss, grad=grad)
+        if post:
+            loss2, res["post"], res["blk"], res["dur"], res["exf"] = WO.label_posterior(kind, wrt, labels, x64, ll, tl, window, blank, weight)
+            assert np.array_equal(loss, loss2)
+        for a in res.values():
             a.setflags(write=False)
-        _ORACLE[k] = dict(loss=loss, grad=grad, post=post, blk=blk, dur=dur)
+        _ORACLE[k] = res
     return _ORACLE[k]
 
 
@@ -325,16 +331,20 @@ def test_formats(kind):
         check(ref, got, window, tl, f"{kind} bfloat16 checkpoint={ck}", free["loss"], grad_tol=1e-4 + 2.0 ** -9)
 
 
-def _raw_calls(kind, x, labels, ll, tl, window, fill, tf=64):
-    """The three C entry points themselves on outputs and an exact-size workspace prefilled with the byte `fill`."""
+def _raw_calls(kind, x, labels, ll, tl, window, fill, tf=64, blank=0, U=None, window_stride=None, d_loss=None):
+    """The three C entry points themselves on outputs and an exact-size workspace prefilled with the byte `fill`.  U, window_stride
+    and d_loss as in tests/test_gpu_windowed.py's _raw_calls: the width of `labels` is always the label stride."""
     from tf_seq2seq_losses_amd import _lib
     lib = _lib.load()
     B, T, V = x.shape
-    U = labels.shape[1]
+    label_stride = labels.shape[1]
+    U = label_stride if U is None else U
+    window_stride = 2 * window.shape[1] if window_stride is None else window_stride
     k = KINDS.index(kind)
     t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl, win=window).items()}
-    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(), t["tl"].data_ptr(), 0,
-            t["win"].data_ptr(), 2 * U, ctypes.c_float(WEIGHT), B, T, V, U, tf)
+    dl = None if d_loss is None else dev(np.asarray(d_loss, np.float32))
+    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), label_stride, t["ll"].data_ptr(), t["tl"].data_ptr(), blank,
+            t["win"].data_ptr(), window_stride, ctypes.c_float(WEIGHT), B, T, V, U, tf)
 
     def buf(shape, dtype):
         n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
@@ -349,7 +359,8 @@ def _raw_calls(kind, x, labels, ll, tl, window, fill, tf=64):
                              ("ckpt_", lib.ctc_amd_long_windowed_loss_grad_ckpt, _lib.long_wildcard_loss_ckpt_workspace_bytes)):
         lg = {name + "loss": buf((B,), torch.float32), name + "grad": buf((B, T, V), torch.float32)}
         w = ws(size(k, B, T, V, U, tf, True))
-        rc = call(*lead, None, *(v.data_ptr() for v in lg.values()), 0, T * V, V, w.data_ptr(), w.numel(), None)
+        rc = call(*lead, None if dl is None else dl.data_ptr(), *(v.data_ptr() for v in lg.values()), 0, T * V, V, w.data_ptr(), w.numel(),
+                  None)
         assert rc == 0, lib.ctc_amd_last_error()
         out.update(lg)
     po = dict(p_loss=buf((B,), torch.float32), post=buf((B, T, U), torch.float32), blk=buf((B, T), torch.float32),

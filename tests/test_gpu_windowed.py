@@ -88,24 +88,25 @@ def lattice_fns(kind, wrt):
             ctc.classic_ctc_long_wildcard_alignment if c else ctc.simplified_ctc_long_wildcard_alignment)
 
 
-def run_all(kind, wrt, x, labels, ll, tl, window, weight=-0.25, long_form=False, d_loss=None, **kw):
-    """Every windowed call of the short form (or the long-form alignment alone) as numpy: dict of outputs."""
+def run_all(kind, wrt, x, labels, ll, tl, window, weight=-0.25, long_form=False, d_loss=None, blank=0, **kw):
+    """Every windowed call of the short form (or the long-form alignment alone) as numpy: dict of outputs.  d_loss: the
+    grad_outputs of the loss (default: ones); kw (max_label_length, and frames_per_tile for the long form) goes to every call."""
     loss_fn, post_fn, align_fn, long_fn = lattice_fns(kind, wrt)
     wk = {} if window is None else {"frame_window": window if isinstance(window, torch.Tensor) else dev(window)}
     lab, l1, l2 = dev(labels), dev(ll), dev(tl)
     out = {}
     if long_form:
-        a = long_fn(lab, dev(x), l1, l2, 0, **wk, **kw)
+        a = long_fn(lab, dev(x), l1, l2, blank, **wk, **kw)
         out.update({"a_" + k: v for k, v in a._asdict().items()})
     else:
         xt = dev(x).clone().requires_grad_(True)
-        loss = loss_fn(lab, xt, l1, l2, 0, wildcard_log_weight=weight, **wk)
+        loss = loss_fn(lab, xt, l1, l2, blank, wildcard_log_weight=weight, **wk, **kw)
         dl = torch.ones_like(loss) if d_loss is None else dev(d_loss)
         (grad,) = torch.autograd.grad(loss, xt, dl)
         out.update(loss=loss.detach(), grad=grad)
-        p = post_fn(lab, dev(x), l1, l2, 0, wildcard_log_weight=weight, **wk)
+        p = post_fn(lab, dev(x), l1, l2, blank, wildcard_log_weight=weight, **wk, **kw)
         out.update({"p_" + k: v for k, v in p._asdict().items()})
-        a = align_fn(lab, dev(x), l1, l2, 0, **wk)
+        a = align_fn(lab, dev(x), l1, l2, blank, **wk, **kw)
         out.update({"a_" + k: v for k, v in a._asdict().items()})
     torch.cuda.synchronize()
     return {k: v.cpu() for k, v in out.items()}
@@ -127,10 +128,10 @@ def check_owners(index, window, ll, tl):
                 assert i < ll[b] and window[b, i, 0] <= t <= window[b, i, 1], (b, t, i, window[b, i])
 
 
-def check_path(kind, wrt, x64, labels, ll, tl, window, got, what):
+def check_path(kind, wrt, x64, labels, ll, tl, window, got, what, blank=0):
     """The alignment against the oracle: an admissible path inside the windows whose float64 value is the oracle's optimum, and the
     score.  (The path itself is not compared: a wildcard frame whose best token is the blank ties with a blank frame.)"""
-    o_score, o_paths, _ = WO.best_path(kind, labels, x64, ll, tl, window, 0, wrt)
+    o_score, o_paths, _ = WO.best_path(kind, labels, x64, ll, tl, window, blank, wrt)
     score, tokens, index = got["a_score"].numpy(), got["a_tokens"].numpy(), got["a_label_index"].numpy()
     check_owners(index, window, ll, tl)
     for b in range(len(ll)):
@@ -141,7 +142,7 @@ def check_path(kind, wrt, x64, labels, ll, tl, window, got, what):
         owned = idx[idx >= 0]
         assert np.array_equal(np.unique(owned), np.arange(L)) and np.all(np.diff(owned) >= 0), (what, b)
         arg = np.asarray(x64[b, :Tb], np.float32).argmax(axis=-1)
-        want_tok = np.where(idx < 0, 0, np.where(labels[b][np.maximum(idx, 0)] == W, arg, labels[b][np.maximum(idx, 0)]))
+        want_tok = np.where(idx < 0, blank, np.where(labels[b][np.maximum(idx, 0)] == W, arg, labels[b][np.maximum(idx, 0)]))
         assert np.array_equal(tokens[b, :Tb], want_tok), (what, b)
         value = float(lp[np.arange(Tb), tokens[b, :Tb]].sum())
         print(f"{what} b={b}: score {score[b]:.6f} oracle {o_score[b]:.6f} path value {value:.6f}")
@@ -153,10 +154,11 @@ def check_path(kind, wrt, x64, labels, ll, tl, window, got, what):
             assert first[i] == fr[0] and last[i] == fr[-1] and np.all(np.diff(fr) == 1), (what, b, i)
 
 
-def check_sums(kind, wrt, x64, labels, ll, tl, window, got, free, weight, what, grad_tol=1e-4):
-    """Loss, gradient and posteriors against the oracle; zero outside the windows; rows sum to 1; at least the unwindowed loss."""
-    o_loss, o_grad = WO.loss_and_grad(kind, wrt, labels, x64, ll, tl, window, 0, weight)
-    _, o_post, o_blk, o_dur, _ = WO.label_posterior(kind, wrt, labels, x64, ll, tl, window, 0, weight)
+def check_sums(kind, wrt, x64, labels, ll, tl, window, got, free, weight, what, grad_tol=1e-4, blank=0):
+    """Loss, gradient and posteriors against the oracle; zero outside the windows; rows sum to 1; at least the unwindowed loss.
+    Returns the oracle's results."""
+    o_loss, o_grad = WO.loss_and_grad(kind, wrt, labels, x64, ll, tl, window, blank, weight)
+    _, o_post, o_blk, o_dur, o_exf = WO.label_posterior(kind, wrt, labels, x64, ll, tl, window, blank, weight)
     loss = got["loss"].numpy().astype(np.float64)
     assert np.isfinite(o_loss).all() and np.isfinite(loss).all(), what
     e_loss = np.abs(loss - o_loss)
@@ -177,6 +179,7 @@ def check_sums(kind, wrt, x64, labels, ll, tl, window, got, free, weight, what, 
     for b in range(B):
         assert np.all(np.abs(total[b, :tl[b]] - 1.0) <= 1e-4), (what, b)
     assert np.all(loss >= free["loss"].numpy() - tol(loss)), what  # fewer paths: no less loss
+    return dict(loss=o_loss, grad=o_grad, post=o_post, blk=o_blk, dur=o_dur, exf=o_exf)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -316,16 +319,22 @@ def test_formats(kind):
     check_path(kind, 0, x64, labels, ll, tl, window, got, f"{kind} bfloat16")
 
 
-def _raw_calls(kind, x, labels, ll, tl, window, fill, long_form):
-    """The C entry points themselves on outputs and a workspace prefilled with the byte `fill`."""
+def _raw_calls(kind, x, labels, ll, tl, window, fill, long_form, blank=0, U=None, window_stride=None, d_loss=None):
+    """The C entry points themselves on outputs and a workspace prefilled with the byte `fill`.  U: the bound the calls, their
+    outputs and their workspaces get (default: the width of `labels`, which is always the label stride); window_stride: that of
+    `window`, any int32 array that holds what it implies (default: 2 * the width of a [B, width, 2] one); d_loss: float32 [B] for
+    the gradient (default: NULL)."""
     from tf_seq2seq_losses_amd import _lib
     lib = _lib.load()
     B, T, V = x.shape
-    U = labels.shape[1]
+    label_stride = labels.shape[1]
+    U = label_stride if U is None else U
+    window_stride = 2 * window.shape[1] if window_stride is None else window_stride
     k = KINDS.index(kind)
     t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl, win=window).items()}
-    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(), t["tl"].data_ptr(), 0,
-            t["win"].data_ptr(), 2 * U)
+    dl = None if d_loss is None else dev(np.asarray(d_loss, np.float32))
+    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), label_stride, t["ll"].data_ptr(), t["tl"].data_ptr(), blank,
+            t["win"].data_ptr(), window_stride)
 
     def buf(shape, dtype):
         n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
@@ -347,7 +356,8 @@ def _raw_calls(kind, x, labels, ll, tl, window, fill, long_form):
         assert rc == 0, lib.ctc_amd_last_error()
         lg = dict(loss=buf((B,), torch.float32), grad=buf((B, T, V), torch.float32))
         w = ws(_lib.wildcard_loss_workspace_bytes(k, B, T, V, U, True))
-        rc = lib.ctc_amd_windowed_loss_grad(*lead, ctypes.c_float(-0.25), B, T, V, U, None, lg["loss"].data_ptr(), lg["grad"].data_ptr(),
+        rc = lib.ctc_amd_windowed_loss_grad(*lead, ctypes.c_float(-0.25), B, T, V, U, None if dl is None else dl.data_ptr(),
+                                            lg["loss"].data_ptr(), lg["grad"].data_ptr(),
                                             0, T * V, V, w.data_ptr(), w.numel(), None)
         assert rc == 0, lib.ctc_amd_last_error()
         po = dict(ploss=buf((B,), torch.float32), post=buf((B, T, U), torch.float32), blk=buf((B, T), torch.float32),

@@ -45,7 +45,7 @@ def owner_sequences(kind, label, T):
             yield tuple(seq)
 
 
-def brute(kind, label, x, window, wrt, weight):
+def brute(kind, label, x, window, wrt, weight, blank=BLANK):
     """(Z, posterior[T, L], blank posterior[T], best score, {owners: score} of every path); emissions from first principles."""
     x = np.asarray(x, dtype=np.float64)
     T, V = x.shape
@@ -58,7 +58,7 @@ def brute(kind, label, x, window, wrt, weight):
         s_sum = s_max = 0.0
         for t, i in enumerate(seq):
             if i < 0:
-                e_sum = e_max = lp[t, BLANK]
+                e_sum = e_max = lp[t, blank]
             elif not (window[i][0] <= t <= window[i][1]):
                 e_sum = e_max = -np.inf
             elif label[i] == W:
@@ -92,20 +92,25 @@ CASES = [  # (label, T, window)
 ]
 
 
-@pytest.mark.parametrize("kind", WO.KINDS)
-@pytest.mark.parametrize("wrt", (0, 1))
-@pytest.mark.parametrize("case", range(len(CASES)))
-def test_against_enumeration(kind, wrt, case):
+def reblank(label, blank):
+    """The labels of a case for another blank: a label equal to it becomes 0, which no case uses.  The map is injective on the
+    labels, so equal neighbours, windows and feasibility stay as they are."""
+    return [0 if k == blank else k for k in label]
+
+
+def enumeration_case(kind, wrt, case, blank):
     label, T, window = CASES[case]
+    label = reblank(label, blank)
+    assert blank not in label
     rng = np.random.default_rng(100 * case + 10 * wrt + (kind == "classic"))
     x = rng.normal(0.0, 2.0, (T, 4))
     if wrt:
         x = x - np.log(np.exp(x).sum(axis=1, keepdims=True)) - rng.uniform(0.0, 0.5, (T, 1))  # sub-normalised log-probabilities
     weight = -0.3
-    Z, post, blk, best, scores = brute(kind, label, x, window, wrt, weight)
+    Z, post, blk, best, scores = brute(kind, label, x, window, wrt, weight, blank)
     win = np.asarray(window, dtype=np.int64).reshape(-1, 2)
-    loss, p, q = WO.posterior_one(kind, label, x, win, BLANK, wrt, weight)
-    score, path, index = WO.best_path_one(kind, label, x, win, BLANK, wrt)
+    loss, p, q = WO.posterior_one(kind, label, x, win, blank, wrt, weight)
+    score, path, index = WO.best_path_one(kind, label, x, win, blank, wrt)
     if Z == 0.0:
         assert case == 4
         assert loss == np.inf and score == -np.inf and path is None and not p.any() and not q.any()
@@ -123,7 +128,23 @@ def test_against_enumeration(kind, wrt, case):
             assert window[i][0] <= t <= window[i][1]
             assert path[t] == (np.asarray(x, np.float32)[t].argmax() if label[i] == W else label[i])
         else:
-            assert path[t] == BLANK
+            assert path[t] == blank
+
+
+@pytest.mark.parametrize("kind", WO.KINDS)
+@pytest.mark.parametrize("wrt", (0, 1))
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_against_enumeration(kind, wrt, case):
+    enumeration_case(kind, wrt, case, BLANK)
+
+
+@pytest.mark.parametrize("kind", WO.KINDS)
+@pytest.mark.parametrize("wrt", (0, 1))
+@pytest.mark.parametrize("blank", (3, 2, 1), ids=("blank=V-1", "blank=2", "blank=1"))
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_against_enumeration_at_a_nonzero_blank(kind, wrt, blank, case):
+    """The same cases and logits with the blank in the last column (V = 4) and in either interior one."""
+    enumeration_case(kind, wrt, case, blank)
 
 
 @pytest.mark.parametrize("kind", WO.KINDS)
@@ -149,6 +170,35 @@ def test_gradient_is_the_derivative_of_the_loss(kind, wrt):
         num[idx] = ((lp_ - lm_) * d_loss).sum() / (2 * h)
     np.testing.assert_allclose(grad, num, rtol=0, atol=2e-8)
     assert not grad[1, 6].any()  # beyond logit_length
+
+
+@pytest.mark.parametrize("kind", WO.KINDS)
+def test_weighted_gradient_is_the_derivative_of_the_weighted_loss_at_a_nonzero_blank(kind):
+    """loss_and_grad(..., d_loss=d) against central differences of sum(d * loss), d with a zero and a negative entry, the blank in
+    the last column (V = 5) and in an interior one."""
+    B, T, V, U = 3, 7, 5, 3
+    ll, tl = np.asarray([3, 2, 3]), np.asarray([7, 6, 7])
+    window = np.asarray([[(0, 2), (1, 5), (3, 6)], [(0, 3), (2, 5), (0, 0)], [(0, 3), (1, 5), (2, 6)]])
+    d_loss = np.asarray([0.0, -1.3, 0.7])
+    h = 1e-6
+    for wrt in (0, 1):
+        for blank in (V - 1, 2):
+            x = np.random.default_rng(70 + 10 * wrt + blank).normal(0.0, 1.5, (B, T, V))
+            labels = np.asarray([reblank(r, blank) for r in ([1, W, 1], [2, 2, 4], [4, 3, W])])
+            assert not (labels == blank).any()
+            loss, grad = WO.loss_and_grad(kind, wrt, labels, x, ll, tl, window, blank, -0.2, d_loss)
+            assert np.isfinite(loss).all()
+            num = np.zeros_like(x)
+            for idx in np.ndindex(*x.shape):
+                xp, xm = x.copy(), x.copy()
+                xp[idx] += h
+                xm[idx] -= h
+                lp_ = WO.loss_and_grad(kind, wrt, labels, xp, ll, tl, window, blank, -0.2)[0]
+                lm_ = WO.loss_and_grad(kind, wrt, labels, xm, ll, tl, window, blank, -0.2)[0]
+                num[idx] = ((lp_ - lm_) * d_loss).sum() / (2 * h)
+            np.testing.assert_allclose(grad, num, rtol=0, atol=2e-8)
+            assert not grad[0].any() and grad[1].any() and grad[2].any()  # the zero weight: exactly zero
+            assert not grad[1, 6].any()  # beyond logit_length
 
 
 @pytest.mark.parametrize("kind", WO.KINDS)
