@@ -1297,6 +1297,82 @@ int ctc_amd_long_windowed_label_posterior(int kind, int wrt,
                                           float *expected_frame, float *peak_posterior, int32_t *peak_frame,
                                           void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Optional wildcards: a wildcard position that may be empty (added under ABI v6: two new entry points with their size queries,
+ * nothing existing changed).  CTC_AMD_WILDCARD stands for a NON-EMPTY run of frames.  Star temporal classification puts a star
+ * between every pair of labels and lets each be empty; a lightly supervised transcript says that something MAY be missing
+ * between two words; a keyword may or may not be preceded by filler.  For those there is a second reserved label value,
+ * CTC_AMD_OPTIONAL_WILDCARD = -3, accepted by
+ *   ctc_amd_optional_wildcard_loss_grad         counterpart: ctc_amd_wildcard_loss_grad   (the loss alone, or with its gradient)
+ *   ctc_amd_optional_wildcard_label_posterior   counterpart: ctc_amd_label_posterior
+ *   ctc_amd_optional_wildcard_best_path         counterpart: ctc_amd_wildcard_best_path
+ * only.  Each is its counterpart in arguments, formats, strides, outputs, limits (U <= CTC_AMD_MAX_U), validation order and
+ * messages, workspace (the size queries return the counterparts' sizes), launches and capture.  In every other entry point -3
+ * stays what it was: a label outside [0, V), an infeasible utterance.  ctc_amd_check_labels keeps rejecting both values.
+ * One limit differs: ctc_amd_optional_wildcard_best_path on the CLASSIC lattice takes U <= CTC_AMD_OPTIONAL_CLASSIC_MAX_U = 512
+ * (CTC_AMD_EINVAL beyond, behind the counterpart's argument checks and before the workspace; the size query says so too): the
+ * chain step for 16 positions per lane does not fit the register file without scratch, and no spilling kernel is shipped.  The
+ * simplified alignment, the loss and the posteriors take U <= CTC_AMD_MAX_U.
+ * There is no long-form, N-best or frame-window variant.
+ *
+ * Let position i be an optional wildcard.  Everything said of a wildcard holds for it when it is used: the emission e_w(t),
+ * contiguous frames, its own posterior column.  In addition it may be skipped:
+ * Classic lattice.  Skipping i adds two sources to the open state of i + 1:
+ *   - the closed state of i - 1, or the start state when i = 0;
+ *   - the open state of i - 1, when label[i + 1] != label[i - 1] or either is a wildcard of either kind.
+ * The closed state of i is reachable only through i's open state, so a path that skips i waits in the closed state of i - 1 and
+ * no path is counted twice.  If i is the last position, the open and closed states of i - 1 are end states too; for
+ * label_length = 1 that is the start state.
+ * Simplified lattice.  State i + 1 may also be entered from state i - 1 (the start state when i = 0), at the cost of label
+ * i + 1's emission.  If i is last, state i - 1 is an end state too.
+ * Equivalence.  The set of state sequences is the disjoint union, over all subsets of the optional positions, of the state
+ * sequences of the transcript with that subset deleted and the remaining optional wildcards made mandatory.  Hence Z is the sum
+ * of those transcripts' Z, and gradients and posteriors are the Z-weighted mixtures, posterior columns mapped back to the
+ * original positions with zero columns for the skipped ones.
+ * Adjacency.  Two optional wildcards may not be adjacent (a chain of skips would need unbounded reach): such an utterance is
+ * infeasible, like a bad label.  An optional wildcard next to a mandatory one is allowed.
+ * Best path.  It is the best over those transcripts.  emission m_t, tokens = a_t where the position is used.  Ties: the candidates
+ * of a position's open state stay in the order stay, closed i - 1, open i - 1, closed i - 2, open i - 2 (simplified: stay, i - 1,
+ * i - 2) with strict comparisons, the end states in the order closed, open of L - 1, closed, open of L - 2: deterministic, the same
+ * bits on every run.  Outputs for a skipped position: first_frame = last_frame = -1 and label_score = 0.0, the log-probability of
+ * an empty run, so that sum_i label_score + the blank frames still equals score.  Back-pointers: the counterpart's words and
+ * workspace size -- classic, source code 3 of a position's 3 bits and the word's one spare bit per position; simplified, a second
+ * bit per position.  A transcript without an optional wildcard returns the counterpart's bits for every output.
+ * Posteriors.  The column of an optional wildcard may sum to less than 1 frame: duration >= 0 there, expected_frame = -1 where
+ * duration is 0.  A frame's values still sum to 1.
+ * Short utterances.  The frames an utterance needs no longer count optional wildcards.  T_b = 0 is feasible, with loss 0, for
+ * label_length = 0 or for a single optional wildcard.
+ * A transcript without an optional wildcard returns the bits of the counterpart for every output.  Numerics and determinism
+ * are the counterparts'; the chain step has two more terms per position.
+ */
+#define CTC_AMD_OPTIONAL_WILDCARD (-3)
+#define CTC_AMD_OPTIONAL_CLASSIC_MAX_U 512
+int ctc_amd_optional_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_optional_wildcard_best_path(int kind, int wrt,
+                                        const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                        const int32_t *labels, int label_stride,
+                                        const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                        int B, int T, int V, int U,
+                                        float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                                        int32_t *first_frame /* may be NULL */, int32_t *last_frame /* may be NULL */,
+                                        float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_optional_wildcard_loss_grad(int kind, int wrt,
+                                        const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                        const int32_t *labels, int label_stride,
+                                        const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                        float wildcard_log_weight, int B, int T, int V, int U,
+                                        const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                        int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_optional_wildcard_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt,
+                                              const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                              const int32_t *labels, int label_stride,
+                                              const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                              float wildcard_log_weight, int B, int T, int V, int U,
+                                              float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                              float *expected_frame, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,601 @@
+"""Optional wildcards on the GPU: the loss, its gradient and the label posteriors with optional_wildcards=True against
+tests/tools/optional_wildcard_oracle.py (float64, pinned in tests/test_optional_wildcard_oracle.py), and the properties
+include/ctc_amd.h promises.  Bars: those of tests/test_gpu_wildcard_loss.py and tests/test_gpu_label_posterior.py, 1e-4 + 1e-6 |loss|
+on the loss, 1e-4 per gradient or posterior element; duration and expected_frame within 2 float32 ulps of a float64 host
+reduction of the returned label_posterior.  The alignment at the bars of tests/test_gpu_wildcard_alignment.py: optimality (oracle
+optimum - float64 value of the returned path) <= 1e-6 absolute; score, every label_score and sum(label_score) + the blank frames
+against score <= 1e-4 + 1e-6 |score|.  The classic alignment takes U <= 512 with optional wildcards (include/ctc_amd.h): at the two
+larger shapes the classic call must raise, the simplified one is checked."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from tests.tools import optional_wildcard_oracle as OO
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+W, Q = OO.WILDCARD, OO.OPTIONAL
+KINDS = OO.KINDS
+# (B, T, V, U): the smallest shape of every tier of the existing grid: NL = 1, 1, 2, 4, 8, 16, 16
+SHAPES = [(4, 12, 5, 3), (2, 88, 8, 64), (2, 89, 8, 65), (2, 169, 8, 129), (2, 329, 8, 257), (2, 649, 8, 513), (2, 1288, 8, 1024)]
+WEIGHT = -0.25
+
+
+def tol(s):
+    return 1e-4 + 1e-6 * np.abs(s)
+
+
+def nl_for(U):
+    nl = 1
+    while 64 * nl < U:
+        nl *= 2
+    return nl
+
+
+def need_frames(kind, lab):
+    """Frames the transcript needs when every optional wildcard is skipped: one per remaining position and, classic, a blank
+    between equal ordinary neighbours among them."""
+    rest = [int(k) for k in lab if k != Q]
+    n = len(rest)
+    if kind == "classic":
+        n += sum(1 for a, b in zip(rest, rest[1:]) if a == b and a != W)
+    return n
+
+
+def draw(kind, B, T, V, U, seed, scale=1.0, blank=0):
+    """(x, labels, ll, tl).  Utterance 0 has label_length U and every frame, with optional wildcards where the two-back exchange of
+    the chain can go wrong -- positions 0 and L - 1, NL k - 1 and NL k + 1 for a lane k in the middle, NL k for the last lane in
+    use (k = 63 where U reaches it) -- and utterance 1 the positions in between (adjacent ones are infeasible, so they cannot
+    share an utterance): NL k of the middle lane, between two EQUAL labels, and NL k - 1, NL k + 1 of the last lane.  Further
+    utterances draw theirs at random.  Mandatory wildcards are sprinkled over all of them."""
+    rng = np.random.default_rng(seed)
+    NL = nl_for(U)
+    x = (rng.standard_normal((B, T, V)) * scale).astype(np.float32)
+    toks = np.asarray([k for k in range(V) if k != blank])
+    labels = toks[rng.integers(0, V - 1, (B, U))].astype(np.int32)
+    labels[rng.random((B, U)) < 0.1] = W
+    ll = rng.integers((U + 1) // 2, U + 1, B).astype(np.int32)
+    ll[0] = U
+    tl = np.zeros(B, np.int32)
+    for b in range(B):
+        L = int(ll[b])
+        km, kl = ((L - 1) // NL) // 2, (L - 1) // NL
+        if b == 0:
+            want = [0, L - 1, NL * km - 1, NL * km + 1, NL * kl]
+        elif b == 1:
+            want = [NL * km, NL * kl - 1, NL * kl + 1]
+            if 0 < NL * km < L - 1:
+                labels[b, NL * km - 1] = labels[b, NL * km + 1] = toks[0]
+        else:
+            want = list(rng.integers(0, L, max(1, L // 3)))
+        for i in sorted(set(int(i) for i in want)):
+            if 0 <= i < L and not (i > 0 and labels[b, i - 1] == Q) and not (i + 1 < L and labels[b, i + 1] == Q):
+                labels[b, i] = Q
+        need = need_frames(kind, labels[b, :L])
+        assert need <= T, (need, T)
+        tl[b] = T if b == 0 else int(rng.integers(need, T + 1))
+    return x, labels, ll, tl
+
+
+def dev(a):
+    return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def lattice_fns(kind, wrt):
+    import tf_seq2seq_losses_amd as ctc
+    cls = ctc.ClassicCtcLossData if kind == "classic" else ctc.SimplifiedCtcLossData
+    if wrt:
+        return tuple((lambda *a, _f=f, **k: _f(*a[:4], a[4], cls, **k)) for f in (
+            ctc.ctc_wildcard_loss_from_logproba, ctc.ctc_label_posterior_from_logproba))
+    c = kind == "classic"
+    return (ctc.classic_ctc_wildcard_loss if c else ctc.simplified_ctc_wildcard_loss,
+            ctc.classic_ctc_label_posterior if c else ctc.simplified_ctc_label_posterior)
+
+
+def run_all(kind, wrt, x, labels, ll, tl, weight=WEIGHT, d_loss=None, blank=0, optional=True, **kw):
+    """The loss, its gradient and the label posteriors as a dict of CPU tensors.  x: numpy or a device tensor in any format."""
+    loss_fn, post_fn = lattice_fns(kind, wrt)
+    lab, l1, l2 = dev(labels), dev(ll), dev(tl)
+    ok = {"optional_wildcards": True} if optional else {}
+    xt = dev(x).detach().requires_grad_(True)
+    loss = loss_fn(lab, xt, l1, l2, blank, wildcard_log_weight=weight, **ok, **kw)
+    dl = torch.ones_like(loss) if d_loss is None else dev(d_loss)
+    (grad,) = torch.autograd.grad(loss, xt, dl)
+    out = dict(loss=loss.detach(), grad=grad)
+    p = post_fn(lab, dev(x).detach(), l1, l2, blank, wildcard_log_weight=weight, **ok, **kw)
+    out.update({"p_" + k: v for k, v in p._asdict().items()})
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+def same_bits(a, b, keys=None):
+    for k in (keys or a.keys()):
+        u, v = a[k].contiguous().reshape(-1), b[k].contiguous().reshape(-1)
+        assert u.dtype == v.dtype and u.shape == v.shape, k
+        assert torch.equal(u.view(torch.uint8), v.view(torch.uint8)), k
+
+
+def check(kind, wrt, x64, labels, ll, tl, got, what, weight=WEIGHT, d_loss=None, blank=0, grad_tol=1e-4):
+    """Every output against the oracle; duration and expected_frame against the float64 sums over the returned float32 matrix (the
+    statistics kernel is the existing one: its bar is that of tests/test_gpu_label_posterior.py, 2 float32 ulps)."""
+    ref_loss, ref_grad = OO.loss_and_grad(kind, wrt, labels, x64, ll, tl, blank, weight, d_loss)
+    _, post, blk, dur, exf = OO.label_posterior(kind, wrt, labels, x64, ll, tl, blank, weight)
+    loss = got["loss"].numpy().astype(np.float64)
+    fin = np.isfinite(ref_loss)
+    print(f"{what}: loss err {np.abs(loss[fin] - ref_loss[fin]).max(initial=0.0):.3g}  "
+          f"grad err {np.abs(got['grad'].float().numpy() - ref_grad).max(initial=0.0):.3g}  "
+          f"posterior err {np.abs(got['p_label_posterior'].numpy() - post).max(initial=0.0):.3g}")
+    assert np.array_equal(np.isfinite(loss), fin), what
+    assert np.all(np.abs(loss[fin] - ref_loss[fin]) <= tol(ref_loss[fin])), what
+    assert np.array_equal(got["p_loss"].numpy(), got["loss"].numpy()), what
+    assert np.abs(got["grad"].float().numpy() - ref_grad).max(initial=0.0) <= grad_tol, what
+    assert np.abs(got["p_label_posterior"].numpy() - post).max(initial=0.0) <= 1e-4, what
+    assert np.abs(got["p_blank_posterior"].numpy() - blk).max(initial=0.0) <= 1e-4, what
+    T = x64.shape[1]
+    pg = got["p_label_posterior"].numpy().astype(np.float64)
+    sums = pg.sum(axis=2) + got["p_blank_posterior"].numpy()
+    for b in range(len(ll)):
+        if fin[b]:
+            assert np.abs(sums[b, :min(max(int(tl[b]), 0), T)] - 1.0).max(initial=0.0) <= 1e-4, what  # a frame's values sum to 1
+    d, e = got["p_duration"].numpy(), got["p_expected_frame"].numpy()
+    hd = pg.sum(axis=1)  # (zero beyond T_b and L and for the infeasible)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        he = np.where(hd > 0.0, (np.arange(T)[None, :, None] * pg).sum(axis=1) / hd, -1.0)
+    assert np.all(np.abs(d - hd) <= 2 * np.spacing(hd.astype(np.float32))), what
+    assert np.all(np.abs(e - he) <= 2 * np.spacing(np.abs(he).astype(np.float32))), what
+    assert np.all((d >= 0.0) & (d <= T * (1 + 1e-6))), what  # the column of an optional wildcard: anything from 0 to T frames
+    assert np.all(np.abs(d - dur) <= T * 1e-4), what        # (a sum of at most T elements, each within 1e-4)
+    assert np.all((e == -1.0) == (d == 0.0)), what
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_against_the_oracle(shape, kind):
+    B, T, V, U = shape
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=U)
+    assert (labels[0] == Q).sum() >= 2 and (labels[1, :ll[1]] == Q).any()
+    d_loss = np.linspace(0.5, 1.5, B).astype(np.float32)
+    got = run_all(kind, 0, x, labels, ll, tl, d_loss=d_loss)
+    check(kind, 0, x.astype(np.float64), labels, ll, tl, got, f"{kind} {shape}", d_loss=d_loss)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[2], SHAPES[3]], ids=lambda s: "x".join(map(str, s)))
+def test_log_probabilities_and_no_weight(shape, kind):
+    B, T, V, U = shape
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=100 + U)
+    lp = (torch.log_softmax(torch.from_numpy(x), dim=-1) - 0.125).numpy()  # (used as they stand: need not be normalised)
+    check(kind, 1, lp.astype(np.float64), labels, ll, tl, run_all(kind, 1, lp, labels, ll, tl, weight=0.0), f"{kind} wrt=1", weight=0.0)
+
+
+def special_batch(kind):
+    """The cases the mandatory wildcard cannot express, in one batch of U = 11, T = 12, V = 6:
+    0  the STC pattern (a star at every even position) with T_b = 8 < 2 L + 1 = 23 -- and < L = 11: feasible only because stars
+       may be empty;  1  a lone optional wildcard and no frame: loss 0;  2  the same with frames;  3  adjacent optional wildcards:
+    infeasible;  4  an empty label;  5  [a ? b] with as many frames as labels: every star is skipped;  6  [a ? a] on three frames."""
+    V, U, T = 6, 11, 12
+    rng = np.random.default_rng(7)
+    x = rng.standard_normal((7, T, V)).astype(np.float32)
+    labels = np.full((7, U), 1, np.int32)
+    labels[0] = [Q, 1, Q, 2, Q, 2, Q, 3, Q, 4, Q]
+    labels[1, 0] = labels[2, 0] = Q
+    labels[3, :4] = [1, Q, Q, 2]
+    labels[5, :3] = [2, Q, 3]
+    labels[6, :3] = [2, Q, 2]
+    ll = np.asarray([11, 1, 1, 4, 0, 3, 3], np.int32)
+    tl = np.asarray([8, 0, 5, 12, 6, 2, 3], np.int32)
+    return x, labels, ll, tl
+
+
+@pytest.mark.parametrize("wrt", [0, 1])
+@pytest.mark.parametrize("kind", KINDS)
+def test_what_only_an_optional_wildcard_can_express(kind, wrt):
+    x, labels, ll, tl = special_batch(kind)
+    if wrt:
+        x = torch.log_softmax(torch.from_numpy(x), dim=-1).numpy()
+    got = run_all(kind, wrt, x, labels, ll, tl)
+    check(kind, wrt, x.astype(np.float64), labels, ll, tl, got, f"{kind} special")
+    loss = got["loss"].numpy()
+    assert np.isfinite(loss[0]) and loss[1] == 0.0 and np.isfinite(loss[2]) and np.isposinf(loss[3]) and np.isfinite(loss[4])
+    assert not got["grad"][3].any() and not got["p_label_posterior"][3].any()
+    mandatory = run_all(kind, wrt, x, np.where(labels == Q, W, labels).astype(np.int32), ll, tl, optional=False)
+    assert np.isposinf(mandatory["loss"].numpy()[[0, 1, 5]]).all()  # with mandatory wildcards those utterances are infeasible
+    if kind == "simplified":  # as many frames as labels: the star of utterance 5 is skipped on every path, exactly
+        assert got["p_duration"][5, 1] == 0.0 and got["p_expected_frame"][5, 1] == -1.0
+    assert 0.0 < got["p_duration"][6, 1] < 3.0  # [a ? a] on three frames: a blank a, or a star a -- the star shares frame 1
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_planted_logits_skip_or_use_the_star(kind):
+    """[1 ? 2] on four frames, logits of +-12 (a foreign token costs 24 nats a frame) and a weight of -12 a star frame.  Planted
+    1 1 2 2 (classic) / 1 2 _ _ (simplified): a star frame loses 12 nats against the planted path, duration ~ e^-12 < 1e-3.
+    Planted 1 3 3 2: a star frame (-12) beats a foreign frame (-24) by 12 nats: duration 2 and expected_frame 1.5 to 1e-3."""
+    V, T, WT = 5, 4, -12.0
+    skip = [1, 1, 2, 2] if kind == "classic" else [1, 2, 0, 0]
+    x = np.full((2, T, V), -12.0, np.float32)
+    for t in range(T):
+        x[0, t, skip[t]] = 12.0
+        x[1, t, [1, 3, 3, 2][t]] = 12.0
+    labels = np.asarray([[1, Q, 2], [1, Q, 2]], np.int32)
+    ll, tl = np.asarray([3, 3], np.int32), np.asarray([T, T], np.int32)
+    got = run_all(kind, 0, x, labels, ll, tl, weight=WT)
+    check(kind, 0, x.astype(np.float64), labels, ll, tl, got, f"{kind} planted", weight=WT)
+    assert got["p_duration"][0, 1] < 1e-3 and abs(float(got["p_duration"][1, 1]) - 2.0) < 1e-3
+    assert abs(float(got["p_expected_frame"][1, 1]) - 1.5) < 1e-3
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[2], SHAPES[3], SHAPES[4], SHAPES[5]], ids=lambda s: "x".join(map(str, s)))
+def test_without_an_optional_wildcard_the_bits_are_the_existing_calls(shape, kind):
+    """The added terms are -inf: exp2 gives +0, added behind the existing terms, and the maximum is unchanged."""
+    B, T, V, U = shape
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=200 + U)
+    labels = np.where(labels == Q, W, labels).astype(np.int32)
+    tl[-1] = max(1, int(ll[-1]) // 2)  # an infeasible utterance too
+    same_bits(run_all(kind, 0, x, labels, ll, tl), run_all(kind, 0, x, labels, ll, tl, optional=False))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_minus_three_without_the_keyword_is_still_a_bad_label(kind):
+    B, T, V, U = SHAPES[0]
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=5)
+    got = run_all(kind, 0, x, labels, ll, tl, optional=False)
+    bad = np.asarray([(labels[b, :ll[b]] == Q).any() for b in range(B)])
+    assert bad.any() and np.array_equal(np.isposinf(got["loss"].numpy()), bad)
+    assert not got["grad"][torch.from_numpy(bad)].any()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("fmt", ["bfloat16", "float16", "time_major", "offset"])
+def test_formats(fmt, kind):
+    B, T, V, U = 3, 90, 260, 20
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=31)
+    xt = torch.from_numpy(x).to(DEV)
+    grad_tol = 1e-4
+    if fmt in ("bfloat16", "float16"):
+        xt = xt.to(getattr(torch, fmt))
+        grad_tol = 1e-4 + (2.0 ** -8 if fmt == "bfloat16" else 2.0 ** -11)  # (the gradient comes back in the logits' type: |g| <= 1)
+    elif fmt == "time_major":
+        xt = xt.transpose(0, 1).contiguous().transpose(0, 1)
+        assert xt.stride(1) == B * V
+    else:
+        big = torch.zeros(B * T * V + 3, device=DEV)
+        big[3:] = xt.reshape(-1)
+        xt = big[3:].view(B, T, V)  # (12 bytes past a 16-byte boundary: the element-wise access path)
+    x64 = xt.double().cpu().numpy()
+    check(kind, 0, x64, labels, ll, tl, run_all(kind, 0, xt, labels, ll, tl), f"{kind} {fmt}", grad_tol=grad_tol)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("blank", [3, 7])
+def test_non_zero_blank(blank, kind):
+    B, T, V, U = SHAPES[2]
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=300 + blank, blank=blank)
+    assert not (labels == blank).any()
+    check(kind, 0, x.astype(np.float64), labels, ll, tl, run_all(kind, 0, x, labels, ll, tl, blank=blank), f"{kind} blank={blank}", blank=blank)
+
+
+def _raw_calls(kind, x, labels, ll, tl, fill):
+    """The two C entry points on outputs and workspaces prefilled with `fill`."""
+    from tf_seq2seq_losses_amd import _lib
+    lib = _lib.load()
+    B, T, V = x.shape
+    U = labels.shape[1]
+    k = KINDS.index(kind)
+    t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl).items()}
+    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(), t["tl"].data_ptr(), 0,
+            ctypes.c_float(WEIGHT), B, T, V, U)
+
+    def buf(shape, dtype=torch.float32):
+        n = int(np.prod(shape)) * 4
+        return torch.full((max(n, 1),), fill, dtype=torch.uint8, device=DEV)[:n].view(dtype).reshape(shape)
+
+    lg = dict(loss=buf((B,)), grad=buf((B, T, V)))
+    w = torch.full((_lib.wildcard_loss_workspace_bytes(k, B, T, V, U, True),), fill, dtype=torch.uint8, device=DEV)
+    rc = lib.ctc_amd_optional_wildcard_loss_grad(*lead, None, lg["loss"].data_ptr(), lg["grad"].data_ptr(), 0, T * V, V, w.data_ptr(),
+                                                 w.numel(), None)
+    assert rc == 0, lib.ctc_amd_last_error()
+    po = dict(ploss=buf((B,)), post=buf((B, T, U)), blk=buf((B, T)), dur=buf((B, U)), exf=buf((B, U)))
+    w2 = torch.full((_lib.label_posterior_workspace_bytes(k, B, T, V, U),), fill, dtype=torch.uint8, device=DEV)
+    rc = lib.ctc_amd_optional_wildcard_label_posterior(*lead, *(v.data_ptr() for v in po.values()), w2.data_ptr(), w2.numel(), None)
+    assert rc == 0, lib.ctc_amd_last_error()
+    torch.cuda.synchronize()
+    return {n: v.cpu() for n, v in {**lg, **po}.items()}
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_prefilled_outputs_and_a_second_run(kind):
+    """Every element of every output has a writer and nothing depends on arrival order: 0x00 and 0xFF in the outputs and the
+    workspace, and a second run, give the same bits."""
+    B, T, V, U = SHAPES[3]
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=41)
+    tl[-1] = 3  # an infeasible utterance: its outputs are written too
+    a = _raw_calls(kind, x, labels, ll, tl, 0x00)
+    same_bits(a, _raw_calls(kind, x, labels, ll, tl, 0xFF))
+    same_bits(a, _raw_calls(kind, x, labels, ll, tl, 0xFF))
+    assert np.isposinf(a["loss"].numpy()[-1]) and np.isfinite(a["loss"].numpy()[0])
+
+
+def test_graph_capture_replays():
+    import tf_seq2seq_losses_amd as ctc
+    B, T, V, U = SHAPES[3]
+    x, labels, ll, tl = draw("classic", B, T, V, U, seed=61)
+    eager = run_all("classic", 0, x, labels, ll, tl)
+    xs, lab, l1, l2 = dev(x), dev(labels), dev(ll), dev(tl)
+
+    def work():
+        xg = xs.clone().requires_grad_(True)
+        loss = ctc.classic_ctc_wildcard_loss(lab, xg, l1, l2, 0, wildcard_log_weight=WEIGHT, max_label_length=U, optional_wildcards=True)
+        (g,) = torch.autograd.grad(loss.sum(), xg)
+        p = ctc.classic_ctc_label_posterior(lab, xs, l1, l2, 0, wildcard_log_weight=WEIGHT, max_label_length=U, optional_wildcards=True)
+        return dict(loss=loss.detach(), grad=g, p_label_posterior=p.label_posterior, p_duration=p.duration)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        work()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = work()
+    graph.replay()
+    torch.cuda.synchronize()
+    same_bits(eager, {k: v.cpu() for k, v in out.items()}, ["loss", "grad", "p_label_posterior", "p_duration"])
+
+
+def test_autograd_and_the_keyword():
+    import tf_seq2seq_losses_amd as ctc
+    assert ctc.OPTIONAL_WILDCARD == -3 == Q
+    B, T, V, U = SHAPES[0]
+    x, labels, ll, tl = draw("classic", B, T, V, U, seed=9)
+    xt = dev(x).requires_grad_(True)
+    loss = ctc.classic_ctc_wildcard_loss(dev(labels), xt, dev(ll), dev(tl), 0, wildcard_log_weight=WEIGHT, optional_wildcards=True)
+    (g,) = torch.autograd.grad(loss.sum(), xt, create_graph=True)
+    ref_loss, ref_grad = OO.loss_and_grad("classic", 0, labels, x.astype(np.float64), ll, tl, 0, WEIGHT)
+    assert np.all(np.abs(loss.detach().cpu().numpy() - ref_loss) <= tol(ref_loss))
+    assert np.abs(g.detach().cpu().numpy() - ref_grad).max() <= 1e-4
+    with pytest.raises(RuntimeError):
+        torch.autograd.grad(g.sum(), xt)
+    win = torch.zeros((B, U, 2), dtype=torch.int32, device=DEV)
+    win[..., 1] = T
+    for fn in (ctc.classic_ctc_wildcard_loss, ctc.simplified_ctc_wildcard_loss, ctc.classic_ctc_label_posterior,
+               ctc.simplified_ctc_label_posterior):
+        with pytest.raises(ValueError):
+            fn(dev(labels), dev(x), dev(ll), dev(tl), 0, frame_window=win, optional_wildcards=True)
+    for fn in (ctc.ctc_wildcard_loss_from_logproba, ctc.ctc_label_posterior_from_logproba):
+        with pytest.raises(ValueError):
+            fn(dev(labels), dev(x), dev(ll), dev(tl), 0, None, frame_window=win, optional_wildcards=True)
+    with pytest.raises(ValueError):  # check_labels describes what the plain losses accept: neither wildcard value
+        ctc.check_labels(dev(labels), dev(ll), V, 0)
+
+
+# ---- the alignment ----
+ALIGN_NAMES = ("score", "tokens", "label_index", "first_frame", "last_frame", "label_score")
+
+
+def align_fn(kind, wrt):
+    import tf_seq2seq_losses_amd as ctc
+    if wrt:
+        cls = ctc.ClassicCtcLossData if kind == "classic" else ctc.SimplifiedCtcLossData
+        return lambda *a, **k: ctc.ctc_wildcard_alignment_from_logproba(*a[:4], a[4], cls, **k)
+    return ctc.classic_ctc_wildcard_alignment if kind == "classic" else ctc.simplified_ctc_wildcard_alignment
+
+
+def run_align(kind, wrt, x, labels, ll, tl, blank=0, optional=True, **kw):
+    ok = {"optional_wildcards": True} if optional else {}
+    a = align_fn(kind, wrt)(dev(labels), dev(x), dev(ll), dev(tl), blank, **ok, **kw)
+    torch.cuda.synchronize()
+    return {k: getattr(a, k).cpu() for k in ALIGN_NAMES}
+
+
+def classic_too_long(kind, U):
+    return kind == "classic" and U > 512
+
+
+def check_align(kind, wrt, x, labels, ll, tl, got, what, blank=0):
+    """x: the float32 values the kernel read (numpy).  Per utterance: the path is admissible for the transcript of the positions
+    it uses (their order, contiguity, tokens), optimal, and the per-label outputs are what the path says."""
+    o_score, o_rest = OO.best_path(kind, labels, x, ll, tl, blank, wrt)
+    g = {k: v.numpy() for k, v in got.items()}
+    B, T = x.shape[0], x.shape[1]
+    worst = dict(gap=0.0, err=0.0, lab=0.0, total=0.0)
+    from tests.tools.wildcard_oracle import _lp, argmax_tokens
+    for b in range(B):
+        Tb, L = min(max(int(tl[b]), 0), T), max(int(ll[b]), 0)
+        if o_rest[b] is None:
+            assert g["score"][b] == -np.inf and np.all(g["tokens"][b] == -1) and np.all(g["label_index"][b] == -1), (what, b)
+            assert np.all(g["first_frame"][b] == -1) and np.all(g["last_frame"][b] == -1) and np.all(g["label_score"][b] == -np.inf), (what, b)
+            continue
+        tok, idx, lab = g["tokens"][b], g["label_index"][b], labels[b, :L]
+        assert np.all(tok[Tb:] == -1) and np.all(idx[Tb:] == -1), (what, b)
+        tok, idx = tok[:Tb], idx[:Tb]
+        assert np.all(tok[idx < 0] == blank) and np.all((idx >= -1) & (idx < L)) and np.all(np.diff(idx[idx >= 0]) >= 0), (what, b)
+        arg = argmax_tokens(x[b, :Tb])
+        lp = _lp(x[b, :Tb], wrt)
+        plp = lp[np.arange(Tb), tok]
+        first, last = np.full(L, -1), np.full(L, -1)
+        prev = -1  # the last used position
+        for i in range(L):
+            fr = np.nonzero(idx == i)[0]
+            if len(fr) == 0:
+                assert lab[i] == Q, (what, b, i)  # only an optional wildcard may be skipped
+                continue
+            assert np.all(np.diff(fr) == 1), (what, b, i)
+            first[i], last[i] = fr[0], fr[-1]
+            if lab[i] in (W, Q):
+                assert np.array_equal(tok[fr], arg[fr]), (what, b, i)
+            else:
+                assert np.all(tok[fr] == lab[i]), (what, b, i)
+                assert kind == "classic" or len(fr) == 1, (what, b, i)
+            if prev >= 0:
+                if kind == "classic" and lab[i] not in (W, Q) and lab[prev] == lab[i]:
+                    assert first[i] > last[prev] + 1, (what, b, i)  # equal labels, also over a skipped star, need a blank between
+                if kind == "simplified" and lab[prev] in (W, Q):
+                    assert first[i] == last[prev] + 1, (what, b, i)
+            prev = i
+        if kind == "simplified" and prev >= 0 and lab[prev] in (W, Q):
+            assert last[prev] == Tb - 1, (what, b)
+        gap = o_score[b] - float(sum(plp))
+        err = abs(float(g["score"][b]) - o_score[b])
+        assert -1e-6 <= gap <= 1e-6, (what, b, gap)
+        assert err <= tol(o_score[b]), (what, b, g["score"][b], o_score[b])
+        assert np.array_equal(g["first_frame"][b, :L], first) and np.array_equal(g["last_frame"][b, :L], last), (what, b)
+        assert np.all(g["first_frame"][b, L:] == -1) and np.all(g["last_frame"][b, L:] == -1) and np.all(g["label_score"][b, L:] == -np.inf), (what, b)
+        total = float(sum(plp[idx < 0]))
+        for i in range(L):
+            want = float(sum(plp[first[i]:last[i] + 1])) if first[i] >= 0 else 0.0
+            if first[i] < 0:
+                assert g["label_score"][b, i] == 0.0, (what, b, i)  # an empty run, exactly
+            worst["lab"] = max(worst["lab"], abs(g["label_score"][b, i] - want))
+            assert abs(g["label_score"][b, i] - want) <= tol(want), (what, b, i)
+            total += float(g["label_score"][b, i])
+        assert abs(total - float(g["score"][b])) <= tol(g["score"][b]), (what, b, total)
+        worst.update(gap=max(worst["gap"], abs(gap)), err=max(worst["err"], err), total=max(worst["total"], abs(total - float(g["score"][b]))))
+    print(f"{what}: optimality gap {worst['gap']:.3e}, |score - oracle| {worst['err']:.3e}, |label_score - float64| {worst['lab']:.3e}, "
+          f"|sum(label_score) + blanks - score| {worst['total']:.3e}", flush=True)
+    return o_score
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_alignment_against_the_oracle(shape, kind):
+    B, T, V, U = shape
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=U)
+    if classic_too_long(kind, U):
+        with pytest.raises(ValueError, match="512"):
+            run_align(kind, 0, x, labels, ll, tl)
+        return
+    got = run_align(kind, 0, x, labels, ll, tl)
+    o_score = check_align(kind, 0, x, labels, ll, tl, got, f"{kind} {shape} alignment")
+    assert np.all(np.isfinite(o_score))
+    loss = run_all(kind, 0, x, labels, ll, tl, weight=0.0)["loss"].numpy().astype(np.float64)
+    assert np.all(-loss >= got["score"].numpy() - tol(loss))  # the sum over all paths is at least the best one (w = 0: e_w >= m_t)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_alignment_of_what_only_an_optional_wildcard_can_express(kind):
+    x, labels, ll, tl = special_batch(kind)
+    for wrt in (0, 1):
+        xx = torch.log_softmax(torch.from_numpy(x), dim=-1).numpy() if wrt else x
+        got = run_align(kind, wrt, xx, labels, ll, tl)
+        o = check_align(kind, wrt, xx, labels, ll, tl, got, f"{kind} special alignment wrt={wrt}")
+        assert np.isfinite(o[0]) and o[1] == 0.0 and np.isneginf(o[3]) and np.isfinite(o[5])
+        assert got["score"][1] == 0.0 and got["label_score"][1, 0] == 0.0 and got["first_frame"][1, 0] == -1
+    if kind == "simplified":  # as many frames as labels: the star is skipped
+        assert got["first_frame"][5, 1] == -1 and got["label_score"][5, 1] == 0.0
+    mandatory = run_align(kind, 0, x, np.where(labels == Q, W, labels).astype(np.int32), ll, tl, optional=False)
+    assert np.isneginf(mandatory["score"].numpy()[[0, 1, 5]]).all()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_planted_best_path_skips_or_uses_the_star(kind):
+    """[1 ? 2], logits of +-12.  Utterance 0 has two frames, planted 1 2: a used star needs a frame of its own, which would leave
+    label 1 or 2 without one, so the best path provably skips it (in (max, +) a star frame is never worth less than a label's, so
+    with a frame to spare nothing can be proved).  Utterance 1 has four, planted 1 3 3 2: the star provably takes frames 1 and 2
+    (m_t = +12 there against -12 for either label or the blank, 24 nats a frame)."""
+    V, T = 5, 4
+    x = np.full((2, T, V), -12.0, np.float32)
+    for t in range(T):
+        x[0, t, [1, 2, 0, 0][t]] = 12.0
+        x[1, t, [1, 3, 3, 2][t]] = 12.0
+    labels = np.asarray([[1, Q, 2], [1, Q, 2]], np.int32)
+    ll, tl = np.asarray([3, 3], np.int32), np.asarray([2, T], np.int32)
+    got = run_align(kind, 0, x, labels, ll, tl)
+    check_align(kind, 0, x, labels, ll, tl, got, f"{kind} planted alignment")
+    assert got["first_frame"][0].tolist() == [0, -1, 1] and got["last_frame"][0].tolist() == [0, -1, 1]
+    assert got["label_score"][0, 1] == 0.0 and got["tokens"][0].tolist() == [1, 2, -1, -1]
+    assert got["first_frame"][1].tolist() == [0, 1, 3] and got["last_frame"][1].tolist() == [0, 2, 3]
+    assert got["tokens"][1].tolist() == [1, 3, 3, 2] and got["label_index"][1].tolist() == [0, 1, 1, 2]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[2], SHAPES[3], SHAPES[4], SHAPES[5]], ids=lambda s: "x".join(map(str, s)))
+def test_alignment_without_an_optional_wildcard_is_the_existing_call(shape, kind):
+    B, T, V, U = shape
+    if classic_too_long(kind, U):
+        B, T, V, U = 2, 640, 8, 512  # the largest the classic call takes (NL = 8)
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=200 + U)
+    labels = np.where(labels == Q, W, labels).astype(np.int32)
+    tl[-1] = max(1, int(ll[-1]) // 2)
+    same_bits(run_align(kind, 0, x, labels, ll, tl), run_align(kind, 0, x, labels, ll, tl, optional=False))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_alignment_minus_three_without_the_keyword_and_the_window(kind):
+    import tf_seq2seq_losses_amd as ctc
+    B, T, V, U = SHAPES[0]
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=5)
+    got = run_align(kind, 0, x, labels, ll, tl, optional=False)
+    bad = np.asarray([(labels[b, :ll[b]] == Q).any() for b in range(B)])
+    assert bad.any() and np.array_equal(np.isneginf(got["score"].numpy()), bad)
+    win = torch.zeros((B, U, 2), dtype=torch.int32, device=DEV)
+    with pytest.raises(ValueError):
+        align_fn(kind, 0)(dev(labels), dev(x), dev(ll), dev(tl), 0, frame_window=win, optional_wildcards=True)
+    with pytest.raises(ValueError):
+        ctc.ctc_wildcard_alignment_from_logproba(dev(labels), dev(x), dev(ll), dev(tl), 0, None, frame_window=win, optional_wildcards=True)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("fmt", ["bfloat16", "float16", "time_major", "offset"])
+def test_alignment_formats_and_blank(fmt, kind):
+    B, T, V, U = 3, 90, 260, 20
+    blank = 259 if fmt == "offset" else 0
+    x, labels, ll, tl = draw(kind, B, T, V, U, seed=33, blank=blank)
+    xt = torch.from_numpy(x).to(DEV)
+    if fmt in ("bfloat16", "float16"):
+        xt = xt.to(getattr(torch, fmt))
+    elif fmt == "time_major":
+        xt = xt.transpose(0, 1).contiguous().transpose(0, 1)
+    else:
+        big = torch.zeros(B * T * V + 3, device=DEV)
+        big[3:] = xt.reshape(-1)
+        xt = big[3:].view(B, T, V)
+    check_align(kind, 0, xt.float().cpu().numpy(), labels, ll, tl, run_align(kind, 0, xt, labels, ll, tl, blank=blank), f"{kind} {fmt} alignment", blank=blank)
+
+
+def test_alignment_determinism_prefill_and_graph():
+    """0x00 / 0xFF in the outputs and the workspace, a second run and a replayed graph: the same bits."""
+    import tf_seq2seq_losses_amd as ctc
+    from tf_seq2seq_losses_amd import _lib
+    lib = _lib.load()
+    B, T, V, U = SHAPES[3]
+    for kind in KINDS:
+        x, labels, ll, tl = draw(kind, B, T, V, U, seed=43)
+        tl[-1] = 3
+        k = KINDS.index(kind)
+        t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl).items()}
+        runs = []
+        for fill in (0x00, 0xFF, 0xFF):
+            def buf(shape, dtype):
+                n = int(np.prod(shape)) * 4
+                return torch.full((n,), fill, dtype=torch.uint8, device=DEV).view(dtype).reshape(shape)
+            out = dict(score=buf((B,), torch.float32), tokens=buf((B, T), torch.int32), label_index=buf((B, T), torch.int32),
+                       first_frame=buf((B, U), torch.int32), last_frame=buf((B, U), torch.int32), label_score=buf((B, U), torch.float32))
+            w = torch.full((_lib.wildcard_best_path_workspace_bytes(k, B, T, V, U),), fill, dtype=torch.uint8, device=DEV)
+            rc = lib.ctc_amd_optional_wildcard_best_path(k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(),
+                                                         t["tl"].data_ptr(), 0, B, T, V, U, *(v.data_ptr() for v in out.values()),
+                                                         w.data_ptr(), w.numel(), None)
+            assert rc == 0, lib.ctc_amd_last_error()
+            torch.cuda.synchronize()
+            runs.append({n: v.cpu() for n, v in out.items()})
+        same_bits(runs[0], runs[1])
+        same_bits(runs[0], runs[2])
+        same_bits(runs[0], run_align(kind, 0, x, labels, ll, tl))
+        assert np.isneginf(runs[0]["score"].numpy()[-1]) and np.isfinite(runs[0]["score"].numpy()[0])
+    xs, lab, l1, l2 = t["x"], t["labels"], t["ll"], t["tl"]
+    work = lambda: ctc.simplified_ctc_wildcard_alignment(lab, xs, l1, l2, 0, max_label_length=U, optional_wildcards=True)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        work()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        a = work()
+    graph.replay()
+    torch.cuda.synchronize()
+    same_bits(runs[0], {n: getattr(a, n).cpu() for n in ALIGN_NAMES})

@@ -19,6 +19,8 @@ WS_LOSS_GRAD, WS_ALPHA_BETA, WS_HESSIAN, WS_HVP, WS_LOSS_GRAD_LOGITS = 0, 1, 2, 
 OK, EINVAL, EWORKSPACE, EHIP, ELABEL = 0, -1, -2, -3, -4
 F32, BF16, F16 = 0, 1, 2
 WILDCARD = -2  # CTC_AMD_WILDCARD: the label value of a wildcard position (ctc_amd_wildcard_best_path)
+OPTIONAL_CLASSIC_MAX_U = 512  # CTC_AMD_OPTIONAL_CLASSIC_MAX_U: the classic optional-wildcard alignment's U
+OPTIONAL_WILDCARD = -3  # CTC_AMD_OPTIONAL_WILDCARD: a wildcard position that may be empty (ctc_amd_optional_wildcard_loss_grad)
 LONG_MAX_U, LONG_FRAMES_MULTIPLE, LONG_FRAMES_DEFAULT = 65536, 4, 128  # CTC_AMD_LONG_*: ctc_amd_long_best_path
 PREFIX_MAX, PREFIX_GROUP = 64, 8  # CTC_AMD_PREFIX_MAX, CTC_AMD_PREFIX_GROUP
 NBEST_MAX, NBEST_GROUP = 64, 8  # CTC_AMD_NBEST_MAX, CTC_AMD_NBEST_GROUP: hypotheses per utterance, and per workgroup (one logits read)
@@ -124,6 +126,16 @@ SIGNATURES = {
     "ctc_amd_long_windowed_best_path": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int] + _COMMON_EX[11:] +
                                         [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                          _c_void_p, _c_size_t, _c_void_p]),
+    # optional wildcards: the counterparts' arguments
+    "ctc_amd_optional_wildcard_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
+    "ctc_amd_optional_wildcard_best_path": (_c_int, _COMMON_EX + [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                                  _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_optional_wildcard_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
+    "ctc_amd_optional_wildcard_loss_grad": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
+                                            [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_optional_wildcard_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
+    "ctc_amd_optional_wildcard_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
+                                                  [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     # ... and the three long-form ones of the summed lattice, in the same manner
     "ctc_amd_long_windowed_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                         [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),

@@ -22,6 +22,16 @@
 // WIN (ctc_amd_windowed_best_path): every lane holds the (first, last) frames of its own NL positions and the
 // producers write -inf for a position whose frame lies outside them -- a wildcard's m_t included, so on the simplified lattice the
 // horizontal step behind a wildcard costs its ring slot instead of the wave-uniform m_t.  Nothing behind the ring knows of windows.
+// OPT (ctc_amd_optional_wildcard_best_path): a label equal to ALIGN_OPTIONAL is a wildcard position that may be
+// skipped.  Two mask bits per position, set once (`skip`: the position before me is optional; `skipo`: classic, the open -> open
+// step over it is allowed) add two candidates to the open state, behind the existing ones and with strict comparisons too:
+//     O'[i] = max(O[i], C[i-1], O[i-1] if allowed, C[i-2] if skip, O[i-2] if skipo) + e[i]     (position -1 is the start state)
+//     S'[i] = max(S[i] + h, S[i-1] + e[i], S[i-2] + e[i] if skip)
+// The state two positions back comes from the lane's own registers or by one more DPP shift.  Back-pointers fit the same words:
+// classic, source code 3 of the open state = "two back" and the spare bit 3 NL + j says closed (0) or open (1); simplified, a second
+// bit NL + j = "entered from two back".  A last optional position makes the states before it end states (candidates in the order
+// closed, open of L - 1, then closed, open of L - 2 or the start state).  A skipped position reports first = last = -1 and a
+// label_score of 0, the log-probability of an empty run.
 // Every output element has one writer, no atomics: the same bits on every run.
 #include <type_traits>
 
@@ -79,12 +89,13 @@ __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-template <int KIND, int NL, bool WIN>
+template <int KIND, int NL, bool WIN, bool OPT>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem p, char *__restrict__ ws, size_t off_lp, size_t off_at,
                                                                    float *__restrict__ score, int *__restrict__ tokens,
                                                                    int *__restrict__ label_index, int *__restrict__ first_frame,
                                                                    int *__restrict__ last_frame, float *__restrict__ label_score,
                                                                    const int32_t *__restrict__ win, int wstride) {
+  static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
   typedef typename BpWord<NL>::type Word;
   typedef typename std::conditional<NL == 16, unsigned long long, unsigned int>::type Bits;
   constexpr int UP = 64 * NL;
@@ -103,6 +114,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   __shared__ double lse_s[ALIGN_PW];
   __shared__ double fin_s;
   __shared__ int fin_open_s;
+  [[maybe_unused]] __shared__ int fin_pos_s;  // OPT: the end state's position, L - 1 or L - 2 (-1: the start state)
   float *const ring = reinterpret_cast<float *>(smem);
 
   const int b = blockIdx.x;
@@ -117,17 +129,34 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   for (int i = tid; i < UP; i += ALIGN_THREADS) {
     int tok = -1;
     if (i < L) tok = label_at(p, label_row(p, b), i);
-    lab_s[i] = tok == ALIGN_WILDCARD ? ALIGN_WILDCARD : emits(p, tok) ? tok : -1;
+    lab_s[i] = tok == ALIGN_WILDCARD || (OPT && tok == ALIGN_OPTIONAL) ? tok : emits(p, tok) ? tok : -1;
     first_s[i] = -1; last_s[i] = -1;
   }
   __syncthreads();
+  auto is_wild = [](int tok) { return tok == ALIGN_WILDCARD || (OPT && tok == ALIGN_OPTIONAL); };
+  [[maybe_unused]] bool last_opt = false;  // OPT: the last position is optional: the states before it are end states too
+  if constexpr (OPT) {  // an optional wildcard beside another one is a bad label: no emission, no skip
+    bool pair[(UP + ALIGN_THREADS - 1) / ALIGN_THREADS];
+#pragma unroll
+    for (int q = 0; q < (UP + ALIGN_THREADS - 1) / ALIGN_THREADS; ++q) {
+      const int i = tid + q * ALIGN_THREADS;
+      pair[q] = i < UP && lab_s[i] == ALIGN_OPTIONAL &&
+                ((i > 0 && lab_s[i - 1] == ALIGN_OPTIONAL) || (i + 1 < UP && lab_s[i + 1] == ALIGN_OPTIONAL));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < (UP + ALIGN_THREADS - 1) / ALIGN_THREADS; ++q)
+      if (pair[q]) lab_s[tid + q * ALIGN_THREADS] = -1;
+    __syncthreads();
+    last_opt = L > 0 && lab_s[L - 1] == ALIGN_OPTIONAL;
+  }
 
   int lab[NL];
-  unsigned wild = 0;  // bit j = position lane * NL + j is a wildcard
+  unsigned wild = 0;  // bit j = position lane * NL + j is a wildcard (OPT: of either kind)
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     lab[j] = lab_s[lane * NL + j];
-    if (lab[j] == ALIGN_WILDCARD) wild |= 1u << j;
+    if (is_wild(lab[j])) wild |= 1u << j;
   }
   [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position lane * NL + j may own (from label_length on: never read, empty)
   if constexpr (WIN) {
@@ -159,7 +188,20 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
     const int i = lane * NL + j;
     if (KIND == 0 && i > 0) {
       const int prev = lab_s[i - 1];
-      if (lab[j] != prev || lab[j] == ALIGN_WILDCARD || prev == ALIGN_WILDCARD) allow |= 1u << j;
+      if (lab[j] != prev || is_wild(lab[j]) || is_wild(prev)) allow |= 1u << j;
+    }
+  }
+  // OPT: bit j of `skip` = the position before lane * NL + j is an optional wildcard; of `skipo` = (classic) the open -> open step
+  // over it is allowed
+  [[maybe_unused]] unsigned skip = 0, skipo = 0;
+  if constexpr (OPT) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = lane * NL + j;
+      if (i >= 1 && lab_s[i - 1] == ALIGN_OPTIONAL) {
+        skip |= 1u << j;
+        if (KIND == 0 && i >= 2 && (lab[j] != lab_s[i - 2] || is_wild(lab[j]) || is_wild(lab_s[i - 2]))) skipo |= 1u << j;
+      }
     }
   }
   double lse = 0.0;  // producers: sum of the LSE of this wavefront's frames
@@ -274,6 +316,13 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
       if (KIND == 0) {
         const double pO = from_prev_lane(O[NL - 1], NINF);
         const double pC = from_prev_lane(C[NL - 1], cs);
+        // OPT: the position two before the lane's first: the previous lane's last but one (NL = 1: two lanes back; before lane 0
+        // lies the start state, and nothing before that)
+        [[maybe_unused]] double pO2 = NINF, pC2 = NINF;
+        if constexpr (OPT) {
+          pO2 = from_prev_lane(NL == 1 ? pO : O[NL > 1 ? NL - 2 : 0], NINF);
+          pC2 = from_prev_lane(NL == 1 ? pC : C[NL > 1 ? NL - 2 : 0], NINF);
+        }
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double qO = j > 0 ? O[j > 0 ? j - 1 : 0] : pO;
@@ -283,6 +332,15 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
           unsigned src = 0;
           if (qC > best) { best = qC; src = 1; }
           if (a2 > best) { best = a2; src = 2; }
+          if constexpr (OPT) {  // over an optional wildcard: closed i - 2, then open i - 2
+            const double rC = j > 1 ? C[j > 1 ? j - 2 : 0] : j == 1 ? pC : pC2;
+            const double rO = j > 1 ? O[j > 1 ? j - 2 : 0] : j == 1 ? pO : pO2;
+            if (((skip >> j) & 1u) && rC > best) { best = rC; src = 3; }
+            if (((skipo >> j) & 1u) && rO > best) {
+              best = rO; src = 3;
+              bits |= (Bits)1 << (3 * NL + j);
+            }
+          }
           const unsigned sc = O[j] > C[j] ? 1u : 0u;
           const double bc = sc ? O[j] : C[j];
           O[j] = best + (double)e[j];
@@ -292,12 +350,22 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
       } else {
         const double emd = (double)em;
         const double pS = from_prev_lane(C[NL - 1], cs);
+        [[maybe_unused]] double pS2 = NINF;
+        if constexpr (OPT) pS2 = from_prev_lane(NL == 1 ? pS : C[NL > 1 ? NL - 2 : 0], NINF);
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
           const double d = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? (WIN ? (double)e[j] : emd) : ebd);
           const unsigned sd = d > h ? 1u : 0u;
-          C[j] = sd ? d : h;
+          double best = sd ? d : h;
+          if constexpr (OPT) {  // entered over an optional wildcard, from two positions back
+            const double r = ((skip >> j) & 1u) ? (j > 1 ? C[j > 1 ? j - 2 : 0] : j == 1 ? pS : pS2) + (double)e[j] : NINF;
+            if (r > best) {
+              best = r;
+              bits |= (Bits)1 << (NL + j);
+            }
+          }
+          C[j] = best;
           bits |= (Bits)sd << j;
         }
       }
@@ -323,11 +391,35 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
     for (int j = 1; j < NL; ++j)
       if (j == jj) { cv = C[j]; ov = O[j]; }
     if (L == 0) {
-      if (lane == 0) { fin_s = cs; fin_open_s = 0; }
-    } else if (lane == i / NL) {
-      const bool op = KIND == 0 && ov > cv;
-      fin_s = op ? ov : cv;
-      fin_open_s = op ? 1 : 0;
+      if (lane == 0) {
+        fin_s = cs; fin_open_s = 0;
+        if constexpr (OPT) fin_pos_s = -1;
+      }
+    } else {
+      [[maybe_unused]] double c2 = NINF, o2 = NINF;  // OPT: the states of position L - 2 (L = 1: the start state), in every lane
+      if constexpr (OPT) {
+        if (last_opt) {
+          const int i2 = L >= 2 ? L - 2 : 0, j2 = i2 & (NL - 1);
+          c2 = C[0]; o2 = O[0];
+#pragma unroll
+          for (int j = 1; j < NL; ++j)
+            if (j == j2) { c2 = C[j]; o2 = O[j]; }
+          c2 = __shfl(c2, i2 / NL);
+          o2 = KIND == 0 ? __shfl(o2, i2 / NL) : NINF;
+          if (L == 1) { c2 = cs; o2 = NINF; }
+        }
+      }
+      if (lane == i / NL) {
+        const bool op = KIND == 0 && ov > cv;
+        double fin = op ? ov : cv;
+        int fopen = op ? 1 : 0, fpos = L - 1;
+        if constexpr (OPT) {
+          if (c2 > fin) { fin = c2; fopen = 0; fpos = L - 2; }
+          if (o2 > fin) { fin = o2; fopen = 1; fpos = L - 2; }
+        }
+        fin_s = fin; fin_open_s = fopen;
+        if constexpr (OPT) fin_pos_s = fpos;
+      }
     }
   } else if (lane == 0) {
     lse_s[wave - 1] = lse;
@@ -353,7 +445,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
     for (int i = tid; i < U; i += ALIGN_THREADS) {
       if (first_out) first_out[i] = -1;
       if (last_out) last_out[i] = -1;
-      if (ls_out) ls_out[i] = -__builtin_inff();
+      if (ls_out) ls_out[i] = (OPT && feasible && i < L) ? 0.f : -__builtin_inff();  // (feasible without frames: an empty run)
     }
     return;
   }
@@ -371,7 +463,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
     for (int k = tid - 64; k < n16; k += ALIGN_THREADS - 64) dst[k] = src[k];
   };
   const int nblk = (Tb + BF - 1) / BF;
-  int si = L - 1, sopen = fin_open_s;  // state after the frame being decoded
+  int si = OPT ? fin_pos_s : L - 1, sopen = fin_open_s;  // state after the frame being decoded
   int nxt = -1;                        // label index of the frame behind the one being decoded
   if (wave > 0) fetch(nblk - 1);
   __syncthreads();
@@ -396,15 +488,23 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
               const unsigned src = c & 3u;
               if (src == 1) { --si; sopen = 0; ends = 1; }
               else if (src == 2) { --si; ends = 1; }
+              else if (OPT && src == 3) {  // over an optional wildcard: the spare bit says which state two back
+                sopen = (int)((unsigned)(word >> (3 * NL + (si & (NL - 1)))) & 1u);
+                si -= 2; ends = 1;
+              }
             } else if (c & 4u) {
               sopen = 1;
             }
+          } else if (OPT && ((unsigned)(word >> (NL + (si & (NL - 1)))) & 1u)) {  // entered from two back (it outranks bit j)
+            tok = lab_s[si]; idx = si;
+            si -= 2; ends = 1;
           } else if ((unsigned)(word >> (si & (NL - 1))) & 1u) {
             tok = lab_s[si]; idx = si;
             --si; ends = 1;
-          } else if (lab_s[si] == ALIGN_WILDCARD) {  // a horizontal step behind a wildcard's entry: still the wildcard's
+          } else if (is_wild(lab_s[si])) {  // a horizontal step behind a wildcard's entry: still the wildcard's
             tok = ALIGN_WILDCARD; idx = si;
           }
+          if (OPT && tok == ALIGN_OPTIONAL) tok = ALIGN_WILDCARD;  // (the sentinel of "a_t goes here")
           if (si < 0) sopen = 0;
         }
         if (idx >= 0 && idx != nxt) ends |= 2u;
@@ -433,6 +533,8 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
       if (f >= 0) {
         s = 0.0;
         for (int t = f; t <= l; ++t) s += lpw[t];
+      } else if (OPT && lab_s[i] == ALIGN_OPTIONAL) {
+        s = 0.0;  // skipped: an empty run
       }
     }
     if (first_out) first_out[i] = f;
@@ -441,10 +543,10 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   }
 }
 
-template <int KIND, int NL, bool WIN>
+template <int KIND, int NL, bool WIN, bool OPT>
 hipError_t launch_align_wild(const Problem &p, char *ws, size_t off_lp, size_t off_at, float *score, int *tokens, int *label_index,
                              int *first_frame, int *last_frame, float *label_score, const int32_t *win, int wstride, hipStream_t st) {
-  hipLaunchKernelGGL((align_wild_kernel<KIND, NL, WIN>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
+  hipLaunchKernelGGL((align_wild_kernel<KIND, NL, WIN, OPT>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
                      label_index, first_frame, last_frame, label_score, win, wstride);
   return hipGetLastError();
 }
@@ -455,22 +557,28 @@ size_t align_wild_workspace_bytes(int B, int T, int U) {
   return r256((size_t)B * T * 64 * bp_word_bytes(nl_for(U))) + r256((size_t)B * T * 8) + r256((size_t)B * T * 4);
 }
 
-#define CTC_ALIGN_WILD_ROW(KIND, WIN)                                                                                  \
-  {launch_align_wild<KIND, 1, WIN>, launch_align_wild<KIND, 2, WIN>, launch_align_wild<KIND, 4, WIN>, launch_align_wild<KIND, 8, WIN>, \
-   launch_align_wild<KIND, 16, WIN>}
+#define CTC_ALIGN_WILD_ROW(KIND, WIN, OPT)                                                                                       \
+  {launch_align_wild<KIND, 1, WIN, OPT>, launch_align_wild<KIND, 2, WIN, OPT>, launch_align_wild<KIND, 4, WIN, OPT>, \
+   launch_align_wild<KIND, 8, WIN, OPT>, launch_align_wild<KIND, 16, WIN, OPT>}
 
 hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
-                          float *label_score, hipStream_t st, const int32_t *frame_window, int window_stride) {
+                          float *label_score, hipStream_t st, const int32_t *frame_window, int window_stride, bool optional_wildcards) {
   typedef hipError_t Launch(const Problem &, char *, size_t, size_t, float *, int *, int *, int *, int *, float *, const int32_t *, int,
                             hipStream_t);
-  static Launch *const table[2][2][5] = {{CTC_ALIGN_WILD_ROW(0, false), CTC_ALIGN_WILD_ROW(1, false)},
-                                         {CTC_ALIGN_WILD_ROW(0, true), CTC_ALIGN_WILD_ROW(1, true)}};
+  static Launch *const table[3][2][5] = {{CTC_ALIGN_WILD_ROW(0, false, false), CTC_ALIGN_WILD_ROW(1, false, false)},
+                                         {CTC_ALIGN_WILD_ROW(0, true, false), CTC_ALIGN_WILD_ROW(1, true, false)},
+                                         // (classic, NL = 16 with OPT needs scratch: not built, U <= ALIGN_OPTIONAL_CLASSIC_MAX_U)
+                                         {{launch_align_wild<0, 1, false, true>, launch_align_wild<0, 2, false, true>,
+                                           launch_align_wild<0, 4, false, true>, launch_align_wild<0, 8, false, true>, nullptr},
+                                          CTC_ALIGN_WILD_ROW(1, false, true)}};
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
-  if (lg < 0 || p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
+  if (lg < 0 || p.kind < 0 || p.kind > 1 || (frame_window && optional_wildcards)) return hipErrorInvalidValue;
   const size_t off_lp = r256((size_t)p.B * p.T * 64 * bp_word_bytes(NL));
   const size_t off_at = off_lp + r256((size_t)p.B * p.T * 8);
-  return table[frame_window ? 1 : 0][p.kind][lg](p, ws, off_lp, off_at, score, tokens, label_index, first_frame, last_frame, label_score,
+  Launch *const launch = table[optional_wildcards ? 2 : frame_window ? 1 : 0][p.kind][lg];
+  if (!launch) return hipErrorInvalidValue;
+  return launch(p, ws, off_lp, off_at, score, tokens, label_index, first_frame, last_frame, label_score,
                                                  frame_window, window_stride, st);
 }
 

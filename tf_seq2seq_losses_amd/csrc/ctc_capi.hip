@@ -873,21 +873,61 @@ int ctc_amd_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, in
   return CTC_AMD_OK;
 }
 
+static_assert(ctc::ALIGN_OPTIONAL == CTC_AMD_OPTIONAL_WILDCARD && ctc::ALIGN_OPTIONAL_CLASSIC_MAX_U == CTC_AMD_OPTIONAL_CLASSIC_MAX_U,
+              "the alignment kernel's optional wildcard label and its classic limit are the ABI's");
+
+// the one limit of its own that ctc_amd_optional_wildcard_best_path has (behind the counterpart's checks, before the workspace)
+static int check_optional_alignment(bool optional_wildcards, int kind, int U) {
+  if (optional_wildcards && kind == CTC_AMD_CLASSIC && U > CTC_AMD_OPTIONAL_CLASSIC_MAX_U)
+    return fail(CTC_AMD_EINVAL, "U=%d exceeds CTC_AMD_OPTIONAL_CLASSIC_MAX_U=%d of the classic optional-wildcard alignment", U,
+                CTC_AMD_OPTIONAL_CLASSIC_MAX_U);
+  return CTC_AMD_OK;
+}
+
+// One body for ctc_amd_windowed_best_path and ctc_amd_optional_wildcard_best_path (which has no window).
+static int wildcard_best_path_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                   int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                   const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride, int B,
+                                   int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame,
+                                   int32_t *last_frame, float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
+  if (!pre.go) return pre.rc;
+  if (int rc = check_alignment(score, tokens, T, V)) return rc;
+  if (int rc = check_window(frame_window, window_stride, U)) return rc;
+  if (int rc = check_optional_alignment(optional_wildcards, kind, U)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
+  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
+                              static_cast<hipStream_t>(stream), frame_window, window_stride, optional_wildcards),
+          "wildcard alignment launch");
+  return CTC_AMD_OK;
+}
+
 // The four windowed entry points are their counterparts with a frame window; the counterparts are they with none.
 int ctc_amd_windowed_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
                                int blank_index, const int32_t *frame_window, int window_stride, int B, int T, int V, int U, float *score,
                                int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame, float *label_score,
                                void *workspace, size_t workspace_bytes, void *stream) {
-  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
-  const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false);
-  if (!pre.go) return pre.rc;
-  if (int rc = check_alignment(score, tokens, T, V)) return rc;
-  if (int rc = check_window(frame_window, window_stride, U)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
-                              static_cast<hipStream_t>(stream), frame_window, window_stride), "wildcard alignment launch");
-  return CTC_AMD_OK;
+  return wildcard_best_path_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                 label_length, logit_length, blank_index, frame_window, window_stride, B, T, V, U, score, tokens,
+                                 label_index, first_frame, last_frame, label_score, workspace, workspace_bytes, stream);
+}
+
+// The back-pointer words have room for the two further sources: the counterpart's workspace.
+int ctc_amd_optional_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  if (int rc = ctc_amd_wildcard_best_path_workspace_bytes(kind, B, T, V, U, out_bytes)) return rc;
+  return check_optional_alignment(true, kind, U);
+}
+
+int ctc_amd_optional_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                        int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                        const int32_t *logit_length, int blank_index, int B, int T, int V, int U, float *score,
+                                        int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
+                                        float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
+  return wildcard_best_path_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                 label_length, logit_length, blank_index, nullptr, 0, B, T, V, U, score, tokens, label_index, first_frame,
+                                 last_frame, label_score, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
@@ -963,6 +1003,7 @@ int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int l
 }
 
 static_assert(ctc::WILD_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the loss kernel's wildcard label is the ABI's");
+static_assert(ctc::WILD_LOSS_OPTIONAL == CTC_AMD_OPTIONAL_WILDCARD, "the loss kernel's optional wildcard label is the ABI's");
 
 int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
   if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
@@ -971,11 +1012,13 @@ int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, 
 }
 
 // The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
-int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
-                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
-                               int blank_index, const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T,
-                               int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
-                               int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+// One body for ctc_amd_windowed_loss_grad and ctc_amd_optional_wildcard_loss_grad (which has no window).
+static int wildcard_loss_grad_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                   int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                   const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
+                                   float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss, void *grad,
+                                   int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
   const Prelude pre = prelude(c, f, grad != nullptr);
@@ -985,8 +1028,33 @@ int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits
   const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
   CTC_TRY(ctc::run_wild_loss(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
-                             frame_window, window_stride), "wildcard loss launch");
+                             frame_window, window_stride, optional_wildcards), "wildcard loss launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                               const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                               int blank_index, const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T,
+                               int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                               int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  return wildcard_loss_grad_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                 label_length, logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U,
+                                 d_loss, loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
+}
+
+// Optional wildcards: the counterpart's arguments, checks and workspace; CTC_AMD_OPTIONAL_WILDCARD is accepted in the labels.
+int ctc_amd_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
+  return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, want_grad, out_bytes);
+}
+
+int ctc_amd_optional_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                        int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                        const int32_t *logit_length, int blank_index, float wildcard_log_weight, int B, int T, int V, int U,
+                                        const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                        int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  return wildcard_loss_grad_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                 label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad,
+                                 grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
@@ -1064,12 +1132,13 @@ int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U
   return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
 }
 
-int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
-                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
-                                     const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
-                                     float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
-                                     float *blank_posterior, float *duration, float *expected_frame, void *workspace,
-                                     size_t workspace_bytes, void *stream) {
+// One body for ctc_amd_windowed_label_posterior and ctc_amd_optional_wildcard_label_posterior (which has no window).
+static int label_posterior_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
+                                float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                float *blank_posterior, float *duration, float *expected_frame, void *workspace, size_t workspace_bytes,
+                                void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
   const Prelude pre = prelude(c, f, false);
@@ -1082,9 +1151,36 @@ int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int 
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, ctc::wild_loss_workspace_bytes(kind, B, T, U, true), NullWs::Refused)) return rc;
   CTC_TRY(ctc::run_label_posterior(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
-                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream), frame_window, window_stride),
+                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream), frame_window, window_stride,
+                                   optional_wildcards),
           "label posterior launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                     const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
+                                     float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                     float *blank_posterior, float *duration, float *expected_frame, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+  return label_posterior_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                              logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U, loss,
+                              label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_optional_wildcard_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  return ctc_amd_label_posterior_workspace_bytes(kind, B, T, V, U, out_bytes);
+}
+
+int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                              int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                              const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                              float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                              float *blank_posterior, float *duration, float *expected_frame, void *workspace,
+                                              size_t workspace_bytes, void *stream) {
+  return label_posterior_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                              logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss, label_posterior,
+                              blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,

@@ -34,6 +34,13 @@
 // NL positions; the producers write -inf for an ordinary position whose frame lies outside them and, into the ring slot of a wildcard
 // position (which holds -inf otherwise and is never read), the gate 0 / -inf that the chain adds to the wave-uniform e_w.  The row
 // stage and the statistics know nothing of windows.
+// OPT (ctc_amd_optional_wildcard_loss_grad / _label_posterior): a label equal to WILD_LOSS_OPTIONAL is a
+// wildcard position that may be skipped.  Two mask bits per position, set once (`skip`: the position before me is optional; `skipo`:
+// classic, the open -> open step over it is allowed), add to the recursions above
+//     O'[i] += C[i-2] if skip, O[i-2] if skipo          S'[i] += S[i-2] + e[i] if skip          (position -1 is the start state)
+// with the state two positions back taken from the lane's own registers or by one more DPP shift, and the beta sweep the mirror
+// image; a last optional position makes the states before it end states.  The further terms come behind the existing ones in the
+// sums: -inf there leaves the bits as they are.  The row stage counts the optional wildcard as a wildcard; nothing else knows of it.
 // A saved row of frame t: per position i the pair (O, C) (classic, AFTER frame t) or S (simplified, BEFORE frame t), then the start
 // state: (2 or 1) * UP + 2 doubles.  After the beta sweep the first 8 bytes of position i hold
 //   classic:    (posterior of O[i] after frame t,  posterior of C[i] = a blank behind label i)
@@ -85,6 +92,20 @@ __device__ __forceinline__ double wl_lse(double a, double b, double c) {
   return mm + (double)flog2((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm)));
 }
 
+// ... four and five operands (OPT): the further terms are added behind the first three, so operands of -inf there leave the bits
+// of the three-operand result as they are
+__device__ __forceinline__ double wl_lse(double a, double b, double c, double d) {
+  const double m = fmax(fmax(a, b), fmax(c, d));
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2(((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm))) + fexp2((float)(d - mm)));
+}
+__device__ __forceinline__ double wl_lse(double a, double b, double c, double d, double e) {
+  const double m = fmax(fmax(fmax(a, b), fmax(c, d)), e);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2((((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm))) + fexp2((float)(d - mm))) +
+                            fexp2((float)(e - mm)));
+}
+
 // the gradient's workspace (MODE 0: unused)
 struct WlWs {
   double *rows;  // [B][T][SRD] saved alpha rows, then the posteriors
@@ -99,9 +120,10 @@ struct WlPostWs : WlWs {
 };
 template <int MODE> using WlArg = std::conditional_t<MODE == 3, WlPostWs, WlWs>;
 
-template <int KIND, int NL, int MODE, bool WIN>
+template <int KIND, int NL, int MODE, bool WIN, bool OPT>
 __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss,
                                                                const WlArg<MODE> ws, const int32_t *__restrict__ win, int wstride) {
+  static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
   constexpr bool BACK = MODE >= 2;              // a beta sweep: frames from T_b - 1 down
   constexpr int UP = 64 * NL;
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
@@ -142,16 +164,25 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   for (int i = tid; i < UP; i += WL_THREADS) {
     int tok = -1;
     if (i < L) tok = label_at(p, label_row(p, b), i);
-    lab_s[i] = tok == WILD_LOSS_WILDCARD ? WILD_LOSS_WILDCARD : emits(p, tok) ? tok : -1;
+    int cls = tok == WILD_LOSS_WILDCARD ? WILD_LOSS_WILDCARD : emits(p, tok) ? tok : -1;
+    if constexpr (OPT) {  // an optional wildcard; beside another one it is a bad label: no emission, no skip
+      if (tok == WILD_LOSS_OPTIONAL) {
+        const int32_t *const lr = label_row(p, b);
+        const bool pair = (i > 0 && label_at(p, lr, i - 1) == WILD_LOSS_OPTIONAL) || (i + 1 < L && label_at(p, lr, i + 1) == WILD_LOSS_OPTIONAL);
+        cls = pair ? -1 : WILD_LOSS_OPTIONAL;
+      }
+    }
+    lab_s[i] = cls;
   }
   __syncthreads();
 
+  auto is_wild = [](int tok) { return tok == WILD_LOSS_WILDCARD || (OPT && tok == WILD_LOSS_OPTIONAL); };
   int lab[NL];
-  unsigned wild = 0;  // bit j = position lane * NL + j is a wildcard
+  unsigned wild = 0;  // bit j = position lane * NL + j is a wildcard (OPT: of either kind)
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     lab[j] = lab_s[lane * NL + j];
-    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+    if (is_wild(lab[j])) wild |= 1u << j;
   }
   [[maybe_unused]] int wf[NL], wl[NL];  // WIN: the frames position lane * NL + j may own (from label_length on: never read, empty)
   if constexpr (WIN) {
@@ -178,8 +209,23 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   auto allowed = [&](int i) {
     if (i <= 0 || i >= UP) return false;
     const int a = lab_s[i], q = lab_s[i - 1];
-    return a != q || a == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD;
+    return a != q || is_wild(a) || is_wild(q);
   };
+  // OPT: bit q of `skip` = the position before lane * NL + q is an optional wildcard, so this one may also be entered from two
+  // positions back; bit q of `skipo` = (classic) ... from the open state there too.  q runs to NL + 1: the beta sweep looks two ahead
+  [[maybe_unused]] unsigned skip = 0, skipo = 0;
+  [[maybe_unused]] bool last_opt = false;  // the last position is optional: the states before it are end states too
+  if constexpr (OPT) {
+#pragma unroll
+    for (int q = 0; q < NL + 2; ++q) {
+      const int i = lane * NL + q;
+      if (i >= 1 && i < UP && lab_s[i - 1] == WILD_LOSS_OPTIONAL) {
+        skip |= 1u << q;
+        if (KIND == 0 && i >= 2 && (lab_s[i] != lab_s[i - 2] || is_wild(lab_s[i]) || is_wild(lab_s[i - 2]))) skipo |= 1u << q;
+      }
+    }
+    last_opt = L > 0 && lab_s[L - 1] == WILD_LOSS_OPTIONAL;
+  }
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     O[j] = NINF; C[j] = NINF;
@@ -187,8 +233,8 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
   }
   if constexpr (BACK) {  // behind the last frame only the end states have any mass
 #pragma unroll
-    for (int j = 0; j < NL; ++j) O[j] = C[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
-    cs = L == 0 ? 0.0 : NINF;
+    for (int j = 0; j < NL; ++j) O[j] = C[j] = (lane * NL + j == L - 1 || (OPT && last_opt && lane * NL + j == L - 2)) ? 0.0 : NINF;
+    cs = (L == 0 || (OPT && last_opt && L == 1)) ? 0.0 : NINF;
     if (KIND == 0) allow_nx = allowed((lane + 1) * NL) ? 1 : 0;
   }
 
@@ -300,21 +346,42 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       if (KIND == 0) {
         const double pO = from_prev_lane(O[NL - 1], NINF);
         const double pC = from_prev_lane(C[NL - 1], cs);
+        // OPT: the position two before the lane's first: the previous lane's last but one (NL = 1: two lanes back; before lane 0
+        // lies the start state, and nothing before that)
+        [[maybe_unused]] double pO2 = NINF, pC2 = NINF;
+        if constexpr (OPT) {
+          pO2 = from_prev_lane(NL == 1 ? pO : O[NL > 1 ? NL - 2 : 0], NINF);
+          pC2 = from_prev_lane(NL == 1 ? pC : C[NL > 1 ? NL - 2 : 0], NINF);
+        }
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double qO = j > 0 ? O[j > 0 ? j - 1 : 0] : pO;
           const double qC = j > 0 ? C[j > 0 ? j - 1 : 0] : pC;
           const double a2 = ((allow >> j) & 1u) ? qO : NINF;
-          const double o = wl_lse(O[j], qC, a2) + em(j);
+          double o;
+          if constexpr (OPT) {
+            const double rO = j > 1 ? O[j > 1 ? j - 2 : 0] : j == 1 ? pO : pO2;
+            const double rC = j > 1 ? C[j > 1 ? j - 2 : 0] : j == 1 ? pC : pC2;
+            o = wl_lse(O[j], qC, a2, ((skip >> j) & 1u) ? rC : NINF, ((skipo >> j) & 1u) ? rO : NINF) + em(j);
+          } else {
+            o = wl_lse(O[j], qC, a2) + em(j);
+          }
           C[j] = wl_lse(C[j], O[j]) + eb;
           O[j] = o;
         }
       } else {
         const double pS = from_prev_lane(C[NL - 1], cs);
+        [[maybe_unused]] double pS2 = NINF;
+        if constexpr (OPT) pS2 = from_prev_lane(NL == 1 ? pS : C[NL > 1 ? NL - 2 : 0], NINF);
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
-          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), q + em(j));
+          if constexpr (OPT) {
+            const double r = j > 1 ? C[j > 1 ? j - 2 : 0] : j == 1 ? pS : pS2;
+            C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), q + em(j), ((skip >> j) & 1u) ? r + em(j) : NINF);
+          } else {
+            C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), q + em(j));
+          }
         }
       }
       cs += eb;
@@ -397,23 +464,47 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         // beta back over frame t: x = what entering O[i] with this frame is worth
         double x = O[0] + em(0);
         const double xl = from_next_lane(x, NINF);
-        cs = wl_lse(cs + eb, x);
+        if constexpr (OPT) {
+          // the mirror image of the alpha step: what entering the open states one and two positions ahead is worth; beyond the
+          // lane's own they are the next lane's first two (NL = 1: the next two lanes')
+          double x1 = NL > 1 ? O[NL > 1 ? 1 : 0] + em(NL > 1 ? 1 : 0) : xl;
+          const double xl2 = from_next_lane(x1, NINF);
+          cs = wl_lse(cs + eb, x, ((skip >> 1) & 1u) ? x1 : NINF);
 #pragma unroll
-        for (int j = 0; j < NL; ++j) {
-          const double xn = j + 1 < NL ? O[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
-          const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
-          const double cb = C[j] + eb;
-          O[j] = wl_lse(x, cb, al ? xn : NINF);
-          C[j] = wl_lse(cb, xn);
-          x = xn;
+          for (int j = 0; j < NL; ++j) {
+            const double x2 = j + 2 < NL ? O[j + 2 < NL ? j + 2 : 0] + em(j + 2 < NL ? j + 2 : 0) : j + 2 == NL ? xl : xl2;
+            const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+            const double cb = C[j] + eb;
+            O[j] = wl_lse(x, cb, al ? x1 : NINF, ((skipo >> (j + 2)) & 1u) ? x2 : NINF);
+            C[j] = wl_lse(cb, x1, ((skip >> (j + 2)) & 1u) ? x2 : NINF);
+            x = x1;
+            x1 = x2;
+          }
+        } else {
+          cs = wl_lse(cs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? O[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+            const double cb = C[j] + eb;
+            O[j] = wl_lse(x, cb, al ? xn : NINF);
+            C[j] = wl_lse(cb, xn);
+            x = xn;
+          }
         }
       } else {
         const double ap0 = from_prev_lane(A[NL - 1], Acs);
+        [[maybe_unused]] double ap00 = NINF;  // OPT: alpha two positions before the lane's first
+        if constexpr (OPT) ap00 = from_prev_lane(NL == 1 ? ap0 : A[NL > 1 ? NL - 2 : 0], NINF);
         [[maybe_unused]] float pl[NL], pb = 0.f;
         if (MODE == 3 && lane == 0) pb = post(Acs + eb + cs);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          if constexpr (OPT) {  // entered from one position back or, over an optional wildcard, from two
+            const double ap2 = j > 1 ? A[j > 1 ? j - 2 : 0] : j == 1 ? ap0 : ap00;
+            ap = wl_lse(ap, ((skip >> j) & 1u) ? ap2 : NINF);
+          }
           const bool wj = ((wild >> j) & 1u) != 0;
           const double h = wj ? ewj(j) : eb;
           const float pe = post(ap + em(j) + C[j]), ps = post(A[j] + h + C[j]);
@@ -428,12 +519,24 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         else if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
         double x = C[0] + em(0);
         const double xl = from_next_lane(x, NINF);
-        cs = wl_lse(cs + eb, x);
+        if constexpr (OPT) {
+          double x1 = NL > 1 ? C[NL > 1 ? 1 : 0] + em(NL > 1 ? 1 : 0) : xl;
+          const double xl2 = from_next_lane(x1, NINF);
+          cs = wl_lse(cs + eb, x, ((skip >> 1) & 1u) ? x1 : NINF);
 #pragma unroll
-        for (int j = 0; j < NL; ++j) {
-          const double xn = j + 1 < NL ? C[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
-          C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), xn);
-          x = xn;
+          for (int j = 0; j < NL; ++j) {
+            const double x2 = j + 2 < NL ? C[j + 2 < NL ? j + 2 : 0] + em(j + 2 < NL ? j + 2 : 0) : j + 2 == NL ? xl : xl2;
+            C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), x1, ((skip >> (j + 2)) & 1u) ? x2 : NINF);
+            x1 = x2;
+          }
+        } else {
+          cs = wl_lse(cs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? C[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            C[j] = wl_lse(C[j] + (((wild >> j) & 1u) ? ewj(j) : eb), xn);
+            x = xn;
+          }
         }
       }
     }
@@ -464,6 +567,19 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       if (j == jj) { cv = C[j]; ov = O[j]; }
     double v = cs;
     if (L > 0) v = KIND == 0 ? wl_lse(ov, cv) : cv;
+    if constexpr (OPT) {  // the last position may be empty: the states before it end the utterance too (every lane takes part)
+      if (last_opt) {
+        const int i2 = L >= 2 ? L - 2 : 0, j2 = i2 & (NL - 1);
+        double c2 = C[0], o2 = O[0];
+#pragma unroll
+        for (int j = 1; j < NL; ++j)
+          if (j == j2) { c2 = C[j]; o2 = O[j]; }
+        c2 = __shfl(c2, i2 / NL);
+        o2 = __shfl(o2, i2 / NL);
+        const double v2 = L == 1 ? cs : KIND == 0 ? wl_lse(o2, c2) : c2;
+        v = wl_lse(v, v2);
+      }
+    }
     if (too_long) v = NINF;
     if (lane == (L > 0 ? i / NL : 0)) {
       loss[b] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
@@ -477,7 +593,7 @@ constexpr int WLG_WAVES = 4;
 constexpr int WLG_CH = 1024;  // columns per pass
 constexpr int WLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units of 2^-40, so |bin| < U 2^40
 
-template <int KIND>
+template <int KIND, bool OPT>
 __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Problem p, const int UP, const float *__restrict__ d_loss,
                                                                        const WlWs ws, void *__restrict__ grad) {
   constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
@@ -542,7 +658,7 @@ __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Pro
     for (int i = lane; i < L; i += 64) {
       const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
       const int tok = label_at(p, lab, i);
-      const bool w = tok == WILD_LOSS_WILDCARD;
+      const bool w = tok == WILD_LOSS_WILDCARD || (OPT && tok == WILD_LOSS_OPTIONAL);  // (OPT: a feasible utterance has no bad pair)
       const unsigned rel = (unsigned)(tok - c0);
       if (!w && emits(p, tok) && rel < (unsigned)WLG_CH)
         atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, WLG_FIX)));
@@ -617,31 +733,33 @@ __global__ __launch_bounds__(64 * LS_SLICES) void label_stat_kernel(const Proble
   expected_frame[(size_t)b * p.U + i] = d > 0.0 ? (float)(m / d) : -1.f;
 }
 
-template <int KIND, int NL, int MODE, bool WIN>
+template <int KIND, int NL, int MODE, bool WIN, bool OPT>
 hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const int32_t *win, int wstride, hipStream_t st) {
-  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE, WIN>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws, win, wstride);
+  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE, WIN, OPT>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws, win, wstride);
   return hipGetLastError();
 }
 
-// the window of a call: nullptr runs the WIN = false kernels
+// the window of a call: nullptr runs the WIN = false kernels; optional: the OPT kernels (never with a window)
 struct WlWindow {
   const int32_t *ptr;
   int stride;
+  bool optional;
 };
 
-#define CTC_WILD_LOSS_ROW(KIND, WIN)                                                                                     \
-  {launch_wild_loss<KIND, 1, MODE, WIN>, launch_wild_loss<KIND, 2, MODE, WIN>, launch_wild_loss<KIND, 4, MODE, WIN>, \
-   launch_wild_loss<KIND, 8, MODE, WIN>, launch_wild_loss<KIND, 16, MODE, WIN>}
+#define CTC_WILD_LOSS_ROW(KIND, WIN, OPT)                                                                                             \
+  {launch_wild_loss<KIND, 1, MODE, WIN, OPT>, launch_wild_loss<KIND, 2, MODE, WIN, OPT>, launch_wild_loss<KIND, 4, MODE, WIN, OPT>, \
+   launch_wild_loss<KIND, 8, MODE, WIN, OPT>, launch_wild_loss<KIND, 16, MODE, WIN, OPT>}
 
 template <int MODE>
 hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const WlWindow &fw, hipStream_t st) {
   typedef hipError_t Launch(const Problem &, double, float *, const WlArg<MODE> &, const int32_t *, int, hipStream_t);
-  static Launch *const table[2][2][5] = {{CTC_WILD_LOSS_ROW(0, false), CTC_WILD_LOSS_ROW(1, false)},
-                                         {CTC_WILD_LOSS_ROW(0, true), CTC_WILD_LOSS_ROW(1, true)}};
+  static Launch *const table[3][2][5] = {{CTC_WILD_LOSS_ROW(0, false, false), CTC_WILD_LOSS_ROW(1, false, false)},
+                                         {CTC_WILD_LOSS_ROW(0, true, false), CTC_WILD_LOSS_ROW(1, true, false)},
+                                         {CTC_WILD_LOSS_ROW(0, false, true), CTC_WILD_LOSS_ROW(1, false, true)}};
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
-  if (lg < 0 || p.kind < 0 || p.kind > 1) return hipErrorInvalidValue;
-  return table[fw.ptr ? 1 : 0][p.kind][lg](p, w2, loss, ws, fw.ptr, fw.stride, st);
+  if (lg < 0 || p.kind < 0 || p.kind > 1 || (fw.ptr && fw.optional)) return hipErrorInvalidValue;
+  return table[fw.optional ? 2 : fw.ptr ? 1 : 0][p.kind][lg](p, w2, loss, ws, fw.ptr, fw.stride, st);
 }
 
 inline size_t wl_al(size_t x) { return (x + 255) & ~size_t(255); }
@@ -663,9 +781,9 @@ size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad) 
 }
 
 hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
-                         hipStream_t st, const int32_t *frame_window, int window_stride) {
+                         hipStream_t st, const int32_t *frame_window, int window_stride, bool optional_wildcards) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
-  const WlWindow fw{frame_window, window_stride};
+  const WlWindow fw{frame_window, window_stride, optional_wildcards};
   if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, fw, st);
   const int UP = 64 * nl_for(p.U);
   const WlWs ws = wl_regions(p, wsp);
@@ -673,16 +791,23 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
   if (p.T == 0) return hipSuccess;  // no rows
   if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, fw, st)) return e;
   const unsigned blocks = (unsigned)(((long)p.B * p.T + WLG_WAVES - 1) / WLG_WAVES);
-  if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
-  else hipLaunchKernelGGL((wild_grad_row_kernel<1>), dim3(blocks), dim3(64 * WLG_WAVES), 0, st, p, UP, d_loss, ws, grad);
+  const dim3 grid(blocks), block(64 * WLG_WAVES);
+  if (optional_wildcards) {
+    if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0, true>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+    else hipLaunchKernelGGL((wild_grad_row_kernel<1, true>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+  } else if (p.kind == 0) {
+    hipLaunchKernelGGL((wild_grad_row_kernel<0, false>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+  } else {
+    hipLaunchKernelGGL((wild_grad_row_kernel<1, false>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+  }
   return hipGetLastError();
 }
 
 hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
                                float *duration, float *expected_frame, char *wsp, hipStream_t st, const int32_t *frame_window,
-                               int window_stride) {
+                               int window_stride, bool optional_wildcards) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
-  const WlWindow fw{frame_window, window_stride};
+  const WlWindow fw{frame_window, window_stride, optional_wildcards};
   WlPostWs ws;
   static_cast<WlWs &>(ws) = wl_regions(p, wsp);
   ws.post = label_posterior;

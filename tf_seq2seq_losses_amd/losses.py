@@ -263,6 +263,7 @@ def ctc_alignment_from_logproba(labels, logprobas, label_length, logit_length, b
 # forced alignment of partial transcripts (wildcard labels): an extension, the reference has no counterpart
 # --------------------------------------------------------------------------------------------------
 WILDCARD = _lib.WILDCARD  # -2: the label value of a wildcard position
+OPTIONAL_WILDCARD = _lib.OPTIONAL_WILDCARD  # -3: a wildcard position that may be empty (only with optional_wildcards=True)
 
 
 def ctc_frame_window(first_frame: TensorLike, last_frame: TensorLike, logit_length: TensorLike, *, before: int = 0,
@@ -303,7 +304,10 @@ class CtcWildcardAlignment(NamedTuple):
 
 
 def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index,
-                    max_label_length=None, frame_window=None) -> CtcWildcardAlignment:
+                    max_label_length=None, frame_window=None,
+                    optional_wildcards: bool = False) -> CtcWildcardAlignment:
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("frame_window and optional_wildcards=True cannot be combined")
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -314,6 +318,8 @@ def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_len
     with torch.no_grad():  # a path is not differentiable: the result is detached
         prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
                             host_max_label_length=max_label_length)
+        if optional_wildcards:
+            return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep, optional_wildcards=True))
         if frame_window is None:
             return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep))
         return CtcWildcardAlignment(*ops.wildcard_best_path(ops.KINDS[kind_name], wrt, prep, _as_tensor(frame_window)))
@@ -321,7 +327,8 @@ def _wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_len
 
 def classic_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                    blank_index: Union[int, torch.Tensor] = 0, *,
-                                   max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
+                                   max_label_length: Optional[int] = None, frame_window=None,
+                    optional_wildcards: bool = False) -> CtcWildcardAlignment:
     """Forced alignment of a partial transcript on the classic lattice.  As classic_ctc_alignment, but a label equal to WILDCARD
     (-2) stands for any non-empty run of frames with any tokens on them: untranscribed speech before, after or inside the known
     words (free start and end are a wildcard as the first and last label).  A wildcard's frames score their best token and report
@@ -331,28 +338,35 @@ def classic_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label
     frame_window [batch, U, 2] int32 / int64 on the logits' device, (first, last) inclusive per
     label position -- the convention of first_frame / last_frame; see ctc_frame_window -- lets position i own frame t only if
     first <= t <= last (label_index[b, t] == i only inside it; blank frames are free; a wildcard obeys
-    its window like any label).  An empty window (first > last), or windows that admit no path, make the sample infeasible."""
+    its window like any label).  An empty window (first > last), or windows that admit no path, make the sample infeasible.
+    optional_wildcards=True also accepts OPTIONAL_WILDCARD (-3), a wildcard position the path may skip: a skipped position has
+    first_frame = last_frame = -1 and label_score 0, and score stays the sum of the label scores and the blank frames.  Two of them
+    may not be adjacent (score -inf); not with frame_window (ValueError); on the classic lattice at most 512 label positions
+    (ValueError).  With False, -3 is a malformed label as before."""
     return _wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length,
-                           frame_window)
+                           frame_window, optional_wildcards)
 
 
 def simplified_ctc_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                       blank_index: Union[int, torch.Tensor] = 0, *,
-                                      max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
+                                      max_label_length: Optional[int] = None, frame_window=None,
+                    optional_wildcards: bool = False) -> CtcWildcardAlignment:
     """The same on the simplified lattice (every other non-blank frame emits exactly one label): a wildcard owns every frame from
     its entry until the next label's frame.  Same arguments and return value as classic_ctc_wildcard_alignment; check_labels keeps
-    rejecting -2 here as well.  frame_window constrains the frame at which a label is emitted, and every frame a wildcard owns."""
+    rejecting -2 here as well.  frame_window constrains the frame at which a label is emitted, and every frame a wildcard owns.
+    optional_wildcards as in classic_ctc_wildcard_alignment, up to 1024 label positions."""
     return _wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, max_label_length,
-                           frame_window)
+                           frame_window, optional_wildcards)
 
 
 def ctc_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
-                                         max_label_length: Optional[int] = None, frame_window=None) -> CtcWildcardAlignment:
+                                         max_label_length: Optional[int] = None, frame_window=None,
+                    optional_wildcards: bool = False) -> CtcWildcardAlignment:
     """The same for log-probabilities used as they stand (the counterpart of ctc_alignment_from_logproba); ctc_loss_data_cls
     selects the lattice (default: ClassicCtcLossData).  check_labels keeps rejecting -2 here as well."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                           max_label_length, frame_window)
+                           max_label_length, frame_window, optional_wildcards)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -495,10 +509,12 @@ class _WildcardLossFn(torch.autograd.Function):
     interpreted).  Backward is not itself differentiable: a second derivative raises."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, frame_window):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, frame_window, optional_wildcards=False):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U, weight)
         ctx.window = {} if frame_window is None else {"frame_window": frame_window}  # (no window: the call as it always was)
+        if optional_wildcards:
+            ctx.window["optional_wildcards"] = True
         return ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
                                       wildcard_log_weight=weight, want_grad=False, **ctx.window)[0]
 
@@ -509,11 +525,17 @@ class _WildcardLossFn(torch.autograd.Function):
         kind, wrt, blank, U, weight = ctx.call
         _, grad = ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
                                          wildcard_log_weight=weight, **ctx.window)
-        return grad, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None
+
+
+def _no_window_with_optional(frame_window, optional_wildcards):
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("frame_window and optional_wildcards=True cannot be combined")
 
 
 def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                   max_label_length=None, frame_window=None) -> torch.Tensor:
+                   max_label_length=None, frame_window=None, optional_wildcards=False) -> torch.Tensor:
+    _no_window_with_optional(frame_window, optional_wildcards)
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -527,8 +549,11 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
     kind = ops.KINDS[kind_name]
     window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
+    if optional_wildcards:
+        window["optional_wildcards"] = True
     if x.requires_grad and torch.is_grad_enabled():
-        return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, window.get("frame_window"))
+        return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight,
+                                     window.get("frame_window"), bool(optional_wildcards))
     with torch.no_grad():  # forward only: the result is detached
         return ops.wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
                                       wildcard_log_weight=weight, want_grad=False, **window)[0]
@@ -536,7 +561,8 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
 
 def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                               blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                              max_label_length: Optional[int] = None, frame_window=None) -> torch.Tensor:
+                              max_label_length: Optional[int] = None, frame_window=None,
+                              optional_wildcards: bool = False) -> torch.Tensor:
     """CTC loss of a partial transcript on the classic lattice (wildcard CTC / star temporal classification).  As classic_ctc_loss,
     but a label equal to WILDCARD (-2) stands for any non-empty run of frames with any tokens on them: the lattice of
     classic_ctc_wildcard_alignment, summed over all its paths instead of maximised.  Returns loss [batch] float32 = -ln Z, with a
@@ -549,28 +575,33 @@ def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_leng
     label position -- the convention of first_frame / last_frame; see ctc_frame_window -- lets position i own frame t only if
     first <= t <= last: the time-restricted loss of latency-controlled training (every token within a
     tolerance of a reference alignment).  Paths outside the windows are left out of Z, so the loss is at least the unconstrained
-    one; windows that admit no path give +inf and a zero gradient.  A transcript without wildcards is plain CTC with windows."""
+    one; windows that admit no path give +inf and a zero gradient.  A transcript without wildcards is plain CTC with windows.
+    optional_wildcards=True also accepts OPTIONAL_WILDCARD (-3): a wildcard position that may take no frame at all (the star of
+    star temporal classification, "something may be missing here").  Z then sums over every choice of used and skipped optional
+    positions; two of them may not be adjacent (+inf); it cannot be combined with frame_window (ValueError).  With False, -3 is a
+    malformed label as before."""
     return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length, frame_window)
+                          max_label_length, frame_window, optional_wildcards)
 
 
 def simplified_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                  blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                 max_label_length: Optional[int] = None, frame_window=None) -> torch.Tensor:
+                                 max_label_length: Optional[int] = None, frame_window=None,
+                                 optional_wildcards: bool = False) -> torch.Tensor:
     """The same on the simplified lattice: entering a wildcard and every stay behind it emit the wildcard's weight instead of a
     token's or the blank's probability.  Same arguments and return value as classic_ctc_wildcard_loss."""
     return _wildcard_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length, frame_window)
+                          max_label_length, frame_window, optional_wildcards)
 
 
 def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                     wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
-                                    frame_window=None) -> torch.Tensor:
+                                    frame_window=None, optional_wildcards: bool = False) -> torch.Tensor:
     """The same for log-probabilities used as they stand: a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]);
     ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                          wildcard_log_weight, max_label_length, frame_window)
+                          wildcard_log_weight, max_label_length, frame_window, optional_wildcards)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -697,7 +728,8 @@ class CtcLabelPosterior(NamedTuple):
 
 
 def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                     max_label_length=None, frame_window=None) -> CtcLabelPosterior:
+                     max_label_length=None, frame_window=None, optional_wildcards=False) -> CtcLabelPosterior:
+    _no_window_with_optional(frame_window, optional_wildcards)
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -710,6 +742,8 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
         raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
     window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
+    if optional_wildcards:
+        window["optional_wildcards"] = True
     with torch.no_grad():  # forward only: the result is detached
         return CtcLabelPosterior(*ops.label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
                                                       _blank(blank_index), U, wildcard_log_weight=weight, **window))
@@ -717,36 +751,40 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
 
 def classic_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                 blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                max_label_length: Optional[int] = None, frame_window=None) -> CtcLabelPosterior:
+                                max_label_length: Optional[int] = None, frame_window=None,
+                                optional_wildcards: bool = False) -> CtcLabelPosterior:
     """The soft alignment of a transcript on the classic lattice: the occupancy matrix of a forward-backward pass, where
     classic_ctc_alignment returns the single best path.  label_posterior[b, t, i] is the probability that frame t emits label
     position i; a frame's remaining mass is blank_posterior[b, t].  Labels may contain WILDCARD (-2), with the lattice and
     wildcard_log_weight of classic_ctc_wildcard_loss; without one this is plain CTC.  Arguments as classic_ctc_wildcard_loss
     (float32 / bfloat16 / float16 logits, any batch / time strides, read in place); returns CtcLabelPosterior, float32 on the
     logits' device, not differentiable.  check_labels keeps rejecting -2.  frame_window as in classic_ctc_wildcard_loss:
-    label_posterior is exactly 0 outside a position's window and every frame still sums to 1."""
+    label_posterior is exactly 0 outside a position's window and every frame still sums to 1.  optional_wildcards as in
+    classic_ctc_wildcard_loss: the column of an OPTIONAL_WILDCARD (-3) may sum to less than one frame (duration >= 0, expected_frame
+    -1 where it is 0); every frame still sums to 1."""
     return _label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                            max_label_length, frame_window)
+                            max_label_length, frame_window, optional_wildcards)
 
 
 def simplified_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                    blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
-                                   max_label_length: Optional[int] = None, frame_window=None) -> CtcLabelPosterior:
+                                   max_label_length: Optional[int] = None, frame_window=None,
+                                   optional_wildcards: bool = False) -> CtcLabelPosterior:
     """The same on the simplified lattice: label_posterior[b, t, i] is the probability that label i is emitted at frame t (so an
     ordinary label's duration is 1 and expected_frame is its expected emission frame); a wildcard also owns the frames spent
     behind it.  Same arguments and return value as classic_ctc_label_posterior."""
     return _label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length, frame_window)
+                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards)
 
 
 def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                       wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
-                                      frame_window=None) -> CtcLabelPosterior:
+                                      frame_window=None, optional_wildcards: bool = False) -> CtcLabelPosterior:
     """The same for log-probabilities used as they stand (a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]));
     ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length, frame_window)
+                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards)
 
 
 # --------------------------------------------------------------------------------------------------

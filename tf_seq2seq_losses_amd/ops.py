@@ -441,11 +441,18 @@ def _frame_window(what: str, frame_window: torch.Tensor, B: int, U: int, dev) ->
     return frame_window, 2 * int(frame_window.shape[1])
 
 
-def wildcard_best_path(kind: int, wrt: int, p: Prepared, frame_window: Optional[torch.Tensor] = None):
+def wildcard_best_path(kind: int, wrt: int, p: Prepared, frame_window: Optional[torch.Tensor] = None, optional_wildcards: bool = False):
     """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
     label_score[B,U] float32): the best path of the lattice whose labels may be wildcards (_lib.WILDCARD), and where every label
     lies on it (ctc_amd_wildcard_best_path).  Reads the logits in the format `p` holds them in, as best_path does.  frame_window
-    [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_best_path."""
+    [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_best_path.  optional_wildcards: labels may also hold
+    _lib.OPTIONAL_WILDCARD, a wildcard that may be skipped (ctc_amd_optional_wildcard_best_path; not with a window; classic:
+    U <= _lib.OPTIONAL_CLASSIC_MAX_U)."""
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("wildcard_best_path: frame_window and optional_wildcards cannot be combined")
+    if optional_wildcards and kind == _lib.CLASSIC and p.U > _lib.OPTIONAL_CLASSIC_MAX_U:
+        raise ValueError(f"wildcard_best_path: optional wildcards on the classic lattice take at most {_lib.OPTIONAL_CLASSIC_MAX_U} "
+                         f"label positions, got U = {p.U}")
     lib = _lib.load()
     score = torch.empty(p.B, dtype=torch.float32, device=p.device)
     tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
@@ -467,6 +474,12 @@ def wildcard_best_path(kind: int, wrt: int, p: Prepared, frame_window: Optional[
             rc = lib.ctc_amd_windowed_best_path(*p.common_ex(kind, wrt)[:11], _ptr(fw), fws, p.B, p.T, p.V, p.U, *(_ptr(t) for t in out),
                                                 ws.data_ptr(), ws.numel(), _stream(p.device))
         _lib.check(rc, "ctc_amd_windowed_best_path")
+        return out
+    if optional_wildcards:
+        with _on_device(p.device):
+            rc = lib.ctc_amd_optional_wildcard_best_path(*p.common_ex(kind, wrt), *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(),
+                                                         _stream(p.device))
+        _lib.check(rc, "ctc_amd_optional_wildcard_best_path")
         return out
     with _on_device(p.device):
         rc = lib.ctc_amd_wildcard_best_path(*p.common_ex(kind, wrt), *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(),
@@ -704,14 +717,19 @@ def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
 def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                        blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
                        grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
-                       want_grad: bool = True, frame_window: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       want_grad: bool = True, frame_window: Optional[torch.Tensor] = None,
+                       optional_wildcards: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(loss[B] float32, grad[B, T, V] or None): the CTC loss of transcripts whose labels may be wildcards (_lib.WILDCARD), summed
     over all paths of the lattice, and its gradient times d_loss[b] (default: ones) with respect to x (ctc_amd_wildcard_loss_grad).
     want_grad=False is the forward-only launch and returns None for the gradient.  An utterance whose loss is +inf gets a zero
     gradient and its d_loss is not interpreted.  labels [B, W]; U bounds every label_length (default: W, or the maximum inside when
     W is large).  Takes the logits as greedy_decode does (float32 / bfloat16 / float16, any batch and time strides, read in place);
     grad has grad_dtype (default: the logits') and the logits' layout where that is dense, a contiguous one otherwise.
-    frame_window [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_loss_grad.  Does not synchronise."""
+    frame_window [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_loss_grad.  optional_wildcards: labels may
+    also hold _lib.OPTIONAL_WILDCARD, a wildcard that may be empty (ctc_amd_optional_wildcard_loss_grad; not with a window).  Does not
+    synchronise."""
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("wildcard_loss_grad: frame_window and optional_wildcards cannot be combined")
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -747,6 +765,14 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
                                                 float(wildcard_log_weight), B, T, V, U, _ptr(d_loss), _ptr(loss),
                                                 _ptr(grad) if with_grad else None, _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
         _lib.check(rc, "ctc_amd_windowed_loss_grad")
+        return loss, grad
+    if optional_wildcards:
+        with _on_device(dev):
+            rc = lib.ctc_amd_optional_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                         _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight),
+                                                         B, T, V, U, _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
+                                                         _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_optional_wildcard_loss_grad")
         return loss, grad
     with _on_device(dev):
         rc = lib.ctc_amd_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
@@ -842,13 +868,15 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
 
 def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True,
-                    frame_window: Optional[torch.Tensor] = None):
+                    frame_window: Optional[torch.Tensor] = None, optional_wildcards: bool = False):
     """(loss[B], label_posterior[B, T, U], blank_posterior[B, T], duration[B, U], expected_frame[B, U]), all float32: with what
     probability every frame belongs to every label position (or to the blank) over all paths of the lattice, and per position the
     expected number of frames and the soft timestamp (ctc_amd_label_posterior).  Labels may be wildcards (_lib.WILDCARD); the loss
     is wildcard_loss_grad's forward-only one, bit for bit.  want_stats=False skips the statistics launch and returns None for the
-    last two.  Arguments as wildcard_loss_grad (frame_window: ctc_amd_windowed_label_posterior); every element of every output is
-    written.  Does not synchronise."""
+    last two.  Arguments as wildcard_loss_grad (frame_window: ctc_amd_windowed_label_posterior; optional_wildcards:
+    ctc_amd_optional_wildcard_label_posterior); every element of every output is written.  Does not synchronise."""
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("label_posterior: frame_window and optional_wildcards cannot be combined")
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -876,6 +904,14 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
                                                       float(wildcard_log_weight), B, T, V, U, _ptr(loss), _ptr(post), _ptr(blk),
                                                       _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
         _lib.check(rc, "ctc_amd_windowed_label_posterior")
+        return loss, post, blk, dur, exf
+    if optional_wildcards:
+        with _on_device(dev):
+            rc = lib.ctc_amd_optional_wildcard_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels),
+                                                               W, _ptr(label_length), _ptr(logit_length), int(blank),
+                                                               float(wildcard_log_weight), B, T, V, U, _ptr(loss), _ptr(post), _ptr(blk),
+                                                               _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_optional_wildcard_label_posterior")
         return loss, post, blk, dur, exf
     with _on_device(dev):
         rc = lib.ctc_amd_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
