@@ -1313,7 +1313,8 @@ int ctc_amd_long_windowed_label_posterior(int kind, int wrt,
  * (CTC_AMD_EINVAL beyond, behind the counterpart's argument checks and before the workspace; the size query says so too): the
  * chain step for 16 positions per lane does not fit the register file without scratch, and no spilling kernel is shipped.  The
  * simplified alignment, the loss and the posteriors take U <= CTC_AMD_MAX_U.
- * There is no long-form, N-best or frame-window variant.
+ * The long-form loss, gradient and label posteriors take it too (below); there is no long-form alignment, N-best or frame-window
+ * variant.
  *
  * Let position i be an optional wildcard.  Everything said of a wildcard holds for it when it is used: the emission e_w(t),
  * contiguous frames, its own posterior column.  In addition it may be skipped:
@@ -1372,6 +1373,58 @@ int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt,
                                               float wildcard_log_weight, int B, int T, int V, int U,
                                               float *loss, float *label_posterior, float *blank_posterior, float *duration,
                                               float *expected_frame, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Optional wildcards above 1024 labels: the long-form loss, gradient and label posteriors (added under ABI v6: three new entry
+ * points with their size queries, nothing existing changed).  CTC_AMD_OPTIONAL_WILDCARD with the definition above, word for word,
+ * for label_length <= CTC_AMD_LONG_MAX_U, accepted by
+ *   ctc_amd_long_optional_wildcard_loss_grad         counterpart: ctc_amd_long_wildcard_loss_grad
+ *   ctc_amd_long_optional_wildcard_loss_grad_ckpt    counterpart: ctc_amd_long_wildcard_loss_grad_ckpt
+ *   ctc_amd_long_optional_wildcard_label_posterior   counterpart: ctc_amd_long_label_posterior
+ * Each is its counterpart in arguments, formats, strides, outputs, limits, validation order and messages, launches, capture and
+ * determinism: the same bits on every run, for every frames_per_tile and batch composition, from both workspaces.  Two adjacent
+ * optional wildcards make the utterance infeasible wherever the pair falls, a label-block boundary (positions 1023 / 1024)
+ * included: loss +inf, zero gradient, zero posteriors, expected_frame -1.  A transcript without an optional wildcard returns the
+ * counterpart's bits for every output; at one label block the loss, gradient, label_posterior, duration and expected_frame are
+ * the bits of the short-form optional entry points.
+ * Workspace.  A skip reaches two positions back, across a label-block boundary, so two more column buffers lie behind the
+ * counterpart's workspace: with K = ceil(U / 1024) label blocks, 16 * B * (K - 1) * T bytes (the state of position k * 1024 - 2
+ * before every frame) and, with a gradient or for the posteriors, 8 * B * (K - 1) * T more (what entering position
+ * (k + 1) * 1024 + 1 with a frame is worth), each rounded up to 256.  The three size queries return the counterparts' sizes plus
+ * those terms (K = 1: the same size).  The workspace may hold anything on entry.
+ * Short utterances.  An utterance of L positions needs at least L / 2 frames, not L: the tiles that run are chosen by that bound
+ * (position i is unreachable before frame i / 2), and what is infeasible beyond it falls out of the lattice.
+ * Not included: the long-form alignment, the N-best calls, frame windows together with optional wildcards, and star temporal
+ * classification's exclusion of the following label.
+ */
+int ctc_amd_long_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                        size_t *out_bytes /*host*/);
+int ctc_amd_long_optional_wildcard_loss_grad(int kind, int wrt,
+                                             const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                             const int32_t *labels, int label_stride,
+                                             const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                             float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                             const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                             int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_optional_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                             size_t *out_bytes /*host*/);
+int ctc_amd_long_optional_wildcard_loss_grad_ckpt(int kind, int wrt,
+                                                  const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                                  const int32_t *labels, int label_stride,
+                                                  const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                                  float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                                  const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                                  int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile,
+                                                                   size_t *out_bytes /*host*/);
+int ctc_amd_long_optional_wildcard_label_posterior(int kind, int wrt,
+                                                   const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                                   const int32_t *labels, int label_stride,
+                                                   const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                                   float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                                   float *loss, float *label_posterior /* may be NULL */, float *blank_posterior,
+                                                   float *duration, float *expected_frame, float *peak_posterior, int32_t *peak_frame,
+                                                   void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,18 @@ SIGNATURES = {
     "ctc_amd_long_windowed_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                               [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    # ... and the three long-form ones with optional wildcards: the arguments of ctc_amd_long_wildcard_loss_grad / _grad_ckpt and
+    # ctc_amd_long_label_posterior
+    "ctc_amd_long_optional_wildcard_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile, want_grad
+    "ctc_amd_long_optional_wildcard_loss_grad": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
+                                                 [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_optional_wildcard_loss_ckpt_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile, want_grad
+    "ctc_amd_long_optional_wildcard_loss_grad_ckpt": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
+                                                      [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
+    "ctc_amd_long_optional_wildcard_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
+                                                       [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                        _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
@@ -310,6 +322,27 @@ def long_wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U
 def label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_label_posterior_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_label_posterior_workspace_bytes")
+    return int(out.value)
+
+
+def long_optional_wildcard_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0, want_grad: bool = True) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_optional_wildcard_loss_workspace_bytes(kind, B, T, V, U, frames_per_tile, int(want_grad), ctypes.byref(out)),
+          "ctc_amd_long_optional_wildcard_loss_workspace_bytes")
+    return int(out.value)
+
+
+def long_optional_wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0, want_grad: bool = True) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_optional_wildcard_loss_ckpt_workspace_bytes(kind, B, T, V, U, frames_per_tile, int(want_grad), ctypes.byref(out)),
+          "ctc_amd_long_optional_wildcard_loss_ckpt_workspace_bytes")
+    return int(out.value)
+
+
+def long_optional_wildcard_label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes")
     return int(out.value)
 
 

@@ -408,23 +408,27 @@ int log_domain_setup(const Common &c, size_t extra, void *workspace, size_t work
 }
 
 static_assert(ctc::LONG_LOSS_WILDCARD == CTC_AMD_WILDCARD, "the tiled loss kernel's wildcard label is the ABI's");
+static_assert(ctc::LONG_LOSS_OPTIONAL == CTC_AMD_OPTIONAL_WILDCARD, "the tiled loss kernel's optional wildcard label is the ABI's");
 
 // ctc_amd_long_wildcard_loss_grad and its checkpointed twin, which differ in the plan function alone (long_loss_ckpt_plan refuses
 // what long_loss_plan refuses, and is long_loss_plan without a gradient).  The window is looked at behind every check of the unwindowed
-// call but the workspace's.
-using LongLossPlanFn = bool(int, int, int, int, int, int, ctc::LongLossPlan *);
-int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, const Common &c, const Format &f, const int32_t *frame_window, int window_stride,
-                                 float wildcard_log_weight, int frames_per_tile, const float *d_loss, float *loss, void *grad,
+// call but the workspace's.  optional_wildcards (ctc_amd_long_optional_wildcard_loss_grad / _grad_ckpt, which have no window): the
+// same checks, the plan with the two further column buffers.
+using LongLossPlanFn = bool(int, int, int, int, int, int, ctc::LongLossPlan *, int);
+int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, bool optional_wildcards, const Common &c, const Format &f,
+                                 const int32_t *frame_window, int window_stride, float wildcard_log_weight, int frames_per_tile, const float *d_loss, float *loss, void *grad,
                                  void *workspace, size_t workspace_bytes, void *stream) {
   const Prelude pre = prelude(c, f, grad != nullptr, CTC_AMD_LONG_MAX_U);
   if (!pre.go) return pre.rc;
   if (int rc = check_wildcard_loss(wildcard_log_weight, loss, c.B, c.T, c.V, grad != nullptr)) return rc;
   ctc::LongLossPlan plan;
-  if (!plan_fn(c.kind, c.B, c.T, c.U, frames_per_tile, grad != nullptr, &plan)) return bad_tiling(frames_per_tile, c.B, c.T, c.U);
+  if (!plan_fn(c.kind, c.B, c.T, c.U, frames_per_tile, grad != nullptr, &plan, optional_wildcards ? 1 : 0))
+    return bad_tiling(frames_per_tile, c.B, c.T, c.U);
   if (int rc = check_window(frame_window, window_stride, c.U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
   CTC_TRY(ctc::run_loss_long(pre.p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
-                             static_cast<hipStream_t>(stream), frame_window, window_stride), "long wildcard loss launch");
+                             static_cast<hipStream_t>(stream), frame_window, window_stride, optional_wildcards),
+          "long wildcard loss launch");
   return CTC_AMD_OK;
 }
 
@@ -1073,6 +1077,46 @@ int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, in
   });
 }
 
+// The three long-form entry points with optional wildcards are their counterparts' bodies with the flag set:
+// the same checks in the same order with the same words, and a plan that holds two more column buffers.
+int ctc_amd_long_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                        size_t *out_bytes) {
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan, 1);
+  });
+}
+
+int ctc_amd_long_optional_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                             int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                             const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                             float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                             const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                             int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss, grad,
+                                      workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_long_optional_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                                             size_t *out_bytes) {
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan, 1);
+  });
+}
+
+int ctc_amd_long_optional_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                                  int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                                  const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                                  float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                                  const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                                  int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss,
+                                      grad, workspace, workspace_bytes, stream);
+}
+
 // The three long-form windowed entry points are their counterparts with a frame window; the counterparts are they with none.
 int ctc_amd_long_windowed_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
@@ -1082,7 +1126,7 @@ int ctc_amd_long_windowed_loss_grad(int kind, int wrt, const void *logits, int l
                                     void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile, d_loss,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile, d_loss,
                                       loss, grad, workspace, workspace_bytes, stream);
 }
 
@@ -1112,7 +1156,7 @@ int ctc_amd_long_windowed_loss_grad_ckpt(int kind, int wrt, const void *logits, 
                                          void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile,
                                       d_loss, loss, grad, workspace, workspace_bytes, stream);
 }
 
@@ -1200,13 +1244,14 @@ int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, 
 
 // It begins like ctc_amd_long_wildcard_loss_grad with a gradient, whose messages it gives (the row stage always runs); its own
 // outputs come behind that.
-int ctc_amd_long_windowed_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
-                                          int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
-                                          const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
-                                          float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile, float *loss,
-                                          float *label_posterior, float *blank_posterior, float *duration, float *expected_frame,
-                                          float *peak_posterior, int32_t *peak_frame, void *workspace, size_t workspace_bytes,
-                                          void *stream) {
+// One body for ctc_amd_long_windowed_label_posterior and ctc_amd_long_optional_wildcard_label_posterior (which has no window).
+static int long_label_posterior_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype,
+                                     int64_t logits_stride_b, int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                     const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                     const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T, int V, int U,
+                                     int frames_per_tile, float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                     float *expected_frame, float *peak_posterior, int32_t *peak_frame, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, CTC_AMD_F32, logits_stride_b, logits_stride_t};  // (no gradient: nothing reads the second half)
   const Prelude pre = prelude(c, f, false, CTC_AMD_LONG_MAX_U);
@@ -1216,14 +1261,46 @@ int ctc_amd_long_windowed_label_posterior(int kind, int wrt, const void *logits,
   if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
   if (!peak_posterior != !peak_frame) return fail(CTC_AMD_EINVAL, "peak_posterior and peak_frame must both be given or both be NULL");
   ctc::LongPostPlan plan;
-  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
+  if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan, optional_wildcards ? 1 : 0)) return bad_tiling(frames_per_tile, B, T, U);
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
   CTC_TRY(ctc::run_long_label_posterior(pre.p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
                                         peak_posterior, peak_frame, static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
-                                        frame_window, window_stride),
+                                        frame_window, window_stride, optional_wildcards),
           "long label posterior launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_long_windowed_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                          int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                          const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
+                                          float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile, float *loss,
+                                          float *label_posterior, float *blank_posterior, float *duration, float *expected_frame,
+                                          float *peak_posterior, int32_t *peak_frame, void *workspace, size_t workspace_bytes,
+                                          void *stream) {
+  return long_label_posterior_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                   label_length, logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U,
+                                   frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior,
+                                   peak_frame, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile,
+                                                                   size_t *out_bytes) {
+  return long_query<ctc::LongPostPlan>(kind, B, T, V, U, frames_per_tile, out_bytes,
+                                       [=](ctc::LongPostPlan *plan) { return ctc::long_post_plan(kind, B, T, U, frames_per_tile, plan, 1); });
+}
+
+int ctc_amd_long_optional_wildcard_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                                   int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                                   const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                                   float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                                   float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                                   float *expected_frame, float *peak_posterior, int32_t *peak_frame, void *workspace,
+                                                   size_t workspace_bytes, void *stream) {
+  return long_label_posterior_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                   label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, frames_per_tile,
+                                   loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior, peak_frame,
+                                   workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,

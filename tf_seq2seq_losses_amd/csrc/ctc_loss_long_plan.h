@@ -37,9 +37,21 @@ CTC_LL_HD bool long_loss_tile_active(int Tb, int L, int k, int j, int TF, int UB
   if ((long long)j * TF + TF - 1 < (long long)k * UB) return false;
   return true;
 }
+// Optional wildcards: a position may take no frame, but no two such positions are adjacent, so position i
+// is log 0 before frame i / 2 and L positions need L / 2 frames: the first and the last test on those bounds.  A tile that runs
+// over states that nothing reaches carries log 0 and changes no bit; what is infeasible falls out of the lattice.
+CTC_LL_HD bool long_loss_tile_active_opt(int Tb, int L, int k, int j, int TF, int UB = LONG_UB) {
+  if (L / 2 > Tb) return false;
+  if ((long long)j * TF >= Tb) return false;
+  if (k > 0 && (long long)k * UB >= L) return false;
+  if ((long long)j * TF + TF - 1 < (long long)k * UB / 2) return false;
+  return true;
+}
 // (all four for a tile that runs)
 // alpha: the block's first tile starts from log 0 (block 0, tile 0: from the start state); every other reads the row buffer
 CTC_LL_HD bool long_loss_alpha_fresh(int k, int j, int TF, int UB = LONG_UB) { return (long long)j * TF <= (long long)k * UB; }
+// (optional wildcards: the tile before it in time did not run, by the last test of long_loss_tile_active_opt)
+CTC_LL_HD bool long_loss_alpha_fresh_opt(int k, int j, int TF, int UB = LONG_UB) { return (long long)j * TF <= (long long)k * UB / 2; }
 // alpha: block k + 1 has labels, so this tile stores the column (its last position before every frame); the tile to the right then
 // runs for every frame range in which it could read it
 CTC_LL_HD bool long_loss_has_right(int L, int k, int UB = LONG_UB) { return (long long)(k + 1) * UB < L; }
@@ -48,6 +60,9 @@ CTC_LL_HD bool long_loss_beta_fresh(int Tb, int j, int TF) { return (long long)(
 // beta: the tile to the right ran on an earlier launch and stored its column (else: log 0)
 CTC_LL_HD bool long_loss_beta_has_right(int Tb, int L, int k, int j, int TF, int UB = LONG_UB) {
   return long_loss_has_right(L, k, UB) && long_loss_tile_active(Tb, L, k + 1, j, TF, UB);
+}
+CTC_LL_HD bool long_loss_beta_has_right_opt(int Tb, int L, int k, int j, int TF, int UB = LONG_UB) {
+  return long_loss_has_right(L, k, UB) && long_loss_tile_active_opt(Tb, L, k + 1, j, TF, UB);
 }
 
 // ---- where things live ----
@@ -87,12 +102,27 @@ struct LongLossPlan {
   int ckpt;       // 1: the checkpointed layout (long_loss_ckpt_plan with a gradient); off_row is then [B][K][Jc], off_rows the ring
   size_t off_col, off_row, off_stat, off_logp, off_flag;  // both paths
   size_t off_colb, off_rowb, off_rows;                    // the gradient's (want_grad == 0: all equal to total)
+  int opt;                     // 1: optional wildcards, the two further column buffers behind everything else
+  size_t off_col2, off_colb2;  // (opt == 0: unused)
   size_t total;
 };
 
+// Optional wildcards: a skip reaches two positions back, so a second alpha column (position k * UB - 2
+// before every frame) and, with a gradient, a second beta column (the worth of entering position (k + 1) * UB + 1 with the frame)
+// cross a block boundary.  They lie behind the plan as it was: every other offset is the counterpart's.
+inline void long_loss_plan_add_optional(LongLossPlan *P) {
+  const size_t b = (size_t)P->B, t = (size_t)P->T, k = (size_t)P->K;
+  size_t o = P->total;
+  P->opt = 1;
+  P->off_col2 = o;  o = long_r256(o + b * (k - 1) * t * 16);  // [B][K - 1][T] pairs (O, C) of float64
+  P->off_colb2 = o;
+  if (P->want_grad) o = long_r256(o + b * (k - 1) * t * 8);   // [B][K - 1][T] float64
+  P->total = o;
+}
+
 // false: what long_plan refuses (frames_per_tile, sizes, the tile grid), or, with a gradient, a row stage of more than 2^31 - 1
 // workgroups (four rows (b, t) each)
-inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out) {
+inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out, int opt = 0) {
   LongPlan A;
   if (kind < 0 || kind > 1 || !long_plan(B, T, U, frames_per_tile, &A)) return false;
   if (want_grad && ((long long)B * T + 3) / 4 > 0x7fffffffLL) return false;
@@ -113,6 +143,8 @@ inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, i
   P.off_rows = o;
   if (want_grad) o = long_r256(o + b * k * t * (size_t)long_loss_row_doubles(kind) * 8);  // saved rows: [B][K][T][S * 1024 + 2] float64
   P.total = o;
+  P.opt = 0; P.off_col2 = P.off_colb2 = o;
+  if (opt) long_loss_plan_add_optional(&P);
   *out = P;
   return true;
 }
@@ -120,9 +152,9 @@ inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, i
 // The checkpointed call's plan.  Without a gradient it is long_loss_plan's (the call runs the existing forward).  With one, two terms
 // differ: the alpha row buffers become the checkpoints [B][K][Jc], and the saved rows become the ring [B][K][min(R * TF, T)] rows,
 // never more than the T rows it replaces.  Refuses what long_loss_plan refuses.
-inline bool long_loss_ckpt_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out) {
+inline bool long_loss_ckpt_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out, int opt = 0) {
   LongLossPlan P;
-  if (!long_loss_plan(kind, B, T, U, frames_per_tile, want_grad, &P)) return false;
+  if (!long_loss_plan(kind, B, T, U, frames_per_tile, want_grad, &P, want_grad ? 0 : opt)) return false;
   if (!want_grad) { *out = P; return true; }
   P.ckpt = 1;
   const size_t b = (size_t)P.B, t = (size_t)P.T, k = (size_t)P.K;
@@ -135,6 +167,8 @@ inline bool long_loss_ckpt_plan(int kind, int B, int T, int U, int frames_per_ti
   P.off_rowb = o; o = long_r256(o + b * k * LONG_ROW_DOUBLES * 8);
   P.off_rows = o; o = long_r256(o + b * k * long_loss_ring_frames(P.K, P.T, P.TF) * (size_t)long_loss_row_doubles(kind) * 8);  // the ring
   P.total = o;
+  P.off_col2 = P.off_colb2 = o;
+  if (opt) long_loss_plan_add_optional(&P);
   *out = P;
   return true;
 }
@@ -153,9 +187,9 @@ constexpr int LONG_POST_WAVES = 4;
 CTC_LL_HD size_t long_post_row_groups(int B, int nt) { return ((size_t)B * (size_t)nt + LONG_POST_WAVES - 1) / LONG_POST_WAVES; }
 CTC_LL_HD size_t long_post_stat_groups(int B, int U) { return ((size_t)B * (((size_t)U + 63) / 64) + LONG_POST_WAVES - 1) / LONG_POST_WAVES; }
 // false: what long_loss_ckpt_plan refuses with a gradient, or a posterior stage of more than 2^31 - 1 workgroups
-inline bool long_post_plan(int kind, int B, int T, int U, int frames_per_tile, LongPostPlan *out) {
+inline bool long_post_plan(int kind, int B, int T, int U, int frames_per_tile, LongPostPlan *out, int opt = 0) {
   LongPostPlan P;
-  if (!long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, 1, &P.L)) return false;
+  if (!long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, 1, &P.L, opt)) return false;
   if (long_post_row_groups(B, T < P.L.TF ? T : P.L.TF) + long_post_stat_groups(B, U) > 2147483647u) return false;
   size_t o = P.L.total;
   P.off_acc = o;  o = long_r256(o + (size_t)B * (size_t)U * 16);

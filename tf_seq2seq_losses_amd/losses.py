@@ -607,8 +607,11 @@ def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_lengt
 # --------------------------------------------------------------------------------------------------
 # long-form loss and gradient (transcripts beyond 1024 labels, wildcards included): an extension, no counterpart in the reference
 # --------------------------------------------------------------------------------------------------
-def _long_loss_call(frame_window):
-    """ops.long_wildcard_loss_grad, or with a window ops.long_windowed_loss_grad bound to it (no window: the call as it always was)."""
+def _long_loss_call(frame_window, optional_wildcards=False):
+    """ops.long_wildcard_loss_grad, or with a window ops.long_windowed_loss_grad bound to it (no window: the call as it always was);
+    with optional wildcards ops.long_optional_wildcard_loss_grad."""
+    if optional_wildcards:
+        return ops.long_optional_wildcard_loss_grad
     if frame_window is None:
         return ops.long_wildcard_loss_grad
     return partial(ops.long_windowed_loss_grad, frame_window)
@@ -619,11 +622,13 @@ class _LongLossFn(torch.autograd.Function):
     ONE call with d_loss.  Backward is not itself differentiable: a second derivative raises."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf, checkpoint, frame_window):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, tf, checkpoint, frame_window,
+                optional_wildcards=False):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U, weight, tf, checkpoint)
         ctx.window = frame_window
-        return _long_loss_call(frame_window)(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
+        ctx.optional = optional_wildcards
+        return _long_loss_call(frame_window, optional_wildcards)(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
                                              wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
 
     @staticmethod
@@ -631,13 +636,15 @@ class _LongLossFn(torch.autograd.Function):
     def backward(ctx, d_loss):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U, weight, tf, checkpoint = ctx.call
-        _, grad = _long_loss_call(ctx.window)(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
-                                              wildcard_log_weight=weight, frames_per_tile=tf, checkpoint=checkpoint)
-        return grad, None, None, None, None, None, None, None, None, None, None, None
+        _, grad = _long_loss_call(ctx.window, ctx.optional)(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U,
+                                                            grad_dtype=x.dtype, wildcard_log_weight=weight, frames_per_tile=tf,
+                                                            checkpoint=checkpoint)
+        return grad, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-               frames_per_tile=None, max_label_length=None, checkpoint=False, frame_window=None) -> torch.Tensor:
+               frames_per_tile=None, max_label_length=None, checkpoint=False, frame_window=None, optional_wildcards=False) -> torch.Tensor:
+    _no_window_with_optional(frame_window, optional_wildcards)
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -654,16 +661,16 @@ def _long_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, 
     window = None if frame_window is None else _as_tensor(frame_window)
     if x.requires_grad and torch.is_grad_enabled():
         return _LongLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight, tf, bool(checkpoint),
-                                 window)
+                                 window, bool(optional_wildcards))
     with torch.no_grad():  # forward only: the result is detached
-        return _long_loss_call(window)(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
+        return _long_loss_call(window, bool(optional_wildcards))(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
                                        wildcard_log_weight=weight, want_grad=False, frames_per_tile=tf)[0]
 
 
 def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                           blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                           frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
-                          checkpoint: bool = False, frame_window=None) -> torch.Tensor:
+                          checkpoint: bool = False, optional_wildcards: bool = False, frame_window=None) -> torch.Tensor:
     """CTC loss of a long recording on the classic lattice: classic_ctc_wildcard_loss (without a WILDCARD label, -2, the plain CTC
     loss; with one, the loss of a partial transcript) for transcripts of up to 65536 labels, computed on the tiled lattice of
     classic_ctc_long_alignment (`frames_per_tile`: None for 128, otherwise a positive multiple of 4; the loss and the gradient do not
@@ -679,31 +686,40 @@ def classic_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: 
     same call either way.  check_labels keeps rejecting -2.  frame_window [batch, U, 2] as in classic_ctc_wildcard_loss, in absolute
     frames and for every label block: the windows ctc_frame_window makes of a classic_ctc_long_wildcard_alignment hold every token of
     the recording within a tolerance of that alignment, with either `checkpoint` setting and the same bits from both; no result
-    depends on where a window's edges fall relative to tiles.  The workspaces are those of the unwindowed call."""
+    depends on where a window's edges fall relative to tiles.  The workspaces are those of the unwindowed call.
+    optional_wildcards=True also accepts OPTIONAL_WILDCARD (-3), a wildcard position that may take no frame, as in
+    classic_ctc_wildcard_loss and with its definition, at any length up to 65536: a lightly supervised transcript of a long recording,
+    or a star between every pair of labels (then L positions need only about L / 2 frames).  Two of them may not be adjacent (+inf, a
+    zero gradient), wherever the pair falls; both `checkpoint` settings give the same bits; without a -3 the bits are those of False;
+    the workspace holds 24 * batch * (K - 1) * max_length bytes more.  It cannot be combined with frame_window (ValueError).  With
+    False, -3 is a bad label as before."""
     return _long_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint, frame_window)
+                      frames_per_tile, max_label_length, checkpoint, frame_window, optional_wildcards)
 
 
 def simplified_ctc_long_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                              blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                              frames_per_tile: Optional[int] = None, max_label_length: Optional[int] = None,
-                             checkpoint: bool = False, frame_window=None) -> torch.Tensor:
+                             checkpoint: bool = False, optional_wildcards: bool = False, frame_window=None) -> torch.Tensor:
     """The same on the simplified lattice.  Same arguments and return value as classic_ctc_long_loss; backward holds
     8 * batch * K * max_length * 1026 bytes, with checkpoint=True 8 * batch * K * (J * 2056 + min(K, J) * TF * 1026), the same bits.
-    frame_window as in classic_ctc_long_loss: a wildcard's horizontal frames obey its window too."""
+    frame_window as in classic_ctc_long_loss: a wildcard's horizontal frames obey its window too.  optional_wildcards as in
+    classic_ctc_long_loss, with the definition of simplified_ctc_wildcard_loss."""
     return _long_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint, frame_window)
+                      frames_per_tile, max_label_length, checkpoint, frame_window, optional_wildcards)
 
 
 def ctc_long_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                 wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
-                                max_label_length: Optional[int] = None, checkpoint: bool = False, frame_window=None) -> torch.Tensor:
+                                max_label_length: Optional[int] = None, checkpoint: bool = False, optional_wildcards: bool = False,
+                                frame_window=None) -> torch.Tensor:
     """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The
     gradient is with respect to logprobas.  checkpoint and both workspace formulas as in classic_ctc_long_loss /
-    simplified_ctc_long_loss: the same bits from the smaller workspace.  frame_window as in classic_ctc_long_loss."""
+    simplified_ctc_long_loss: the same bits from the smaller workspace.  frame_window and optional_wildcards as in
+    classic_ctc_long_loss."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index, wildcard_log_weight,
-                      frames_per_tile, max_label_length, checkpoint, frame_window)
+                      frames_per_tile, max_label_length, checkpoint, frame_window, optional_wildcards)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -808,7 +824,9 @@ class CtcLongLabelPosterior(NamedTuple):
 
 
 def _long_label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                          frames_per_tile=None, max_label_length=None, dense=True, frame_window=None) -> CtcLongLabelPosterior:
+                          frames_per_tile=None, max_label_length=None, dense=True, frame_window=None,
+                          optional_wildcards=False) -> CtcLongLabelPosterior:
+    _no_window_with_optional(frame_window, optional_wildcards)
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -823,6 +841,10 @@ def _long_label_posterior(kind_name: str, wrt: int, labels, x, label_length, log
     tf = 0 if frames_per_tile is None else int(frames_per_tile)
     window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
     with torch.no_grad():  # forward only: the result is detached
+        if optional_wildcards:
+            return CtcLongLabelPosterior(*ops.long_optional_wildcard_label_posterior(
+                ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), U,
+                wildcard_log_weight=weight, frames_per_tile=tf, dense=bool(dense)))
         return CtcLongLabelPosterior(*ops.long_label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
                                                                _blank(blank_index), U, wildcard_log_weight=weight, frames_per_tile=tf,
                                                                dense=bool(dense), **window))
@@ -862,6 +884,44 @@ def ctc_long_label_posterior_from_logproba(labels, logprobas, label_length, logi
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
                                  wildcard_log_weight, frames_per_tile, max_label_length, dense)
+
+
+def classic_ctc_long_optional_wildcard_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike,
+                                                       logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                                                       wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                                       max_label_length: Optional[int] = None,
+                                                       dense: bool = True) -> CtcLongLabelPosterior:
+    """classic_ctc_long_label_posterior for transcripts that may also hold OPTIONAL_WILDCARD (-3), a wildcard position that may take
+    no frame: classic_ctc_label_posterior(optional_wildcards=True) at up to 65536 labels.  The loss is
+    classic_ctc_long_loss(optional_wildcards=True)'s, bit for bit; the column of an optional position may sum to less than one frame
+    and its duration is the expected number of frames it takes (about 0: the position was skipped); every frame's label_posterior and
+    blank_posterior still sum to 1.  Two adjacent -3 make the sample infeasible (loss +inf, zeros, expected_frame -1).  dense=False
+    as in classic_ctc_long_label_posterior.  (A function of its own because the signature of that one is kept as it is.)  Returns
+    CtcLongLabelPosterior on the logits' device, not differentiable."""
+    return _long_label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, None, True)
+
+
+def simplified_ctc_long_optional_wildcard_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike,
+                                                          logit_length: TensorLike, blank_index: Union[int, torch.Tensor] = 0, *,
+                                                          wildcard_log_weight: float = 0.0, frames_per_tile: Optional[int] = None,
+                                                          max_label_length: Optional[int] = None,
+                                                          dense: bool = True) -> CtcLongLabelPosterior:
+    """The same on the simplified lattice: simplified_ctc_long_label_posterior with optional wildcards.  Same arguments and return
+    value as classic_ctc_long_optional_wildcard_label_posterior."""
+    return _long_label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, None, True)
+
+
+def ctc_long_optional_wildcard_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0,
+                                                             ctc_loss_data_cls=None, *, wildcard_log_weight: float = 0.0,
+                                                             frames_per_tile: Optional[int] = None,
+                                                             max_label_length: Optional[int] = None,
+                                                             dense: bool = True) -> CtcLongLabelPosterior:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _long_label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                                 wildcard_log_weight, frames_per_tile, max_label_length, dense, None, True)
 
 
 def classic_ctc_long_windowed_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,

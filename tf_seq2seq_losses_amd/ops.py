@@ -800,6 +800,19 @@ def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.
                            want_grad, frames_per_tile, checkpoint)
 
 
+def long_optional_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                                     logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
+                                     grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0, want_grad: bool = True,
+                                     frames_per_tile: int = 0, checkpoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """long_wildcard_loss_grad whose labels may also hold _lib.OPTIONAL_WILDCARD, a wildcard position that may take no frame (as in
+    wildcard_loss_grad(optional_wildcards=True); two of them may not be adjacent: +inf and a zero gradient):
+    ctc_amd_long_optional_wildcard_loss_grad / _grad_ckpt.  The same arguments and return value; the workspace holds two more column
+    buffers (24 * B * (ceil(U / 1024) - 1) * T bytes with a gradient, 16 without).  Without such a label the bits of
+    long_wildcard_loss_grad.  Not with frame windows.  Does not synchronise."""
+    return _long_loss_grad(None, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                           want_grad, frames_per_tile, checkpoint, optional_wildcards=True)
+
+
 def long_windowed_loss_grad(frame_window: torch.Tensor, kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor,
                             label_length: torch.Tensor, logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None,
                             U: Optional[int] = None, grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
@@ -815,7 +828,9 @@ def long_windowed_loss_grad(frame_window: torch.Tensor, kind: int, wrt: int, lab
 
 
 def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
-                    want_grad, frames_per_tile, checkpoint):
+                    want_grad, frames_per_tile, checkpoint, optional_wildcards=False):
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("long_wildcard_loss_grad: frame_window and optional_wildcards cannot be combined")
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"long_wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("long_wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -833,11 +848,15 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
     if grad_dtype not in _DTYPES:
         raise ValueError(f"long_wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
     with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
-    name = "long_wildcard_loss_grad_ckpt" if checkpoint else "long_wildcard_loss_grad"
+    stem = "long_optional_wildcard_loss_grad" if optional_wildcards else "long_wildcard_loss_grad"
+    name = stem + "_ckpt" if checkpoint else stem
     key = (name, kind, B, T, V, U, int(frames_per_tile), with_grad)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
-        size = _lib.long_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_wildcard_loss_workspace_bytes
+        if optional_wildcards:
+            size = _lib.long_optional_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_optional_wildcard_loss_workspace_bytes
+        else:
+            size = _lib.long_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_wildcard_loss_workspace_bytes
         n = _WS_BYTES[key] = size(kind, B, T, V, U, int(frames_per_tile), with_grad)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
@@ -857,7 +876,10 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
         _lib.check(rc, "ctc_amd_" + wname)
         return loss, grad
     with _on_device(dev):
-        call = lib.ctc_amd_long_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_wildcard_loss_grad
+        if optional_wildcards:
+            call = lib.ctc_amd_long_optional_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_optional_wildcard_loss_grad
+        else:
+            call = lib.ctc_amd_long_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_wildcard_loss_grad
         rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
                   _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
                   int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
@@ -933,17 +955,35 @@ def long_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Ten
     want_peak=False return None for the pair.  frames_per_tile as in long_wildcard_loss_grad; no output depends on it.  frame_window
     as in label_posterior, frames absolute: ctc_amd_long_windowed_label_posterior.  Every element of every output is written.  Does
     not synchronise."""
+    return _long_label_posterior("long_label_posterior", False, kind, wrt, labels, x, label_length, logit_length, blank, U,
+                                 wildcard_log_weight, frames_per_tile, dense, want_stats, want_peak, frame_window)
+
+
+def long_optional_wildcard_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                                           logit_length: torch.Tensor, blank: int, U: Optional[int] = None,
+                                           wildcard_log_weight: float = 0.0, frames_per_tile: int = 0, dense: bool = True,
+                                           want_stats: bool = True, want_peak: bool = True):
+    """long_label_posterior whose labels may also hold _lib.OPTIONAL_WILDCARD (ctc_amd_long_optional_wildcard_label_posterior): the
+    same arguments but the window, the same seven outputs.  The column of an optional position may sum to less than one frame, and
+    its duration is the expected number of frames it takes; the loss is long_optional_wildcard_loss_grad's, bit for bit.  Does not
+    synchronise."""
+    return _long_label_posterior("long_optional_wildcard_label_posterior", True, kind, wrt, labels, x, label_length, logit_length, blank, U,
+                                 wildcard_log_weight, frames_per_tile, dense, want_stats, want_peak, None)
+
+
+def _long_label_posterior(what, optional_wildcards, kind, wrt, labels, x, label_length, logit_length, blank, U, wildcard_log_weight,
+                          frames_per_tile, dense, want_stats, want_peak, frame_window):
     if labels.dim() != 2 or label_length.dim() != 1:
-        raise ValueError(f"long_label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
-    labels, x, label_length, logit_length, U, _, W = _nbest_args("long_label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
-                                                                 logit_length, U)
+        raise ValueError(f"{what}: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args(what, labels.unsqueeze(1), x, label_length.unsqueeze(1), logit_length, U)
     lib = _lib.load()
     dev = x.device
     B, T, V = (int(s) for s in x.shape)
-    key = ("long_label_posterior", kind, B, T, V, U, int(frames_per_tile))
+    key = (what, kind, B, T, V, U, int(frames_per_tile))
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = _lib.long_label_posterior_workspace_bytes(kind, B, T, V, U, int(frames_per_tile))
+        size = _lib.long_optional_wildcard_label_posterior_workspace_bytes if optional_wildcards else _lib.long_label_posterior_workspace_bytes
+        n = _WS_BYTES[key] = size(kind, B, T, V, U, int(frames_per_tile))
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     post = torch.empty((B, T, U), dtype=torch.float32, device=dev) if dense else None
     blk = torch.empty((B, T), dtype=torch.float32, device=dev)
@@ -964,12 +1004,12 @@ def long_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Ten
                                                            _stream(dev))
         _lib.check(rc, "ctc_amd_long_windowed_label_posterior")
         return loss, post, blk, dur, exf, peak, pfr
-    with _on_device(dev):
-        rc = lib.ctc_amd_long_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
-                                              _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
-                                              int(frames_per_tile), _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(peak),
-                                              _ptr(pfr), _ptr(ws), n, _stream(dev))
-    _lib.check(rc, "ctc_amd_long_label_posterior")
+    name = "ctc_amd_long_optional_wildcard_label_posterior" if optional_wildcards else "ctc_amd_long_label_posterior"
+    with _on_device(dev):  # (the two entry points have one argument list)
+        rc = getattr(lib, name)(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W, _ptr(label_length),
+                                _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U, int(frames_per_tile), _ptr(loss),
+                                _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(peak), _ptr(pfr), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, name)
     return loss, post, blk, dur, exf, peak, pfr
 
 
