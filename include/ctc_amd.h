@@ -1345,6 +1345,8 @@ int ctc_amd_long_windowed_label_posterior(int kind, int wrt,
  * label_length = 0 or for a single optional wildcard.
  * A transcript without an optional wildcard returns the bits of the counterpart for every output.  Numerics and determinism
  * are the counterparts'; the chain step has two more terms per position.
+ * d_loss[b] == 0: the gradient of utterance b is +0 in every element, as for an infeasible utterance (the counterparts return
+ * 0 * g, which is -0 where g is negative); the long-form entry points below do the same.
  */
 #define CTC_AMD_OPTIONAL_WILDCARD (-3)
 #define CTC_AMD_OPTIONAL_CLASSIC_MAX_U 512

@@ -156,11 +156,13 @@ def check(ref, got, tl, what, grad_rel=0.0):
         assert np.all(np.abs(total[b, :tl[b]] - 1.0) <= 1e-4), (what, b)
 
 
-def draw(B, T, U, seed, ll=None, tl=None, p_wild=0.08, p_opt=0.08, scale=1.0):
-    """Random logits and labels with wildcards of both kinds, no two optional ones adjacent."""
+def draw(B, T, U, seed, ll=None, tl=None, p_wild=0.08, p_opt=0.08, scale=1.0, V=V, blank=0):
+    """Random logits and labels with wildcards of both kinds, no two optional ones adjacent.  A blank other than 0: the labels
+    drawn equal to it become 0."""
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((B, T, V)) * scale).astype(np.float32)
     labels = rng.integers(1, V, (B, U)).astype(np.int32)
+    labels[labels == blank] = 0
     labels[rng.random((B, U)) < p_wild] = W
     for b in range(B):
         for i in np.nonzero(rng.random(U) < p_opt)[0]:
@@ -171,12 +173,14 @@ def draw(B, T, U, seed, ll=None, tl=None, p_wild=0.08, p_opt=0.08, scale=1.0):
     return x, labels, ll, tl
 
 
-def put(labels, b, at):
+def put(labels, b, at, V=V, blank=0):
     """Optional wildcards at the positions `at` of utterance b, ordinary labels around them."""
     for i in at:
         for j in (i - 1, i + 1):
             if 0 <= j < labels.shape[1] and labels[b, j] == O:
                 labels[b, j] = 1 + (j % (V - 1))
+                if labels[b, j] == blank:
+                    labels[b, j] = 0
         labels[b, i] = O
 
 
@@ -415,16 +419,21 @@ def test_formats_strides_and_blank(kind):
     check(ref, run(kind, 0, x, lab5, ll, tl, blank=blank), tl, f"{kind} blank={blank}")
 
 
-def _raw_calls(kind, x, labels, ll, tl, fill, tf=64):
-    """The three C entry points themselves on outputs and an exact-size workspace prefilled with the byte `fill`."""
+def _raw_calls(kind, x, labels, ll, tl, fill, tf=64, blank=0, d_loss=None, like_x=False):
+    """The three C entry points themselves on outputs and an exact-size workspace prefilled with the byte `fill`.  x: numpy, or a
+    device tensor of any of the three element types and any strides with a contiguous token axis.  like_x: the gradients have the
+    type and strides of x, and their whole buffers are returned too (grad_storage, ckpt_grad_storage)."""
     from tf_seq2seq_losses_amd import _lib
     lib = _lib.load()
-    B, T, _ = x.shape
+    B, T, V = x.shape
     U = labels.shape[1]
     k = KINDS.index(kind)
     t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl).items()}
-    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(), t["tl"].data_ptr(), 0,
-            ctypes.c_float(WEIGHT), B, T, V, U, tf)
+    xt = t["x"]
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+    lead = (k, 0, xt.data_ptr(), code[xt.dtype], xt.stride(0), xt.stride(1), t["labels"].data_ptr(), U, t["ll"].data_ptr(),
+            t["tl"].data_ptr(), blank, ctypes.c_float(WEIGHT), B, T, V, U, tf)
+    dl = None if d_loss is None else dev(np.asarray(d_loss, np.float32))
 
     def buf(shape, dtype):
         n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
@@ -435,8 +444,14 @@ def _raw_calls(kind, x, labels, ll, tl, fill, tf=64):
                              ("ckpt_", lib.ctc_amd_long_optional_wildcard_loss_grad_ckpt,
                               _lib.long_optional_wildcard_loss_ckpt_workspace_bytes)):
         lg = {name + "loss": buf((B,), torch.float32), name + "grad": buf((B, T, V), torch.float32)}
+        if like_x:
+            n = (B - 1) * xt.stride(0) + (T - 1) * xt.stride(1) + V
+            out[name + "grad_storage"] = buf((n,), xt.dtype)
+            lg[name + "grad"] = out[name + "grad_storage"].as_strided((B, T, V), xt.stride())
+        g = lg[name + "grad"]
         w = torch.full((size(k, B, T, V, U, tf, True),), fill, dtype=torch.uint8, device=DEV)
-        rc = call(*lead, None, *(v.data_ptr() for v in lg.values()), 0, T * V, V, w.data_ptr(), w.numel(), None)
+        rc = call(*lead, None if dl is None else dl.data_ptr(), *(v.data_ptr() for v in lg.values()), code[g.dtype], g.stride(0),
+                  g.stride(1), w.data_ptr(), w.numel(), None)
         assert rc == 0, lib.ctc_amd_last_error()
         out.update(lg)
     po = dict(p_loss=buf((B,), torch.float32), post=buf((B, T, U), torch.float32), blk=buf((B, T), torch.float32),

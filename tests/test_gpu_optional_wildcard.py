@@ -117,11 +117,13 @@ def same_bits(a, b, keys=None):
         assert torch.equal(u.view(torch.uint8), v.view(torch.uint8)), k
 
 
-def check(kind, wrt, x64, labels, ll, tl, got, what, weight=WEIGHT, d_loss=None, blank=0, grad_tol=1e-4):
+def check(kind, wrt, x64, labels, ll, tl, got, what, weight=WEIGHT, d_loss=None, blank=0, grad_tol=1e-4, ref=None):
     """Every output against the oracle; duration and expected_frame against the float64 sums over the returned float32 matrix (the
-    statistics kernel is the existing one: its bar is that of tests/test_gpu_label_posterior.py, 2 float32 ulps)."""
-    ref_loss, ref_grad = OO.loss_and_grad(kind, wrt, labels, x64, ll, tl, blank, weight, d_loss)
-    _, post, blk, dur, exf = OO.label_posterior(kind, wrt, labels, x64, ll, tl, blank, weight)
+    statistics kernel is the existing one: its bar is that of tests/test_gpu_label_posterior.py, 2 float32 ulps).  ref: the oracle's
+    (loss, grad, label_posterior, blank_posterior, duration, expected_frame) for these arguments, where the caller has them."""
+    if ref is None:
+        ref = OO.loss_and_grad(kind, wrt, labels, x64, ll, tl, blank, weight, d_loss) + OO.label_posterior(kind, wrt, labels, x64, ll, tl, blank, weight)[1:]
+    ref_loss, ref_grad, post, blk, dur, exf = ref
     loss = got["loss"].numpy().astype(np.float64)
     fin = np.isfinite(ref_loss)
     print(f"{what}: loss err {np.abs(loss[fin] - ref_loss[fin]).max(initial=0.0):.3g}  "
@@ -277,25 +279,34 @@ def test_non_zero_blank(blank, kind):
     check(kind, 0, x.astype(np.float64), labels, ll, tl, run_all(kind, 0, x, labels, ll, tl, blank=blank), f"{kind} blank={blank}", blank=blank)
 
 
-def _raw_calls(kind, x, labels, ll, tl, fill):
-    """The two C entry points on outputs and workspaces prefilled with `fill`."""
+def _raw_calls(kind, x, labels, ll, tl, fill, blank=0, d_loss=None, like_x=False):
+    """The two C entry points on outputs and workspaces prefilled with `fill`.  x: numpy, or a device tensor of any of the three
+    element types and any strides with a contiguous token axis.  like_x: the gradient has the type and strides of x, and its whole
+    buffer is returned too (grad_storage)."""
     from tf_seq2seq_losses_amd import _lib
     lib = _lib.load()
     B, T, V = x.shape
     U = labels.shape[1]
     k = KINDS.index(kind)
     t = {n: dev(a) for n, a in dict(x=x, labels=labels, ll=ll, tl=tl).items()}
-    lead = (k, 0, t["x"].data_ptr(), 0, T * V, V, t["labels"].data_ptr(), U, t["ll"].data_ptr(), t["tl"].data_ptr(), 0,
-            ctypes.c_float(WEIGHT), B, T, V, U)
+    xt = t["x"]
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+    lead = (k, 0, xt.data_ptr(), code[xt.dtype], xt.stride(0), xt.stride(1), t["labels"].data_ptr(), U, t["ll"].data_ptr(),
+            t["tl"].data_ptr(), blank, ctypes.c_float(WEIGHT), B, T, V, U)
+    dl = None if d_loss is None else dev(np.asarray(d_loss, np.float32))
 
     def buf(shape, dtype=torch.float32):
-        n = int(np.prod(shape)) * 4
+        n = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
         return torch.full((max(n, 1),), fill, dtype=torch.uint8, device=DEV)[:n].view(dtype).reshape(shape)
 
     lg = dict(loss=buf((B,)), grad=buf((B, T, V)))
+    if like_x:
+        lg["grad_storage"] = buf(((B - 1) * xt.stride(0) + (T - 1) * xt.stride(1) + V,), xt.dtype)
+        lg["grad"] = lg["grad_storage"].as_strided((B, T, V), xt.stride())
+    g = lg["grad"]
     w = torch.full((_lib.wildcard_loss_workspace_bytes(k, B, T, V, U, True),), fill, dtype=torch.uint8, device=DEV)
-    rc = lib.ctc_amd_optional_wildcard_loss_grad(*lead, None, lg["loss"].data_ptr(), lg["grad"].data_ptr(), 0, T * V, V, w.data_ptr(),
-                                                 w.numel(), None)
+    rc = lib.ctc_amd_optional_wildcard_loss_grad(*lead, None if dl is None else dl.data_ptr(), lg["loss"].data_ptr(), g.data_ptr(),
+                                                 code[g.dtype], g.stride(0), g.stride(1), w.data_ptr(), w.numel(), None)
     assert rc == 0, lib.ctc_amd_last_error()
     po = dict(ploss=buf((B,)), post=buf((B, T, U)), blk=buf((B, T)), dur=buf((B, U)), exf=buf((B, U)))
     w2 = torch.full((_lib.label_posterior_workspace_bytes(k, B, T, V, U),), fill, dtype=torch.uint8, device=DEV)

@@ -190,3 +190,26 @@ def test_best_path_edges(kind):
     x, lab = _x(9, 6, 3, 0), [W, 1, 1, 2, W, 3]  # no optional wildcard: the existing oracle exactly
     a, b = VO.best_path_one(kind, np.asarray(lab), x), OO.best_path_one(kind, lab, x)
     assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+
+@pytest.mark.parametrize("wrt", [0, 1])
+@pytest.mark.parametrize("kind", OO.KINDS)
+def test_weighted_gradient_at_the_last_blank(kind, wrt):
+    """blank = V - 1 and a d_loss with a zero and a negative value: the gradient is d_loss[b] times the unweighted mixture over
+    subsets (the GPU tests of d_loss rest on the oracle's weighted gradient)."""
+    V, T, blank, weight = 5, 8, 4, -0.7
+    labs = ([Q, 0, 1, Q, 3], [2, Q, 2, W, 0], [0, 1, Q])
+    d_loss = np.asarray([0.0, -1.5, 2.5])
+    x = np.stack([_x(T, V, 40 + b, wrt) for b in range(3)])
+    labels = np.full((3, 5), 1, dtype=np.int64)
+    for b, lab in enumerate(labs):
+        labels[b, :len(lab)] = lab
+    ll = [len(lab) for lab in labs]
+    loss, grad = OO.loss_and_grad(kind, wrt, labels, x, ll, [T] * 3, blank, weight, d_loss)
+    plain = OO.loss_and_grad(kind, wrt, labels, x, ll, [T] * 3, blank, weight)
+    assert np.array_equal(loss, plain[0])  # the loss is unaffected by d_loss
+    for b, lab in enumerate(labs):
+        ref_loss, ref_grad, _, _ = _mixture(kind, lab, x[b], blank, wrt, weight)
+        assert np.isfinite(ref_loss) and abs(loss[b] - ref_loss) < TOL and np.abs(ref_grad).max() > 1e-3
+        assert np.abs(grad[b] - d_loss[b] * ref_grad).max() < TOL
+    assert not grad[0].any()

@@ -827,6 +827,12 @@ __device__ __forceinline__ void loss_long_row(const Problem &p, const LongLossWs
     return;
   }
   const float dl = d_loss ? d_loss[b] : 1.f;
+  if constexpr (OPT) {  // a weight of zero: +0 throughout, as above (0 * a negative element would be -0)
+    if (dl == 0.f) {
+      for (int c = lane * 4; c < V; c += 256) gput4(c, make_float4(0.f, 0.f, 0.f, 0.f));
+      return;
+    }
+  }
   const float4 sv = *reinterpret_cast<const float4 *>(w.stat + ((size_t)b * p.T + t) * 4);
   const float mx = sv.y, l2s = sv.z;
   const int L = label_count(p, b);  // (feasible: L <= U)

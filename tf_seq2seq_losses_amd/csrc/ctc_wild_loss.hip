@@ -644,6 +644,12 @@ __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Pro
     return;
   }
   const float dl = d_loss ? d_loss[b] : 1.f;
+  if constexpr (OPT) {  // a weight of zero: +0 throughout, as above (0 * a negative element would be -0)
+    if (dl == 0.f) {
+      for (int k = lane * 4; k < V; k += 256) gput4(k, make_float4(0.f, 0.f, 0.f, 0.f));
+      return;
+    }
+  }
   const float4 sv = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
   const float mx = sv.y, l2s = sv.z;
   const int L = label_count(p, b);  // (feasible: L <= U <= UP)
