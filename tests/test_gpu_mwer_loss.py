@@ -26,36 +26,47 @@ def dev(a, dtype=None):
     return torch.tensor(np.asarray(a, dtype), device=DEV)
 
 
-def call(entry, labels, x, ll, tl, **kw):
+def call(entry, labels, x, ll, tl, blank=0, **kw):
     import tf_seq2seq_losses_amd as ctc
     kind = entry.split("-")[0]
     if entry.endswith("logproba"):
         cls = ctc.ClassicCtcLossData if kind == "classic" else ctc.SimplifiedCtcLossData
-        return ctc.ctc_mwer_loss_from_logproba(labels, x, ll, tl, 0, cls, **kw)
-    return (ctc.classic_ctc_mwer_loss if kind == "classic" else ctc.simplified_ctc_mwer_loss)(labels, x, ll, tl, 0, **kw)
+        return ctc.ctc_mwer_loss_from_logproba(labels, x, ll, tl, blank, cls, **kw)
+    return (ctc.classic_ctc_mwer_loss if kind == "classic" else ctc.simplified_ctc_mwer_loss)(labels, x, ll, tl, blank, **kw)
 
 
 @functools.lru_cache(maxsize=None)
-def case():
-    """Explicit lists with a duplicate, a masked entry, an entry infeasible for the lattice and an utterance without a feasible entry."""
+def case(V=6, blank=0):
+    """Explicit lists with a duplicate, a masked entry, an entry infeasible for the lattice and an utterance without a feasible entry.
+    Another V or blank: new logits, and the same lists on five tokens spread from the first to the last non-blank column (token i
+    of the default draw becomes the i-th of them), so that the risks are those of the default draw; those five columns and the
+    blank's are raised by ln(V / 6), so that the list's posterior is spread as it is at V = 6 (unbiased, one entry holds all of it
+    up to 1e-15, and the loss and its gradient vanish)."""
     rng = np.random.default_rng(12)
-    B, T, V, N = 3, 12, 6, 4
+    B, T, N = 3, 12, 4
     x = (1.5 * rng.standard_normal((B, T, V))).astype(np.float32)
     tl = np.asarray([12, 3, 1], np.int32)
     hyp = np.full((B, N, T), -1, np.int32)
     hl = np.asarray([[3, 4, 3, 2], [2, 4, 1, 0], [2, 3, 2, 4]], np.int32)
-    for b in range(B):
-        for n in range(N):
-            hyp[b, n, :hl[b, n]] = rng.integers(1, V, hl[b, n])
-    hyp[0, 2] = hyp[0, 0]                       # a duplicate
-    hyp[1, 0, :2] = (3, 3)                      # needs 3 frames on the classic lattice, 2 on the simplified: feasible in 3
+    ll = np.asarray([4, 2, 3], np.int32)
+    if (V, blank) == (6, 0):
+        for b in range(B):
+            for n in range(N):
+                hyp[b, n, :hl[b, n]] = rng.integers(1, V, hl[b, n])
+        hyp[0, 2] = hyp[0, 0]                       # a duplicate
+        hyp[1, 0, :2] = (3, 3)                      # needs 3 frames on the classic lattice, 2 on the simplified: feasible in 3
+        labels = rng.integers(1, V, (B, 4)).astype(np.int32)
+    else:
+        toks = [c for c in range(V) if c != blank]
+        spread = np.asarray([-1] + [toks[(i * (len(toks) - 1)) // 4] for i in range(5)], np.int32)
+        x[..., spread[1:].tolist() + [blank]] += np.float32(np.log(V / 6.0))
+        _, _, hyp6, _, _, labels6, _ = case()
+        hyp, labels = spread[np.maximum(hyp6, 0)], spread[labels6]
     score = np.zeros((B, N), np.float32) - np.arange(N, dtype=np.float32)
     score[0, 3] = -np.inf                       # masked
     score[1, 2] = -np.inf                       # masked
     # utterance 1: three frames, entry 1 has four labels (infeasible on both lattices)
     # utterance 2: one frame, every entry has two labels or more (nothing is feasible)
-    labels = rng.integers(1, V, (B, 4)).astype(np.int32)
-    ll = np.asarray([4, 2, 3], np.int32)
     for a in (x, tl, hyp, hl, score, labels, ll):
         a.setflags(write=False)
     return x, tl, hyp, hl, score, labels, ll
@@ -63,19 +74,24 @@ def case():
 
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_explicit_hypotheses_against_the_reference(entry):
+    check_explicit(entry)
+
+
+def check_explicit(entry, V=6, blank=0):
+    """case(V, blank) through `entry` against the reference."""
     import tf_seq2seq_losses_amd as ctc
     kind, wrt = entry.split("-")[0], int(entry.endswith("logproba"))
-    x, tl, hyp, hl, score, labels, ll = case()
+    x, tl, hyp, hl, score, labels, ll = case(V, blank)
     if wrt:
         x = O.logit_to_logproba(np.asarray(x, np.float64), 2).astype(np.float32)
     mask = np.isfinite(score)
-    want = E.mwer_reference(kind, wrt, hyp, hl, mask, x, tl, 0, labels, ll)
+    want = E.mwer_reference(kind, wrt, hyp, hl, mask, x, tl, blank, labels, ll)
     used = mask & np.isfinite(want["hyp_loss"])
     assert used[0].sum() == 3 and not used[1, 1] and used[1, 0] and used[1, 3] and not used[2].any(), used
 
     xt = dev(x).requires_grad_(True)
     beam = ctc.CtcBeamDecoding(dev(score), dev(hyp), dev(hl))
-    out = call(entry, dev(labels), xt, dev(ll), dev(tl), hypotheses=beam)
+    out = call(entry, dev(labels), xt, dev(ll), dev(tl), blank, hypotheses=beam)
     assert isinstance(out, ctc.CtcMwerLoss) and out.hypotheses.labels is beam.labels
     assert out.loss.shape == (3,) and out.risk.shape == (3, 4) == out.log_posterior.shape
     assert out.loss.dtype == out.risk.dtype == out.log_posterior.dtype == torch.float32
@@ -92,7 +108,7 @@ def test_explicit_hypotheses_against_the_reference(entry):
     hl_tol = 1e-4 + 1e-6 * np.abs(np.where(used, want["hyp_loss"], 0.0))
     pbound = 2.0 * hl_tol.max(axis=1, keepdims=True) + 1e-6 * np.abs(np.where(used, want["log_posterior"], 0.0))
     perr = np.abs(np.where(used, logp, 0.0) - np.where(used, want["log_posterior"], 0.0))
-    print(f"MWER-MEASURE {entry}: loss {loss.tolist()} reference {want['loss'].tolist()}; worst |loss - reference| {lerr.max():.3e}, "
+    print(f"MWER-MEASURE {entry} V={V} blank={blank}: loss {loss.tolist()} reference {want['loss'].tolist()}; worst |loss - reference| {lerr.max():.3e}, "
           f"worst |grad - reference| {gerr.max():.3e}, bound per utterance {bound.tolist()}, sum |c| "
           f"{np.abs(want['c']).sum(axis=1).tolist()}, worst |log_posterior - reference| {perr.max():.3e} (bound {pbound.min():.3e}), "
           f"largest |grad| {np.abs(want['grad']).max():.3g}", flush=True)
@@ -109,9 +125,13 @@ def test_explicit_hypotheses_against_the_reference(entry):
 def test_own_beam_search_equals_the_explicit_call(entry):
     """The same functions on the same inputs: equal bits.  The labels of utterance 1 are its best hypothesis (four frames: at most
     four labels), so that its list holds risk 0 beside risks >= 1 and the gradient compared is not a tensor of zeros."""
+    check_own_search(entry)
+
+
+def check_own_search(entry, V=6, blank=0):
     import tf_seq2seq_losses_amd as ctc
     kind, wrt = entry.split("-")[0], int(entry.endswith("logproba"))
-    x, _, _, _, _, labels, ll = case()
+    x, _, _, _, _, labels, ll = case(V, blank)
     tl = np.asarray([12, 4, 1], np.int32)
     if wrt:
         x = O.logit_to_logproba(np.asarray(x, np.float64), 2).astype(np.float32)
@@ -119,17 +139,17 @@ def test_own_beam_search_equals_the_explicit_call(entry):
     x2 = dev(x).requires_grad_(True)
     if wrt:
         cls = ctc.ClassicCtcLossData if kind == "classic" else ctc.SimplifiedCtcLossData
-        beam = ctc.ctc_beam_search_from_logproba(x2, dev(tl), 0, cls, **kw)
+        beam = ctc.ctc_beam_search_from_logproba(x2, dev(tl), blank, cls, **kw)
     else:
-        beam = (ctc.classic_ctc_beam_search if kind == "classic" else ctc.simplified_ctc_beam_search)(x2, dev(tl), 0, **kw)
+        beam = (ctc.classic_ctc_beam_search if kind == "classic" else ctc.simplified_ctc_beam_search)(x2, dev(tl), blank, **kw)
     labels, ll = labels.copy(), ll.copy()
     ll[1] = int(beam.label_length[1, 0])
     labels[1, :ll[1]] = beam.labels[1, 0, :ll[1]].cpu().numpy()
-    explicit = call(entry, dev(labels), x2, dev(ll), dev(tl), hypotheses=beam)
+    explicit = call(entry, dev(labels), x2, dev(ll), dev(tl), blank, hypotheses=beam)
     explicit.loss.sum().backward()
 
     x1 = dev(x).requires_grad_(True)
-    own = call(entry, dev(labels), x1, dev(ll), dev(tl), **kw)
+    own = call(entry, dev(labels), x1, dev(ll), dev(tl), blank, **kw)
     # the search leaves the logits' graph alone: a leaf without a gradient yet, detached hypotheses
     assert x1.is_leaf and x1.grad is None and x1.requires_grad
     assert not own.hypotheses.score.requires_grad and not own.hypotheses.labels.requires_grad
@@ -143,7 +163,7 @@ def test_own_beam_search_equals_the_explicit_call(entry):
     assert torch.isfinite(own.loss).all() and torch.isfinite(x1.grad).all()
     want_risk = E.edit_distances(beam.labels.cpu().numpy(), beam.label_length.cpu().numpy(), labels, ll)
     risk = own.risk.cpu().numpy()
-    print(f"MWER-MEASURE own search {entry}: risk {risk.tolist()} loss {own.loss.tolist()} largest |grad| per utterance "
+    print(f"MWER-MEASURE own search {entry} V={V} blank={blank}: risk {risk.tolist()} loss {own.loss.tolist()} largest |grad| per utterance "
           f"{x1.grad.abs().amax(dim=(1, 2)).tolist()}", flush=True)
     assert np.array_equal(risk, want_risk.astype(np.float32))
     assert ll[1] <= 4 and risk[1, 0] == 0.0 and risk[1, 1] >= 1.0 and bool(torch.isfinite(beam.score[1, 1]))

@@ -65,9 +65,10 @@ def check_grad(got, want, want_loss, w, what, sixteen=False):
     assert np.all(err <= bound), (what, float(err.max()))
 
 
-def check_all(kind, wrt, labels, x, ll, tl, blank, w, what, U=None, xt=None, grad_dtype=None, sixteen=False):
-    """Loss against the oracle and bit for bit against ops.nbest_loss, gradient against the oracle, rows beyond T_b exactly zero."""
-    want_loss, want = NG.nbest_loss_and_grad(kind, wrt, labels, x, ll, tl, blank, w)
+def check_all(kind, wrt, labels, x, ll, tl, blank, w, what, U=None, xt=None, grad_dtype=None, sixteen=False, ref=None):
+    """Loss against the oracle and bit for bit against ops.nbest_loss, gradient against the oracle, rows beyond T_b exactly zero.
+    ref: the oracle's (loss, grad) on these inputs where the caller has it already."""
+    want_loss, want = NG.nbest_loss_and_grad(kind, wrt, labels, x, ll, tl, blank, w) if ref is None else ref
     src = x if xt is None else xt
     loss, grad, _ = run(kind, wrt, labels, src, ll, tl, blank, w, U, grad_dtype)
     F.check(loss, want_loss, what)
