@@ -13,6 +13,7 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import ctc_oracle as O
+from tests.tools.second_order_reference import fd64_exact as _fd64_exact
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -148,20 +149,6 @@ def test_autograd_second_order_uses_hvp(kind, monkeypatch):
     dense = second(wts)
     assert torch.isfinite(fast).all()
     assert ((fast - dense).abs().max() / max(1.0, dense.abs().max().item())).item() < TOL
-
-
-def _fd64_exact(kind, inp, v, eps=2e-3):
-    """Directional derivative of the float64 NumPy oracle's gradient along v, by central differences at eps and 2 eps with
-    Richardson extrapolation (error O(eps^4)); logits and direction are taken in float64 exactly as the GPU sees them."""
-    x = inp["logits"].astype(np.float64)
-    vv = v.astype(np.float64)
-
-    def grad(z):
-        d = O.ctc_loss(kind, inp["labels"], z, inp["label_length"], inp["logit_length"], 0)
-        return O.logits_gradient(d, z)
-    d1 = (grad(x + eps * vv) - grad(x - eps * vv)) / (2 * eps)
-    d2 = (grad(x + 2 * eps * vv) - grad(x - 2 * eps * vv)) / (4 * eps)
-    return (4.0 * d1 - d2) / 3.0
 
 
 @pytest.mark.parametrize("kind", ["classic", "simplified"])
