@@ -520,6 +520,36 @@ int ctc_amd_nbest_loss_grad(int kind, int wrt,
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same gradient from block checkpoints (added under ABI v6: two new entry points, nothing existing changed).  Arguments, results,
+ * rules (the zero rule for +inf losses, padding frames, every element written, the same bits on every run, no floating-point
+ * atomics) and validation are those of ctc_amd_nbest_loss_grad, checked by the same code in the same order; loss has the bits of
+ * ctc_amd_nbest_loss.  The gradient differs from ctc_amd_nbest_loss_grad's in rounding only (the blank's share is reduced per
+ * hypothesis before it is weighted).
+ * U <= 256: two launches (T == 0 or B == 0: as above).  The alpha sweep stores every chain's float64 state once per block of
+ * F = 16 / NL frames; ONE workgroup per utterance then walks its ceil(N / CTC_AMD_NBEST_GROUP) groups in order and, per block of
+ * frames from the last to the first, re-runs alpha from the checkpoint in registers, steps beta and hands the float32 posteriors
+ * to the row stage through LDS: no per-frame state or posterior reaches memory.  With S, NL and r256 as above:
+ *   ctc_amd_nbest_loss_grad_ckpt_workspace_bytes = r256(8 * B * N * ceil(T / F) * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B * N)
+ *                                                  + (N > CTC_AMD_NBEST_GROUP ? r256(4 * B * T * V) : 0)
+ * -- the checkpoints, the row statistics, log2 P and, when an utterance has more than one group, a float32 accumulator of the
+ * gradient (the first group writes it, later ones subtract from it, the last converts: a 16-bit gradient is rounded once).  No term
+ * grows with B * N * T * U.  B = 256, T = 1000, U = 128, N = 8: 0.53 GB classic, 0.27 GB simplified.  At small B and large N the
+ * groups of an utterance run one after the other on one compute unit.
+ * U > 256 (blocks of at most two frames would save nothing): the call IS ctc_amd_nbest_loss_grad, bit for bit, and the size query
+ * returns ctc_amd_nbest_loss_grad_workspace_bytes.
+ * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_nbest_loss_grad_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes /*host*/);
+int ctc_amd_nbest_loss_grad_ckpt(int kind, int wrt,
+                                 const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride,
+                                 const int32_t *label_length /* [B][N] */, const int32_t *logit_length, int blank_index,
+                                 int B, int T, int V, int U, int N,
+                                 const float *weight /* [B][N] */, float *loss /* [B][N] */,
+                                 void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * N-best forced alignment (added under ABI v6: two new entry points, nothing existing changed): where each of N label sequences
  * per utterance lies in time.  What N calls of ctc_amd_best_path on labels + n * label_stride would give, from one read of the
  * logits per group of CTC_AMD_NBEST_GROUP hypotheses and with eight chains per workgroup.  Hypothesis (b, n) lies at

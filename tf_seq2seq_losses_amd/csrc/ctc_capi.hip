@@ -822,18 +822,20 @@ int ctc_amd_nbest_loss(int kind, int wrt, const void *logits, int logits_dtype, 
   return CTC_AMD_OK;
 }
 
-int ctc_amd_nbest_loss_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+// The two N-best gradients (three launches with saved rows; block checkpoints and one fused backward launch) take the same
+// arguments through the same checks: one copy, the route is the only difference.
+static int nbest_grad_query(bool ckpt, int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
   if (int rc = check_query_shape(kind, B, T, V, U, out_bytes)) return rc;
   if (int rc = check_nbest(B, V, N)) return rc;
-  *out_bytes = ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
+  *out_bytes = ckpt ? ctc::nbest_grad_ckpt_workspace_bytes(kind, B, T, V, U, N) : ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
   return CTC_AMD_OK;
 }
 
-int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
-                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
-                            int blank_index, int B, int T, int V, int U, int N, const float *weight, float *loss, void *grad,
-                            int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes,
-                            void *stream) {
+static int nbest_grad_call(bool ckpt, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                           int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                           const int32_t *logit_length, int blank_index, int B, int T, int V, int U, int N, const float *weight,
+                           float *loss, void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                           size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
   const Prelude pre = prelude(c, f, true);  // (the gradient's strides are looked at before its pointer)
@@ -841,10 +843,40 @@ int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dt
   if (int rc = check_nbest(B, V, N)) return rc;
   if (!weight || !loss || !grad) return fail(CTC_AMD_EINVAL, "null weight / loss / grad pointer");
   if (int rc = check_row_grid(B, T, 4)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N), NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_nbest_grad(pre.p, N, weight, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+  const size_t need = ckpt ? ctc::nbest_grad_ckpt_workspace_bytes(kind, B, T, V, U, N) : ctc::nbest_grad_workspace_bytes(kind, B, T, V, U, N);
+  if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::Refused)) return rc;
+  CTC_TRY((ckpt ? ctc::run_nbest_grad_ckpt : ctc::run_nbest_grad)(pre.p, N, weight, loss, grad, static_cast<char *>(workspace),
+                                                                  static_cast<hipStream_t>(stream)),
           "N-best loss gradient launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_nbest_loss_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+  return nbest_grad_query(false, kind, B, T, V, U, N, out_bytes);
+}
+
+int ctc_amd_nbest_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                            const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                            int blank_index, int B, int T, int V, int U, int N, const float *weight, float *loss, void *grad,
+                            int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace, size_t workspace_bytes,
+                            void *stream) {
+  return nbest_grad_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                         logit_length, blank_index, B, T, V, U, N, weight, loss, grad, grad_dtype, grad_stride_b, grad_stride_t,
+                         workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_nbest_loss_grad_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {
+  return nbest_grad_query(true, kind, B, T, V, U, N, out_bytes);
+}
+
+int ctc_amd_nbest_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                 int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                 const int32_t *logit_length, int blank_index, int B, int T, int V, int U, int N, const float *weight,
+                                 float *loss, void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  return nbest_grad_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+                         logit_length, blank_index, B, T, V, U, N, weight, loss, grad, grad_dtype, grad_stride_b, grad_stride_t,
+                         workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_nbest_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int N, size_t *out_bytes) {

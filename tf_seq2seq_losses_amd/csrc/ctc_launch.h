@@ -55,6 +55,11 @@ hipError_t run_nbest(const Problem &p, int N, float *loss, hipStream_t st);
 // holds the float64 rows of every hypothesis and frame, the row statistics and log2 P
 size_t nbest_grad_workspace_bytes(int kind, int B, int T, int V, int U, int N);
 hipError_t run_nbest_grad(const Problem &p, int N, const float *weight, float *loss, void *grad, char *ws, hipStream_t st);
+// ... and the same gradient from block checkpoints (U <= 256; above, both forward to the pair before): an alpha sweep that stores one
+// state per block of frames, then ONE launch that recomputes alpha per block, steps beta and runs the row stage out of LDS.  The
+// workspace holds the checkpoints, the row statistics, log2 P and, for N > NBEST_G, a float32 accumulator of the gradient
+size_t nbest_grad_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int N);
+hipError_t run_nbest_grad_ckpt(const Problem &p, int N, const float *weight, float *loss, void *grad, char *ws, hipStream_t st);
 
 // ctc_edit.hip: edit distance of every hypothesis (b, n) to its utterance's reference; one wavefront per pair, one launch, no workspace
 hipError_t run_edit_distance(const int *hyp, int hyp_stride, const int *hyp_length, const int *ref, int ref_stride, const int *ref_length,

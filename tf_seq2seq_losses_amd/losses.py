@@ -1177,14 +1177,15 @@ class CtcNbestLoss(NamedTuple):
 
 class _NbestLossFn(torch.autograd.Function):
     """loss[B, N] of ops.nbest_loss with a gradient for the logits: forward is the forward-only launch and keeps nothing but the
-    inputs; backward is ONE ops.nbest_loss_grad call with weight = d_loss (where the loss is +inf the incoming gradient is not
+    inputs; backward is ONE ops.nbest_loss_grad call (`checkpoint`: ops.nbest_loss_grad_ckpt) with weight = d_loss (where the loss is +inf the incoming gradient is not
     interpreted: the NaN / inf that the backward of `where` and `logsumexp` produce there do no harm).  Backward is not itself
     differentiable."""
 
     @staticmethod
-    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U):
+    def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, checkpoint=False):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U)
+        ctx.grad_op = ops.nbest_loss_grad_ckpt if checkpoint else ops.nbest_loss_grad
         return ops.nbest_loss(kind, wrt, labels, x, label_length, logit_length, blank, U)
 
     @staticmethod
@@ -1192,8 +1193,8 @@ class _NbestLossFn(torch.autograd.Function):
     def backward(ctx, d_loss):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U = ctx.call
-        _, grad = ops.nbest_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype)
-        return grad, None, None, None, None, None, None, None
+        _, grad = ctx.grad_op(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype)
+        return grad, None, None, None, None, None, None, None, None
 
 
 def _nbest_tail(loss, hypothesis_mask) -> CtcNbestLoss:
@@ -1208,7 +1209,7 @@ def _nbest_tail(loss, hypothesis_mask) -> CtcNbestLoss:
 
 
 def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, hypothesis_mask=None,
-           max_label_length=None, differentiable=False) -> CtcNbestLoss:
+           max_label_length=None, differentiable=False, checkpoint=False) -> CtcNbestLoss:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -1225,7 +1226,8 @@ def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blan
     U = None if max_label_length is None else max(0, min(int(labels.shape[2]), int(max_label_length)))
     if differentiable and x.requires_grad and torch.is_grad_enabled():
         # the mask and the log_posterior arithmetic are ordinary torch operations on the attached loss
-        loss = _NbestLossFn.apply(x, labels, label_length, logit_length, ops.KINDS[kind_name], wrt, _blank(blank_index), U)
+        loss = _NbestLossFn.apply(x, labels, label_length, logit_length, ops.KINDS[kind_name], wrt, _blank(blank_index), U,
+                                  bool(checkpoint))
         return _nbest_tail(loss, hypothesis_mask)
     with torch.no_grad():  # forward only: the result is detached
         loss = ops.nbest_loss(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), U)
@@ -1234,7 +1236,8 @@ def _nbest(kind_name: str, wrt: int, labels, x, label_length, logit_length, blan
 
 def classic_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                            blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
-                           max_label_length: Optional[int] = None, differentiable: bool = False) -> CtcNbestLoss:
+                           max_label_length: Optional[int] = None, differentiable: bool = False,
+                           checkpoint: bool = False) -> CtcNbestLoss:
     """The exact classic CTC loss of N label sequences per utterance against the same logits, the logits read once per group of
     eight hypotheses instead of once each: what re-ranks an N-best list (the scores of classic_ctc_beam_search are sums inside
     the beam: lower bounds) and turns it into confidences.
@@ -1253,30 +1256,34 @@ def classic_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length:
             objective such as (log_posterior.exp() * risk).sum() trains end to end.  Backward is ONE call, whatever nbest is: the
             gradient of sum_n d_loss[b, n] * loss[b, n], to which a hypothesis with loss +inf contributes exactly zero.  First
             derivatives only: backward is not itself differentiable.  The values are the same bits either way.
+        checkpoint: (keyword only) with `differentiable`: backward is the gradient from block checkpoints
+            (ctc_amd_nbest_loss_grad_ckpt): one state per block of frames instead of one per frame, an eighth of the workspace at
+            128 labels, and the posteriors never leave the chip.  The same gradient up to rounding.  False: today's path, bit for bit.
     Returns: CtcNbestLoss(loss, log_posterior), both [batch, nbest] float32 (detached unless `differentiable`; logits that
         require grad are accepted either way).  A duplicate hypothesis is counted twice in log_posterior.  nbest <= 64; a
         hypothesis that is infeasible or malformed (a label outside [0, num_tokens) or equal to the blank, a negative length
         counts as empty) has loss +inf and changes no other entry."""
     return _nbest("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length,
-                  differentiable)
+                  differentiable, checkpoint)
 
 
 def simplified_ctc_nbest_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                               blank_index: Union[int, torch.Tensor] = 0, *, hypothesis_mask: Optional[TensorLike] = None,
-                              max_label_length: Optional[int] = None, differentiable: bool = False) -> CtcNbestLoss:
+                              max_label_length: Optional[int] = None, differentiable: bool = False,
+                              checkpoint: bool = False) -> CtcNbestLoss:
     """The same on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
-    classic_ctc_nbest_loss, `differentiable` (first derivatives only) included."""
+    classic_ctc_nbest_loss, `differentiable` (first derivatives only) and `checkpoint` included."""
     return _nbest("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, hypothesis_mask, max_label_length,
-                  differentiable)
+                  differentiable, checkpoint)
 
 
 def ctc_nbest_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *,
                                  hypothesis_mask: Optional[TensorLike] = None, max_label_length: Optional[int] = None,
-                                 differentiable: bool = False) -> CtcNbestLoss:
+                                 differentiable: bool = False, checkpoint: bool = False) -> CtcNbestLoss:
     """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba).  With `differentiable` the
     gradient is the one with respect to the log-probabilities (first derivatives only: backward is not itself differentiable)."""
     return _nbest(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                  hypothesis_mask, max_label_length, differentiable)
+                  hypothesis_mask, max_label_length, differentiable, checkpoint)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1510,7 +1517,7 @@ class CtcMwerLoss(NamedTuple):
 
 
 def _mwer(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, beam_width, top_k, nbest, hypotheses,
-          max_label_length) -> CtcMwerLoss:
+          max_label_length, checkpoint=False) -> CtcMwerLoss:
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     label_length = _as_tensor(label_length, torch.int32)
@@ -1524,7 +1531,7 @@ def _mwer(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank
     with torch.no_grad():
         risk = ops.edit_distance(hypotheses.labels, hypotheses.label_length, labels, label_length).to(torch.float32)
     nb = _nbest(kind_name, wrt, hypotheses.labels, x, hypotheses.label_length, logit_length, blank_index, mask, max_label_length,
-                differentiable=True)
+                differentiable=True, checkpoint=checkpoint)
     used = torch.isfinite(nb.loss)  # unmasked and feasible
     zero = torch.zeros_like(risk)
     mean = torch.where(used, risk, zero).sum(dim=1, keepdim=True) / used.sum(dim=1, keepdim=True).clamp(min=1).to(torch.float32)
@@ -1534,7 +1541,8 @@ def _mwer(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank
 
 def classic_ctc_mwer_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                           blank_index: Union[int, torch.Tensor] = 0, *, beam_width: int = 16, top_k: int = 16, nbest: int = 8,
-                          hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None) -> CtcMwerLoss:
+                          hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None,
+                          checkpoint: bool = False) -> CtcMwerLoss:
     """Minimum word error rate (expected risk) training on the classic lattice, end to end on the device: an N-best list, the edit
     distance of every hypothesis to the labels as its risk, the exact posterior of every hypothesis within the list, and
         loss[b] = sum over the used n of  exp(log_posterior[b, n]) * (risk[b, n] - mean risk of the used hypotheses of b)
@@ -1549,30 +1557,32 @@ def classic_ctc_mwer_loss(labels: TensorLike, logits: TensorLike, label_length: 
             width], label_length [batch, nbest]); an entry whose score is not finite is masked.
         max_label_length: (keyword only) an upper bound, known on the host, on the HYPOTHESES' lengths, as
             classic_ctc_nbest_loss takes it (a beam search's label tensor is as wide as the logits are long).
+        checkpoint: (keyword only) as in classic_ctc_nbest_loss: backward from block checkpoints; False is today's path.
     Returns: CtcMwerLoss(loss [batch], risk [batch, nbest], log_posterior [batch, nbest], hypotheses).  The gradient reaches the
         logits through log_posterior only (risk is a constant); backward is the one call of classic_ctc_nbest_loss's.  First
         derivatives only.  No host synchronisation beyond the one look at max(label_length) that classic_ctc_nbest_loss takes for
         a wide label tensor without `max_label_length`."""
     return _mwer("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, beam_width, top_k, nbest,
-                 hypotheses, max_label_length)
+                 hypotheses, max_label_length, checkpoint)
 
 
 def simplified_ctc_mwer_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                              blank_index: Union[int, torch.Tensor] = 0, *, beam_width: int = 16, top_k: int = 16, nbest: int = 8,
-                             hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None) -> CtcMwerLoss:
+                             hypotheses: Optional[CtcBeamDecoding] = None, max_label_length: Optional[int] = None,
+                             checkpoint: bool = False) -> CtcMwerLoss:
     """The same on the simplified lattice (every non-blank frame is a label).  Same arguments and return value as
     classic_ctc_mwer_loss."""
     return _mwer("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, beam_width, top_k, nbest,
-                 hypotheses, max_label_length)
+                 hypotheses, max_label_length, checkpoint)
 
 
 def ctc_mwer_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index, ctc_loss_data_cls, *, beam_width: int = 16,
                                 top_k: int = 16, nbest: int = 8, hypotheses: Optional[CtcBeamDecoding] = None,
-                                max_label_length: Optional[int] = None) -> CtcMwerLoss:
+                                max_label_length: Optional[int] = None, checkpoint: bool = False) -> CtcMwerLoss:
     """The same for log-probabilities used as they stand (the counterpart of ctc_loss_from_logproba); the gradient is the one with
     respect to the log-probabilities."""
     return _mwer(ctc_loss_data_cls.kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                 beam_width, top_k, nbest, hypotheses, max_label_length)
+                 beam_width, top_k, nbest, hypotheses, max_label_length, checkpoint)
 
 
 # --------------------------------------------------------------------------------------------------

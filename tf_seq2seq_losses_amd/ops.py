@@ -678,27 +678,28 @@ def nbest_loss(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label
 
 def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, weight: torch.Tensor, U: Optional[int] = None,
-                    grad_dtype: Optional[torch.dtype] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    grad_dtype: Optional[torch.dtype] = None, _ckpt: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(loss[B, N] float32, grad[B, T, V]): the losses of nbest_loss, bit for bit, and the gradient of sum_n weight[b, n] * loss[b, n]
     with respect to x (ctc_amd_nbest_loss_grad).  A hypothesis whose loss is +inf contributes nothing and its weight is not
     interpreted (it may be NaN or infinite).  Arguments as nbest_loss; weight [B, N]; grad is contiguous, of grad_dtype (default:
     the element type the logits are passed in).  Does not synchronise."""
-    labels, x, label_length, logit_length, U, N, W = _nbest_args("nbest_loss_grad", labels, x, label_length, logit_length, U)
+    name = "nbest_loss_grad_ckpt" if _ckpt else "nbest_loss_grad"  # (the two calls differ in the C symbols alone)
+    labels, x, label_length, logit_length, U, N, W = _nbest_args(name, labels, x, label_length, logit_length, U)
     lib = _lib.load()
     dev = x.device
     B, T, V = (int(s) for s in x.shape)
     if tuple(weight.shape) != (B, N):
-        raise ValueError(f"nbest_loss_grad: weight must be [B, N] = {(B, N)}, got {tuple(weight.shape)}")
+        raise ValueError(f"{name}: weight must be [B, N] = {(B, N)}, got {tuple(weight.shape)}")
     if not (weight.dtype == torch.float32 and weight.device == dev and weight.is_contiguous()):
         weight = weight.to(device=dev, dtype=torch.float32).contiguous()
     if grad_dtype is None:
         grad_dtype = x.dtype
     if grad_dtype not in _DTYPES:
-        raise ValueError(f"nbest_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
-    key = ("nbest_loss_grad", kind, B, T, V, U, N)
+        raise ValueError(f"{name}: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
+    key = (name, kind, B, T, V, U, N)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and N, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = _lib.nbest_loss_grad_workspace_bytes(kind, B, T, V, U, N)
+        n = _WS_BYTES[key] = getattr(_lib, name + "_workspace_bytes")(kind, B, T, V, U, N)
     loss = torch.empty((B, N), dtype=torch.float32, device=dev)
     grad = torch.empty((B, T, V), dtype=grad_dtype, device=dev)
     if B == 0:
@@ -707,11 +708,19 @@ def nbest_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
         return nbest_loss(kind, wrt, labels, x, label_length, logit_length, blank, U), grad
     ws = torch.empty(n, dtype=torch.uint8, device=dev)
     with _on_device(dev):
-        rc = lib.ctc_amd_nbest_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
-                                         _ptr(label_length), _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(weight), _ptr(loss),
-                                         _ptr(grad), _DTYPES[grad_dtype], T * V, V, _ptr(ws), n, _stream(dev))
-    _lib.check(rc, "ctc_amd_nbest_loss_grad")
+        rc = getattr(lib, "ctc_amd_" + name)(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                             _ptr(label_length), _ptr(logit_length), int(blank), B, T, V, U, N, _ptr(weight), _ptr(loss),
+                                             _ptr(grad), _DTYPES[grad_dtype], T * V, V, _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_" + name)
     return loss, grad
+
+
+def nbest_loss_grad_ckpt(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                         logit_length: torch.Tensor, blank: int, weight: torch.Tensor, U: Optional[int] = None,
+                         grad_dtype: Optional[torch.dtype] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """nbest_loss_grad from block checkpoints (ctc_amd_nbest_loss_grad_ckpt): the same arguments and results, the loss bit for bit,
+    the gradient up to rounding; for U <= 256 two launches and a workspace without a term in B * N * T * U."""
+    return nbest_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, weight, U, grad_dtype, _ckpt=True)
 
 
 def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
