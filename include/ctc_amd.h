@@ -1426,8 +1426,9 @@ int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt,
  * those terms (K = 1: the same size).  The workspace may hold anything on entry.
  * Short utterances.  An utterance of L positions needs at least L / 2 frames, not L: the tiles that run are chosen by that bound
  * (position i is unreachable before frame i / 2), and what is infeasible beyond it falls out of the lattice.
- * Not included: the long-form alignment, the N-best calls, frame windows together with optional wildcards, and star temporal
- * classification's exclusion of the following label.
+ * Not included: the long-form alignment, the N-best calls and frame windows together with optional wildcards (DESIGN.md
+ * section 7).  Star temporal classification's exclusion of the following label: the short-form entry points at the end of this
+ * header.
  */
 int ctc_amd_long_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
                                                         size_t *out_bytes /*host*/);
@@ -1457,6 +1458,71 @@ int ctc_amd_long_optional_wildcard_label_posterior(int kind, int wrt,
                                                    float *loss, float *label_posterior /* may be NULL */, float *blank_posterior,
                                                    float *duration, float *expected_frame, float *peak_posterior, int32_t *peak_frame,
                                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Star temporal classification: the star excludes the label that follows it (added under ABI v6: three new entry points with their
+ * size queries, nothing existing changed).  In STC as published (Pratap et al. 2022) the star in front of label y is <star>\y:
+ * every token except y.  Without that a star may swallow frames that show the label it stands in front of, one token sequence
+ * matches under many segmentations, and a star's last frame and the next label's first frame are ambiguous.
+ *   ctc_amd_star_loss_grad          counterpart: ctc_amd_wildcard_loss_grad / ctc_amd_optional_wildcard_loss_grad
+ *   ctc_amd_star_label_posterior    counterpart: ctc_amd_label_posterior / ctc_amd_optional_wildcard_label_posterior
+ *   ctc_amd_star_best_path          counterpart: ctc_amd_wildcard_best_path / ctc_amd_optional_wildcard_best_path
+ * Each takes its counterpart's arguments plus `int optional_wildcards` behind blank_index: 0 selects the first counterpart (-3 is a
+ * bad label), anything else the second (CTC_AMD_OPTIONAL_WILDCARD is accepted, with every rule above, the classic alignment's
+ * U <= CTC_AMD_OPTIONAL_CLASSIC_MAX_U included).  Formats, strides, outputs, limits, validation order and messages, launches and
+ * capture are the counterpart's; there is no frame-window, long-form or N-best variant.
+ * Which token is excluded.  A wildcard position i (either kind) whose position i + 1 exists (i + 1 < label_length) and is an
+ * ordinary, valid label y_i (in [0, V), not the blank) excludes y_i on every one of its frames.  A wildcard that is last, or is
+ * followed by another wildcard of either kind, excludes nothing.  The wildcard's frames are: classic lattice, its open-state
+ * frames; simplified lattice, the entry into the wildcard and the stays behind it.  An optional wildcard that is skipped has no
+ * frames; the skip itself is unchanged.
+ * Emission.  The lattices, skips, w = wildcard_log_weight and infeasibility are the counterparts'.  Summed lattice:
+ *   e_w,i(t) = w + ln(sum_{k != y_i} exp lp[t, k])
+ * which is w + ln(1 - p_t(y_i)) for logits and w + LSE_t + ln(1 - p_t(y_i)) for log-probabilities, with p = softmax(x), or
+ * exp(x - LSE_t) for log-probabilities.  If y_i holds all of a row's mass the emission is -inf.
+ * Gradient.  gamma_t(k) (the posterior of the ordinary positions and the blank that emit k at t), Gamma_{t,i} (the posterior of
+ * wildcard position i at t) and d_loss are the counterpart's.  With c_i = Gamma_{t,i} / (1 - p_t(y_i)), taken as 0 where Gamma is
+ * 0 and as Gamma_{t,i} where nothing is excluded, C = sum_i c_i over the wildcard positions and D(k) = sum_{i : y_i = k} c_i:
+ *   logits:             grad[t, k] = d_loss * (p_k * (1 - (C - D(k))) - gamma_t(k))
+ *   log-probabilities:  grad[t, k] = d_loss * (-gamma_t(k) - p_k * (C - D(k)))
+ * Without any exclusion D = 0 and C = Gamma_t: the counterpart's formula.  Zero beyond T_b and for infeasible utterances; an
+ * utterance with an excluding wildcard and d_loss[b] == 0 gets +0 in every element.
+ * Label posteriors.  The counterpart's definition on this lattice; `loss` has the bits of ctc_amd_star_loss_grad's; every frame
+ * still sums to 1.
+ * Best path (max, +).  A frame of wildcard position i scores the best token other than y_i and reports it in `tokens`; ties go
+ * to the lowest token.  first_frame, last_frame, label_score and score follow from that.
+ * Same bits.  An utterance in which no wildcard has an ordinary successor returns the bits of the counterpart for every output.
+ * Numerics.  1 - p is never formed from the row's full sum: the row statistics of an utterance with an
+ * excluding wildcard are (max, sum of the rest), so that 1 - p keeps its relative precision for p up to 1 - 1e-7.  Sums over
+ * positions are integer (fixed point): no floating-point atomics, a fixed order, the same bits on every run.
+ * Workspace.  Loss and posteriors: the counterpart's size.  Best path: the counterpart's regions with two tokens per frame in
+ * the last one: r256(B T 64 w) + r256(8 B T) + r256(8 B T) bytes, w the back-pointer word of the counterpart.
+ */
+int ctc_amd_star_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_star_loss_grad(int kind, int wrt,
+                           const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride,
+                           const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                           float wildcard_log_weight, int B, int T, int V, int U,
+                           const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                           int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_star_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_star_label_posterior(int kind, int wrt,
+                                 const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride,
+                                 const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                                 float wildcard_log_weight, int B, int T, int V, int U,
+                                 float *loss, float *label_posterior, float *blank_posterior, float *duration,
+                                 float *expected_frame, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_star_best_path_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_star_best_path(int kind, int wrt,
+                           const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride,
+                           const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                           int B, int T, int V, int U,
+                           float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                           int32_t *first_frame /* may be NULL */, int32_t *last_frame /* may be NULL */,
+                           float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,17 @@ SIGNATURES = {
     "ctc_amd_optional_wildcard_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
     "ctc_amd_optional_wildcard_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
                                                   [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    # star temporal classification (a wildcard excludes the label that follows it): the counterparts' arguments with
+    # optional_wildcards behind blank_index
+    "ctc_amd_star_best_path_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, optional_wildcards, B, T, V, U
+    "ctc_amd_star_best_path": (_c_int, _COMMON_EX[:11] + [_c_int] + _COMMON_EX[11:] +
+                               [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_star_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
+    "ctc_amd_star_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                               [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_star_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
+    "ctc_amd_star_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                     [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     # ... and the three long-form ones of the summed lattice, in the same manner
     "ctc_amd_long_windowed_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                         [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
@@ -290,6 +301,13 @@ def nbest_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, N
 def wildcard_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_wildcard_best_path_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_wildcard_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def star_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, optional_wildcards: bool = False) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_star_best_path_workspace_bytes(kind, int(optional_wildcards), B, T, V, U, ctypes.byref(out)),
+          "ctc_amd_star_best_path_workspace_bytes")
     return int(out.value)
 
 

@@ -19,5 +19,12 @@ size_t align_wild_workspace_bytes(int B, int T, int U);
 hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
                           float *label_score, hipStream_t st, const int32_t *frame_window = nullptr, int window_stride = 0,
                           bool optional_wildcards = false);
+// ctc_amd_star_best_path: the call above in which a wildcard position excludes the ordinary label that
+// follows it (ctc_align_wild.hip compiled with -DCTC_STAR).  Its workspace holds two tokens per frame (the best and the runner-up) in
+// the last region; no frame window; the classic limit with optional wildcards is the same
+size_t star_align_workspace_bytes(int B, int T, int U);
+hipError_t run_star_align(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
+                          float *label_score, hipStream_t st, const int32_t *frame_window = nullptr, int window_stride = 0,
+                          bool optional_wildcards = false);
 
 }  // namespace ctc

@@ -32,6 +32,11 @@
 // bit NL + j = "entered from two back".  A last optional position makes the states before it end states (candidates in the order
 // closed, open of L - 1, then closed, open of L - 2 or the start state).  A skipped position reports first = last = -1 and a
 // label_score of 0, the log-probability of an empty run.
+// XN (ctc_amd_star_best_path; this file compiled a second time with -DCTC_STAR): a wildcard position whose
+// next position is an ordinary label y excludes y.  The row pass carries the two best tokens (m1, k1, m2, k2), lowest token on ties,
+// through the wave reduction; such a position takes m1 unless k1 = y, then m2, into its ring slot (on the simplified lattice the
+// horizontal step behind it costs the slot as well), a_t becomes the pair (k1, k2) in the workspace and the back-trace reports the
+// token that was scored.
 // Every output element has one writer, no atomics: the same bits on every run.
 #include <type_traits>
 
@@ -83,19 +88,45 @@ __device__ __forceinline__ void stat_add4(float &m, int &idx, float &s, const fl
   }
 }
 
+// XN: the same with the runner-up: m2 = the best element other than the one at idx, i2 = the lowest index holding it (NO_INDEX before
+// the second element).  An element equal to m stays behind it and may be the runner-up
+__device__ __forceinline__ void stat2_add1(float &m, int &idx, float &m2, int &i2, const float v, int k) {
+  // (selects of values: as two branches that store to either pair the compiler chooses between the addresses and the callers'
+  // arrays stay in memory)
+  const bool first = v > m, second = v > m2;
+  const float nm2 = first ? m : second ? v : m2;
+  const int ni2 = first ? idx : second ? k : i2;
+  m2 = nm2; i2 = ni2;
+  m = first ? v : m;
+  idx = first ? k : idx;
+}
+__device__ __forceinline__ void stat2_add4(float &m, int &idx, float &m2, int &i2, float &s, const float4 v, int k, bool with_sum) {
+  const float mo = fmaxf(m, FLT_LOWEST);
+  stat2_add1(m, idx, m2, i2, v.x, k);
+  stat2_add1(m, idx, m2, i2, v.y, k + 1);
+  stat2_add1(m, idx, m2, i2, v.z, k + 2);
+  stat2_add1(m, idx, m2, i2, v.w, k + 3);
+  if (with_sum) {
+    const float mn = fmaxf(m, FLT_LOWEST);
+    s = s * fexp2((mo - mn) * LOG2E) +
+        ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
+  }
+}
+
 // wave-wide minimum of unsigned values, the same value in every lane (the reduction of ctc_common.h with v_min_u32)
 __device__ __forceinline__ unsigned wave_min_u(unsigned v) {
   asm(CTC_WAVE_REDUCE_ASM("v_min_u32_dpp") : "+v"(v));
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-template <int KIND, int NL, bool WIN, bool OPT>
+template <int KIND, int NL, bool WIN, bool OPT, bool XN>
 __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem p, char *__restrict__ ws, size_t off_lp, size_t off_at,
                                                                    float *__restrict__ score, int *__restrict__ tokens,
                                                                    int *__restrict__ label_index, int *__restrict__ first_frame,
                                                                    int *__restrict__ last_frame, float *__restrict__ label_score,
                                                                    const int32_t *__restrict__ win, int wstride) {
   static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
+  static_assert(!(WIN && XN), "frame windows and the exclusion of the next label are not combined");
   typedef typename BpWord<NL>::type Word;
   typedef typename std::conditional<NL == 16, unsigned long long, unsigned int>::type Bits;
   constexpr int UP = 64 * NL;
@@ -169,13 +200,24 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
     }
   }
 
+  // XN: the token a wildcard position excludes: that of an ordinary position right behind it, -1 where there is none
+  [[maybe_unused]] int nx[NL];
+  auto excluded = [&](int i) {
+    const int nt = i + 1 < UP ? lab_s[i + 1] : -1;
+    return (is_wild(lab_s[i]) && nt >= 0) ? nt : -1;
+  };
+  if constexpr (XN) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) nx[j] = excluded(lane * NL + j);
+  }
+
   const int esz = dt == 0 ? 4 : 2;
   const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
   // vector row accesses (16 bytes of float32, 8 bytes of 16-bit elements) need aligned rows; element-wise otherwise
   const bool vec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
   Word *const bp = reinterpret_cast<Word *>(ws) + (size_t)b * T * 64;
   double *const lpw = reinterpret_cast<double *>(ws + off_lp) + (size_t)b * T;  // the sweep: LSE_t; the back-trace: lp[t, pi_t]
-  int *const atw = reinterpret_cast<int *>(ws + off_at) + (size_t)b * T;        // a_t
+  int *const atw = reinterpret_cast<int *>(ws + off_at) + (size_t)b * T * (XN ? 2 : 1);  // a_t (XN: the pair k1, k2)
 
   // ---- the sweep ----
   // chain state (wave 0)
@@ -232,8 +274,13 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
       // so their results are the same bits (an element past V enters as -inf: it never wins and adds exp(-inf) = 0)
       float m[G], s[G];
       int ix[G];
+      [[maybe_unused]] float m2[G];  // XN: the runner-up of the lane's elements
+      [[maybe_unused]] int ix2[G];
 #pragma unroll
-      for (int g = 0; g < G; ++g) { m[g] = -__builtin_inff(); s[g] = 0.f; ix[g] = lane * 4 < V ? lane * 4 : NO_INDEX; }
+      for (int g = 0; g < G; ++g) {
+        m[g] = -__builtin_inff(); s[g] = 0.f; ix[g] = lane * 4 < V ? lane * 4 : NO_INDEX;
+        if constexpr (XN) { m2[g] = -__builtin_inff(); ix2[g] = NO_INDEX; }
+      }
       for (int k = lane * 4; k < V; k += 256) {
         float4 v[G];
 #pragma unroll
@@ -249,10 +296,16 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
           }
         }
 #pragma unroll
-        for (int g = 0; g < G; ++g) stat_add4(m[g], ix[g], s[g], v[g], k, with_sum);
+        for (int g = 0; g < G; ++g) {
+          if constexpr (XN) stat2_add4(m[g], ix[g], m2[g], ix2[g], s[g], v[g], k, with_sum);
+          else stat_add4(m[g], ix[g], s[g], v[g], k, with_sum);
+        }
       }
       float M[G];
+      [[maybe_unused]] float M2[G];  // XN: the best token other than k1, and both tokens
+      [[maybe_unused]] int K1[G], K2[G];
       int my_a = 0;
+      [[maybe_unused]] int my_a2 = 0;
       double my_lse = 0.0;
 #pragma unroll
       for (int g = 0; g < G; ++g) {
@@ -260,6 +313,19 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
         // every lane whose maximum is the row's offers its lowest index; an all -inf row: every lane does, index 0 wins
         unsigned a = wave_min_u(m[g] == M[g] ? (unsigned)ix[g] : (unsigned)NO_INDEX);
         if (a >= (unsigned)V) a = 0;  // (NaN rows only: unspecified, but a token of the vocabulary)
+        if constexpr (XN) {
+          // the lane that holds k1 offers its runner-up, every other lane its own best: the best token other than k1
+          const bool has = m[g] == M[g] && (unsigned)ix[g] == a;
+          const float mg = m[g], m2g = m2[g];  // (values first: a choice between the array elements themselves keeps the arrays in memory)
+          const int ig = ix[g], i2g = ix2[g];
+          const float cm = has ? m2g : mg;
+          const int ci = has ? i2g : ig;
+          M2[g] = wave_max(cm);
+          unsigned a2 = wave_min_u(cm == M2[g] ? (unsigned)ci : (unsigned)NO_INDEX);
+          if (a2 >= (unsigned)V) a2 = 0;  // (V = 1: there is no other token; its score is -inf)
+          K1[g] = (int)a; K2[g] = (int)a2;
+          if (lane == g) my_a2 = (int)a2;
+        }
         double l = 0.0;
         if (with_sum) {
           const float Mf = fmaxf(M[g], FLT_LOWEST);
@@ -270,7 +336,8 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
         if (lane == g) { my_a = (int)a; my_lse = l; }
       }
       if (lane < G && t0 + f0 + lane < Tb) {
-        atw[t0 + f0 + lane] = my_a;
+        if constexpr (XN) *reinterpret_cast<int2 *>(atw + 2 * (t0 + f0 + lane)) = make_int2(my_a, my_a2);
+        else atw[t0 + f0 + lane] = my_a;
         lpw[t0 + f0 + lane] = my_lse;
       }
 #pragma unroll
@@ -280,6 +347,9 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
 #pragma unroll
           for (int j = 0; j < NL; ++j) {
             float v = ((wild >> j) & 1u) ? M[g] : e[g][j];
+            if constexpr (XN) {  // the best token other than the excluded one
+              if (nx[j] >= 0 && K1[g] == nx[j]) v = M2[g];
+            }
             if constexpr (WIN) {
               if (t0 + f0 + g < wf[j] || t0 + f0 + g > wl[j]) v = -__builtin_inff();
             }
@@ -355,7 +425,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
 #pragma unroll
         for (int j = NL - 1; j >= 0; --j) {
           const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
-          const double d = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? (WIN ? (double)e[j] : emd) : ebd);
+          const double d = q + (double)e[j], h = C[j] + (((wild >> j) & 1u) ? ((WIN || XN) ? (double)e[j] : emd) : ebd);
           const unsigned sd = d > h ? 1u : 0u;
           double best = sd ? d : h;
           if constexpr (OPT) {  // entered over an optional wildcard, from two positions back
@@ -513,7 +583,14 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
       }
       if (lane < nf) {
         const int t = f0 + lane;
-        if (mytok == ALIGN_WILDCARD) mytok = atw[t];
+        if constexpr (XN) {  // the token that was scored: k1 unless the position excludes it
+          if (mytok == ALIGN_WILDCARD) {
+            const int2 a = *reinterpret_cast<const int2 *>(atw + 2 * t);
+            mytok = a.x == excluded(myidx) ? a.y : a.x;
+          }
+        } else if (mytok == ALIGN_WILDCARD) {
+          mytok = atw[t];
+        }
         tok_out[t] = mytok;
         if (idx_out) idx_out[t] = myidx;
         lpw[t] = (double)row_load1(xb + (size_t)((long)t * p.xst) * esz, mytok, dt) - lpw[t];  // (log-probability input: LSE_t = 0)
@@ -543,37 +620,52 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_wild_kernel(const Problem
   }
 }
 
-template <int KIND, int NL, bool WIN, bool OPT>
+template <int KIND, int NL, bool WIN, bool OPT, bool XN>
 hipError_t launch_align_wild(const Problem &p, char *ws, size_t off_lp, size_t off_at, float *score, int *tokens, int *label_index,
                              int *first_frame, int *last_frame, float *label_score, const int32_t *win, int wstride, hipStream_t st) {
-  hipLaunchKernelGGL((align_wild_kernel<KIND, NL, WIN, OPT>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
+  hipLaunchKernelGGL((align_wild_kernel<KIND, NL, WIN, OPT, XN>), dim3(p.B), dim3(ALIGN_THREADS), 0, st, p, ws, off_lp, off_at, score, tokens,
                      label_index, first_frame, last_frame, label_score, win, wstride);
   return hipGetLastError();
 }
 
 }  // namespace
 
-size_t align_wild_workspace_bytes(int B, int T, int U) {
-  return r256((size_t)B * T * 64 * bp_word_bytes(nl_for(U))) + r256((size_t)B * T * 8) + r256((size_t)B * T * 4);
+#ifdef CTC_STAR
+constexpr bool AL_XN = true;
+#define CTC_AL_NAME(base, star) star
+#else
+constexpr bool AL_XN = false;
+#define CTC_AL_NAME(base, star) base
+#endif
+
+// (CTC_STAR: star_align_workspace_bytes, with two tokens per frame in the last region)
+size_t CTC_AL_NAME(align_wild_workspace_bytes, star_align_workspace_bytes)(int B, int T, int U) {
+  return r256((size_t)B * T * 64 * bp_word_bytes(nl_for(U))) + r256((size_t)B * T * 8) + r256((size_t)B * T * (AL_XN ? 8 : 4));
 }
 
 #define CTC_ALIGN_WILD_ROW(KIND, WIN, OPT)                                                                                       \
-  {launch_align_wild<KIND, 1, WIN, OPT>, launch_align_wild<KIND, 2, WIN, OPT>, launch_align_wild<KIND, 4, WIN, OPT>, \
-   launch_align_wild<KIND, 8, WIN, OPT>, launch_align_wild<KIND, 16, WIN, OPT>}
+  {launch_align_wild<KIND, 1, WIN, OPT, AL_XN>, launch_align_wild<KIND, 2, WIN, OPT, AL_XN>, launch_align_wild<KIND, 4, WIN, OPT, AL_XN>, \
+   launch_align_wild<KIND, 8, WIN, OPT, AL_XN>, launch_align_wild<KIND, 16, WIN, OPT, AL_XN>}
 
-hipError_t run_align_wild(const Problem &p, char *ws, float *score, int *tokens, int *label_index, int *first_frame, int *last_frame,
-                          float *label_score, hipStream_t st, const int32_t *frame_window, int window_stride, bool optional_wildcards) {
+// (CTC_STAR: run_star_align, the XN kernels: no window)
+hipError_t CTC_AL_NAME(run_align_wild, run_star_align)(const Problem &p, char *ws, float *score, int *tokens, int *label_index,
+                                                       int *first_frame, int *last_frame, float *label_score, hipStream_t st,
+                                                       const int32_t *frame_window, int window_stride, bool optional_wildcards) {
   typedef hipError_t Launch(const Problem &, char *, size_t, size_t, float *, int *, int *, int *, int *, float *, const int32_t *, int,
                             hipStream_t);
   static Launch *const table[3][2][5] = {{CTC_ALIGN_WILD_ROW(0, false, false), CTC_ALIGN_WILD_ROW(1, false, false)},
+#ifdef CTC_STAR
+                                         {{}, {}},
+#else
                                          {CTC_ALIGN_WILD_ROW(0, true, false), CTC_ALIGN_WILD_ROW(1, true, false)},
+#endif
                                          // (classic, NL = 16 with OPT needs scratch: not built, U <= ALIGN_OPTIONAL_CLASSIC_MAX_U)
-                                         {{launch_align_wild<0, 1, false, true>, launch_align_wild<0, 2, false, true>,
-                                           launch_align_wild<0, 4, false, true>, launch_align_wild<0, 8, false, true>, nullptr},
+                                         {{launch_align_wild<0, 1, false, true, AL_XN>, launch_align_wild<0, 2, false, true, AL_XN>,
+                                           launch_align_wild<0, 4, false, true, AL_XN>, launch_align_wild<0, 8, false, true, AL_XN>, nullptr},
                                           CTC_ALIGN_WILD_ROW(1, false, true)}};
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
-  if (lg < 0 || p.kind < 0 || p.kind > 1 || (frame_window && optional_wildcards)) return hipErrorInvalidValue;
+  if (lg < 0 || p.kind < 0 || p.kind > 1 || (frame_window && optional_wildcards) || (AL_XN && frame_window)) return hipErrorInvalidValue;
   const size_t off_lp = r256((size_t)p.B * p.T * 64 * bp_word_bytes(NL));
   const size_t off_at = off_lp + r256((size_t)p.B * p.T * 8);
   Launch *const launch = table[optional_wildcards ? 2 : frame_window ? 1 : 0][p.kind][lg];

@@ -920,8 +920,9 @@ static int check_optional_alignment(bool optional_wildcards, int kind, int U) {
   return CTC_AMD_OK;
 }
 
-// One body for ctc_amd_windowed_best_path and ctc_amd_optional_wildcard_best_path (which has no window).
-static int wildcard_best_path_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+// One body for ctc_amd_windowed_best_path, ctc_amd_optional_wildcard_best_path and ctc_amd_star_best_path (which have no window;
+// `star`: a wildcard excludes the label that follows it, on a workspace of its own size).
+static int wildcard_best_path_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride, int B,
                                    int T, int V, int U, float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame,
@@ -932,9 +933,11 @@ static int wildcard_best_path_call(bool optional_wildcards, int kind, int wrt, c
   if (int rc = check_alignment(score, tokens, T, V)) return rc;
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_optional_alignment(optional_wildcards, kind, U)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, ctc::align_wild_workspace_bytes(B, T, U), NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_align_wild(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame, label_score,
-                              static_cast<hipStream_t>(stream), frame_window, window_stride, optional_wildcards),
+  const size_t need = star ? ctc::star_align_workspace_bytes(B, T, U) : ctc::align_wild_workspace_bytes(B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::Refused)) return rc;
+  CTC_TRY((star ? ctc::run_star_align : ctc::run_align_wild)(pre.p, static_cast<char *>(workspace), score, tokens, label_index, first_frame,
+                                                             last_frame, label_score, static_cast<hipStream_t>(stream), frame_window,
+                                                             window_stride, optional_wildcards),
           "wildcard alignment launch");
   return CTC_AMD_OK;
 }
@@ -945,7 +948,7 @@ int ctc_amd_windowed_best_path(int kind, int wrt, const void *logits, int logits
                                int blank_index, const int32_t *frame_window, int window_stride, int B, int T, int V, int U, float *score,
                                int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame, float *label_score,
                                void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_best_path_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_best_path_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, frame_window, window_stride, B, T, V, U, score, tokens,
                                  label_index, first_frame, last_frame, label_score, workspace, workspace_bytes, stream);
 }
@@ -961,9 +964,27 @@ int ctc_amd_optional_wildcard_best_path(int kind, int wrt, const void *logits, i
                                         const int32_t *logit_length, int blank_index, int B, int T, int V, int U, float *score,
                                         int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
                                         float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_best_path_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_best_path_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, nullptr, 0, B, T, V, U, score, tokens, label_index, first_frame,
                                  last_frame, label_score, workspace, workspace_bytes, stream);
+}
+
+// Star temporal classification's exclusion of the following label: the counterparts' bodies with `star` set.
+int ctc_amd_star_best_path_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, size_t *out_bytes) {
+  if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
+  if (int rc = check_optional_alignment(optional_wildcards != 0, kind, U)) return rc;  // (no size for a call that cannot run)
+  *out_bytes = ctc::star_align_workspace_bytes(B, T, U);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_star_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                           int blank_index, int optional_wildcards, int B, int T, int V, int U, float *score, int32_t *tokens,
+                           int32_t *label_index, int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+  return wildcard_best_path_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+                                 label_stride, label_length, logit_length, blank_index, nullptr, 0, B, T, V, U, score, tokens, label_index,
+                                 first_frame, last_frame, label_score, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
@@ -1048,8 +1069,8 @@ int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, 
 }
 
 // The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
-// One body for ctc_amd_windowed_loss_grad and ctc_amd_optional_wildcard_loss_grad (which has no window).
-static int wildcard_loss_grad_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+// One body for ctc_amd_windowed_loss_grad, ctc_amd_optional_wildcard_loss_grad and ctc_amd_star_loss_grad (which have no window).
+static int wildcard_loss_grad_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
                                    float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss, void *grad,
@@ -1063,8 +1084,9 @@ static int wildcard_loss_grad_call(bool optional_wildcards, int kind, int wrt, c
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
-  CTC_TRY(ctc::run_wild_loss(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
-                             frame_window, window_stride, optional_wildcards), "wildcard loss launch");
+  CTC_TRY((star ? ctc::run_star_loss : ctc::run_wild_loss)(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
+                                                           static_cast<hipStream_t>(stream), frame_window, window_stride,
+                                                           optional_wildcards), "wildcard loss launch");
   return CTC_AMD_OK;
 }
 
@@ -1073,7 +1095,7 @@ int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits
                                int blank_index, const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T,
                                int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
                                int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_loss_grad_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_loss_grad_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U,
                                  d_loss, loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
@@ -1088,9 +1110,23 @@ int ctc_amd_optional_wildcard_loss_grad(int kind, int wrt, const void *logits, i
                                         const int32_t *logit_length, int blank_index, float wildcard_log_weight, int B, int T, int V, int U,
                                         const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
                                         int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_loss_grad_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_loss_grad_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad,
                                  grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_star_loss_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
+  return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, want_grad, out_bytes);
+}
+
+int ctc_amd_star_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                           const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                           int blank_index, int optional_wildcards, float wildcard_log_weight, int B, int T, int V, int U,
+                           const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+  return wildcard_loss_grad_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+                                 label_stride, label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss,
+                                 loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
@@ -1208,8 +1244,9 @@ int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U
   return ctc_amd_wildcard_loss_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
 }
 
-// One body for ctc_amd_windowed_label_posterior and ctc_amd_optional_wildcard_label_posterior (which has no window).
-static int label_posterior_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+// One body for ctc_amd_windowed_label_posterior, ctc_amd_optional_wildcard_label_posterior and ctc_amd_star_label_posterior (which
+// have no window).
+static int label_posterior_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                 int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                 const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
                                 float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
@@ -1226,9 +1263,10 @@ static int label_posterior_call(bool optional_wildcards, int kind, int wrt, cons
   if (int rc = check_vocab(V, " of the label posteriors")) return rc;
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, ctc::wild_loss_workspace_bytes(kind, B, T, U, true), NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_label_posterior(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
-                                   static_cast<char *>(workspace), static_cast<hipStream_t>(stream), frame_window, window_stride,
-                                   optional_wildcards),
+  CTC_TRY((star ? ctc::run_star_label_posterior : ctc::run_label_posterior)(pre.p, wildcard_log_weight, loss, label_posterior,
+                                                                            blank_posterior, duration, expected_frame,
+                                                                            static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
+                                                                            frame_window, window_stride, optional_wildcards),
           "label posterior launch");
   return CTC_AMD_OK;
 }
@@ -1239,7 +1277,7 @@ int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int 
                                      float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
                                      float *blank_posterior, float *duration, float *expected_frame, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-  return label_posterior_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+  return label_posterior_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
                               logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U, loss,
                               label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
@@ -1254,9 +1292,23 @@ int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt, const void *log
                                               float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
                                               float *blank_posterior, float *duration, float *expected_frame, void *workspace,
                                               size_t workspace_bytes, void *stream) {
-  return label_posterior_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+  return label_posterior_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
                               logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss, label_posterior,
                               blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_star_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  return ctc_amd_label_posterior_workspace_bytes(kind, B, T, V, U, out_bytes);
+}
+
+int ctc_amd_star_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                 int blank_index, int optional_wildcards, float wildcard_log_weight, int B, int T, int V, int U, float *loss,
+                                 float *label_posterior, float *blank_posterior, float *duration, float *expected_frame, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+  return label_posterior_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+                              label_stride, label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss,
+                              label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,

@@ -23,5 +23,12 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
 hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
                                float *duration, float *expected_frame, char *ws, hipStream_t st, const int32_t *frame_window = nullptr,
                                int window_stride = 0, bool optional_wildcards = false);
+// ctc_amd_star_loss_grad / ctc_amd_star_label_posterior: the two calls above in which a wildcard position
+// excludes the ordinary label that follows it (ctc_wild_loss.hip compiled with -DCTC_STAR).  The same workspace; no frame window
+hipError_t run_star_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws, hipStream_t st,
+                         const int32_t *frame_window = nullptr, int window_stride = 0, bool optional_wildcards = false);
+hipError_t run_star_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+                                    float *duration, float *expected_frame, char *ws, hipStream_t st, const int32_t *frame_window = nullptr,
+                                    int window_stride = 0, bool optional_wildcards = false);
 
 }  // namespace ctc

@@ -41,6 +41,17 @@
 // with the state two positions back taken from the lane's own registers or by one more DPP shift, and the beta sweep the mirror
 // image; a last optional position makes the states before it end states.  The further terms come behind the existing ones in the
 // sums: -inf there leaves the bits as they are.  The row stage counts the optional wildcard as a wildcard; nothing else knows of it.
+// XN (ctc_amd_star_loss_grad / _label_posterior; this file compiled a second time with -DCTC_STAR): a wildcard
+// position i whose position i + 1 is an ordinary label y excludes y: e_w,i(t) = e_w(t) + ln(1 - p_t(y)).  An utterance with such a
+// position (`excl`, the same in every thread) takes the row statistics as (max, sum of the REST): the online update never adds the
+// maximum's own 1 to the sum, so 1 - p is S_rest / (S_rest + 1) where y holds the maximum and (S_rest + 1 - e_y) / (S_rest + 1)
+// elsewhere, and neither form cancels.  The producers gather x[t, y] for the wildcard positions and write log2(1 - p_t(y)) into their
+// ring slots (0 where nothing is excluded); the chain adds the slot to e_w as WIN adds its gate.  The beta sweep (MODE 2) holds that
+// slot when it forms the posteriors: for a wildcard position it saves c_i = Gamma_{t,i} 2^-slot = Gamma_{t,i} / (1 - p_t(y_i)) in
+// Gamma's place and the frame's largest c in the statistics' fourth float (0 otherwise).  The row stage scatters c_i by y_i into a
+// second set of integer bins D(k) in a fixed-point unit taken from that largest c, sums C in the same unit and streams out
+// d_loss * ((1 - (C - D(k))) softmax - bins) (log-probabilities: -(C - D(k))): C - D(k) is an exact integer difference.  An
+// utterance without such a position runs the code of the XN = false kernels: the same bits.
 // A saved row of frame t: per position i the pair (O, C) (classic, AFTER frame t) or S (simplified, BEFORE frame t), then the start
 // state: (2 or 1) * UP + 2 doubles.  After the beta sweep the first 8 bytes of position i hold
 //   classic:    (posterior of O[i] after frame t,  posterior of C[i] = a blank behind label i)
@@ -77,6 +88,17 @@ __device__ __forceinline__ void wl_stat_add4(float &m, float &s, const float4 v)
   s = s * fexp2((m - mn) * LOG2E) +
       ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
   m = mn;
+}
+
+// XN: running (max, sum of exp(x - max) over the REST) of one lane: the element that holds the maximum adds nothing, so the sum of a
+// row with one dominant token keeps its relative precision.  m starts at the lowest finite float, s at 0
+__device__ __forceinline__ void wl_rest_add1(float &m, float &s, const float v) {
+  const float d = fexp2(-fabsf(v - m) * LOG2E);
+  if (v > m) { s = (s + 1.f) * d; m = v; }
+  else s += d;
+}
+__device__ __forceinline__ void wl_rest_add4(float &m, float &s, const float4 v) {
+  wl_rest_add1(m, s, v.x); wl_rest_add1(m, s, v.y); wl_rest_add1(m, s, v.z); wl_rest_add1(m, s, v.w);
 }
 
 // base-2 log(2^a + 2^b [+ 2^c]) of float64 operands that may be -inf (log 0): differences against the maximum, or against 0
@@ -120,10 +142,11 @@ struct WlPostWs : WlWs {
 };
 template <int MODE> using WlArg = std::conditional_t<MODE == 3, WlPostWs, WlWs>;
 
-template <int KIND, int NL, int MODE, bool WIN, bool OPT>
+template <int KIND, int NL, int MODE, bool WIN, bool OPT, bool XN>
 __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, const double w2, float *__restrict__ loss,
                                                                const WlArg<MODE> ws, const int32_t *__restrict__ win, int wstride) {
   static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
+  static_assert(!(WIN && XN), "frame windows and the exclusion of the next label are not combined");
   constexpr bool BACK = MODE >= 2;              // a beta sweep: frames from T_b - 1 down
   constexpr int UP = 64 * NL;
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;  // doubles of a saved row per lane
@@ -194,6 +217,23 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       wl[j] = i < L ? wb[2 * i + 1] : -1;
     }
   }
+  // XN: the token a wildcard position excludes: that of an ordinary position right behind it (the next lane's first for the lane's
+  // last position), -1 where there is none; excl: the utterance has such a position (every wavefront sees all of them)
+  [[maybe_unused]] int nx[NL];
+  [[maybe_unused]] bool excl = false;
+  if constexpr (XN) {
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = lane * NL + j;
+      const int nt = i + 1 < UP ? lab_s[i + 1] : -1;
+      nx[j] = (((wild >> j) & 1u) && nt >= 0) ? nt : -1;
+      any = any || nx[j] >= 0;
+    }
+    // INVARIANT shared with wild_grad_row_kernel, which decides the same from the labels themselves: lab_s is -1 past the label's
+    // length and for a label that does not emit, so `lab_s[i + 1] >= 0` here is `i + 1 < L && emits(label i + 1)` there
+    excl = __builtin_amdgcn_ballot_w64(any) != 0ull;
+  }
 
   const int esz = dt == 0 ? 4 : 2;
   const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
@@ -258,8 +298,14 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       for (int g = 0; g < G; ++g) {
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          const float v = row_load1(row[g], lab[j] >= 0 ? lab[j] : blank, dt);
-          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+          if constexpr (XN) {  // a wildcard position gathers the token it excludes
+            const int tk = lab[j] >= 0 ? lab[j] : nx[j];
+            const float v = row_load1(row[g], tk >= 0 ? tk : blank, dt);
+            e[g][j] = tk >= 0 ? v : -__builtin_inff();
+          } else {
+            const float v = row_load1(row[g], lab[j] >= 0 ? lab[j] : blank, dt);
+            e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+          }
         }
         eb[g] = row_load1(row[g], blank, dt);
       }
@@ -272,19 +318,40 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
 #pragma unroll
         for (int g = 0; g < G; ++g) v[g] = vec ? wl_row_load4(row[g], k, dt) : wl_row_load4_elem(row[g], k, V, dt);
 #pragma unroll
-        for (int g = 0; g < G; ++g) wl_stat_add4(m[g], s[g], v[g]);
+        for (int g = 0; g < G; ++g) {
+          if (XN && excl) wl_rest_add4(m[g], s[g], v[g]);
+          else wl_stat_add4(m[g], s[g], v[g]);
+        }
       }
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         float M = wave_max(m[g]);
-        const float S = wave_sum(s[g] * fexp2((m[g] - M) * LOG2E));
-        float l2s = flog2(S);
-        if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+        float l2s;
+        [[maybe_unused]] float Sr = 0.f, Mr = 0.f;  // XN: the sum of the rest, the row's own maximum
+        if (XN && excl) {
+          // the lowest lane at the maximum keeps its 1 out; every other lane's own maximum is part of the rest
+          const unsigned long long at = __builtin_amdgcn_ballot_w64(m[g] == M);
+          const bool own = lane == (int)__builtin_ctzll(at);
+          Sr = wave_sum(own ? s[g] : (s[g] + 1.f) * fexp2((m[g] - M) * LOG2E));
+          Mr = M;
+          l2s = flog2(Sr + 1.f);
+          if (!(M > -3.402823466e38f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf
+        } else {
+          const float S = wave_sum(s[g] * fexp2((m[g] - M) * LOG2E));
+          l2s = flog2(S);
+          if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+        }
         if (q0 + f0 + g < Tb) {
           float *const r = rb + (f0 + g) * RS;
 #pragma unroll
           for (int j = 0; j < NL; ++j) {
             float v = e[g][j];
+            if constexpr (XN) {  // log2(1 - p_t(y)) for a wildcard position that excludes y, 0 for one that excludes nothing
+              if (excl && ((wild >> j) & 1u)) {
+                const float num = v == Mr ? Sr : (Sr + 1.f) - fexp2((v - Mr) * LOG2E);
+                v = nx[j] >= 0 ? flog2(num) - l2s : 0.f;
+              }
+            }
             if constexpr (WIN) {
               const int t = real_t(q0 + f0 + g);
               if ((wild >> j) & 1u) v = 0.f;  // the gate of e_w
@@ -335,7 +402,8 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
       const Frame fr = frame_of(rr);
       const double eb = fr.eb;
-      auto ewj = [&](int j) { return WIN ? fr.ew + (double)e[j] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      // (WIN: the ring slot of a wildcard is its gate, 0 or -inf; XN, in an utterance that excludes: log2(1 - p_t(y)))
+      auto ewj = [&](int j) { return (WIN || (XN && excl)) ? fr.ew + (double)e[j] : fr.ew; };
       auto em = [&](int j) { return ((wild >> j) & 1u) ? ewj(j) : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = MODE == 1 ? myrows + (size_t)(t0 + f) * SRD : nullptr;
       if (MODE == 1 && KIND == 1) {  // the state BEFORE the frame
@@ -433,7 +501,8 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
       for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
       const Frame fr = frame_of(rr);
       const double eb = fr.eb;
-      auto ewj = [&](int j) { return WIN ? fr.ew + (double)e[j] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      // (WIN: the ring slot of a wildcard is its gate, 0 or -inf; XN, in an utterance that excludes: log2(1 - p_t(y)))
+      auto ewj = [&](int j) { return (WIN || (XN && excl)) ? fr.ew + (double)e[j] : fr.ew; };
       auto em = [&](int j) { return ((wild >> j) & 1u) ? ewj(j) : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
       double A[NS], Acs;
       if constexpr (PF) {
@@ -456,9 +525,24 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
           }
           put_post(t, pl, pb);
         } else {
+          [[maybe_unused]] float cm = 0.f;  // XN: the frame's largest c
 #pragma unroll
-          for (int j = 0; j < NL; ++j)
-            *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(post(A[2 * j] + O[j]), post(A[2 * j + 1] + C[j]));
+          for (int j = 0; j < NL; ++j) {
+            float g = post(A[2 * j] + O[j]);
+            if constexpr (XN) {  // a wildcard's Gamma becomes c = Gamma / (1 - p): the slot is log2(1 - p)
+              if (excl && ((wild >> j) & 1u)) {
+                g = g > 0.f ? g * fexp2(-e[j]) : 0.f;
+                cm = fmaxf(cm, g);
+              }
+            }
+            *reinterpret_cast<float2 *>(r + lane * NS + 2 * j) = make_float2(g, post(A[2 * j + 1] + C[j]));
+          }
+          if constexpr (XN) {
+            if (excl) {
+              cm = wave_max(cm);
+              if (lane == 0) ws.stat[((size_t)b * p.T + t) * 4 + 3] = cm;
+            }
+          }
           if (lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
         }
         // beta back over frame t: x = what entering O[i] with this frame is worth
@@ -497,6 +581,7 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
         [[maybe_unused]] double ap00 = NINF;  // OPT: alpha two positions before the lane's first
         if constexpr (OPT) ap00 = from_prev_lane(NL == 1 ? ap0 : A[NL > 1 ? NL - 2 : 0], NINF);
         [[maybe_unused]] float pl[NL], pb = 0.f;
+        [[maybe_unused]] float cm = 0.f;  // XN, MODE 2: the frame's largest c
         if (MODE == 3 && lane == 0) pb = post(Acs + eb + cs);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
@@ -507,12 +592,26 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
           }
           const bool wj = ((wild >> j) & 1u) != 0;
           const double h = wj ? ewj(j) : eb;
-          const float pe = post(ap + em(j) + C[j]), ps = post(A[j] + h + C[j]);
+          float pe = post(ap + em(j) + C[j]), ps = post(A[j] + h + C[j]);
+          if constexpr (XN && MODE == 2) {  // a wildcard's two shares of Gamma become those of c = Gamma / (1 - p)
+            if (excl && wj) {
+              const float f = fexp2(-e[j]);
+              pe = pe > 0.f ? pe * f : 0.f;
+              ps = ps > 0.f ? ps * f : 0.f;
+              cm = fmaxf(cm, pe + ps);
+            }
+          }
           if constexpr (MODE == 3) {  // a stay emits the wildcard behind a wildcard, the blank otherwise
             pl[j] = wj ? pe + ps : pe;
             pb += wj ? 0.f : ps;
           } else {
             *reinterpret_cast<float2 *>(r + lane * NS + j) = make_float2(pe, ps);
+          }
+        }
+        if constexpr (XN && MODE == 2) {
+          if (excl) {
+            cm = wave_max(cm);
+            if (lane == 0) ws.stat[((size_t)b * p.T + t) * 4 + 3] = cm;
           }
         }
         if constexpr (MODE == 3) put_post(t, pl, pb);
@@ -592,15 +691,17 @@ __global__ __launch_bounds__(WL_THREADS) void wild_loss_kernel(const Problem p, 
 constexpr int WLG_WAVES = 4;
 constexpr int WLG_CH = 1024;  // columns per pass
 constexpr int WLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units of 2^-40, so |bin| < U 2^40
+constexpr int WLG_CH_XN = WLG_CH / 2;  // XN: two sets of bins per wavefront in the same LDS, so passes of half as many columns
 
-template <int KIND, bool OPT>
+template <int KIND, bool OPT, bool XN>
 __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Problem p, const int UP, const float *__restrict__ d_loss,
                                                                        const WlWs ws, void *__restrict__ grad) {
   constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
-  __shared__ unsigned long long bins_all[WLG_WAVES][WLG_CH];
+  constexpr int WAVES = WLG_WAVES;
+  __shared__ unsigned long long bins_all[WAVES][WLG_CH];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long row = (long)blockIdx.x * WLG_WAVES + wv;
+  const long row = (long)blockIdx.x * WAVES + wv;
   if (row >= (long)p.B * p.T) return;  // (wavefront-uniform; nothing below synchronises beyond the wavefront)
   unsigned long long *const bins = bins_all[wv];
   const int b = (int)(row / p.T), t = (int)(row % p.T);
@@ -655,6 +756,86 @@ __global__ __launch_bounds__(64 * WLG_WAVES) void wild_grad_row_kernel(const Pro
   const int L = label_count(p, b);  // (feasible: L <= U <= UP)
   const char *const r = reinterpret_cast<const char *>(ws.rows) + ((size_t)b * p.T + t) * ((size_t)wl_row_doubles(KIND, UP) * 8);
   const int32_t *const lab = label_row(p, b);
+
+  if constexpr (XN) {
+    // the beta sweep left c_i = Gamma_{t,i} / (1 - p_t(y_i)) in Gamma's place (Gamma itself where nothing is excluded) and the frame's
+    // largest c in the statistics' fourth float; y_i: the token position i excludes (-1: none)
+    __shared__ unsigned long long csum_all[WAVES];
+    constexpr int CH = WLG_CH_XN;  // gamma's bins in the first half of the wavefront's bins, D's in the second
+    auto c_of = [&](int i, const float2 pq, int &y) {
+      const int nt = i + 1 < L ? label_at(p, lab, i + 1) : -1;
+      y = emits(p, nt) ? nt : -1;
+      return KIND == 1 ? pq.x + pq.y : pq.x;
+    };
+    auto wild_at = [&](int tok) { return tok == WILD_LOSS_WILDCARD || (OPT && tok == WILD_LOSS_OPTIONAL); };
+    // INVARIANT shared with wild_loss_kernel's `excl`: a wildcard position i with i + 1 < L and emits(label i + 1).  Only then did
+    // the sweeps take the other statistics and leave c and its maximum; otherwise the fourth float is 0 and is not read
+    bool any = false;
+    for (int i = lane; i + 1 < L; i += 64) any = any || (wild_at(label_at(p, lab, i)) && emits(p, label_at(p, lab, i + 1)));
+    if (__builtin_amdgcn_ballot_w64(any) != 0ull) {  // (wavefront-uniform; an utterance that excludes nothing: the code below)
+      if (dl == 0.f) {  // a weight of zero: +0 throughout
+        for (int k = lane * 4; k < V; k += 256) gput4(k, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+      }
+      // c is not bounded by 1: the unit of its bins comes from the frame.  cmax < 2^ex, so c 2^sh < 2^50 and 1024 of them < 2^60
+      int ex;
+      (void)__builtin_frexpf(sv.w, &ex);
+      const int sh = 50 - ex;
+      unsigned long long *const dbins = bins + CH;
+      float blk = 0.f;
+      unsigned long long ctot = 0ull;
+      for (int c0 = 0; c0 < V; c0 += CH) {
+#pragma unroll
+        for (int q = 0; q < WLG_CH / 64; ++q) bins[lane + 64 * q] = 0ull;  // (both halves)
+        if (c0 == 0 && lane == 0) csum_all[wv] = 0ull;
+        wave_lds_fence();
+        unsigned long long cl = 0ull;
+        for (int i = lane; i < L; i += 64) {
+          const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+          const int tok = label_at(p, lab, i);
+          const bool w = wild_at(tok);
+          const unsigned rel = (unsigned)(tok - c0);
+          if (!w && emits(p, tok) && rel < (unsigned)CH)
+            atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, WLG_FIX)));
+          if (w) {
+            int y;
+            const unsigned long long q = (unsigned long long)__float2ll_rn(__builtin_ldexpf(c_of(i, pq, y), sh));
+            cl += q;
+            if (y >= 0 && (unsigned)(y - c0) < (unsigned)CH) atomicAdd(&dbins[y - c0], q);
+          }
+          if (c0 == 0 && !(KIND == 1 && w)) blk += pq.y;
+        }
+        if (c0 == 0) {
+          if (lane == 0) blk += *reinterpret_cast<const float *>(r + (size_t)UP * SLOT);
+          blk = wave_sum(blk);
+          atomicAdd(&csum_all[wv], cl);
+        }
+        wave_lds_fence();
+        if (c0 == 0) ctot = csum_all[wv];
+#pragma unroll
+        for (int q = 0; q < CH / 256; ++q) {
+          const int k = c0 + lane * 4 + 256 * q;
+          if (k < V) {
+            const float4 xv = xvec ? wl_row_load4(x, k, xdt) : wl_row_load4_elem(x, k, V, xdt);
+            float o[4];
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+              const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[k - c0 + cc]), -WLG_FIX) + (k + cc == blank ? blk : 0.f);
+              // C - D(k): an integer difference, exact
+              const float cd = __builtin_ldexpf(__ll2float_rn((long long)(ctot - dbins[k - c0 + cc])), -sh);
+              const float c = p.wrt == 0 ? 1.f - cd : -cd;
+              const float sm = c == 0.f ? 0.f : c * fexp2((xs[cc] - mx) * LOG2E - l2s);
+              o[cc] = dl * (sm - bin);
+            }
+            gput4(k, make_float4(o[0], o[1], o[2], o[3]));
+          }
+        }
+        wave_lds_fence();
+      }
+      return;
+    }
+  }
 
   float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
   for (int c0 = 0; c0 < V; c0 += WLG_CH) {
@@ -739,9 +920,9 @@ __global__ __launch_bounds__(64 * LS_SLICES) void label_stat_kernel(const Proble
   expected_frame[(size_t)b * p.U + i] = d > 0.0 ? (float)(m / d) : -1.f;
 }
 
-template <int KIND, int NL, int MODE, bool WIN, bool OPT>
+template <int KIND, int NL, int MODE, bool WIN, bool OPT, bool XN>
 hipError_t launch_wild_loss(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const int32_t *win, int wstride, hipStream_t st) {
-  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE, WIN, OPT>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws, win, wstride);
+  hipLaunchKernelGGL((wild_loss_kernel<KIND, NL, MODE, WIN, OPT, XN>), dim3(p.B), dim3(WL_THREADS), 0, st, p, w2, loss, ws, win, wstride);
   return hipGetLastError();
 }
 
@@ -752,16 +933,24 @@ struct WlWindow {
   bool optional;
 };
 
-#define CTC_WILD_LOSS_ROW(KIND, WIN, OPT)                                                                                             \
-  {launch_wild_loss<KIND, 1, MODE, WIN, OPT>, launch_wild_loss<KIND, 2, MODE, WIN, OPT>, launch_wild_loss<KIND, 4, MODE, WIN, OPT>, \
-   launch_wild_loss<KIND, 8, MODE, WIN, OPT>, launch_wild_loss<KIND, 16, MODE, WIN, OPT>}
+#define CTC_WILD_LOSS_ROW(KIND, WIN, OPT, XN)                                                                                    \
+  {launch_wild_loss<KIND, 1, MODE, WIN, OPT, XN>, launch_wild_loss<KIND, 2, MODE, WIN, OPT, XN>,                                 \
+   launch_wild_loss<KIND, 4, MODE, WIN, OPT, XN>, launch_wild_loss<KIND, 8, MODE, WIN, OPT, XN>,                                 \
+   launch_wild_loss<KIND, 16, MODE, WIN, OPT, XN>}
 
 template <int MODE>
 hipError_t run_wild_mode(const Problem &p, double w2, float *loss, const WlArg<MODE> &ws, const WlWindow &fw, hipStream_t st) {
   typedef hipError_t Launch(const Problem &, double, float *, const WlArg<MODE> &, const int32_t *, int, hipStream_t);
-  static Launch *const table[3][2][5] = {{CTC_WILD_LOSS_ROW(0, false, false), CTC_WILD_LOSS_ROW(1, false, false)},
-                                         {CTC_WILD_LOSS_ROW(0, true, false), CTC_WILD_LOSS_ROW(1, true, false)},
-                                         {CTC_WILD_LOSS_ROW(0, false, true), CTC_WILD_LOSS_ROW(1, false, true)}};
+#ifdef CTC_STAR  // this unit holds the XN kernels alone: no window, both values of `optional`
+  static Launch *const table[3][2][5] = {{CTC_WILD_LOSS_ROW(0, false, false, true), CTC_WILD_LOSS_ROW(1, false, false, true)},
+                                         {{}, {}},
+                                         {CTC_WILD_LOSS_ROW(0, false, true, true), CTC_WILD_LOSS_ROW(1, false, true, true)}};
+  if (fw.ptr) return hipErrorInvalidValue;
+#else
+  static Launch *const table[3][2][5] = {{CTC_WILD_LOSS_ROW(0, false, false, false), CTC_WILD_LOSS_ROW(1, false, false, false)},
+                                         {CTC_WILD_LOSS_ROW(0, true, false, false), CTC_WILD_LOSS_ROW(1, true, false, false)},
+                                         {CTC_WILD_LOSS_ROW(0, false, true, false), CTC_WILD_LOSS_ROW(1, false, true, false)}};
+#endif
   const int NL = nl_for(p.U);
   const int lg = NL == 1 ? 0 : NL == 2 ? 1 : NL == 4 ? 2 : NL == 8 ? 3 : NL == 16 ? 4 : -1;
   if (lg < 0 || p.kind < 0 || p.kind > 1 || (fw.ptr && fw.optional)) return hipErrorInvalidValue;
@@ -779,15 +968,24 @@ WlWs wl_regions(const Problem &p, char *wsp) {
 
 }  // namespace
 
+#ifdef CTC_STAR
+constexpr bool WL_XN = true;
+#define CTC_WL_NAME(base, star) star
+#else
+constexpr bool WL_XN = false;
+#define CTC_WL_NAME(base, star) base
 // saved rows, then the row statistics, then log2 Z: each region rounded up to 256 bytes (include/ctc_amd.h has the formula)
 size_t wild_loss_workspace_bytes(int kind, int B, int T, int U, bool want_grad) {
   if (!want_grad) return 0;
   const size_t rows = (size_t)B * T * wl_row_doubles(kind, 64 * nl_for(U)) * 8;
   return wl_al(rows) + wl_al((size_t)B * T * 16) + wl_al((size_t)B * 8);
 }
+#endif
 
-hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
-                         hipStream_t st, const int32_t *frame_window, int window_stride, bool optional_wildcards) {
+// (CTC_STAR: run_star_loss, the XN kernels on the same workspace)
+hipError_t CTC_WL_NAME(run_wild_loss, run_star_loss)(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
+                                                     char *wsp, hipStream_t st, const int32_t *frame_window, int window_stride,
+                                                     bool optional_wildcards) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
   const WlWindow fw{frame_window, window_stride, optional_wildcards};
   if (!grad) return run_wild_mode<0>(p, w2, loss, WlWs{nullptr, nullptr, nullptr}, fw, st);
@@ -796,22 +994,25 @@ hipError_t run_wild_loss(const Problem &p, float wildcard_log_weight, const floa
   if (hipError_t e = run_wild_mode<1>(p, w2, loss, ws, fw, st)) return e;
   if (p.T == 0) return hipSuccess;  // no rows
   if (hipError_t e = run_wild_mode<2>(p, w2, loss, ws, fw, st)) return e;
-  const unsigned blocks = (unsigned)(((long)p.B * p.T + WLG_WAVES - 1) / WLG_WAVES);
-  const dim3 grid(blocks), block(64 * WLG_WAVES);
+  constexpr int WAVES = WLG_WAVES;
+  const unsigned blocks = (unsigned)(((long)p.B * p.T + WAVES - 1) / WAVES);
+  const dim3 grid(blocks), block(64 * WAVES);
   if (optional_wildcards) {
-    if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0, true>), grid, block, 0, st, p, UP, d_loss, ws, grad);
-    else hipLaunchKernelGGL((wild_grad_row_kernel<1, true>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+    if (p.kind == 0) hipLaunchKernelGGL((wild_grad_row_kernel<0, true, WL_XN>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+    else hipLaunchKernelGGL((wild_grad_row_kernel<1, true, WL_XN>), grid, block, 0, st, p, UP, d_loss, ws, grad);
   } else if (p.kind == 0) {
-    hipLaunchKernelGGL((wild_grad_row_kernel<0, false>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+    hipLaunchKernelGGL((wild_grad_row_kernel<0, false, WL_XN>), grid, block, 0, st, p, UP, d_loss, ws, grad);
   } else {
-    hipLaunchKernelGGL((wild_grad_row_kernel<1, false>), grid, block, 0, st, p, UP, d_loss, ws, grad);
+    hipLaunchKernelGGL((wild_grad_row_kernel<1, false, WL_XN>), grid, block, 0, st, p, UP, d_loss, ws, grad);
   }
   return hipGetLastError();
 }
 
-hipError_t run_label_posterior(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
-                               float *duration, float *expected_frame, char *wsp, hipStream_t st, const int32_t *frame_window,
-                               int window_stride, bool optional_wildcards) {
+hipError_t CTC_WL_NAME(run_label_posterior, run_star_label_posterior)(const Problem &p, float wildcard_log_weight, float *loss,
+                                                                      float *label_posterior, float *blank_posterior, float *duration,
+                                                                      float *expected_frame, char *wsp, hipStream_t st,
+                                                                      const int32_t *frame_window, int window_stride,
+                                                                      bool optional_wildcards) {
   const double w2 = (double)wildcard_log_weight * LOG2E_D;
   const WlWindow fw{frame_window, window_stride, optional_wildcards};
   WlPostWs ws;
