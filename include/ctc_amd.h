@@ -1427,8 +1427,8 @@ int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt,
  * Short utterances.  An utterance of L positions needs at least L / 2 frames, not L: the tiles that run are chosen by that bound
  * (position i is unreachable before frame i / 2), and what is infeasible beyond it falls out of the lattice.
  * Not included: the long-form alignment, the N-best calls and frame windows together with optional wildcards (DESIGN.md
- * section 7).  Star temporal classification's exclusion of the following label: the short-form entry points at the end of this
- * header.
+ * section 7).  Star temporal classification's exclusion of the following label: the entry points at the end of this header,
+ * ctc_amd_long_star_* for these three.
  */
 int ctc_amd_long_optional_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad,
                                                         size_t *out_bytes /*host*/);
@@ -1470,7 +1470,8 @@ int ctc_amd_long_optional_wildcard_label_posterior(int kind, int wrt,
  * Each takes its counterpart's arguments plus `int optional_wildcards` behind blank_index: 0 selects the first counterpart (-3 is a
  * bad label), anything else the second (CTC_AMD_OPTIONAL_WILDCARD is accepted, with every rule above, the classic alignment's
  * U <= CTC_AMD_OPTIONAL_CLASSIC_MAX_U included).  Formats, strides, outputs, limits, validation order and messages, launches and
- * capture are the counterpart's; there is no frame-window, long-form or N-best variant.
+ * capture are the counterpart's; the long-form loss, gradient and label posteriors follow below; there is no frame-window,
+ * long-form alignment or N-best variant.
  * Which token is excluded.  A wildcard position i (either kind) whose position i + 1 exists (i + 1 < label_length) and is an
  * ordinary, valid label y_i (in [0, V), not the blank) excludes y_i on every one of its frames.  A wildcard that is last, or is
  * followed by another wildcard of either kind, excludes nothing.  The wildcard's frames are: classic lattice, its open-state
@@ -1523,6 +1524,53 @@ int ctc_amd_star_best_path(int kind, int wrt,
                            float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
                            int32_t *first_frame /* may be NULL */, int32_t *last_frame /* may be NULL */,
                            float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The exclusion above 1024 labels: the long-form loss, gradient and label posteriors (added under ABI v6: three new entry points
+ * with their size queries, nothing existing changed).  The definition above, word for word, for label_length <=
+ * CTC_AMD_LONG_MAX_U:
+ *   ctc_amd_long_star_loss_grad         counterpart: ctc_amd_long_wildcard_loss_grad / ctc_amd_long_optional_wildcard_loss_grad
+ *   ctc_amd_long_star_loss_grad_ckpt    counterpart: ctc_amd_long_wildcard_loss_grad_ckpt / ..._optional_wildcard_loss_grad_ckpt
+ *   ctc_amd_long_star_label_posterior   counterpart: ctc_amd_long_label_posterior / ..._optional_wildcard_label_posterior
+ * Each takes its counterpart's arguments plus `int optional_wildcards` behind blank_index (0: the first counterpart, anything else:
+ * the second), and is that counterpart in formats, strides, outputs, limits, validation order and messages, launches, capture and
+ * determinism: the same bits on every run, for every frames_per_tile and batch composition, from both workspaces.  The wildcard at
+ * position k * 1024 + 1023 excludes label[(k + 1) * 1024]: a label-block boundary changes nothing.  An utterance in which no
+ * wildcard has an ordinary successor returns the counterpart's bits for every output; at one label block the loss, gradient,
+ * label_posterior, duration and expected_frame are the bits of ctc_amd_star_loss_grad / ctc_amd_star_label_posterior.
+ * Workspace.  The counterpart's, byte for byte: the three size queries take optional_wildcards behind kind and return the
+ * counterpart's size.  (Of an excluding utterance the fourth float of the per-frame row statistics holds the sum of the rest, and
+ * the padding double of a saved row the largest c of its frame and label block.)  The workspace may hold anything on entry.
+ * Not included: the long-form alignment, the N-best calls and frame windows together with the exclusion.
+ */
+int ctc_amd_long_star_loss_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                           int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_long_star_loss_grad(int kind, int wrt,
+                                const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                const int32_t *labels, int label_stride,
+                                const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                                float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_star_loss_ckpt_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_long_star_loss_grad_ckpt(int kind, int wrt,
+                                     const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                     const int32_t *labels, int label_stride,
+                                     const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                                     float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                     const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                     int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_star_label_posterior_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                      size_t *out_bytes /*host*/);
+int ctc_amd_long_star_label_posterior(int kind, int wrt,
+                                      const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                      const int32_t *labels, int label_stride,
+                                      const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                                      float wildcard_log_weight, int B, int T, int V, int U, int frames_per_tile,
+                                      float *loss, float *label_posterior /* may be NULL */, float *blank_posterior,
+                                      float *duration, float *expected_frame, float *peak_posterior, int32_t *peak_frame,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

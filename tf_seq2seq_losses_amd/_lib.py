@@ -169,6 +169,18 @@ SIGNATURES = {
     "ctc_amd_long_optional_wildcard_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +
                                                        [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                         _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    # ... and the three long-form ones of star temporal classification: those arguments with optional_wildcards behind blank_index
+    # (size queries: behind kind)
+    "ctc_amd_long_star_loss_workspace_bytes": (_c_int, [_c_int] * 8 + [ctypes.POINTER(_c_size_t)]),  # kind, optional_wildcards, B, T, V, U, frames_per_tile, want_grad
+    "ctc_amd_long_star_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                    [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_star_loss_ckpt_workspace_bytes": (_c_int, [_c_int] * 8 + [ctypes.POINTER(_c_size_t)]),
+    "ctc_amd_long_star_loss_grad_ckpt": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                         [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_star_label_posterior_workspace_bytes": (_c_int, [_c_int] * 7 + [ctypes.POINTER(_c_size_t)]),  # kind, optional_wildcards, B, T, V, U, frames_per_tile
+    "ctc_amd_long_star_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
+                                          [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
@@ -370,6 +382,22 @@ def long_optional_wildcard_label_posterior_workspace_bytes(kind: int, B: int, T:
     check(load().ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
           "ctc_amd_long_optional_wildcard_label_posterior_workspace_bytes")
     return int(out.value)
+
+
+def long_star_loss_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0, want_grad: bool = True,
+                                   optional_wildcards: bool = False, checkpoint: bool = False) -> int:
+    out = _c_size_t(0)
+    name = "ctc_amd_long_star_loss_ckpt_workspace_bytes" if checkpoint else "ctc_amd_long_star_loss_workspace_bytes"
+    check(getattr(load(), name)(kind, int(optional_wildcards), B, T, V, U, frames_per_tile, int(want_grad), ctypes.byref(out)), name)
+    return out.value
+
+
+def long_star_label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0,
+                                              optional_wildcards: bool = False) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_star_label_posterior_workspace_bytes(kind, int(optional_wildcards), B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_star_label_posterior_workspace_bytes")
+    return out.value
 
 
 def long_label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0) -> int:

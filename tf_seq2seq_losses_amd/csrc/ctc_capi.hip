@@ -413,9 +413,10 @@ static_assert(ctc::LONG_LOSS_OPTIONAL == CTC_AMD_OPTIONAL_WILDCARD, "the tiled l
 // ctc_amd_long_wildcard_loss_grad and its checkpointed twin, which differ in the plan function alone (long_loss_ckpt_plan refuses
 // what long_loss_plan refuses, and is long_loss_plan without a gradient).  The window is looked at behind every check of the unwindowed
 // call but the workspace's.  optional_wildcards (ctc_amd_long_optional_wildcard_loss_grad / _grad_ckpt, which have no window): the
-// same checks, the plan with the two further column buffers.
+// same checks, the plan with the two further column buffers.  star (ctc_amd_long_star_loss_grad / _grad_ckpt, no window either): the
+// same checks and the same plan, the kernels in which a wildcard excludes the label that follows it.
 using LongLossPlanFn = bool(int, int, int, int, int, int, ctc::LongLossPlan *, int);
-int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, bool optional_wildcards, const Common &c, const Format &f,
+int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, bool star, bool optional_wildcards, const Common &c, const Format &f,
                                  const int32_t *frame_window, int window_stride, float wildcard_log_weight, int frames_per_tile, const float *d_loss, float *loss, void *grad,
                                  void *workspace, size_t workspace_bytes, void *stream) {
   const Prelude pre = prelude(c, f, grad != nullptr, CTC_AMD_LONG_MAX_U);
@@ -426,8 +427,9 @@ int long_wildcard_loss_grad_impl(LongLossPlanFn *plan_fn, bool optional_wildcard
     return bad_tiling(frames_per_tile, c.B, c.T, c.U);
   if (int rc = check_window(frame_window, window_stride, c.U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_loss_long(pre.p, plan, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
-                             static_cast<hipStream_t>(stream), frame_window, window_stride, optional_wildcards),
+  CTC_TRY((star ? ctc::run_star_loss_long : ctc::run_loss_long)(pre.p, plan, wildcard_log_weight, d_loss, loss, grad,
+                                                                static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
+                                                                frame_window, window_stride, optional_wildcards),
           "long wildcard loss launch");
   return CTC_AMD_OK;
 }
@@ -1162,7 +1164,7 @@ int ctc_amd_long_optional_wildcard_loss_grad(int kind, int wrt, const void *logi
                                              int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss, grad,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, false, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss, grad,
                                       workspace, workspace_bytes, stream);
 }
 
@@ -1181,8 +1183,47 @@ int ctc_amd_long_optional_wildcard_loss_grad_ckpt(int kind, int wrt, const void 
                                                   int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, false, true, c, f, nullptr, 0, wildcard_log_weight, frames_per_tile, d_loss, loss,
                                       grad, workspace, workspace_bytes, stream);
+}
+
+// The three long-form entry points of star temporal classification's exclusion are the counterparts' bodies
+// with `star` set: the same checks in the same order with the same words, on the counterparts' plans (nothing is added to them).
+int ctc_amd_long_star_loss_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile, int want_grad,
+                                           size_t *out_bytes) {
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan, optional_wildcards ? 1 : 0);
+  });
+}
+
+int ctc_amd_long_star_loss_grad(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                int blank_index, int optional_wildcards, float wildcard_log_weight, int B, int T, int V, int U,
+                                int frames_per_tile, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, true, optional_wildcards != 0, c, f, nullptr, 0, wildcard_log_weight,
+                                      frames_per_tile, d_loss, loss, grad, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_long_star_loss_ckpt_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                int want_grad, size_t *out_bytes) {
+  return long_query<ctc::LongLossPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongLossPlan *plan) {
+    return ctc::long_loss_ckpt_plan(kind, B, T, U, frames_per_tile, want_grad != 0, plan, optional_wildcards ? 1 : 0);
+  });
+}
+
+int ctc_amd_long_star_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                     int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                     const int32_t *logit_length, int blank_index, int optional_wildcards, float wildcard_log_weight,
+                                     int B, int T, int V, int U, int frames_per_tile, const float *d_loss, float *loss, void *grad,
+                                     int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+  const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
+  const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, true, optional_wildcards != 0, c, f, nullptr, 0, wildcard_log_weight,
+                                      frames_per_tile, d_loss, loss, grad, workspace, workspace_bytes, stream);
 }
 
 // The three long-form windowed entry points are their counterparts with a frame window; the counterparts are they with none.
@@ -1194,7 +1235,7 @@ int ctc_amd_long_windowed_loss_grad(int kind, int wrt, const void *logits, int l
                                     void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile, d_loss,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_plan, false, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile, d_loss,
                                       loss, grad, workspace, workspace_bytes, stream);
 }
 
@@ -1224,7 +1265,7 @@ int ctc_amd_long_windowed_loss_grad_ckpt(int kind, int wrt, const void *logits, 
                                          void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Format f{logits_dtype, logits_stride_b, logits_stride_t, grad_dtype, grad_stride_b, grad_stride_t};
-  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile,
+  return long_wildcard_loss_grad_impl(ctc::long_loss_ckpt_plan, false, false, c, f, frame_window, window_stride, wildcard_log_weight, frames_per_tile,
                                       d_loss, loss, grad, workspace, workspace_bytes, stream);
 }
 
@@ -1328,8 +1369,9 @@ int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, 
 
 // It begins like ctc_amd_long_wildcard_loss_grad with a gradient, whose messages it gives (the row stage always runs); its own
 // outputs come behind that.
-// One body for ctc_amd_long_windowed_label_posterior and ctc_amd_long_optional_wildcard_label_posterior (which has no window).
-static int long_label_posterior_call(bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype,
+// One body for ctc_amd_long_windowed_label_posterior, ctc_amd_long_optional_wildcard_label_posterior and
+// ctc_amd_long_star_label_posterior (which have no window).
+static int long_label_posterior_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype,
                                      int64_t logits_stride_b, int64_t logits_stride_t, const int32_t *labels, int label_stride,
                                      const int32_t *label_length, const int32_t *logit_length, int blank_index,
                                      const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T, int V, int U,
@@ -1348,9 +1390,9 @@ static int long_label_posterior_call(bool optional_wildcards, int kind, int wrt,
   if (!ctc::long_post_plan(kind, B, T, U, frames_per_tile, &plan, optional_wildcards ? 1 : 0)) return bad_tiling(frames_per_tile, B, T, U);
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_long_label_posterior(pre.p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
-                                        peak_posterior, peak_frame, static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
-                                        frame_window, window_stride, optional_wildcards),
+  CTC_TRY((star ? ctc::run_star_long_label_posterior : ctc::run_long_label_posterior)(
+              pre.p, plan, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior, peak_frame,
+              static_cast<char *>(workspace), static_cast<hipStream_t>(stream), frame_window, window_stride, optional_wildcards),
           "long label posterior launch");
   return CTC_AMD_OK;
 }
@@ -1362,7 +1404,7 @@ int ctc_amd_long_windowed_label_posterior(int kind, int wrt, const void *logits,
                                           float *label_posterior, float *blank_posterior, float *duration, float *expected_frame,
                                           float *peak_posterior, int32_t *peak_frame, void *workspace, size_t workspace_bytes,
                                           void *stream) {
-  return long_label_posterior_call(false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return long_label_posterior_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                    label_length, logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U,
                                    frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior,
                                    peak_frame, workspace, workspace_bytes, stream);
@@ -1381,10 +1423,29 @@ int ctc_amd_long_optional_wildcard_label_posterior(int kind, int wrt, const void
                                                    float *loss, float *label_posterior, float *blank_posterior, float *duration,
                                                    float *expected_frame, float *peak_posterior, int32_t *peak_frame, void *workspace,
                                                    size_t workspace_bytes, void *stream) {
-  return long_label_posterior_call(true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return long_label_posterior_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                    label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, frames_per_tile,
                                    loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior, peak_frame,
                                    workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_long_star_label_posterior_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                      size_t *out_bytes) {
+  return long_query<ctc::LongPostPlan>(kind, B, T, V, U, frames_per_tile, out_bytes, [=](ctc::LongPostPlan *plan) {
+    return ctc::long_post_plan(kind, B, T, U, frames_per_tile, plan, optional_wildcards ? 1 : 0);
+  });
+}
+
+int ctc_amd_long_star_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                      int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                      const int32_t *logit_length, int blank_index, int optional_wildcards, float wildcard_log_weight,
+                                      int B, int T, int V, int U, int frames_per_tile, float *loss, float *label_posterior,
+                                      float *blank_posterior, float *duration, float *expected_frame, float *peak_posterior,
+                                      int32_t *peak_frame, void *workspace, size_t workspace_bytes, void *stream) {
+  return long_label_posterior_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+                                   label_stride, label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U,
+                                   frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame, peak_posterior,
+                                   peak_frame, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_label_posterior(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,

@@ -33,4 +33,16 @@ hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, flo
                                     int *peak_frame, char *ws, hipStream_t st, const int32_t *frame_window = nullptr,
                                     int window_stride = 0, bool optional_wildcards = false);
 
+// ctc_amd_long_star_loss_grad / _grad_ckpt / _label_posterior: the two calls above in which a wildcard
+// position of either kind excludes the ordinary label that follows it (ctc_loss_long.hip compiled with -DCTC_STAR).  The same plans
+// and workspaces, offset for offset: the sum of the rest rides in the row statistics' fourth float, the largest c of a frame in the
+// saved row's spare double.  No frame window (hipErrorInvalidValue)
+hipError_t run_star_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss,
+                              void *grad, char *ws, hipStream_t st, const int32_t *frame_window = nullptr, int window_stride = 0,
+                              bool optional_wildcards = false);
+hipError_t run_star_long_label_posterior(const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss,
+                                         float *label_posterior, float *blank_posterior, float *duration, float *expected_frame,
+                                         float *peak_posterior, int *peak_frame, char *ws, hipStream_t st,
+                                         const int32_t *frame_window = nullptr, int window_stride = 0, bool optional_wildcards = false);
+
 }  // namespace ctc

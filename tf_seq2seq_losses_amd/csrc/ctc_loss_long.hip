@@ -39,6 +39,16 @@
 // labels reach from k * UB - 2 to k * UB + UB + 1, and whether a -3 is optional or half of a bad pair is read off the labels themselves;
 // behind an optional last position the finish kernels and the first beta tiles take position L - 2 as an end state too; the tiles that
 // run are long_loss_tile_active_opt's.  Where OPT is off, the source is the parent's expression for expression: the same device code.
+// The exclusion of the next label (XN, never with WIN; ctc_amd_long_star_loss_grad / _grad_ckpt / _label_posterior, DESIGN.md section
+// 5.30; this file compiled a second time with -DCTC_STAR): a wildcard position i of either kind whose position i + 1 is an ordinary
+// label y emits e_w + ln(1 - p_t(y)).  Whether an utterance has such a position (`excl`) is asked of the labels themselves by every
+// tile and the row stage (ll_excluding_at over the whole transcript): then label block 0 takes the row statistics as (max, sum of the
+// REST) and keeps the sum of the rest in the record's fourth float for the blocks to its right; the producers of both tiles gather
+// x[t, y] for their wildcard positions (y of position k * UB + UB - 1 is label[(k + 1) * UB]: the label copy reaches one further) and
+// write log2(1 - p_t(y)) into the wildcard's ring slot, 0 where nothing is excluded; the chain adds the slot to e_w.  The beta tile
+// that feeds the row stage (XG) saves c = Gamma 2^-slot in Gamma's place and the largest c of its frame in the saved row's spare
+// double, one per (b, k, t); the row stage takes the maximum over k, scatters c by y into integer bins D and forms C - D(k) as an
+// integer difference.  An utterance without such a position runs the statements of the XN = false path: the same bits.
 // Which tiles run is long_loss_tile_active (ctc_loss_long_plan.h), asked by all of them; nothing unwritten is read.  No workgroup
 // waits for another: no flags, no cooperative launch, no floating-point atomics, vector stores only, one writer per element.
 #include "ctc_loss_long.h"
@@ -74,6 +84,24 @@ __device__ __forceinline__ void ll_stat_add4(float &m, float &s, const float4 v)
   s = s * fexp2((m - mn) * LOG2E) +
       ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
   m = mn;
+}
+
+// XN: running (max, sum of exp(x - max) over the REST) of one lane, the online update of ctc_wild_loss.hip: the element that holds
+// the maximum adds nothing, so the sum of a row with one dominant token keeps its relative precision.  m starts at the lowest finite
+// float, s at 0
+__device__ __forceinline__ void ll_rest_add1(float &m, float &s, const float v) {
+  const float d = fexp2(-fabsf(v - m) * LOG2E);
+  if (v > m) { s = (s + 1.f) * d; m = v; }
+  else s += d;
+}
+__device__ __forceinline__ void ll_rest_add4(float &m, float &s, const float4 v) {
+  ll_rest_add1(m, s, v.x); ll_rest_add1(m, s, v.y); ll_rest_add1(m, s, v.z); ll_rest_add1(m, s, v.w);
+}
+// XN: log2(1 - p_t(y)) from the frame's record sv = (x[blank], max, log2(S_rest + 1), S_rest) and v = x[t, y]: S_rest / (S_rest + 1)
+// where y holds the maximum, (S_rest + 1 - e_y) / (S_rest + 1) elsewhere; neither cancels.  -inf where y holds all the mass
+__device__ __forceinline__ float ll_log2_rest(const float4 sv, const float v) {
+  const float num = v == sv.y ? sv.w : (sv.w + 1.f) - fexp2((v - sv.y) * LOG2E);
+  return flog2(num) - sv.z;
 }
 
 // base-2 log(2^a + 2^b [+ 2^c]) of float64 operands that may be -inf (log 0): differences against the maximum, or against 0
@@ -175,6 +203,29 @@ template <bool OPT>
 __device__ __forceinline__ bool ll_is_wild(int tok) {
   return tok == LONG_LOSS_WILDCARD || (OPT && tok == LONG_LOSS_OPTIONAL);
 }
+// XN: position g (< L) is a wildcard that excludes: position g + 1 holds an ordinary valid label.  Asked of the labels themselves,
+// as ll_optional_class is, so every tile, both stages and both workspaces reach the same verdict wherever a block boundary falls
+template <bool OPT>
+__device__ __forceinline__ bool ll_excluding_at(const Problem &p, const int32_t *lr, int g, int L) {
+  return g + 1 < L && ll_is_wild<OPT>(label_at(p, lr, g)) && emits(p, label_at(p, lr, g + 1));
+}
+// XN: the utterance has such a position: every thread of the tile's workgroup looks at its share of the transcript
+template <bool OPT>
+__device__ __forceinline__ bool ll_excludes_tile(const Problem &p, int b, int L) {
+  const int32_t *const lr = label_row(p, b);
+  int any = 0;
+  for (int g = threadIdx.x; g + 1 < L; g += LL_THREADS) any |= ll_excluding_at<OPT>(p, lr, g, L) ? 1 : 0;
+  return __syncthreads_or(any) != 0;
+}
+// XN: the token each of the lane's wildcard positions excludes (-1: none); lab_s[LB + i] is position k * UB + i, up to i = UB
+template <int LB>
+__device__ __forceinline__ void ll_next_tokens(const int *lab_s, int lane, unsigned wild, int *nx) {
+#pragma unroll
+  for (int q = 0; q < NL; ++q) {
+    const int nt = lab_s[LB + lane * NL + q + 1];
+    nx[q] = (((wild >> q) & 1u) && nt >= 0) ? nt : -1;
+  }
+}
 // OPT: bit q of `skip` = the position before k * UB + i0 + q is an optional wildcard, so this one may also be entered from two
 // positions back (position -1: the start state); bit q of `skipo` = (classic) ... from the open state there too.  lab_s holds the
 // positions from k * UB - 2 on
@@ -191,7 +242,7 @@ __device__ __forceinline__ void ll_skip_bits(const int *lab_s, int k, int i0, un
   }
 }
 
-template <int KIND, int MODE, bool WIN, bool OPT>
+template <int KIND, int MODE, bool WIN, bool OPT, bool XN>
 __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Problem p, const double w2, const LlWsArg<OPT> w, int K, int TF,
                                                                      int d, int k_lo, int count, const int32_t *__restrict__ win,
                                                                      int wstride) {
@@ -201,10 +252,12 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   constexpr bool SAVE = MODE == 1 || MODE == 3;  // the chain's state of every frame is stored
   constexpr bool REDO = MODE == 3;               // the forward sweep has run: nothing but the saved rows is written
   static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
+  static_assert(!(WIN && XN), "frame windows and the exclusion of the next label are not combined");
   constexpr int LB = OPT ? 2 : 1;                // lab_s[LB + i]: position k * UB + i
+  constexpr int LN = UB + LB + (XN ? 1 : 0);     // XN: one position further, the label that position k * UB + UB - 1 excludes
   const double NINF = -__builtin_inf();
   __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
-  __shared__ int lab_s[UB + LB];  // positions k * UB - LB .. k * UB + UB - 1
+  __shared__ int lab_s[LN];  // positions k * UB - LB .. k * UB + UB - 1 (XN: .. k * UB + UB)
   __shared__ double col_s[2][F][2 * LB];  // (OPT: behind the pair of position k * UB - 1 that of k * UB - 2)
 
   const int b = blockIdx.x / count, k = k_lo + blockIdx.x % count, j = d - k;
@@ -221,9 +274,11 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
   const bool fresh = OPT ? long_loss_alpha_fresh_opt(k, j, TF) : long_loss_alpha_fresh(k, j, TF);
   const bool has_right = long_loss_has_right(L, k);
 
-  if constexpr (OPT) ll_labels_opt(p, b, k, L, UB + LB, lab_s);
-  else ll_labels(p, b, k, L, UB + LB, lab_s);
+  if constexpr (OPT) ll_labels_opt(p, b, k, L, LN, lab_s);
+  else ll_labels(p, b, k, L, LN, lab_s);
   __syncthreads();
+  [[maybe_unused]] bool excl = false;  // XN: the utterance has a wildcard that excludes (the same in every tile of it)
+  if constexpr (XN) excl = ll_excludes_tile<OPT>(p, b, L);
 
   int lab[NL];
   unsigned wild = 0;  // bit q = position k * UB + lane * NL + q is a wildcard (OPT: of either kind)
@@ -246,6 +301,9 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       wl[q] = g < L ? wb[2 * (size_t)g + 1] : -1;
     }
   }
+
+  [[maybe_unused]] int nx[NL];  // XN: the token each wildcard position excludes (-1: none)
+  if constexpr (XN) ll_next_tokens<LB>(lab_s, lane, wild, nx);
 
   const int esz = dt == 0 ? 4 : 2;
   const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
@@ -301,20 +359,40 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
     float e[NL];
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
-      const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
-      e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+      if constexpr (XN) {  // a wildcard position gathers the token it excludes
+        const int tk = lab[q] >= 0 ? lab[q] : nx[q];
+        const float v = row_load1(xr, tk >= 0 ? tk : blank, dt);
+        e[q] = tk >= 0 ? v : -__builtin_inff();
+      } else {
+        const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
+        e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+      }
     }
     float4 sv;
     if (k == 0 && !REDO) {
       // the row pass.  Both access paths give a lane the same elements in the same order: identical bits
       const float eb = row_load1(xr, blank, dt);
       float m = -3.402823466e38f, s = 0.f;
-      for (int c = lane * 4; c < V; c += 256) ll_stat_add4(m, s, vec ? ll_row_load4(xr, c, dt) : ll_row_load4_elem(xr, c, V, dt));
+      for (int c = lane * 4; c < V; c += 256) {
+        const float4 v = vec ? ll_row_load4(xr, c, dt) : ll_row_load4_elem(xr, c, V, dt);
+        if (XN && excl) ll_rest_add4(m, s, v);
+        else ll_stat_add4(m, s, v);
+      }
       float M = wave_max(m);
-      const float S = wave_sum(s * fexp2((m - M) * LOG2E));
-      float l2s = flog2(S);
-      if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
-      sv = make_float4(eb, M, l2s, 0.f);
+      if (XN && excl) {
+        // the lowest lane at the maximum keeps its 1 out; every other lane's own maximum is part of the rest
+        const unsigned long long at = __builtin_amdgcn_ballot_w64(m == M);
+        const bool own = lane == (int)__builtin_ctzll(at);
+        const float Sr = wave_sum(own ? s : (s + 1.f) * fexp2((m - M) * LOG2E));
+        float l2s = flog2(Sr + 1.f);
+        if (!(M > -3.402823466e38f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf
+        sv = make_float4(eb, M, l2s, Sr);  // the fourth float: the sum of the rest, for the blocks to the right and the beta tiles
+      } else {
+        const float S = wave_sum(s * fexp2((m - M) * LOG2E));
+        float l2s = flog2(S);
+        if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+        sv = make_float4(eb, M, l2s, 0.f);
+      }
       if (lane == 0) *reinterpret_cast<float4 *>(statw + (size_t)t * 4) = sv;
     } else {
       sv = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);  // (tile (0, j) stored it on an earlier launch: the same bits)
@@ -323,6 +401,9 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
       float v = e[q];
+      if constexpr (XN) {  // log2(1 - p_t(y)) for a wildcard position that excludes y, 0 for one that excludes nothing
+        if (excl && ((wild >> q) & 1u)) v = nx[q] >= 0 ? ll_log2_rest(sv, v) : 0.f;
+      }
       if constexpr (WIN) {
         if ((wild >> q) & 1u) v = 0.f;  // the gate of e_w
         if (t < wf[q] || t > wl[q]) v = -__builtin_inff();  // (t: the absolute frame, in the beta tile too)
@@ -347,7 +428,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
       for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
-      auto ewq = [&](int q) { return WIN ? fr.ew + (double)e[q] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      // (WIN: the ring slot of a wildcard is its gate, 0 or -inf; XN, in an utterance that excludes: log2(1 - p_t(y)))
+      auto ewq = [&](int q) { return (WIN || (XN && excl)) ? fr.ew + (double)e[q] : fr.ew; };
       auto em = [&](int q) { return ((wild >> q) & 1u) ? ewq(q) : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = SAVE ? myrows + (size_t)(t0 + f - t_base) * SRD : nullptr;
       if (SAVE && KIND == 1) {  // the state BEFORE the frame
@@ -355,6 +437,7 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_alpha_kernel(const Probl
         for (int q = 0; q < NL; ++q) r[lane * NS + q] = C[q];
         if (k == 0 && lane == 0) r[SRD - 2] = cs;
       }
+      // (XN: the columns hold states BEFORE the frame, which no emission of this frame has touched: no change)
       if (col_out && lane == 63) {  // column out: the last position before this frame
         col_out[(size_t)(t0 + f) * 2] = O[NL - 1];
         col_out[(size_t)(t0 + f) * 2 + 1] = C[NL - 1];
@@ -504,13 +587,15 @@ __global__ __launch_bounds__(256) void loss_long_finish_opt_kernel(const Problem
 }
 
 // CKPT: the saved rows are the ring's (long_loss_row_index), written by alpha MODE 3 on the launch before this one
-template <int KIND, bool CKPT, bool WIN, bool OPT>
+// XN: XG says which stage the saved rows feed, the gradient's row stage (c in Gamma's place) or the posterior stage (Gamma itself)
+template <int KIND, bool CKPT, bool WIN, bool OPT, bool XN, bool XG>
 __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Problem p, const double w2, const LlWsArg<OPT> w, int K, int TF,
                                                                     int d, int k_lo, int count, const int32_t *__restrict__ win,
                                                                     int wstride) {
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
   constexpr int SRD = long_loss_row_doubles(KIND);
   static_assert(!(WIN && OPT), "frame windows and optional wildcards are not combined");
+  static_assert(!(WIN && XN) && (XN || !XG), "frame windows and the exclusion of the next label are not combined");
   constexpr int LB = OPT ? 2 : 1;  // lab_s[LB + i]: position k * UB + i
   const double NINF = -__builtin_inf();
   __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
@@ -537,6 +622,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
   if constexpr (OPT) ll_labels_opt(p, b, k, L, UB + 2 * LB, lab_s);
   else ll_labels(p, b, k, L, UB + 2 * LB, lab_s);
   __syncthreads();
+  [[maybe_unused]] bool excl = false;  // XN: the utterance has a wildcard that excludes (the same in every tile of it)
+  if constexpr (XN) excl = ll_excludes_tile<OPT>(p, b, L);
 
   int lab[NL];
   unsigned wild = 0;
@@ -559,6 +646,9 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
       wl[q] = g < L ? wb[2 * (size_t)g + 1] : -1;
     }
   }
+
+  [[maybe_unused]] int nx[NL];  // XN: the token each wildcard position excludes (-1: none)
+  if constexpr (XN) ll_next_tokens<LB>(lab_s, lane, wild, nx);
 
   const int esz = dt == 0 ? 4 : 2;
   const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
@@ -624,13 +714,26 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
     float e[NL];
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
-      const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
-      e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+      if constexpr (XN) {  // a wildcard position gathers the token it excludes
+        const int tk = lab[q] >= 0 ? lab[q] : nx[q];
+        const float v = row_load1(xr, tk >= 0 ? tk : blank, dt);
+        e[q] = tk >= 0 ? v : -__builtin_inff();
+      } else {
+        const float v = row_load1(xr, lab[q] >= 0 ? lab[q] : blank, dt);
+        e[q] = lab[q] >= 0 ? v : -__builtin_inff();
+      }
     }
     float *const r = ring + ((kb & 1) * F + f) * RS;
+    [[maybe_unused]] float4 sv;
+    if constexpr (XN) {
+      if (excl) sv = *reinterpret_cast<const float4 *>(statw + (size_t)t * 4);
+    }
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
       float v = e[q];
+      if constexpr (XN) {  // the slot of the forward sweep: the same record, the same bits
+        if (excl && ((wild >> q) & 1u)) v = nx[q] >= 0 ? ll_log2_rest(sv, v) : 0.f;
+      }
       if constexpr (WIN) {
         if ((wild >> q) & 1u) v = 0.f;  // the gate of e_w
         if (t < wf[q] || t > wl[q]) v = -__builtin_inff();  // (t: the absolute frame, in the beta tile too)
@@ -661,7 +764,8 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
       for (int q = 0; q < NL; ++q) e[q] = rr[lane * NL + q];
       const LlFrame fr = ll_frame_of(rr, lpin, w2);
       const double eb = fr.eb;
-      auto ewq = [&](int q) { return WIN ? fr.ew + (double)e[q] : fr.ew; };  // (WIN: the ring slot of a wildcard is its gate, 0 or -inf)
+      // (WIN: the ring slot of a wildcard is its gate, 0 or -inf; XN, in an utterance that excludes: log2(1 - p_t(y)))
+      auto ewq = [&](int q) { return (WIN || (XN && excl)) ? fr.ew + (double)e[q] : fr.ew; };
       auto em = [&](int q) { return ((wild >> q) & 1u) ? ewq(q) : fma((double)e[q] - fr.Md, LOG2E_D, fr.nl2s); };
       double *const r = myrows + (size_t)(t - t_base) * SRD;
       double A[NS], Acs = NINF;
@@ -670,12 +774,23 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
       if (k == 0) Acs = r[SRD - 2];
       const double fillR = col_s[kb & 1][f][0];
       auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+      [[maybe_unused]] float cm = 0.f;  // XG: the largest c of the frame in this label block
       if (KIND == 0) {
 #pragma unroll
-        for (int q = 0; q < NL; ++q)
-          *reinterpret_cast<float2 *>(r + lane * NS + 2 * q) = make_float2(post(A[2 * q] + O[q]), post(A[2 * q + 1] + C[q]));
+        for (int q = 0; q < NL; ++q) {
+          float g = post(A[2 * q] + O[q]);
+          if constexpr (XG) {  // a wildcard's Gamma becomes c = Gamma / (1 - p): the slot is log2(1 - p)
+            if (excl && ((wild >> q) & 1u)) {
+              g = g > 0.f ? g * fexp2(-e[q]) : 0.f;
+              cm = fmaxf(cm, g);
+            }
+          }
+          *reinterpret_cast<float2 *>(r + lane * NS + 2 * q) = make_float2(g, post(A[2 * q + 1] + C[q]));
+        }
         if (k == 0 && lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + cs);
         // beta back over frame t: x = what entering O[i] with this frame is worth
+        // (XN: the column holds the worth of ENTERING a position, emission included, and the block that owns the position writes it
+        // with its own slot: no change)
         double x = O[0] + em(0);
         if (colb_out && lane == 0) colb_out[t] = x;
         const double xl = from_next_lane(x, fillR);
@@ -720,9 +835,19 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
             ap = ll_lse(ap, ((skip >> q) & 1u) ? ap2 : NINF);
           }
           const double h = ((wild >> q) & 1u) ? ewq(q) : eb;
-          *reinterpret_cast<float2 *>(r + lane * NS + q) = make_float2(post(ap + em(q) + C[q]), post(A[q] + h + C[q]));
+          float pe = post(ap + em(q) + C[q]), ps = post(A[q] + h + C[q]);
+          if constexpr (XG) {  // a wildcard's two shares of Gamma become those of c = Gamma / (1 - p)
+            if (excl && ((wild >> q) & 1u)) {
+              const float sc = fexp2(-e[q]);
+              pe = pe > 0.f ? pe * sc : 0.f;
+              ps = ps > 0.f ? ps * sc : 0.f;
+              cm = fmaxf(cm, pe + ps);
+            }
+          }
+          *reinterpret_cast<float2 *>(r + lane * NS + q) = make_float2(pe, ps);
         }
         if (k == 0 && lane == 0) *reinterpret_cast<float *>(r + SRD - 2) = post(Acs + eb + cs);
+        // (XN: the worth of entering, written by the block that owns the position: as in the classic branch)
         double x = C[0] + em(0);
         if (colb_out && lane == 0) colb_out[t] = x;
         const double xl = from_next_lane(x, fillR);
@@ -745,6 +870,12 @@ __global__ __launch_bounds__(LL_THREADS) void loss_long_beta_kernel(const Proble
             C[q] = ll_lse(C[q] + (((wild >> q) & 1u) ? ewq(q) : eb), xn);
             x = xn;
           }
+        }
+      }
+      if constexpr (XG) {  // one writer per (b, k, t): the saved row's spare double
+        if (excl) {
+          cm = wave_max(cm);
+          if (lane == 0) *reinterpret_cast<float *>(r + SRD - 1) = cm;
         }
       }
     }
@@ -777,7 +908,13 @@ constexpr int LLG_FIX = 40;   // fixed point: a posterior (in [0, 1]) in units o
 
 // CKPT: the rows (b, t) of one time block, t = t0 .. t0 + nt - 1, from the ring; otherwise all of them (t0 = 0, nt = T)
 // OPT: an optional wildcard counts as a wildcard (a feasible utterance has no bad pair), and the tiles are those of the optional predicate
-template <int KIND, bool CKPT, bool OPT>
+constexpr int LLG_CH_XN = LLG_CH / 2;  // XN: two sets of bins per wavefront in the same LDS, so passes of half as many columns
+// XN: c is not bounded by 1, so the unit of its bins comes from the frame: c < 2^ex (ex from the largest c) enters as c 2^(LLG_CBITS
+// - ex) < 2^LLG_CBITS.  A transcript within one label block takes the short form's unit (1024 of them < 2^60: the same bits as
+// wild_grad_row_kernel); up to 65 536 positions need 2^46 (their sum < 2^62)
+__device__ __forceinline__ int llg_cbits(int L) { return L <= UB ? 50 : 46; }
+
+template <int KIND, bool CKPT, bool OPT, bool XN>
 __device__ __forceinline__ void loss_long_row(const Problem &p, const LongLossWs &w, int K, int TF, int t0, int nt,
                                               const float *__restrict__ d_loss, void *__restrict__ grad) {
   constexpr int SLOT = KIND == 0 ? 16 : 8;  // bytes of a label position in a saved row; its first 8 are the two posteriors
@@ -842,6 +979,91 @@ __device__ __forceinline__ void loss_long_row(const Problem &p, const LongLossWs
   const size_t kstride = long_loss_row_stride(CKPT, K, p.T, TF);
   const int32_t *const lab = label_row(p, b);
 
+  if constexpr (XN) {
+    // The beta tiles left c_i = Gamma_{t,i} / (1 - p_t(y_i)) in Gamma's place (Gamma itself where nothing is excluded) and, per
+    // label block, the frame's largest c in the saved row's spare double.  INVARIANT shared with the tiles' `excl`: only an utterance
+    // with a position of ll_excluding_at took the other statistics and left c and its maxima; otherwise the spare double is not read
+    __shared__ unsigned long long csum_all[LLG_WAVES];
+    constexpr int CH = LLG_CH_XN;  // gamma's bins in the first half of the wavefront's bins, D's in the second
+    constexpr size_t CMAX_AT = ROWB - 8;
+    bool any = false;
+    for (int i = lane; i + 1 < L; i += 64) any = any || ll_excluding_at<OPT>(p, lab, i, L);
+    if (__builtin_amdgcn_ballot_w64(any) != 0ull) {  // (wavefront-uniform; an utterance that excludes nothing: the code below)
+      if (dl == 0.f) {  // a weight of zero: +0 throughout
+        for (int c = lane * 4; c < V; c += 256) gput4(c, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+      }
+      // the largest c of the frame: the label blocks' maxima in the order of the blocks (the beta tiles of different blocks ran on
+      // different launches, each the one writer of its own slot)
+      float cmax = 0.f;
+      for (int k = 0; k < K && (k == 0 || k * UB < L); ++k)
+        if (ll_tile_active<OPT>(Tb, L, k, j, TF))
+          cmax = fmaxf(cmax, *reinterpret_cast<const float *>(rows + (size_t)k * kstride * ROWB + CMAX_AT));
+      int ex;
+      (void)__builtin_frexpf(cmax, &ex);
+      const int sh = llg_cbits(L) - ex;
+      unsigned long long *const dbins = bins + CH;
+      float blk = 0.f;
+      unsigned long long ctot = 0ull;
+      for (int c0 = 0; c0 < V; c0 += CH) {
+#pragma unroll
+        for (int q = 0; q < LLG_CH / 64; ++q) bins[lane + 64 * q] = 0ull;  // (both halves)
+        if (c0 == 0 && lane == 0) csum_all[wv] = 0ull;
+        wave_lds_fence();
+        unsigned long long cl = 0ull;
+        for (int k = 0; k < K && (k == 0 || k * UB < L); ++k) {
+          if (!ll_tile_active<OPT>(Tb, L, k, j, TF)) continue;  // (no posteriors: exactly zero)
+          const char *const r = rows + (size_t)k * kstride * ROWB;
+          const int n = L - k * UB < UB ? L - k * UB : UB;
+          for (int i = lane; i < n; i += 64) {
+            const float2 pq = *reinterpret_cast<const float2 *>(r + (size_t)i * SLOT);
+            const int gi = k * UB + i;
+            const int tok = label_at(p, lab, gi);
+            const bool wc = ll_is_wild<OPT>(tok);
+            const unsigned rel = (unsigned)(tok - c0);
+            if (!wc && emits(p, tok) && rel < (unsigned)CH)
+              atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, LLG_FIX)));
+            if (wc) {
+              const unsigned long long q = (unsigned long long)__float2ll_rn(__builtin_ldexpf(KIND == 1 ? pq.x + pq.y : pq.x, sh));
+              cl += q;
+              const int y = gi + 1 < L ? label_at(p, lab, gi + 1) : -1;  // the token position gi excludes, if it is an ordinary one
+              if (emits(p, y) && (unsigned)(y - c0) < (unsigned)CH) atomicAdd(&dbins[y - c0], q);
+            }
+            if (c0 == 0 && !(KIND == 1 && wc)) blk += pq.y;
+          }
+          if (c0 == 0 && k == 0 && lane == 0) blk += *reinterpret_cast<const float *>(r + (size_t)UB * SLOT);  // the start state
+        }
+        if (c0 == 0) {
+          blk = wave_sum(blk);
+          atomicAdd(&csum_all[wv], cl);
+        }
+        wave_lds_fence();
+        if (c0 == 0) ctot = csum_all[wv];
+#pragma unroll
+        for (int q = 0; q < CH / 256; ++q) {
+          const int col = c0 + lane * 4 + 256 * q;
+          if (col < V) {
+            const float4 xv = xvec ? ll_row_load4(x, col, xdt) : ll_row_load4_elem(x, col, V, xdt);
+            float o[4];
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+              const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[col - c0 + cc]), -LLG_FIX) + (col + cc == blank ? blk : 0.f);
+              // C - D(k): an integer difference, exact
+              const float cd = __builtin_ldexpf(__ll2float_rn((long long)(ctot - dbins[col - c0 + cc])), -sh);
+              const float c = p.wrt == 0 ? 1.f - cd : -cd;
+              const float sm = c == 0.f ? 0.f : c * fexp2((xs[cc] - mx) * LOG2E - l2s);
+              o[cc] = dl * (sm - bin);
+            }
+            gput4(col, make_float4(o[0], o[1], o[2], o[3]));
+          }
+        }
+        wave_lds_fence();
+      }
+      return;
+    }
+  }
+
   float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
   for (int c0 = 0; c0 < V; c0 += LLG_CH) {
 #pragma unroll
@@ -893,15 +1115,15 @@ __device__ __forceinline__ void loss_long_row(const Problem &p, const LongLossWs
     wave_lds_fence();
   }
 }
-template <int KIND, bool OPT>
+template <int KIND, bool OPT, bool XN>
 __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_kernel(const Problem p, const LongLossWs w, int K, int TF,
                                                                        const float *__restrict__ d_loss, void *__restrict__ grad) {
-  loss_long_row<KIND, false, OPT>(p, w, K, TF, 0, p.T, d_loss, grad);
+  loss_long_row<KIND, false, OPT, XN>(p, w, K, TF, 0, p.T, d_loss, grad);
 }
-template <int KIND, bool OPT>
+template <int KIND, bool OPT, bool XN>
 __global__ __launch_bounds__(64 * LLG_WAVES) void loss_long_row_ckpt_kernel(const Problem p, const LongLossWs w, int K, int TF, int t0, int nt,
                                                                             const float *__restrict__ d_loss, void *__restrict__ grad) {
-  loss_long_row<KIND, true, OPT>(p, w, K, TF, t0, nt, d_loss, grad);
+  loss_long_row<KIND, true, OPT, XN>(p, w, K, TF, t0, nt, d_loss, grad);
 }
 
 // ---- the posterior stage of ctc_amd_long_label_posterior: the ring rows of one time block, read a second
@@ -1053,28 +1275,45 @@ struct LlWindow {
   bool optional;
 };
 
+#ifdef CTC_STAR  // this unit holds the XN tiles and row stages alone: no window, both values of `optional`
+constexpr bool LL_XN = true;
+#define CTC_LL_NAME(base, star) star
+#else
+constexpr bool LL_XN = false;
+#define CTC_LL_NAME(base, star) base
+#endif
+
 template <int KIND, int MODE>
 void launch_alpha(const Problem &p, const LongLossPlan &P, double w2, const LongLossWsOpt &wo, const LlWindow &fw, int d, int k_lo, int count,
                   hipStream_t st) {
   if (fw.optional) {
-    hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, MODE, false, true>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2,
-                       wo, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
+    hipLaunchKernelGGL((loss_long_alpha_kernel<KIND, MODE, false, true, LL_XN>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st,
+                       p, w2, wo, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
     return;
   }
   const LongLossWs &w = wo;
-  const auto tile = fw.win ? loss_long_alpha_kernel<KIND, MODE, true, false> : loss_long_alpha_kernel<KIND, MODE, false, false>;
+#ifdef CTC_STAR
+  const auto tile = loss_long_alpha_kernel<KIND, MODE, false, false, true>;
+#else
+  const auto tile = fw.win ? loss_long_alpha_kernel<KIND, MODE, true, false, false> : loss_long_alpha_kernel<KIND, MODE, false, false, false>;
+#endif
   hipLaunchKernelGGL(tile, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
 }
-template <int KIND, bool CKPT>
+// XG (XN alone): the rows feed the gradient's row stage; otherwise (the posterior call, which runs the checkpointed schedule) XG = false
+template <int KIND, bool CKPT, bool XG>
 void launch_beta(const Problem &p, const LongLossPlan &P, double w2, const LongLossWsOpt &wo, const LlWindow &fw, int d, int k_lo, int count,
                  hipStream_t st) {
   if (fw.optional) {
-    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, CKPT, false, true>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2,
-                       wo, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
+    hipLaunchKernelGGL((loss_long_beta_kernel<KIND, CKPT, false, true, LL_XN, XG>), dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0,
+                       st, p, w2, wo, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
     return;
   }
   const LongLossWs &w = wo;
-  const auto tile = fw.win ? loss_long_beta_kernel<KIND, CKPT, true, false> : loss_long_beta_kernel<KIND, CKPT, false, false>;
+#ifdef CTC_STAR
+  const auto tile = loss_long_beta_kernel<KIND, CKPT, false, false, true, XG>;
+#else
+  const auto tile = fw.win ? loss_long_beta_kernel<KIND, CKPT, true, false, false, false> : loss_long_beta_kernel<KIND, CKPT, false, false, false, false>;
+#endif
   hipLaunchKernelGGL(tile, dim3((unsigned)((size_t)p.B * count)), dim3(LL_THREADS), 0, st, p, w2, w, P.K, P.TF, d, k_lo, count, fw.win, fw.stride);
 }
 
@@ -1098,10 +1337,10 @@ hipError_t run_kind(const Problem &p, const LongLossPlan &P, double w2, const fl
   for (int e = 0; e < P.launches; ++e) {
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
-    launch_beta<KIND, false>(p, P, w2, wo, fw, d, k_lo, count, st);
+    launch_beta<KIND, false, LL_XN>(p, P, w2, wo, fw, d, k_lo, count, st);
   }
   const unsigned blocks = (unsigned)(((long)p.B * p.T + LLG_WAVES - 1) / LLG_WAVES);
-  const auto rowk = fw.optional ? loss_long_row_kernel<KIND, true> : loss_long_row_kernel<KIND, false>;
+  const auto rowk = fw.optional ? loss_long_row_kernel<KIND, true, LL_XN> : loss_long_row_kernel<KIND, false, LL_XN>;
   hipLaunchKernelGGL(rowk, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, d_loss, grad);
   return hipGetLastError();
 }
@@ -1144,12 +1383,13 @@ hipError_t run_kind_ckpt(const Problem &p, const LongLossPlan &P, double w2, con
     int d, k_lo, count;
     long_loss_backward_diagonal(P, e, &d, &k_lo, &count);
     launch_alpha<KIND, 3>(p, P, w2, wo, fw, d, k_lo, count, st);
-    launch_beta<KIND, true>(p, P, w2, wo, fw, d, k_lo, count, st);
+    if (LL_XN && !post) launch_beta<KIND, true, LL_XN>(p, P, w2, wo, fw, d, k_lo, count, st);
+    else launch_beta<KIND, true, false>(p, P, w2, wo, fw, d, k_lo, count, st);
     if (d < P.J) {
       const int t0 = d * P.TF, nt = p.T - t0 < P.TF ? p.T - t0 : P.TF;
       if (post) { post_stage(d, nt); continue; }
       const unsigned blocks = (unsigned)(((long)p.B * nt + LLG_WAVES - 1) / LLG_WAVES);
-      const auto rowk = fw.optional ? loss_long_row_ckpt_kernel<KIND, true> : loss_long_row_ckpt_kernel<KIND, false>;
+      const auto rowk = fw.optional ? loss_long_row_ckpt_kernel<KIND, true, LL_XN> : loss_long_row_ckpt_kernel<KIND, false, LL_XN>;
       hipLaunchKernelGGL(rowk, dim3(blocks), dim3(64 * LLG_WAVES), 0, st, p, w, P.K, P.TF, t0, nt, d_loss, grad);
     }
   }
@@ -1173,9 +1413,11 @@ LongLossWsOpt long_loss_ws(char *ws, const LongLossPlan &P) {
 
 }  // namespace
 
-hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard_log_weight, const float *d_loss, float *loss, void *grad,
-                         char *ws, hipStream_t st, const int32_t *frame_window, int window_stride, bool optional_wildcards) {
-  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad)) return hipErrorInvalidValue;
+// (CTC_STAR: run_star_loss_long / run_star_long_label_posterior, the XN kernels on the same plans; no frame window)
+hipError_t CTC_LL_NAME(run_loss_long, run_star_loss_long)(const Problem &p, const LongLossPlan &P, float wildcard_log_weight,
+                                                          const float *d_loss, float *loss, void *grad, char *ws, hipStream_t st,
+                                                          const int32_t *frame_window, int window_stride, bool optional_wildcards) {
+  if (p.kind < 0 || p.kind > 1 || (grad && !P.want_grad) || (P.ckpt && !grad) || (LL_XN && frame_window)) return hipErrorInvalidValue;
   if (optional_wildcards && (frame_window || !P.opt)) return hipErrorInvalidValue;
   const LongLossWsOpt w = long_loss_ws(ws, P);
   const LlWindow fw{frame_window, window_stride, optional_wildcards};
@@ -1185,10 +1427,11 @@ hipError_t run_loss_long(const Problem &p, const LongLossPlan &P, float wildcard
   return p.kind == 0 ? run_kind<0>(p, P, w2, d_loss, loss, grad, w, fw, st) : run_kind<1>(p, P, w2, d_loss, loss, grad, w, fw, st);
 }
 
-hipError_t run_long_label_posterior(const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss, float *label_posterior,
-                                    float *blank_posterior, float *duration, float *expected_frame, float *peak_posterior,
-                                    int *peak_frame, char *ws, hipStream_t st, const int32_t *frame_window, int window_stride,
-                                    bool optional_wildcards) {
+hipError_t CTC_LL_NAME(run_long_label_posterior, run_star_long_label_posterior)(
+    const Problem &p, const LongPostPlan &P, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+    float *duration, float *expected_frame, float *peak_posterior, int *peak_frame, char *ws, hipStream_t st, const int32_t *frame_window,
+    int window_stride, bool optional_wildcards) {
+  if (LL_XN && frame_window) return hipErrorInvalidValue;
   if (p.kind < 0 || p.kind > 1 || !P.L.ckpt || !duration != !expected_frame || !peak_posterior != !peak_frame) return hipErrorInvalidValue;
   if (optional_wildcards && (frame_window || !P.L.opt)) return hipErrorInvalidValue;
   const LongLossWsOpt w = long_loss_ws(ws, P.L);

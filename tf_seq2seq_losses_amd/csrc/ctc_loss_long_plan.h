@@ -120,6 +120,11 @@ inline void long_loss_plan_add_optional(LongLossPlan *P) {
   P->total = o;
 }
 
+// The exclusion of the next label (ctc_amd_long_star_*) adds nothing to any plan: its calls run on the
+// counterpart's plan (opt = 0 or 1), offset for offset.  Of an excluding utterance the fourth float of a row-statistics record holds
+// the sum of the rest, and the padding double of a saved row (index long_loss_row_doubles(kind) - 1) the largest c of that frame in
+// that label block: one writer per (b, k, t) in both layouts.  The size queries are the counterparts' (tests/test_cabi_long_star.py).
+
 // false: what long_plan refuses (frames_per_tile, sizes, the tile grid), or, with a gradient, a row stage of more than 2^31 - 1
 // workgroups (four rows (b, t) each)
 inline bool long_loss_plan(int kind, int B, int T, int U, int frames_per_tile, int want_grad, LongLossPlan *out, int opt = 0) {

@@ -844,6 +844,19 @@ def long_optional_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, 
                            want_grad, frames_per_tile, checkpoint, optional_wildcards=True)
 
 
+def long_star_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                        logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
+                        grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0, want_grad: bool = True,
+                        frames_per_tile: int = 0, checkpoint: bool = False,
+                        optional_wildcards: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """long_wildcard_loss_grad (optional_wildcards: long_optional_wildcard_loss_grad) in which a wildcard position of either kind
+    excludes the ordinary label that follows it, as wildcard_loss_grad(exclude_next_label=True) defines it:
+    ctc_amd_long_star_loss_grad / _grad_ckpt, on the counterpart's workspace.  Without such a position the counterpart's bits.
+    Not with frame windows.  Does not synchronise."""
+    return _long_loss_grad(None, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                           want_grad, frames_per_tile, checkpoint, optional_wildcards=optional_wildcards, exclude_next_label=True)
+
+
 def long_windowed_loss_grad(frame_window: torch.Tensor, kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor,
                             label_length: torch.Tensor, logit_length: torch.Tensor, blank: int, d_loss: Optional[torch.Tensor] = None,
                             U: Optional[int] = None, grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
@@ -859,9 +872,11 @@ def long_windowed_loss_grad(frame_window: torch.Tensor, kind: int, wrt: int, lab
 
 
 def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
-                    want_grad, frames_per_tile, checkpoint, optional_wildcards=False):
+                    want_grad, frames_per_tile, checkpoint, optional_wildcards=False, exclude_next_label=False):
     if optional_wildcards and frame_window is not None:
         raise ValueError("long_wildcard_loss_grad: frame_window and optional_wildcards cannot be combined")
+    if exclude_next_label and frame_window is not None:
+        raise ValueError("long_wildcard_loss_grad: frame_window and exclude_next_label cannot be combined")
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"long_wildcard_loss_grad: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args("long_wildcard_loss_grad", labels.unsqueeze(1), x, label_length.unsqueeze(1),
@@ -881,10 +896,14 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
     with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
     stem = "long_optional_wildcard_loss_grad" if optional_wildcards else "long_wildcard_loss_grad"
     name = stem + "_ckpt" if checkpoint else stem
-    key = (name, kind, B, T, V, U, int(frames_per_tile), with_grad)
+    # (the star calls take their counterparts' sizes from their own queries, under keys of their own)
+    key = ("star:" + name if exclude_next_label else name, kind, B, T, V, U, int(frames_per_tile), with_grad)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
-        if optional_wildcards:
+        if exclude_next_label:
+            def size(*a):
+                return _lib.long_star_loss_workspace_bytes(*a, optional_wildcards=optional_wildcards, checkpoint=checkpoint)
+        elif optional_wildcards:
             size = _lib.long_optional_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_optional_wildcard_loss_workspace_bytes
         else:
             size = _lib.long_wildcard_loss_ckpt_workspace_bytes if checkpoint else _lib.long_wildcard_loss_workspace_bytes
@@ -907,15 +926,20 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
         _lib.check(rc, "ctc_amd_" + wname)
         return loss, grad
     with _on_device(dev):
-        if optional_wildcards:
+        if optional_wildcards and not exclude_next_label:
             call = lib.ctc_amd_long_optional_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_optional_wildcard_loss_grad
         else:
             call = lib.ctc_amd_long_wildcard_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_wildcard_loss_grad
+        if exclude_next_label:  # (the counterparts' arguments with optional_wildcards behind blank_index)
+            star = lib.ctc_amd_long_star_loss_grad_ckpt if checkpoint else lib.ctc_amd_long_star_loss_grad
+
+            def call(*a):
+                return star(*a[:11], int(bool(optional_wildcards)), *a[11:])
         rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
                   _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
                   int(frames_per_tile), _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
                   _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
-    _lib.check(rc, "ctc_amd_" + name)
+    _lib.check(rc, "ctc_amd_" + (("long_star_loss_grad_ckpt" if checkpoint else "long_star_loss_grad") if exclude_next_label else name))
     return loss, grad
 
 
@@ -1013,19 +1037,34 @@ def long_optional_wildcard_label_posterior(kind: int, wrt: int, labels: torch.Te
                                  wildcard_log_weight, frames_per_tile, dense, want_stats, want_peak, None)
 
 
+def long_star_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                              logit_length: torch.Tensor, blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0,
+                              frames_per_tile: int = 0, dense: bool = True, want_stats: bool = True, want_peak: bool = True,
+                              optional_wildcards: bool = False):
+    """long_label_posterior (optional_wildcards: long_optional_wildcard_label_posterior) in which a wildcard position excludes the
+    ordinary label that follows it (ctc_amd_long_star_label_posterior): the same arguments but the window, the same seven outputs;
+    the loss is long_star_loss_grad's, bit for bit.  Does not synchronise."""
+    return _long_label_posterior("long_star_label_posterior", optional_wildcards, kind, wrt, labels, x, label_length, logit_length, blank, U,
+                                 wildcard_log_weight, frames_per_tile, dense, want_stats, want_peak, None, exclude_next_label=True)
+
+
 def _long_label_posterior(what, optional_wildcards, kind, wrt, labels, x, label_length, logit_length, blank, U, wildcard_log_weight,
-                          frames_per_tile, dense, want_stats, want_peak, frame_window):
+                          frames_per_tile, dense, want_stats, want_peak, frame_window, exclude_next_label=False):
     if labels.dim() != 2 or label_length.dim() != 1:
         raise ValueError(f"{what}: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
     labels, x, label_length, logit_length, U, _, W = _nbest_args(what, labels.unsqueeze(1), x, label_length.unsqueeze(1), logit_length, U)
     lib = _lib.load()
     dev = x.device
     B, T, V = (int(s) for s in x.shape)
-    key = (what, kind, B, T, V, U, int(frames_per_tile))
+    key = (what + ("+optional" if exclude_next_label and optional_wildcards else ""), kind, B, T, V, U, int(frames_per_tile))
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V, U and frames_per_tile, which an empty batch would otherwise skip)
         size = _lib.long_optional_wildcard_label_posterior_workspace_bytes if optional_wildcards else _lib.long_label_posterior_workspace_bytes
-        n = _WS_BYTES[key] = size(kind, B, T, V, U, int(frames_per_tile))
+        if exclude_next_label:
+            n = _lib.long_star_label_posterior_workspace_bytes(kind, B, T, V, U, int(frames_per_tile), bool(optional_wildcards))
+        else:
+            n = size(kind, B, T, V, U, int(frames_per_tile))
+        _WS_BYTES[key] = n
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     post = torch.empty((B, T, U), dtype=torch.float32, device=dev) if dense else None
     blk = torch.empty((B, T), dtype=torch.float32, device=dev)
@@ -1047,9 +1086,12 @@ def _long_label_posterior(what, optional_wildcards, kind, wrt, labels, x, label_
         _lib.check(rc, "ctc_amd_long_windowed_label_posterior")
         return loss, post, blk, dur, exf, peak, pfr
     name = "ctc_amd_long_optional_wildcard_label_posterior" if optional_wildcards else "ctc_amd_long_label_posterior"
+    flag = ()
+    if exclude_next_label:  # (that argument list with optional_wildcards behind blank_index)
+        name, flag = "ctc_amd_long_star_label_posterior", (int(bool(optional_wildcards)),)
     with _on_device(dev):  # (the two entry points have one argument list)
         rc = getattr(lib, name)(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W, _ptr(label_length),
-                                _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U, int(frames_per_tile), _ptr(loss),
+                                _ptr(logit_length), int(blank), *flag, float(wildcard_log_weight), B, T, V, U, int(frames_per_tile), _ptr(loss),
                                 _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(peak), _ptr(pfr), _ptr(ws), n, _stream(dev))
     _lib.check(rc, name)
     return loss, post, blk, dur, exf, peak, pfr
