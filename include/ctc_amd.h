@@ -1541,7 +1541,8 @@ int ctc_amd_star_best_path(int kind, int wrt,
  * Workspace.  The counterpart's, byte for byte: the three size queries take optional_wildcards behind kind and return the
  * counterpart's size.  (Of an excluding utterance the fourth float of the per-frame row statistics holds the sum of the rest, and
  * the padding double of a saved row the largest c of its frame and label block.)  The workspace may hold anything on entry.
- * Not included: the long-form alignment, the N-best calls and frame windows together with the exclusion.
+ * Not included: the N-best calls and frame windows together with the exclusion; the long-form alignment is
+ * ctc_amd_long_star_best_path below.
  */
 int ctc_amd_long_star_loss_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
                                            int want_grad, size_t *out_bytes /*host*/);
@@ -1571,6 +1572,49 @@ int ctc_amd_long_star_label_posterior(int kind, int wrt,
                                       float *loss, float *label_posterior /* may be NULL */, float *blank_posterior,
                                       float *duration, float *expected_frame, float *peak_posterior, int32_t *peak_frame,
                                       void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The long-form alignment with optional wildcards and with the exclusion (added under ABI v6: two new entry points with their size
+ * queries, nothing existing changed):
+ *   ctc_amd_long_optional_wildcard_best_path   the arguments of ctc_amd_long_wildcard_best_path
+ *   ctc_amd_long_star_best_path                the same plus `int optional_wildcards` behind blank_index (in the size query: behind kind)
+ * They are ctc_amd_optional_wildcard_best_path and ctc_amd_star_best_path ("Optional wildcards" and the exclusion above), word for
+ * word, for label_length <= CTC_AMD_LONG_MAX_U on both lattices -- the classic lattice included, so this is also the call for the
+ * classic optional-wildcard alignment of 513 .. 1024 positions that CTC_AMD_OPTIONAL_CLASSIC_MAX_U refuses there: a label equal to
+ * CTC_AMD_OPTIONAL_WILDCARD may take no frame (first_frame = last_frame = -1, label_score 0); two adjacent ones make the utterance
+ * infeasible; an optional last position makes position L - 2 (or the start state) an end state; one such label with no frames is
+ * feasible with score 0; a wildcard in front of an ordinary label y scores and reports the best token other than y, the lowest on
+ * ties; one that is last or in front of a wildcard excludes nothing.  In formats, strides, outputs, validation order and messages,
+ * launches, capture and determinism they are ctc_amd_long_wildcard_best_path: every output but score's last bits is the same for every
+ * frames_per_tile and batch composition; a transcript with neither an optional wildcard nor an excluding one returns that call's
+ * tokens, label_index, first_frame, last_frame and label_score; at U <= 512 (classic) / 1024 (simplified) the outputs are the
+ * short-form calls'.  No frame window.
+ * Workspace.  Label blocks of UB = 512 positions on the classic lattice and 1024 on the simplified one, K = max(1, ceil(U / UB)),
+ * J = max(1, ceil(T / frames_per_tile)), r(x) = x rounded up to 256:
+ *   r(256 B K T) + r(16 B (K - 1) T) + r(8 B K (2 UB + 8)) + r(8 B J) + r(4 B T) + r(4 B) + r(8 B T) + r(4 B T) + r(8 B T)
+ *   + r(16 B (K - 1) T) + r(8 B T) + r(4 B T)
+ * bytes, whatever optional_wildcards says.  It may hold anything on entry.
+ */
+int ctc_amd_long_optional_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile,
+                                                             size_t *out_bytes /*host*/);
+int ctc_amd_long_optional_wildcard_best_path(int kind, int wrt,
+                                             const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                             const int32_t *labels, int label_stride,
+                                             const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                             int B, int T, int V, int U, int frames_per_tile,
+                                             float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                                             int32_t *first_frame /* may be NULL */, int32_t *last_frame /* may be NULL */,
+                                             float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
+int ctc_amd_long_star_best_path_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                size_t *out_bytes /*host*/);
+int ctc_amd_long_star_best_path(int kind, int wrt,
+                                const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                const int32_t *labels, int label_stride,
+                                const int32_t *label_length, const int32_t *logit_length, int blank_index, int optional_wildcards,
+                                int B, int T, int V, int U, int frames_per_tile,
+                                float *score, int32_t *tokens, int32_t *label_index /* may be NULL */,
+                                int32_t *first_frame /* may be NULL */, int32_t *last_frame /* may be NULL */,
+                                float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

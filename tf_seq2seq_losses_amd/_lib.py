@@ -181,6 +181,13 @@ SIGNATURES = {
     "ctc_amd_long_star_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                           [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                            _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    # ... and the long-form alignment with optional wildcards / the exclusion: the arguments of ctc_amd_long_wildcard_best_path
+    # (star: optional_wildcards behind blank_index; size query: behind kind)
+    "ctc_amd_long_optional_wildcard_best_path_workspace_bytes": (_c_int, [_c_int] * 6 + [ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
+    "ctc_amd_long_optional_wildcard_best_path": (_c_int, _COMMON_EX + [_c_int] + [_c_void_p] * 6 + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_long_star_best_path_workspace_bytes": (_c_int, [_c_int] * 7 + [ctypes.POINTER(_c_size_t)]),  # kind, optional_wildcards, B, T, V, U, frames_per_tile
+    "ctc_amd_long_star_best_path": (_c_int, _COMMON_EX[:11] + [_c_int] + _COMMON_EX[11:] + [_c_int] + [_c_void_p] * 6 +
+                                    [_c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_edit_distance_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # B, N, R
     "ctc_amd_edit_distance": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p,  # hyp, hyp_stride, hyp_length, ref, ref_stride, ref_length
                                        _c_int, _c_int, _c_int, _c_void_p,                           # B, N, R, distance
@@ -334,6 +341,16 @@ def long_wildcard_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U
     out = _c_size_t(0)
     check(load().ctc_amd_long_wildcard_best_path_workspace_bytes(kind, B, T, V, U, frames_per_tile, ctypes.byref(out)),
           "ctc_amd_long_wildcard_best_path_workspace_bytes")
+    return int(out.value)
+
+
+def long_star_best_path_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, frames_per_tile: int = 0,
+                                        optional_wildcards: bool = False) -> int:
+    """The workspace of the long-form alignment with either keyword (ctc_amd_long_star_best_path_workspace_bytes; the size of
+    ctc_amd_long_optional_wildcard_best_path_workspace_bytes is the same)."""
+    out = _c_size_t(0)
+    check(load().ctc_amd_long_star_best_path_workspace_bytes(kind, int(optional_wildcards), B, T, V, U, frames_per_tile, ctypes.byref(out)),
+          "ctc_amd_long_star_best_path_workspace_bytes")
     return int(out.value)
 
 

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "ctc_align_long.h"
+#include "ctc_align_long_star.h"
 #include "ctc_align_long_wild.h"
 #include "ctc_align_wild.h"
 #include "ctc_amd.h"
@@ -1031,24 +1032,81 @@ int ctc_amd_long_wildcard_best_path_workspace_bytes(int kind, int B, int T, int 
 }
 
 // label_score, like the other per-label outputs, may be null.
-int ctc_amd_long_windowed_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
-                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
-                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride, int B,
-                                    int T, int V, int U, int frames_per_tile, float *score, int32_t *tokens, int32_t *label_index,
-                                    int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace,
-                                    size_t workspace_bytes, void *stream) {
+// One body for ctc_amd_long_windowed_best_path, ctc_amd_long_optional_wildcard_best_path and ctc_amd_long_star_best_path (which have no
+// window).  With neither keyword: the plan and the kernels of ctc_align_long_wild.hip, as ever; with either:
+// those of ctc_align_long_star.hip, whose label blocks and workspace are its own.
+static int long_wildcard_best_path_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype,
+                                        int64_t logits_stride_b, int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                        const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                        const int32_t *frame_window, int window_stride, int B, int T, int V, int U, int frames_per_tile,
+                                        float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame, int32_t *last_frame,
+                                        float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
   const Common c{kind, wrt, logits, labels, label_stride, label_length, logit_length, blank_index, B, T, V, U};
   const Prelude pre = prelude(c, Format::of_logits(logits_dtype, logits_stride_b, logits_stride_t), false, CTC_AMD_LONG_MAX_U);
   if (!pre.go) return pre.rc;
   if (int rc = check_alignment(score, tokens, T, V)) return rc;
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
   ctc::LongWildPlan plan;
-  if (!ctc::long_wild_plan(B, T, U, frames_per_tile, &plan)) return bad_tiling(frames_per_tile, B, T, U);
-  if (int rc = check_workspace(workspace, workspace_bytes, plan.total, NullWs::Refused)) return rc;
-  CTC_TRY(ctc::run_align_long_wild(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
-                                   label_score, static_cast<hipStream_t>(stream), frame_window, window_stride),
-          "long wildcard alignment launch");
+  ctc::LongStarPlan splan;
+  const bool own = star || optional_wildcards;
+  if (!(own ? ctc::long_star_plan(kind, B, T, U, frames_per_tile, &splan) : ctc::long_wild_plan(B, T, U, frames_per_tile, &plan)))
+    return bad_tiling(frames_per_tile, B, T, U);
+  if (int rc = check_workspace(workspace, workspace_bytes, own ? splan.total : plan.total, NullWs::Refused)) return rc;
+  if (own)
+    CTC_TRY(ctc::run_align_long_star(pre.p, splan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                                     label_score, static_cast<hipStream_t>(stream), optional_wildcards, star),
+            "long wildcard alignment launch");
+  else
+    CTC_TRY(ctc::run_align_long_wild(pre.p, plan, static_cast<char *>(workspace), score, tokens, label_index, first_frame, last_frame,
+                                     label_score, static_cast<hipStream_t>(stream), frame_window, window_stride),
+            "long wildcard alignment launch");
   return CTC_AMD_OK;
+}
+
+int ctc_amd_long_windowed_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride, int B,
+                                    int T, int V, int U, int frames_per_tile, float *score, int32_t *tokens, int32_t *label_index,
+                                    int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+  return long_wildcard_best_path_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+                                      label_stride, label_length, logit_length, blank_index, frame_window, window_stride, B, T, V, U,
+                                      frames_per_tile, score, tokens, label_index, first_frame, last_frame, label_score, workspace,
+                                      workspace_bytes, stream);
+}
+
+// The plan of ctc_align_long_star_plan.h for the lattice's block size: one size for both, whatever optional_wildcards says.
+int ctc_amd_long_optional_wildcard_best_path_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {
+  return long_query<ctc::LongStarPlan>(kind, B, T, V, U, frames_per_tile, out_bytes,
+                                       [=](ctc::LongStarPlan *plan) { return ctc::long_star_plan(kind, B, T, U, frames_per_tile, plan); });
+}
+
+int ctc_amd_long_optional_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                             int64_t logits_stride_t, const int32_t *labels, int label_stride,
+                                             const int32_t *label_length, const int32_t *logit_length, int blank_index, int B, int T,
+                                             int V, int U, int frames_per_tile, float *score, int32_t *tokens, int32_t *label_index,
+                                             int32_t *first_frame, int32_t *last_frame, float *label_score, void *workspace,
+                                             size_t workspace_bytes, void *stream) {
+  return long_wildcard_best_path_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                      label_length, logit_length, blank_index, nullptr, 0, B, T, V, U, frames_per_tile, score, tokens,
+                                      label_index, first_frame, last_frame, label_score, workspace, workspace_bytes, stream);
+}
+
+int ctc_amd_long_star_best_path_workspace_bytes(int kind, int optional_wildcards, int B, int T, int V, int U, int frames_per_tile,
+                                                size_t *out_bytes) {
+  (void)optional_wildcards;
+  return ctc_amd_long_optional_wildcard_best_path_workspace_bytes(kind, B, T, V, U, frames_per_tile, out_bytes);
+}
+
+int ctc_amd_long_star_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                const int32_t *logit_length, int blank_index, int optional_wildcards, int B, int T, int V, int U,
+                                int frames_per_tile, float *score, int32_t *tokens, int32_t *label_index, int32_t *first_frame,
+                                int32_t *last_frame, float *label_score, void *workspace, size_t workspace_bytes, void *stream) {
+  return long_wildcard_best_path_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t,
+                                      labels, label_stride, label_length, logit_length, blank_index, nullptr, 0, B, T, V, U,
+                                      frames_per_tile, score, tokens, label_index, first_frame, last_frame, label_score, workspace,
+                                      workspace_bytes, stream);
 }
 
 int ctc_amd_long_wildcard_best_path(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,

@@ -459,7 +459,12 @@ class CtcLongWildcardAlignment(NamedTuple):
 
 
 def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, frames_per_tile=None,
-                         max_label_length=None, frame_window=None) -> CtcLongWildcardAlignment:
+                         max_label_length=None, frame_window=None, optional_wildcards=False,
+                         exclude_next_label=False) -> CtcLongWildcardAlignment:
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("frame_window and optional_wildcards=True cannot be combined")
+    if exclude_next_label and frame_window is not None:
+        raise ValueError("frame_window and exclude_next_label=True cannot be combined")
     x = _as_tensor(x)
     labels = _as_tensor(labels, torch.int32)
     if max_label_length is None:
@@ -471,6 +476,10 @@ def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logi
         prep = ops.Prepared(labels, x.detach(), label_length, logit_length, _blank(blank_index), keep_format=True,
                             host_max_label_length=max_label_length)
         fpt = 0 if frames_per_tile is None else int(frames_per_tile)
+        if optional_wildcards or exclude_next_label:
+            return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep, fpt,
+                                                                         optional_wildcards=bool(optional_wildcards),
+                                                                         exclude_next_label=bool(exclude_next_label)))
         if frame_window is None:
             return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep, fpt))
         return CtcLongWildcardAlignment(*ops.long_wildcard_best_path(ops.KINDS[kind_name], wrt, prep, fpt, _as_tensor(frame_window)))
@@ -478,7 +487,9 @@ def _long_wildcard_align(kind_name: str, wrt: int, labels, x, label_length, logi
 
 def classic_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                         blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
-                                        max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
+                                        max_label_length: Optional[int] = None, frame_window=None,
+                                        optional_wildcards: bool = False,
+                                        exclude_next_label: bool = False) -> CtcLongWildcardAlignment:
     """Forced alignment of a long recording against a partial transcript, on the classic lattice: classic_ctc_wildcard_alignment
     (a label equal to WILDCARD, -2, stands for any non-empty run of frames with any tokens on them; every label gets its first and
     last frame and a label_score) for transcripts of up to 65536 labels, computed on the tiled lattice of
@@ -486,27 +497,35 @@ def classic_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, 
     outputs do not depend on frames_per_tile.  Returns CtcLongWildcardAlignment, not differentiable.  check_labels keeps rejecting
     -2: it validates transcripts for the loss functions.  frame_window as in classic_ctc_wildcard_alignment, in absolute frames:
     approximate timestamps (subtitles, a coarse first pass) pin every label so the path cannot drift into a repeated phrase; every
-    tile of the lattice still runs."""
+    tile of the lattice still runs.  optional_wildcards / exclude_next_label: as in classic_ctc_wildcard_alignment, word for word (a
+    label equal to OPTIONAL_WILDCARD, -3, may take no frame: first_frame = last_frame = -1, label_score 0; a wildcard in front of an
+    ordinary label scores and reports the best token other than that label), for up to 65536 labels -- this is also the call for
+    the classic optional-wildcard alignment of more than 512 positions, which classic_ctc_wildcard_alignment refuses.  Not with
+    frame_window (ValueError)."""
     return _long_wildcard_align("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, frames_per_tile,
-                                max_label_length, frame_window)
+                                max_label_length, frame_window, optional_wildcards, exclude_next_label)
 
 
 def simplified_ctc_long_wildcard_alignment(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                            blank_index: Union[int, torch.Tensor] = 0, *, frames_per_tile: Optional[int] = None,
-                                           max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
+                                           max_label_length: Optional[int] = None, frame_window=None,
+                                           optional_wildcards: bool = False,
+                                           exclude_next_label: bool = False) -> CtcLongWildcardAlignment:
     """The same on the simplified lattice (a wildcard owns every frame from its entry until the next label's frame).  Same arguments
     and return value as classic_ctc_long_wildcard_alignment."""
     return _long_wildcard_align("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
-                                frames_per_tile, max_label_length, frame_window)
+                                frames_per_tile, max_label_length, frame_window, optional_wildcards, exclude_next_label)
 
 
 def ctc_long_wildcard_alignment_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                               frames_per_tile: Optional[int] = None,
-                                              max_label_length: Optional[int] = None, frame_window=None) -> CtcLongWildcardAlignment:
+                                              max_label_length: Optional[int] = None, frame_window=None,
+                                           optional_wildcards: bool = False,
+                                           exclude_next_label: bool = False) -> CtcLongWildcardAlignment:
     """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _long_wildcard_align(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                                frames_per_tile, max_label_length, frame_window)
+                                frames_per_tile, max_label_length, frame_window, optional_wildcards, exclude_next_label)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -528,11 +528,18 @@ def long_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0):
     return out
 
 
-def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0, frame_window: Optional[torch.Tensor] = None):
+def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: int = 0, frame_window: Optional[torch.Tensor] = None,
+                            optional_wildcards: bool = False, exclude_next_label: bool = False):
     """(score[B] float32, tokens[B,T] int32, label_index[B,T] int32, first_frame[B,U] int32, last_frame[B,U] int32,
     label_score[B,U] float32): wildcard_best_path for up to _lib.LONG_MAX_U label positions, on the tiled lattice of long_best_path
     (ctc_amd_long_wildcard_best_path).  Reads the logits in the format `p` holds them in; the workspace is the stream's cached
-    one, as in long_best_path.  frame_window as in wildcard_best_path, frames absolute: ctc_amd_long_windowed_best_path."""
+    one, as in long_best_path.  frame_window as in wildcard_best_path, frames absolute: ctc_amd_long_windowed_best_path.
+    optional_wildcards / exclude_next_label as in wildcard_best_path, on both lattices at every length (kernels and workspace of
+    their own: ctc_amd_long_optional_wildcard_best_path / ctc_amd_long_star_best_path); not with a window."""
+    if optional_wildcards and frame_window is not None:
+        raise ValueError("long_wildcard_best_path: frame_window and optional_wildcards cannot be combined")
+    if exclude_next_label and frame_window is not None:
+        raise ValueError("long_wildcard_best_path: frame_window and exclude_next_label cannot be combined")
     lib = _lib.load()
     score = torch.empty(p.B, dtype=torch.float32, device=p.device)
     tokens = torch.empty((p.B, p.T), dtype=torch.int32, device=p.device)
@@ -543,14 +550,29 @@ def long_wildcard_best_path(kind: int, wrt: int, p: Prepared, frames_per_tile: i
     out = (score, tokens, label_index, first_frame, last_frame, label_score)
     if p.B == 0:
         return out
-    key = ("long_wildcard_best_path", kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
+    own = bool(optional_wildcards or exclude_next_label)
+    key = ("long_star_best_path" if own else "long_wildcard_best_path", kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
     n = _WS_BYTES.get(key)
     if n is None:
-        n = _WS_BYTES[key] = _lib.long_wildcard_best_path_workspace_bytes(kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
+        size = _lib.long_star_best_path_workspace_bytes if own else _lib.long_wildcard_best_path_workspace_bytes
+        n = _WS_BYTES[key] = size(kind, p.B, p.T, p.V, p.U, int(frames_per_tile))
     ck = (p.device, _stream(p.device))
     ws = _WS_CACHE.get(ck)
     if ws is None or ws.numel() < n:
         ws = _WS_CACHE[ck] = torch.empty(max(n, 1), dtype=torch.uint8, device=p.device)
+    if exclude_next_label:
+        with _on_device(p.device):
+            rc = lib.ctc_amd_long_star_best_path(*p.common_ex(kind, wrt)[:11], int(bool(optional_wildcards)), p.B, p.T, p.V, p.U,
+                                                 int(frames_per_tile), *(_ptr(t) for t in out), ws.data_ptr(), ws.numel(),
+                                                 _stream(p.device))
+        _lib.check(rc, "ctc_amd_long_star_best_path")
+        return out
+    if optional_wildcards:
+        with _on_device(p.device):
+            rc = lib.ctc_amd_long_optional_wildcard_best_path(*p.common_ex(kind, wrt), int(frames_per_tile), *(_ptr(t) for t in out),
+                                                              ws.data_ptr(), ws.numel(), _stream(p.device))
+        _lib.check(rc, "ctc_amd_long_optional_wildcard_best_path")
+        return out
     if frame_window is not None:
         fw, fws = _frame_window("long_wildcard_best_path", frame_window, p.B, p.U, p.device)
         with _on_device(p.device):
