@@ -952,6 +952,34 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt,
                                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same loss and gradient from block checkpoints (added under ABI v6: two new entry points, nothing existing changed).  Arguments,
+ * results, rules (the zero rule for +inf losses, padding frames, every element written, the same bits on every run, no
+ * floating-point atomics) and validation are those of ctc_amd_wildcard_loss_grad, checked by the same code in the same order with the
+ * same messages; loss has the bits of the forward-only call; grad == NULL IS that call.  The gradient is formed by the arithmetic of
+ * ctc_amd_wildcard_loss_grad; an utterance whose d_loss is 0 gets +0 throughout.
+ * U <= 256: two launches (T == 0: the first alone).  The alpha sweep stores the chain's float64 state once per block of F = 32 / 16 / 8
+ * frames (NL = 1 / 2 / 4, blocks aligned to frame 0); ONE workgroup of six wavefronts per utterance then walks the blocks from the
+ * last to the first as a three-stage pipeline -- four wavefronts gather a block's label emissions, one re-runs alpha over it from the
+ * checkpoint into LDS, one steps beta and leaves the float32 posteriors in LDS, and the four gatherers turn the posteriors of the
+ * block before into gradient rows -- so no per-frame state or posterior reaches memory.  With S, NL and
+ * r256 as above:
+ *   ctc_amd_wildcard_loss_ckpt_workspace_bytes = r256(8 * B * ceil(T / F) * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B)
+ * -- the checkpoints, the row statistics, log2 Z.  B = 256, T = 1000, U = 128: 37.4 MB classic, 20.9 MB simplified.  want_grad == 0:
+ * 0 bytes.
+ * U > 256: the call IS ctc_amd_wildcard_loss_grad, bit for bit, and the size query returns ctc_amd_wildcard_loss_workspace_bytes.
+ * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_wildcard_loss_grad_ckpt(int kind, int wrt,
+                                    const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride,
+                                    const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                    float wildcard_log_weight, int B, int T, int V, int U,
+                                    const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
+                                    void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Long-form CTC loss and gradient: ctc_amd_wildcard_loss_grad for U <= CTC_AMD_LONG_MAX_U label positions (added under ABI v6: two
  * new entry points, nothing existing changed).  The confidence -ln P(transcript | recording) of a recording aligned with
  * ctc_amd_long_wildcard_best_path, and training on it without cutting it up.

@@ -18,6 +18,7 @@
 #include "ctc_nbest_align.h"
 #include "ctc_prefix.h"
 #include "ctc_wild_loss.h"
+#include "ctc_wild_loss_ckpt.h"
 
 namespace ctc {
 // diagnostic override read by ctc_hessian.hip (ctc_amd_debug_override): process-wide, written only by tests / benchmarks between calls
@@ -1129,8 +1130,9 @@ int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, 
 }
 
 // The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
-// One body for ctc_amd_windowed_loss_grad, ctc_amd_optional_wildcard_loss_grad and ctc_amd_star_loss_grad (which have no window).
-static int wildcard_loss_grad_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+// One body for ctc_amd_windowed_loss_grad, ctc_amd_optional_wildcard_loss_grad and ctc_amd_star_loss_grad (which have no window), and
+// for ctc_amd_wildcard_loss_grad_ckpt (ckpt: no window, star or optional wildcards), which differs in the workspace and the launcher.
+static int wildcard_loss_grad_call(bool ckpt, bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
                                    float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss, void *grad,
@@ -1142,8 +1144,13 @@ static int wildcard_loss_grad_call(bool star, bool optional_wildcards, int kind,
   if (!pre.go) return pre.rc;
   if (int rc = check_wildcard_loss(wildcard_log_weight, loss, B, T, V, grad != nullptr)) return rc;
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
-  const size_t need = ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
+  const size_t need = ckpt ? ctc::wild_loss_ckpt_workspace_bytes(kind, B, T, U, grad != nullptr) : ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
+  if (ckpt) {
+    CTC_TRY(ctc::run_wild_loss_ckpt(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+            "wildcard loss launch");
+    return CTC_AMD_OK;
+  }
   CTC_TRY((star ? ctc::run_star_loss : ctc::run_wild_loss)(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
                                                            static_cast<hipStream_t>(stream), frame_window, window_stride,
                                                            optional_wildcards), "wildcard loss launch");
@@ -1155,7 +1162,7 @@ int ctc_amd_windowed_loss_grad(int kind, int wrt, const void *logits, int logits
                                int blank_index, const int32_t *frame_window, int window_stride, float wildcard_log_weight, int B, int T,
                                int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
                                int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_loss_grad_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_loss_grad_call(false, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U,
                                  d_loss, loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
@@ -1170,7 +1177,7 @@ int ctc_amd_optional_wildcard_loss_grad(int kind, int wrt, const void *logits, i
                                         const int32_t *logit_length, int blank_index, float wildcard_log_weight, int B, int T, int V, int U,
                                         const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
                                         int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_loss_grad_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+  return wildcard_loss_grad_call(false, false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad,
                                  grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
@@ -1184,7 +1191,7 @@ int ctc_amd_star_loss_grad(int kind, int wrt, const void *logits, int logits_dty
                            int blank_index, int optional_wildcards, float wildcard_log_weight, int B, int T, int V, int U,
                            const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
                            void *workspace, size_t workspace_bytes, void *stream) {
-  return wildcard_loss_grad_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+  return wildcard_loss_grad_call(false, true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
                                  label_stride, label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss,
                                  loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
@@ -1197,6 +1204,23 @@ int ctc_amd_wildcard_loss_grad(int kind, int wrt, const void *logits, int logits
   return ctc_amd_windowed_loss_grad(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
                                     logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad, grad_dtype,
                                     grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
+}
+
+// The gradient from block checkpoints: the checks of ctc_amd_wildcard_loss_grad by the same code, another workspace and launcher.
+int ctc_amd_wildcard_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
+  if (int rc = check_query(kind, B, T, V, U, out_bytes)) return rc;
+  *out_bytes = ctc::wild_loss_ckpt_workspace_bytes(kind, B, T, U, want_grad != 0);
+  return CTC_AMD_OK;
+}
+
+int ctc_amd_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                    const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                    int blank_index, float wildcard_log_weight, int B, int T, int V, int U, const float *d_loss, float *loss,
+                                    void *grad, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+  return wildcard_loss_grad_call(true, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                                 label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad,
+                                 grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad, size_t *out_bytes) {

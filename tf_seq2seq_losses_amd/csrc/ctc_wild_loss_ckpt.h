@@ -1,0 +1,22 @@
+// Host launcher of ctc_wild_loss_ckpt.hip (wildcard CTC gradient from block checkpoints), for that unit and ctc_capi.hip.  Host
+// declarations only.
+#pragma once
+#include "ctc_wild_loss.h"
+
+namespace ctc {
+
+// Frames per checkpoint block, by label positions per lane (NL = 1, 2, 4: U <= 64, 128, 256): F * 64 * NL = 2048 lattice positions
+// per block, the most whose alpha rows, emissions and posteriors fit one workgroup's LDS twice over
+constexpr int WILD_CKPT_MAX_U = 256;
+constexpr int wild_ckpt_frames(int NL) { return 2048 / (64 * NL); }
+
+// U <= 256, with a gradient, each region rounded up to 256 bytes: the chain's float64 state BEFORE every block of F frames
+// ([B][ceil(T / F)][S * 64 * NL + 2] doubles, S = 2 classic / 1 simplified), the float32 row statistics ([B][T][4]) and log2 Z ([B]).
+// U > 256: wild_loss_workspace_bytes.  Without a gradient: 0
+size_t wild_loss_ckpt_workspace_bytes(int kind, int B, int T, int U, bool want_grad);
+// grad == nullptr or U > 256: run_wild_loss.  Otherwise two launches: the alpha sweep that stores block checkpoints, the row statistics
+// and log2 Z (the loss has the bits of the forward-only call), then the pipelined backward sweep (T == 0: the first alone)
+hipError_t run_wild_loss_ckpt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
+                              hipStream_t st);
+
+}  // namespace ctc

@@ -1,0 +1,638 @@
+// Wildcard CTC loss and gradient from block checkpoints: ctc_amd_wildcard_loss_grad_ckpt (include/ctc_amd.h), DESIGN.md section 5.32.
+// The gradient of ctc_wild_loss.hip (mandatory wildcard, no window, U <= 256) without a lattice row per frame in memory: two launches.
+//
+//   wild_ckpt_fwd_kernel  the MODE 1 alpha sweep of wild_loss_kernel (its file-local helpers and its body are repeated here; that file
+//       stays as it is) with other stores: the chain's float64 state BEFORE frame k F for every block k of F frames aligned to frame 0,
+//       the per-frame row statistics and log2 Z.  The arithmetic of the loss is the forward-only call's: the same bits.
+//   wild_ckpt_bwd_kernel  one workgroup per utterance, six wavefronts, the K = ceil(T_b / F) blocks walked from the last (partial) one
+//       down in K + 3 steps with ONE raw barrier each.  At step s
+//         producers (waves 2..5)  gather the label emissions of block K - 1 - s into the emission ring (three buffers: a block is read
+//                                 at step s + 1 by the recompute wave and at step s + 2 by the beta wave); the row statistics come
+//                                 from the workspace, the row is not read.  Then the row stage of block K + 2 - s, whose posteriors
+//                                 the beta wave finished in the previous step: wavefront pw takes frames pw, pw + 4, .. with bins of
+//                                 its own, the arithmetic of wild_grad_row_kernel;
+//         recompute (wave 1)      load checkpoint K - s, re-run the alpha step over that block's ring buffer, every frame's float64
+//                                 row (MODE 1's layout) into one of two LDS row buffers;
+//         beta (wave 0)           beta over block K + 1 - s, beta in registers, the alpha row of a frame from the LDS row buffer (read a
+//                                 frame ahead), the posteriors of MODE 2 as float32 pairs into one of two LDS posterior blocks.
+//       Nothing per frame reaches memory but the gradient row itself, which has one writer; no floating-point atomics.  The same
+//       workgroup writes the zero rows of frames t >= T_b, of infeasible utterances and of a zero d_loss.
+//
+// LDS of the backward kernel, F * UP = 2048 (F = 32 / 16 / 8 frames at NL = 1 / 2 / 4), S = 2 classic / 1 simplified:
+//   alpha rows   2 x F x (S UP + 2) doubles     66560 / 66048 / 65792 bytes classic, half of it + 2 F * 8 simplified
+//   ring         3 x F x (UP + 4) floats        26112 / 25344 / 24960
+//   posteriors   2 x F x (2 UP + 4) floats      33792 / 33280 / 33024
+//   bins         4 x 1024 x 8 bytes             32768
+//   labels       UP ints                          256 /   512 /  1024
+// at most 159488 of the 163840 bytes a gfx950 workgroup may hold: one workgroup per CU.
+#include "ctc_wild_loss_ckpt.h"
+
+#include "ctc_lane_ops.h"
+
+namespace ctc {
+namespace {
+
+constexpr int WK_PW = 4;                          // producer wavefronts (both kernels)
+constexpr int WK_FWD_THREADS = 64 * (1 + WK_PW);  // alpha sweep: + the chain
+constexpr int WK_BWD_THREADS = 64 * (2 + WK_PW);  // backward sweep: + the beta wave and the recompute wave
+constexpr int WK_RING = 4096;                     // alpha sweep: label emissions per ring buffer, as wild_loss_kernel
+constexpr int WK_CH = 1024;                       // row stage: columns per pass
+constexpr int WK_FIX = 40;                        // row stage: a posterior in units of 2^-40
+constexpr double LOG2E_D = 1.44269504088896340736;
+
+__device__ __forceinline__ float4 wk_row_load4(const char *row, int k, int dt) {
+  if (dt == 0) return *reinterpret_cast<const float4 *>(row + (size_t)k * 4);
+  const uint2 u = *reinterpret_cast<const uint2 *>(row + (size_t)k * 2);
+  return make_float4(h16_to_f32((unsigned short)(u.x & 0xffffu), dt), h16_to_f32((unsigned short)(u.x >> 16), dt),
+                     h16_to_f32((unsigned short)(u.y & 0xffffu), dt), h16_to_f32((unsigned short)(u.y >> 16), dt));
+}
+// the same four elements one by one (unaligned rows, V no multiple of 4): -inf past the row, which adds nothing to either statistic
+__device__ __forceinline__ float4 wk_row_load4_elem(const char *row, int k, int V, int dt) {
+  const float ninf = -__builtin_inff();
+  return make_float4(row_load1(row, k, dt), k + 1 < V ? row_load1(row, k + 1, dt) : ninf, k + 2 < V ? row_load1(row, k + 2, dt) : ninf,
+                     k + 3 < V ? row_load1(row, k + 3, dt) : ninf);
+}
+// running (max, sum of exp(x - max)) of one lane: four more elements (both access paths end here: identical bits)
+__device__ __forceinline__ void wk_stat_add4(float &m, float &s, const float4 v) {
+  const float mn = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+  s = s * fexp2((m - mn) * LOG2E) +
+      ((fexp2((v.x - mn) * LOG2E) + fexp2((v.y - mn) * LOG2E)) + (fexp2((v.z - mn) * LOG2E) + fexp2((v.w - mn) * LOG2E)));
+  m = mn;
+}
+
+// base-2 log(2^a + 2^b [+ 2^c]) of float64 operands that may be -inf (log 0): differences against the maximum, or against 0
+// when every operand is -inf
+__device__ __forceinline__ double wk_lse(double a, double b) {
+  const double m = fmax(a, b);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2(fexp2((float)(a - mm)) + fexp2((float)(b - mm)));
+}
+__device__ __forceinline__ double wk_lse(double a, double b, double c) {
+  const double m = fmax(fmax(a, b), c);
+  const double mm = m == -__builtin_inf() ? 0.0 : m;
+  return mm + (double)flog2((fexp2((float)(a - mm)) + fexp2((float)(b - mm))) + fexp2((float)(c - mm)));
+}
+
+struct WkWs {
+  double *ck;    // [B][ceil(T / F)][SRD] the chain's state before every block, in the layout of a MODE 1 row
+  float *stat;   // [B][T][4] x[blank], row max, log2 sum exp(x - max) of every frame
+  double *logp;  // [B] log2 Z, -inf for an infeasible utterance
+};
+constexpr int wk_row_doubles(int kind, int UP) { return (kind == 0 ? 2 : 1) * UP + 2; }
+
+// what a ring row says about its frame, in the lattice's units (base-2 logarithms of lp)
+struct WkFrame {
+  double Md, nl2s, eb, ew;
+};
+__device__ __forceinline__ WkFrame wk_frame_of(const float4 sv, bool lpin, double w2) {
+  WkFrame fr;
+  // logits: lp = x - max - ln sum; log-probabilities: lp = x
+  fr.Md = lpin ? 0.0 : (double)sv.y;
+  fr.nl2s = lpin ? 0.0 : -(double)sv.z;
+  fr.eb = fma((double)sv.x - fr.Md, LOG2E_D, fr.nl2s);
+  // e_w = w + ln sum_k exp(lp[t, k]): w for logits, w + LSE_t for log-probabilities; a row of -inf emits nothing
+  fr.ew = sv.z == __builtin_inff() ? -__builtin_inf() : lpin ? w2 + fma((double)sv.y, LOG2E_D, (double)sv.z) : w2;
+  return fr;
+}
+
+// the validated labels of utterance b: -1: no emission, WILD_LOSS_WILDCARD: a wildcard
+template <int UP, int THREADS>
+__device__ __forceinline__ void wk_labels(const Problem &p, int b, int L, int tid, int *lab_s) {
+  for (int i = tid; i < UP; i += THREADS) {
+    int tok = -1;
+    if (i < L) tok = label_at(p, label_row(p, b), i);
+    lab_s[i] = tok == WILD_LOSS_WILDCARD ? WILD_LOSS_WILDCARD : emits(p, tok) ? tok : -1;
+  }
+}
+
+// one alpha step of a lane's NL positions over a frame with label emissions e: wild_loss_kernel's `consume`, without its stores
+template <int KIND, int NL>
+__device__ __forceinline__ void wk_alpha_step(double (&O)[NL], double (&C)[NL], double &cs, const float (&e)[NL], const WkFrame &fr,
+                                              unsigned wild, unsigned allow) {
+  const double NINF = -__builtin_inf();
+  const double eb = fr.eb;
+  auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+  if (KIND == 0) {
+    const double pO = from_prev_lane(O[NL - 1], NINF);
+    const double pC = from_prev_lane(C[NL - 1], cs);
+#pragma unroll
+    for (int j = NL - 1; j >= 0; --j) {
+      const double qO = j > 0 ? O[j > 0 ? j - 1 : 0] : pO;
+      const double qC = j > 0 ? C[j > 0 ? j - 1 : 0] : pC;
+      const double a2 = ((allow >> j) & 1u) ? qO : NINF;
+      const double o = wk_lse(O[j], qC, a2) + em(j);
+      C[j] = wk_lse(C[j], O[j]) + eb;
+      O[j] = o;
+    }
+  } else {
+    const double pS = from_prev_lane(C[NL - 1], cs);
+#pragma unroll
+    for (int j = NL - 1; j >= 0; --j) {
+      const double q = j > 0 ? C[j > 0 ? j - 1 : 0] : pS;
+      C[j] = wk_lse(C[j] + (((wild >> j) & 1u) ? fr.ew : eb), q + em(j));
+    }
+  }
+  cs += eb;
+}
+
+// ---- the alpha sweep with checkpoints ----
+template <int KIND, int NL>
+__global__ __launch_bounds__(WK_FWD_THREADS) void wild_ckpt_fwd_kernel(const Problem p, const double w2, float *__restrict__ loss,
+                                                                       const WkWs ws) {
+  constexpr int UP = 64 * NL;
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
+  constexpr int SRD = wk_row_doubles(KIND, UP);
+  constexpr int F = WK_RING / UP;            // frames per ring buffer: 64, 32, 16
+  constexpr int FC = wild_ckpt_frames(NL);   // frames per checkpoint block: 32, 16, 8 (divides F)
+  constexpr int RS = UP + 4;
+  constexpr int FPW = F / WK_PW;
+  constexpr int G = FPW < 4 ? FPW : 4;
+  const double NINF = -__builtin_inf();
+
+  __shared__ __attribute__((aligned(16))) float ring[2 * F * RS];
+  __shared__ int lab_s[UP];
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = p.V, blank = p.blank, dt = p.xdtype;
+  const bool lpin = p.wrt != 0;
+  const int Tb = frame_count(p, b);
+  int L = label_count(p, b);
+  const bool too_long = too_many_labels(p, L);
+  if (too_long) L = 0;
+
+  wk_labels<UP, WK_FWD_THREADS>(p, b, L, tid, lab_s);
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0;
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    lab[j] = lab_s[lane * NL + j];
+    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+  }
+  const int esz = dt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  const bool vec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
+  const int nck = (p.T + FC - 1) / FC;
+  double *const myck = ws.ck + (size_t)b * nck * SRD;
+
+  double O[NL], C[NL];
+  unsigned allow = 0;
+  double cs = 0.0;
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    O[j] = NINF; C[j] = NINF;
+    const int i = lane * NL + j;
+    if (KIND == 0 && i > 0) {
+      const int a = lab_s[i], q = lab_s[i - 1];
+      if (a != q || a == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD) allow |= 1u << j;
+    }
+  }
+
+  auto produce = [&](int kb) {
+    const int pw = wave - 1, q0 = kb * F;
+    float *const rb = ring + (kb & 1) * F * RS;
+    for (int f0 = pw * FPW; f0 < (pw + 1) * FPW; f0 += G) {
+      if (q0 + f0 >= Tb) break;
+      const char *row[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const int q = q0 + f0 + g;  // past the utterance's end its last frame: valid memory whose results are never stored
+        row[g] = xb + (size_t)((long)(q < Tb ? q : Tb - 1) * p.xst) * esz;
+      }
+      float e[G][NL], eb[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const float v = row_load1(row[g], lab[j] >= 0 ? lab[j] : blank, dt);
+          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+        }
+        eb[g] = row_load1(row[g], blank, dt);
+      }
+      float m[G], s[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) { m[g] = -3.402823466e38f; s[g] = 0.f; }
+      for (int k = lane * 4; k < V; k += 256) {
+        float4 v[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) v[g] = vec ? wk_row_load4(row[g], k, dt) : wk_row_load4_elem(row[g], k, V, dt);
+#pragma unroll
+        for (int g = 0; g < G; ++g) wk_stat_add4(m[g], s[g], v[g]);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float M = wave_max(m[g]);
+        const float S = wave_sum(s[g] * fexp2((m[g] - M) * LOG2E));
+        float l2s = flog2(S);
+        if (!(S > 0.f)) { M = 0.f; l2s = __builtin_inff(); }  // a row of -inf: every emission of the frame is -inf
+        if (q0 + f0 + g < Tb) {
+          float *const r = rb + (f0 + g) * RS;
+#pragma unroll
+          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          if (lane == 0) {
+            *reinterpret_cast<float4 *>(r + UP) = make_float4(eb[g], M, l2s, 0.f);
+            *reinterpret_cast<float4 *>(ws.stat + ((size_t)b * p.T + q0 + f0 + g) * 4) = make_float4(eb[g], M, l2s, 0.f);
+          }
+        }
+      }
+    }
+  };
+
+  auto consume = [&](int kb) {
+    const int t0 = kb * F;
+    const int nf = Tb - t0 < F ? Tb - t0 : F;
+    const float *const rb = ring + (kb & 1) * F * RS;
+    for (int f = 0; f < nf; ++f) {
+      if ((f & (FC - 1)) == 0) {  // the state BEFORE the first frame of a checkpoint block
+        double *const r = myck + (size_t)((t0 + f) / FC) * SRD;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          if (KIND == 0) *reinterpret_cast<double2 *>(r + lane * NS + 2 * j) = make_double2(O[j], C[j]);
+          else r[lane * NS + j] = C[j];
+        }
+        if (lane == 0) r[SRD - 2] = cs;
+      }
+      const float *const rr = rb + f * RS;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
+      wk_alpha_step<KIND, NL>(O, C, cs, e, fr, wild, allow);
+    }
+  };
+
+  const int nb = (Tb + F - 1) / F;
+  if (wave > 0 && nb > 0) produce(0);
+  __syncthreads();
+  for (int kb = 0; kb < nb; ++kb) {
+    if (wave == 0) consume(kb);
+    else if (kb + 1 < nb) produce(kb + 1);
+    __syncthreads();
+  }
+
+  if (wave == 0) {
+    const int i = L - 1, jj = i & (NL - 1);
+    double cv = C[0], ov = O[0];
+#pragma unroll
+    for (int j = 1; j < NL; ++j)
+      if (j == jj) { cv = C[j]; ov = O[j]; }
+    double v = cs;
+    if (L > 0) v = KIND == 0 ? wk_lse(ov, cv) : cv;
+    if (too_long) v = NINF;
+    if (lane == (L > 0 ? i / NL : 0)) {
+      loss[b] = (float)(0.0 - v * LN2_D);  // (-inf: +inf; an empty utterance: +0)
+      ws.logp[b] = v;
+    }
+  }
+}
+
+// four consecutive elements of a gradient row from column k, in its element type; element-wise where the row is not aligned
+__device__ __forceinline__ void wk_grad_put4(char *g, int k, int V, int gdt, bool gvec, const float4 r) {
+  if (gdt == 0) {
+    if (gvec) { *reinterpret_cast<float4 *>(g + (size_t)k * 4) = r; return; }
+    float *const o = reinterpret_cast<float *>(g);
+    o[k] = r.x;
+    if (k + 1 < V) o[k + 1] = r.y;
+    if (k + 2 < V) o[k + 2] = r.z;
+    if (k + 3 < V) o[k + 3] = r.w;
+    return;
+  }
+  auto cv = [&](float f) { return gdt == 1 ? f32_to_bf16(f) : f32_to_f16(f); };
+  const unsigned short h0 = cv(r.x), h1 = cv(r.y), h2 = cv(r.z), h3 = cv(r.w);
+  if (gvec) {
+    *reinterpret_cast<uint2 *>(g + (size_t)k * 2) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2 | ((unsigned)h3 << 16));
+    return;
+  }
+  unsigned short *const o = reinterpret_cast<unsigned short *>(g);
+  o[k] = h0;
+  if (k + 1 < V) o[k + 1] = h1;
+  if (k + 2 < V) o[k + 2] = h2;
+  if (k + 3 < V) o[k + 3] = h3;
+}
+
+// ---- the pipelined backward sweep ----
+template <int KIND, int NL>
+__global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_bwd_kernel(const Problem p, const double w2, const float *__restrict__ d_loss,
+                                                                       const WkWs ws, void *__restrict__ grad) {
+  constexpr int UP = 64 * NL;
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
+  constexpr int SRD = wk_row_doubles(KIND, UP);
+  constexpr int F = wild_ckpt_frames(NL);
+  constexpr int RS = UP + 4;      // ring row: UP label emissions, then the frame's statistics
+  constexpr int PR = 2 * UP + 4;  // posterior row: a float32 pair per position, then the start state's blank posterior
+  constexpr int FPW = F / WK_PW;  // frames per producer wavefront and block: 8, 4, 2
+  constexpr int G = FPW < 4 ? FPW : 4;
+  static_assert(F >= 4 && F % WK_PW == 0, "every producer wavefront takes whole frames of a block");
+  const double NINF = -__builtin_inf();
+
+  __shared__ __attribute__((aligned(16))) double arow[2 * F * SRD];
+  __shared__ __attribute__((aligned(16))) float ring[3 * F * RS];
+  __shared__ __attribute__((aligned(16))) float pst[2 * F * PR];
+  __shared__ unsigned long long bins_all[WK_PW][WK_CH];
+  __shared__ int lab_s[UP];
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = p.V, blank = p.blank, dt = p.xdtype, gdt = p.gdtype;
+  const bool lpin = p.wrt != 0;
+  const int Tb = frame_count(p, b);
+  const int esz = dt == 0 ? 4 : 2, gesz = gdt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  char *const gb = reinterpret_cast<char *>(grad) + (size_t)((long)b * p.gsb) * gesz;
+  const bool xvec = ((V | p.xsb | p.xst) & 3) == 0 && (reinterpret_cast<uintptr_t>(p.logits) & (dt == 0 ? 15 : 7)) == 0;
+  const bool gvec = ((V | p.gsb | p.gst) & 3) == 0 && (reinterpret_cast<uintptr_t>(grad) & (gdt == 0 ? 15 : 7)) == 0;
+
+  // an infinite loss contributes nothing and its d_loss is not interpreted; a weight of zero: +0 throughout
+  const double lP = ws.logp[b];
+  const bool feasible = lP > NINF && lP < -NINF;
+  const float dl = d_loss ? d_loss[b] : 1.f;
+  // padded frames, every frame of an infeasible utterance or of a zero weight: exactly zero
+  const int Tz = (feasible && dl != 0.f) ? Tb : 0;
+  for (int t = Tz + wave; t < p.T; t += WK_BWD_THREADS / 64) {
+    char *const g = gb + (size_t)((long)t * p.gst) * gesz;
+    for (int k = lane * 4; k < V; k += 256) wk_grad_put4(g, k, V, gdt, gvec, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
+  if (Tz == 0) return;  // (the same verdict in every wavefront: nobody waits at a barrier)
+
+  const int L = label_count(p, b);  // (feasible: L <= U <= UP)
+  wk_labels<UP, WK_BWD_THREADS>(p, b, L, tid, lab_s);
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0, allow = 0;
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    const int i = lane * NL + j;
+    lab[j] = lab_s[i];
+    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+    if (KIND == 0 && i > 0) {
+      const int q = lab_s[i - 1];
+      if (lab[j] != q || lab[j] == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD) allow |= 1u << j;
+    }
+  }
+  const int allow_nx = KIND == 0 ? fused::from_next_lane_i((int)(allow & 1u), 0) : 0;
+
+  const int K = (Tb + F - 1) / F;       // blocks of the utterance
+  const int nck = (p.T + F - 1) / F;    // checkpoint rows per utterance
+  auto frames_of = [&](int kb) { return Tb - kb * F < F ? Tb - kb * F : F; };
+
+  // ---- producers, first job: the emissions of block kb into its ring buffer, its statistics from the workspace ----
+  auto gather = [&](int kb) {
+    const int pw = wave - 2, t0 = kb * F;
+    float *const rb = ring + (kb % 3) * F * RS;
+    for (int f0 = pw * FPW; f0 < (pw + 1) * FPW; f0 += G) {
+      if (t0 + f0 >= Tb) break;
+      float e[G][NL];
+      float4 sv[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const int q = t0 + f0 + g, t = q < Tb ? q : Tb - 1;  // past the utterance's end its last frame: never stored
+        const char *const row = xb + (size_t)((long)t * p.xst) * esz;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const float v = row_load1(row, lab[j] >= 0 ? lab[j] : blank, dt);
+          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+        }
+        sv[g] = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (t0 + f0 + g < Tb) {
+          float *const r = rb + (f0 + g) * RS;
+#pragma unroll
+          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          if (lane == 0) *reinterpret_cast<float4 *>(r + UP) = sv[g];
+        }
+      }
+    }
+  };
+
+  // ---- producers, second job: the row stage of block kb from its posterior block; wild_grad_row_kernel's arithmetic ----
+  auto rows = [&](int kb) {
+    const int pw = wave - 2, nf = frames_of(kb);
+    unsigned long long *const bins = bins_all[pw];
+    for (int f = pw; f < nf; f += WK_PW) {
+      const int t = kb * F + f;
+      const float *const pr = pst + ((kb & 1) * F + f) * PR;
+      const char *const x = xb + (size_t)((long)t * p.xst) * esz;
+      char *const g = gb + (size_t)((long)t * p.gst) * gesz;
+      const float4 sv = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
+      const float mx = sv.y, l2s = sv.z;
+      float blk = 0.f, gam = 0.f;  // the blank's share and Gamma_t, lane-wise partial sums in a fixed order
+      for (int c0 = 0; c0 < V; c0 += WK_CH) {
+#pragma unroll
+        for (int q = 0; q < WK_CH / 64; ++q) bins[lane + 64 * q] = 0ull;
+        wave_lds_fence();
+        for (int i = lane; i < L; i += 64) {
+          const float2 pq = *reinterpret_cast<const float2 *>(pr + 2 * i);
+          const int tok = lab_s[i];  // (-1: no emission)
+          const bool w = tok == WILD_LOSS_WILDCARD;
+          const unsigned rel = (unsigned)(tok - c0);
+          if (tok >= 0 && rel < (unsigned)WK_CH)
+            atomicAdd(&bins[rel], (unsigned long long)__float2ll_rn(__builtin_ldexpf(pq.x, WK_FIX)));
+          if (c0 == 0) {
+            if (w) gam += pq.x;
+            if (KIND == 1 && w) gam += pq.y;
+            else blk += pq.y;
+          }
+        }
+        if (c0 == 0) {
+          if (lane == 0) blk += pr[2 * UP];
+          blk = wave_sum(blk);
+          gam = wave_sum(gam);
+        }
+        wave_lds_fence();
+        // logits: (1 - Gamma) softmax - gamma;  log-probabilities: -Gamma exp(x - LSE) - gamma
+        const float c = !lpin ? 1.f - gam : -gam;
+#pragma unroll
+        for (int q = 0; q < WK_CH / 256; ++q) {
+          const int k = c0 + lane * 4 + 256 * q;
+          if (k < V) {
+            const float4 xv = xvec ? wk_row_load4(x, k, dt) : wk_row_load4_elem(x, k, V, dt);
+            float o[4];
+            const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+              const float bin = __builtin_ldexpf(__ll2float_rn((long long)bins[k - c0 + cc]), -WK_FIX) + (k + cc == blank ? blk : 0.f);
+              const float sm = c == 0.f ? 0.f : c * fexp2((xs[cc] - mx) * LOG2E - l2s);
+              o[cc] = dl * (sm - bin);
+            }
+            wk_grad_put4(g, k, V, gdt, gvec, make_float4(o[0], o[1], o[2], o[3]));
+          }
+        }
+        wave_lds_fence();
+      }
+    }
+  };
+
+  // ---- recompute wave: alpha over block kb from its checkpoint, every frame's row into the block's LDS row buffer ----
+  auto recompute = [&](int kb) {
+    const double *const r = ws.ck + ((size_t)b * nck + kb) * SRD;
+    double O[NL], C[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      if (KIND == 0) {
+        const double2 v = *reinterpret_cast<const double2 *>(r + lane * NS + 2 * j);
+        O[j] = v.x; C[j] = v.y;
+      } else {
+        O[j] = NINF; C[j] = r[lane * NS + j];
+      }
+    }
+    double cs = r[SRD - 2];
+    const int nf = frames_of(kb);
+    const float *const rb = ring + (kb % 3) * F * RS;
+    double *const ab = arow + (size_t)(kb & 1) * F * SRD;
+    for (int f = 0; f < nf; ++f) {
+      const float *const rr = rb + f * RS;
+      double *const a = ab + f * SRD;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
+      if (KIND == 1) {  // the state BEFORE the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) a[lane * NS + j] = C[j];
+        if (lane == 0) a[SRD - 2] = cs;
+      }
+      wk_alpha_step<KIND, NL>(O, C, cs, e, fr, wild, allow);
+      if (KIND == 0) {  // the state AFTER the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) *reinterpret_cast<double2 *>(a + lane * NS + 2 * j) = make_double2(O[j], C[j]);
+        if (lane == 0) a[SRD - 2] = cs;
+      }
+    }
+  };
+
+  // ---- beta wave: the posteriors of block kb's frames, last first, and beta back over each; wild_loss_kernel's MODE 2 ----
+  double bO[NL], bC[NL];  // beta: the mass of the frames still to come; behind the last frame only the end states have any
+#pragma unroll
+  for (int j = 0; j < NL; ++j) bO[j] = bC[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
+  double bcs = L == 0 ? 0.0 : NINF;
+  auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+  auto beta_block = [&](int kb) {
+    const int nf = frames_of(kb);
+    const float *const rb = ring + (kb % 3) * F * RS;
+    const double *const ab = arow + (size_t)(kb & 1) * F * SRD;
+    float *const pb = pst + (size_t)(kb & 1) * F * PR;
+    double An[NS], Acsn;
+    auto load_row = [&](int f) {
+      const double *const a = ab + f * SRD;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) An[q] = a[lane * NS + q];
+      Acsn = a[SRD - 2];
+    };
+    load_row(nf - 1);
+    for (int f = nf - 1; f >= 0; --f) {
+      const float *const rr = rb + f * RS;
+      float *const o = pb + f * PR;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
+      const double eb = fr.eb;
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      double A[NS];
+#pragma unroll
+      for (int q = 0; q < NS; ++q) A[q] = An[q];
+      const double Acs = Acsn;
+      if (f > 0) load_row(f - 1);  // the next frame's row, a frame ahead
+      if (KIND == 0) {
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+          *reinterpret_cast<float2 *>(o + 2 * (lane * NL + j)) = make_float2(post(A[2 * j] + bO[j]), post(A[2 * j + 1] + bC[j]));
+        if (lane == 0) o[2 * UP] = post(Acs + bcs);
+        double x = bO[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? bO[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+          const double cb = bC[j] + eb;
+          bO[j] = wk_lse(x, cb, al ? xn : NINF);
+          bC[j] = wk_lse(cb, xn);
+          x = xn;
+        }
+      } else {
+        const double ap0 = from_prev_lane(A[NL - 1], Acs);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          const double h = ((wild >> j) & 1u) ? fr.ew : eb;
+          *reinterpret_cast<float2 *>(o + 2 * (lane * NL + j)) = make_float2(post(ap + em(j) + bC[j]), post(A[j] + h + bC[j]));
+        }
+        if (lane == 0) o[2 * UP] = post(Acs + eb + bcs);
+        double x = bC[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? bC[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          bC[j] = wk_lse(bC[j] + (((wild >> j) & 1u) ? fr.ew : eb), xn);
+          x = xn;
+        }
+      }
+    }
+  };
+
+  // every wavefront derives the same K: the barrier counts match by construction
+  for (int s = 0; s <= K + 2; ++s) {
+    if (wave == 0) {
+      const int kb = K + 1 - s;
+      if (kb >= 0 && kb < K) beta_block(kb);
+    } else if (wave == 1) {
+      const int kb = K - s;
+      if (kb >= 0 && kb < K) recompute(kb);
+    } else {
+      const int kg = K - 1 - s, kr = K + 2 - s;
+      if (kg >= 0) gather(kg);
+      if (kr >= 0 && kr < K) rows(kr);
+    }
+    fused::block_barrier();
+  }
+}
+
+template <int KIND, int NL>
+hipError_t launch_wild_ckpt(const Problem &p, double w2, const float *d_loss, float *loss, void *grad, const WkWs &ws, hipStream_t st) {
+  hipLaunchKernelGGL((wild_ckpt_fwd_kernel<KIND, NL>), dim3(p.B), dim3(WK_FWD_THREADS), 0, st, p, w2, loss, ws);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (p.T == 0) return hipSuccess;  // no rows
+  hipLaunchKernelGGL((wild_ckpt_bwd_kernel<KIND, NL>), dim3(p.B), dim3(WK_BWD_THREADS), 0, st, p, w2, d_loss, ws, grad);
+  return hipGetLastError();
+}
+
+inline size_t wk_al(size_t x) { return (x + 255) & ~size_t(255); }
+inline bool wk_tier(int U) { return U <= WILD_CKPT_MAX_U; }
+inline size_t wk_ck_bytes(int kind, int B, int T, int U) {
+  const int NL = nl_for(U), F = wild_ckpt_frames(NL);
+  return (size_t)B * ((T + F - 1) / F) * wk_row_doubles(kind, 64 * NL) * 8;
+}
+
+}  // namespace
+
+// checkpoints, then the row statistics, then log2 Z: each region rounded up to 256 bytes (include/ctc_amd.h has the formula)
+size_t wild_loss_ckpt_workspace_bytes(int kind, int B, int T, int U, bool want_grad) {
+  if (!want_grad) return 0;
+  if (!wk_tier(U)) return wild_loss_workspace_bytes(kind, B, T, U, true);
+  return wk_al(wk_ck_bytes(kind, B, T, U)) + wk_al((size_t)B * T * 16) + wk_al((size_t)B * 8);
+}
+
+hipError_t run_wild_loss_ckpt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
+                              hipStream_t st) {
+  if (!grad || !wk_tier(p.U)) return run_wild_loss(p, wildcard_log_weight, d_loss, loss, grad, wsp, st);
+  typedef hipError_t Launch(const Problem &, double, const float *, float *, void *, const WkWs &, hipStream_t);
+  static Launch *const table[2][3] = {{launch_wild_ckpt<0, 1>, launch_wild_ckpt<0, 2>, launch_wild_ckpt<0, 4>},
+                                      {launch_wild_ckpt<1, 1>, launch_wild_ckpt<1, 2>, launch_wild_ckpt<1, 4>}};
+  const int NL = nl_for(p.U);
+  if (p.kind < 0 || p.kind > 1 || NL > 4) return hipErrorInvalidValue;
+  const size_t ck = wk_al(wk_ck_bytes(p.kind, p.B, p.T, p.U));
+  const WkWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + ck),
+                reinterpret_cast<double *>(wsp + ck + wk_al((size_t)p.B * p.T * 16))};
+  return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, d_loss, loss, grad, ws, st);
+}
+
+}  // namespace ctc

@@ -538,9 +538,10 @@ class _WildcardLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, frame_window, optional_wildcards=False,
-                exclude_next_label=False):
+                exclude_next_label=False, checkpoint=False):
         ctx.save_for_backward(x, labels, label_length, logit_length)
         ctx.call = (kind, wrt, blank, U, weight)
+        ctx.checkpoint = {"checkpoint": True} if checkpoint else {}  # (the backward call alone: forward keeps no workspace)
         ctx.window = {} if frame_window is None else {"frame_window": frame_window}  # (no window: the call as it always was)
         if optional_wildcards:
             ctx.window["optional_wildcards"] = True
@@ -555,8 +556,8 @@ class _WildcardLossFn(torch.autograd.Function):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U, weight = ctx.call
         _, grad = ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
-                                         wildcard_log_weight=weight, **ctx.window)
-        return grad, None, None, None, None, None, None, None, None, None, None, None
+                                         wildcard_log_weight=weight, **ctx.window, **ctx.checkpoint)
+        return grad, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _no_window_with_optional(frame_window, optional_wildcards):
@@ -570,7 +571,8 @@ def _no_window_with_exclusion(frame_window, exclude_next_label):
 
 
 def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
-                   max_label_length=None, frame_window=None, optional_wildcards=False, exclude_next_label=False) -> torch.Tensor:
+                   max_label_length=None, frame_window=None, optional_wildcards=False, exclude_next_label=False,
+                   checkpoint=False) -> torch.Tensor:
     _no_window_with_optional(frame_window, optional_wildcards)
     _no_window_with_exclusion(frame_window, exclude_next_label)
     x = _as_tensor(x)
@@ -592,7 +594,7 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
         window["exclude_next_label"] = True
     if x.requires_grad and torch.is_grad_enabled():
         return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight,
-                                     window.get("frame_window"), bool(optional_wildcards), bool(exclude_next_label))
+                                     window.get("frame_window"), bool(optional_wildcards), bool(exclude_next_label), bool(checkpoint))
     with torch.no_grad():  # forward only: the result is detached
         return ops.wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
                                       wildcard_log_weight=weight, want_grad=False, **window)[0]
@@ -601,7 +603,8 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
 def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                               blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                               max_label_length: Optional[int] = None, frame_window=None,
-                              optional_wildcards: bool = False, exclude_next_label: bool = False) -> torch.Tensor:
+                              optional_wildcards: bool = False, exclude_next_label: bool = False,
+                              checkpoint: bool = False) -> torch.Tensor:
     """CTC loss of a partial transcript on the classic lattice (wildcard CTC / star temporal classification).  As classic_ctc_loss,
     but a label equal to WILDCARD (-2) stands for any non-empty run of frames with any tokens on them: the lattice of
     classic_ctc_wildcard_alignment, summed over all its paths instead of maximised.  Returns loss [batch] float32 = -ln Z, with a
@@ -622,30 +625,39 @@ def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_leng
     exclude_next_label=True is the star of star temporal classification as published (<star>\\y): a wildcard (either kind) followed
     by an ordinary label y emits every token except y, wildcard_log_weight + ln(1 - p_t(y)) per frame, so it cannot swallow frames
     that show the label behind it.  A wildcard that is last or followed by another wildcard excludes nothing; without such a
-    wildcard the result has the bits of the call without the keyword.  Not with frame_window (ValueError)."""
+    wildcard the result has the bits of the call without the keyword.  Not with frame_window (ValueError).
+    checkpoint=True takes the gradient from block checkpoints (ctc_amd_wildcard_loss_grad_ckpt): for max_label_length <= 256 the
+    backward call keeps one lattice row per block of 32 / 16 / 8 frames instead of one per frame (a workspace 14 times smaller at
+    1000 frames and 128 labels) and hands the rows and posteriors of a block from wavefront to wavefront on chip.  The loss has the
+    same bits, the gradient meets the same bars (a zero incoming gradient gives +0 throughout).  Above 256 labels, and together with
+    frame_window, optional_wildcards=True or exclude_next_label=True, the keyword is accepted and the call is that of
+    checkpoint=False, bit for bit: the checkpointed form of those kernels is owed."""
     return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                          max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 def simplified_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                  blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                                  max_label_length: Optional[int] = None, frame_window=None,
-                                 optional_wildcards: bool = False, exclude_next_label: bool = False) -> torch.Tensor:
+                                 optional_wildcards: bool = False, exclude_next_label: bool = False,
+                                 checkpoint: bool = False) -> torch.Tensor:
     """The same on the simplified lattice: entering a wildcard and every stay behind it emit the wildcard's weight instead of a
-    token's or the blank's probability.  Same arguments and return value as classic_ctc_wildcard_loss."""
+    token's or the blank's probability.  Same arguments and return value as classic_ctc_wildcard_loss (checkpoint=True: owed with
+    frame_window, optional_wildcards and exclude_next_label, where the call is that of checkpoint=False)."""
     return _wildcard_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                          max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                          max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                     wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
                                     frame_window=None, optional_wildcards: bool = False,
-                                    exclude_next_label: bool = False) -> torch.Tensor:
+                                    exclude_next_label: bool = False, checkpoint: bool = False) -> torch.Tensor:
     """The same for log-probabilities used as they stand: a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]);
-    ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas."""
+    ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas.
+    checkpoint=True as in classic_ctc_wildcard_loss (owed with frame_window, optional_wildcards and exclude_next_label)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                          wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                          wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -760,7 +760,8 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
                        blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None,
                        grad_dtype: Optional[torch.dtype] = None, wildcard_log_weight: float = 0.0,
                        want_grad: bool = True, frame_window: Optional[torch.Tensor] = None,
-                       optional_wildcards: bool = False, exclude_next_label: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                       optional_wildcards: bool = False, exclude_next_label: bool = False,
+                       checkpoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """(loss[B] float32, grad[B, T, V] or None): the CTC loss of transcripts whose labels may be wildcards (_lib.WILDCARD), summed
     over all paths of the lattice, and its gradient times d_loss[b] (default: ones) with respect to x (ctc_amd_wildcard_loss_grad).
     want_grad=False is the forward-only launch and returns None for the gradient.  An utterance whose loss is +inf gets a zero
@@ -770,7 +771,10 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
     frame_window [B, U, 2] (first, last inclusive per label position): ctc_amd_windowed_loss_grad.  optional_wildcards: labels may
     also hold _lib.OPTIONAL_WILDCARD, a wildcard that may be empty (ctc_amd_optional_wildcard_loss_grad; not with a window).
     exclude_next_label: a wildcard of either kind emits every token but the ordinary label that follows it (ctc_amd_star_loss_grad;
-    not with a window).  Does not synchronise."""
+    not with a window).  checkpoint: the gradient from block checkpoints (ctc_amd_wildcard_loss_grad_ckpt: for U <= 256 a
+    workspace of one lattice row per block of 32 / 16 / 8 frames instead of one per frame, the same loss bits, a gradient to the
+    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (their
+    checkpointed kernels are owed).  Does not synchronise."""
     if optional_wildcards and frame_window is not None:
         raise ValueError("wildcard_loss_grad: frame_window and optional_wildcards cannot be combined")
     if exclude_next_label and frame_window is not None:
@@ -792,10 +796,11 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
     if grad_dtype not in _DTYPES:
         raise ValueError(f"wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
     with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
-    key = ("wildcard_loss_grad", kind, B, T, V, U, with_grad)
+    ckpt = bool(checkpoint) and frame_window is None and not optional_wildcards and not exclude_next_label
+    key = ("wildcard_loss_grad_ckpt" if ckpt else "wildcard_loss_grad", kind, B, T, V, U, with_grad)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = _lib.wildcard_loss_workspace_bytes(kind, B, T, V, U, with_grad)
+        n = _WS_BYTES[key] = (_lib.wildcard_loss_ckpt_workspace_bytes if ckpt else _lib.wildcard_loss_workspace_bytes)(kind, B, T, V, U, with_grad)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
     if B == 0:
@@ -826,6 +831,14 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
                                                          B, T, V, U, _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
                                                          _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
         _lib.check(rc, "ctc_amd_optional_wildcard_loss_grad")
+        return loss, grad
+    if ckpt:
+        with _on_device(dev):
+            rc = lib.ctc_amd_wildcard_loss_grad_ckpt(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                     _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight),
+                                                     B, T, V, U, _ptr(d_loss), _ptr(loss), _ptr(grad) if with_grad else None,
+                                                     _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n, _stream(dev))
+        _lib.check(rc, "ctc_amd_wildcard_loss_grad_ckpt")
         return loss, grad
     with _on_device(dev):
         rc = lib.ctc_amd_wildcard_loss_grad(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
