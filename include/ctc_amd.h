@@ -1142,6 +1142,40 @@ int ctc_amd_label_posterior(int kind, int wrt,
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same label posteriors from block checkpoints (added under ABI v6: two new entry points, nothing existing changed).  Arguments,
+ * the meaning of all five outputs, every rule (every element written, zeros from T_b and from L on, -1 in expected_frame where
+ * duration is 0, from L on and for infeasible utterances, blank_posterior exactly 1 for t < T_b when label_length == 0, the same bits
+ * on every run, no atomics) and the validation are those of ctc_amd_label_posterior, checked by the same code in the same order with
+ * the same messages; loss has the bits of the forward-only ctc_amd_wildcard_loss_grad.  A posterior is formed by the arithmetic of
+ * ctc_amd_label_posterior (the float32 exp2 of a float64 difference); blank_posterior is summed in another fixed order (per lane
+ * over its positions i, i + 64, .., the start state first in lane 0, then over the wavefront), so its last bit may differ.
+ * U <= 256: two launches, also when T == 0.  Launch 1 is the alpha sweep of ctc_amd_wildcard_loss_grad_ckpt: the chain's float64 state
+ * once per block of F = 32 / 16 / 8 frames (NL = 1 / 2 / 4), the row statistics, log2 Z.  Launch 2: ONE workgroup of six wavefronts
+ * per utterance walks the blocks from the last to the first -- four wavefronts gather a block's label emissions, one re-runs alpha
+ * over it from the checkpoint into LDS, one steps beta and leaves the float32 posteriors in LDS, and the four gatherers write the
+ * posteriors of the block before: a frame's U floats as one contiguous run, its blank_posterior, and the statistics (DESIGN.md
+ * section 5.33).  No per-frame state reaches memory and the matrix is not read back.
+ * duration and expected_frame keep their definition (float64 reductions of the float32 values the call returns, the quotient in
+ * float64 of the two unrounded sums, one rounding each) in another fixed order: writer w = 0 .. 3 sums the frames t = w (mod 4) of
+ * the utterance, blocks of F frames from the last down and the frames of a block upwards; the four sums are then added in the order
+ * of w.  The order depends on T_b alone.  duration == NULL: no statistics work, the other outputs keep their bits.
+ *   ctc_amd_label_posterior_ckpt_workspace_bytes = ctc_amd_wildcard_loss_ckpt_workspace_bytes(want_grad = 1)
+ *                                                = r256(8 * B * ceil(T / F) * (S * 64 * NL + 2)) + r256(16 * B * T) + r256(8 * B)
+ * B = 256, T = 1000, U = 128: 37.4 MB classic against the 532 MB of ctc_amd_label_posterior_workspace_bytes.
+ * U > 256: the call IS ctc_amd_label_posterior, bit for bit, and the size query returns ctc_amd_label_posterior_workspace_bytes.
+ * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_label_posterior_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes /*host*/);
+int ctc_amd_label_posterior_ckpt(int kind, int wrt,
+                                 const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride,
+                                 const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                 float wildcard_log_weight, int B, int T, int V, int U,
+                                 float *loss /* [B] */, float *label_posterior /* [B][T][U] */, float *blank_posterior /* [B][T] */,
+                                 float *duration /* [B][U], may be NULL */, float *expected_frame /* [B][U], may be NULL */,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Long-form label posteriors: ctc_amd_label_posterior for U <= CTC_AMD_LONG_MAX_U label positions, and a per-label confidence that
  * needs no [B][T][U] matrix (added under ABI v6: two new entry points, nothing existing changed).  Which stretches of a ten-minute
  * or one-hour alignment to trust: the best path of ctc_amd_long_wildcard_best_path cannot say, the posteriors can.

@@ -117,6 +117,9 @@ SIGNATURES = {
     "ctc_amd_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +       # .. blank_index, wildcard_log_weight, B, T, V, U
                                 [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,             # loss, label_posterior, blank_posterior, duration, expected_frame
                                  _c_void_p, _c_size_t, _c_void_p]),                                 # ws, bytes, stream
+    "ctc_amd_label_posterior_ckpt_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
+    "ctc_amd_label_posterior_ckpt": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # as ctc_amd_label_posterior
+                                     [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_long_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, frames_per_tile
     "ctc_amd_long_label_posterior": (_c_int, _COMMON_EX[:11] + [ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, wildcard_log_weight, B, T, V, U
                                      [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # frames_per_tile, loss, label_posterior, blank_posterior, duration, expected_frame
@@ -387,6 +390,13 @@ def long_wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U
 def label_posterior_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
     out = _c_size_t(0)
     check(load().ctc_amd_label_posterior_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)), "ctc_amd_label_posterior_workspace_bytes")
+    return int(out.value)
+
+
+def label_posterior_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U: int) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_label_posterior_ckpt_workspace_bytes(kind, B, T, V, U, ctypes.byref(out)),
+          "ctc_amd_label_posterior_ckpt_workspace_bytes")
     return int(out.value)
 
 

@@ -1368,8 +1368,9 @@ int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U
 }
 
 // One body for ctc_amd_windowed_label_posterior, ctc_amd_optional_wildcard_label_posterior and ctc_amd_star_label_posterior (which
-// have no window).
-static int label_posterior_call(bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+// have no window), and for ctc_amd_label_posterior_ckpt (ckpt: no window, star or optional wildcards), which differs in the workspace
+// and the launcher.
+static int label_posterior_call(bool ckpt, bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                 int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                 const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
                                 float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
@@ -1385,7 +1386,13 @@ static int label_posterior_call(bool star, bool optional_wildcards, int kind, in
   if (!duration != !expected_frame) return fail(CTC_AMD_EINVAL, "duration and expected_frame must both be given or both be NULL");
   if (int rc = check_vocab(V, " of the label posteriors")) return rc;
   if (int rc = check_window(frame_window, window_stride, U)) return rc;
-  if (int rc = check_workspace(workspace, workspace_bytes, ctc::wild_loss_workspace_bytes(kind, B, T, U, true), NullWs::Refused)) return rc;
+  const size_t need = ckpt ? ctc::wild_loss_ckpt_workspace_bytes(kind, B, T, U, true) : ctc::wild_loss_workspace_bytes(kind, B, T, U, true);
+  if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::Refused)) return rc;
+  if (ckpt) {
+    CTC_TRY(ctc::run_label_posterior_ckpt(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+                                          static_cast<char *>(workspace), static_cast<hipStream_t>(stream)), "label posterior launch");
+    return CTC_AMD_OK;
+  }
   CTC_TRY((star ? ctc::run_star_label_posterior : ctc::run_label_posterior)(pre.p, wildcard_log_weight, loss, label_posterior,
                                                                             blank_posterior, duration, expected_frame,
                                                                             static_cast<char *>(workspace), static_cast<hipStream_t>(stream),
@@ -1400,7 +1407,7 @@ int ctc_amd_windowed_label_posterior(int kind, int wrt, const void *logits, int 
                                      float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
                                      float *blank_posterior, float *duration, float *expected_frame, void *workspace,
                                      size_t workspace_bytes, void *stream) {
-  return label_posterior_call(false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+  return label_posterior_call(false, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
                               logit_length, blank_index, frame_window, window_stride, wildcard_log_weight, B, T, V, U, loss,
                               label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
@@ -1415,7 +1422,7 @@ int ctc_amd_optional_wildcard_label_posterior(int kind, int wrt, const void *log
                                               float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
                                               float *blank_posterior, float *duration, float *expected_frame, void *workspace,
                                               size_t workspace_bytes, void *stream) {
-  return label_posterior_call(false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
+  return label_posterior_call(false, false, true, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride, label_length,
                               logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss, label_posterior,
                               blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
@@ -1429,7 +1436,7 @@ int ctc_amd_star_label_posterior(int kind, int wrt, const void *logits, int logi
                                  int blank_index, int optional_wildcards, float wildcard_log_weight, int B, int T, int V, int U, float *loss,
                                  float *label_posterior, float *blank_posterior, float *duration, float *expected_frame, void *workspace,
                                  size_t workspace_bytes, void *stream) {
-  return label_posterior_call(true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
+  return label_posterior_call(false, true, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels,
                               label_stride, label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss,
                               label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
@@ -1442,6 +1449,21 @@ int ctc_amd_label_posterior(int kind, int wrt, const void *logits, int logits_dt
   return ctc_amd_windowed_label_posterior(kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                           label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss,
                                           label_posterior, blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
+}
+
+// Label posteriors from block checkpoints: the checks of ctc_amd_label_posterior by the same code, another workspace and launcher.
+int ctc_amd_label_posterior_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, size_t *out_bytes) {
+  return ctc_amd_wildcard_loss_ckpt_workspace_bytes(kind, B, T, V, U, 1, out_bytes);
+}
+
+int ctc_amd_label_posterior_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                 const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                 int blank_index, float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                 float *blank_posterior, float *duration, float *expected_frame, void *workspace, size_t workspace_bytes,
+                                 void *stream) {
+  return label_posterior_call(true, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
+                              label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss, label_posterior,
+                              blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
 }
 
 int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {

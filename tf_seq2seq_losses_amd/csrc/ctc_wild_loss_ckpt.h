@@ -18,5 +18,10 @@ size_t wild_loss_ckpt_workspace_bytes(int kind, int B, int T, int U, bool want_g
 // and log2 Z (the loss has the bits of the forward-only call), then the pipelined backward sweep (T == 0: the first alone)
 hipError_t run_wild_loss_ckpt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
                               hipStream_t st);
+// ctc_amd_label_posterior_ckpt: `ws` is a workspace of wild_loss_ckpt_workspace_bytes(want_grad = true).  U > 256: run_label_posterior.
+// Otherwise two launches: the same alpha sweep, then the backward pipeline whose last stage writes label_posterior [B][T][U],
+// blank_posterior [B][T] and, when duration is given, duration / expected_frame [B][U]; no per-frame row and no second read of the matrix
+hipError_t run_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+                                    float *duration, float *expected_frame, char *ws, hipStream_t st);
 
 }  // namespace ctc

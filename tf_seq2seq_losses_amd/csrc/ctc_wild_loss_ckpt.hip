@@ -25,6 +25,19 @@
 //   bins         4 x 1024 x 8 bytes             32768
 //   labels       UP ints                          256 /   512 /  1024
 // at most 159488 of the 163840 bytes a gfx950 workgroup may hold: one workgroup per CU.
+//
+// Label posteriors from the same checkpoints: ctc_amd_label_posterior_ckpt, DESIGN.md section 5.33.  Launch 1 is wild_ckpt_fwd_kernel.
+//   wild_ckpt_post_kernel  the backward pipeline above (the same steps, barriers, gather, recompute and beta recursion) whose beta
+//       wave leaves MODE 3's split in LDS -- per frame a plane of the labels' shares and a plane of the blank's, then the start
+//       state's -- and whose producers' second job is a posterior writer: wavefront pw takes frames pw, pw + 4, .. of the block the
+//       beta wave finished in the step before, lane l positions l, l + 64, ..: label_posterior[b, t, 0..U) as one contiguous run,
+//       blank_posterior[b, t] summed over the wavefront in a fixed order, and the float32 values just written added to the lane's
+//       float64 sums of duration and t * posterior.  The four writers' sums meet in LDS after the last step; the quotient is taken
+//       in float64 and rounded once.  No statistics launch, no second read of the matrix, no atomics.
+// LDS of the posterior kernel: alpha rows, ring and labels as above, and
+//   posteriors   2 x F x (UP + UP + 4) floats   33792 / 33280 / 33024
+//   partials     2 x 4 x UP doubles              4096 /  8192 / 16384
+// 130816 / 133376 / 141184 bytes classic; the rest of the bins' 32 KB is left unused (deeper buffers would not shorten the beta chain).
 #include "ctc_wild_loss_ckpt.h"
 
 #include "ctc_lane_ops.h"
@@ -596,6 +609,319 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_bwd_kernel(const Pro
   }
 }
 
+// ---- label posteriors from the same checkpoints: the backward pipeline with a posterior writer as its last stage ----
+struct WkPost {
+  float *post;  // [B][T][U] label_posterior
+  float *blk;   // [B][T] blank_posterior
+  float *dur;   // [B][U] duration, or nullptr: no statistics
+  float *exf;   // [B][U] expected_frame (given together with dur)
+};
+
+// a lane's NL consecutive floats of an LDS plane in one store
+template <int NL>
+__device__ __forceinline__ void wk_put_run(float *o, const float (&v)[NL]) {
+  if constexpr (NL == 4) *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  else if constexpr (NL == 2) *reinterpret_cast<float2 *>(o) = make_float2(v[0], v[1]);
+  else o[0] = v[0];
+}
+
+// The gather, recompute and beta roles are wild_ckpt_bwd_kernel's, statement for statement (that kernel keeps its code, so they are
+// repeated and not shared); what differs is what the beta wave leaves in LDS and who takes it from there.
+template <int KIND, int NL>
+__global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Problem p, const double w2, const WkWs ws, const WkPost out) {
+  constexpr int UP = 64 * NL;
+  constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
+  constexpr int SRD = wk_row_doubles(KIND, UP);
+  constexpr int F = wild_ckpt_frames(NL);
+  constexpr int RS = UP + 4;      // ring row: UP label emissions, then the frame's statistics
+  constexpr int PR = 2 * UP + 4;  // posterior row: the plane of the labels' shares, the plane of the blank's, the start state's
+  constexpr int FPW = F / WK_PW;  // frames per producer wavefront and block: 8, 4, 2
+  constexpr int G = FPW < 4 ? FPW : 4;
+  static_assert(F >= 4 && F % WK_PW == 0, "every producer wavefront takes whole frames of a block");
+  static_assert(UP <= WK_BWD_THREADS, "one thread per label position combines the statistics");
+  const double NINF = -__builtin_inf();
+
+  __shared__ __attribute__((aligned(16))) double arow[2 * F * SRD];
+  __shared__ __attribute__((aligned(16))) float ring[3 * F * RS];
+  __shared__ __attribute__((aligned(16))) float pst[2 * F * PR];
+  __shared__ double acc[2][WK_PW][UP];  // the writers' partial sums of duration and of t * posterior
+  __shared__ int lab_s[UP];
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int blank = p.blank, dt = p.xdtype, U = p.U;
+  const bool lpin = p.wrt != 0;
+  const int Tb = frame_count(p, b);
+  const int L = label_count(p, b);
+  const int esz = dt == 0 ? 4 : 2;
+  const char *const xb = reinterpret_cast<const char *>(p.logits) + (size_t)((long)b * p.xsb) * esz;
+  float *const po = out.post + (size_t)b * p.T * U;
+  float *const bo = out.blk + (size_t)b * p.T;
+  const bool want = out.dur != nullptr;
+
+  const double lP = ws.logp[b];
+  const bool feasible = lP > NINF && lP < -NINF;  // (then L <= U <= UP)
+  // Every element has a writer.  Padded frames are zero; an utterance without a lattice to sweep is written here as a whole: zeros
+  // and -1 for an infeasible one or one without frames, and without labels every frame is the blank's, exactly
+  const bool sweep = feasible && Tb > 0 && L > 0;
+  const int Tz = sweep ? Tb : 0;
+  for (size_t q = (size_t)Tz * U + tid; q < (size_t)p.T * U; q += WK_BWD_THREADS) po[q] = 0.f;
+  for (int t = Tz + tid; t < p.T; t += WK_BWD_THREADS) bo[t] = (feasible && t < Tb) ? 1.f : 0.f;  // (t < Tb: only without a sweep)
+  if (!sweep) {  // (the same verdict in every wavefront: nobody waits at a barrier)
+    if (want)
+      for (int i = tid; i < U; i += WK_BWD_THREADS) {
+        out.dur[(size_t)b * U + i] = 0.f;
+        out.exf[(size_t)b * U + i] = -1.f;
+      }
+    return;
+  }
+
+  wk_labels<UP, WK_BWD_THREADS>(p, b, L, tid, lab_s);
+  __syncthreads();
+
+  int lab[NL];
+  unsigned wild = 0, allow = 0;
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    const int i = lane * NL + j;
+    lab[j] = lab_s[i];
+    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+    if (KIND == 0 && i > 0) {
+      const int q = lab_s[i - 1];
+      if (lab[j] != q || lab[j] == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD) allow |= 1u << j;
+    }
+  }
+  const int allow_nx = KIND == 0 ? fused::from_next_lane_i((int)(allow & 1u), 0) : 0;
+
+  const int K = (Tb + F - 1) / F;       // blocks of the utterance
+  const int nck = (p.T + F - 1) / F;    // checkpoint rows per utterance
+  auto frames_of = [&](int kb) { return Tb - kb * F < F ? Tb - kb * F : F; };
+
+  // ---- producers, first job: the emissions of block kb into its ring buffer, its statistics from the workspace ----
+  auto gather = [&](int kb) {
+    const int pw = wave - 2, t0 = kb * F;
+    float *const rb = ring + (kb % 3) * F * RS;
+    for (int f0 = pw * FPW; f0 < (pw + 1) * FPW; f0 += G) {
+      if (t0 + f0 >= Tb) break;
+      float e[G][NL];
+      float4 sv[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const int q = t0 + f0 + g, t = q < Tb ? q : Tb - 1;  // past the utterance's end its last frame: never stored
+        const char *const row = xb + (size_t)((long)t * p.xst) * esz;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const float v = row_load1(row, lab[j] >= 0 ? lab[j] : blank, dt);
+          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+        }
+        sv[g] = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
+      }
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (t0 + f0 + g < Tb) {
+          float *const r = rb + (f0 + g) * RS;
+#pragma unroll
+          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          if (lane == 0) *reinterpret_cast<float4 *>(r + UP) = sv[g];
+        }
+      }
+    }
+  };
+
+  // ---- producers, second job: the posterior writer of block kb.  Wavefront pw takes frames pw, pw + 4, ..; a lane takes positions
+  // lane, lane + 64, ..: a frame's U floats leave as one contiguous run, its blank shares meet in the wavefront in a fixed order,
+  // and the lane adds what it just wrote to its float64 sums: over the frames t = pw (mod 4) of the utterance, last block first ----
+  double dsum[NL], msum[NL];
+#pragma unroll
+  for (int q = 0; q < NL; ++q) dsum[q] = msum[q] = 0.0;
+  auto writer = [&](int kb) {
+    const int pw = wave - 2, nf = frames_of(kb);
+    for (int f = pw; f < nf; f += WK_PW) {
+      const int t = kb * F + f;
+      const float *const pr = pst + ((kb & 1) * F + f) * PR;
+      float *const o = po + (size_t)t * U;
+      float bs = lane == 0 ? pr[2 * UP] : 0.f;
+#pragma unroll
+      for (int q = 0; q < NL; ++q) {
+        const int i = lane + 64 * q;
+        const float v = i < L ? pr[i] : 0.f;  // positions from L on: zeros
+        if (i < U) o[i] = v;
+        if (i < L) bs += pr[UP + i];
+        if (want) {
+          dsum[q] += (double)v;
+          msum[q] += (double)t * (double)v;
+        }
+      }
+      bs = wave_sum(bs);
+      if (lane == 0) bo[t] = bs;
+    }
+  };
+
+  // ---- recompute wave: alpha over block kb from its checkpoint, every frame's row into the block's LDS row buffer ----
+  auto recompute = [&](int kb) {
+    const double *const r = ws.ck + ((size_t)b * nck + kb) * SRD;
+    double O[NL], C[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      if (KIND == 0) {
+        const double2 v = *reinterpret_cast<const double2 *>(r + lane * NS + 2 * j);
+        O[j] = v.x; C[j] = v.y;
+      } else {
+        O[j] = NINF; C[j] = r[lane * NS + j];
+      }
+    }
+    double cs = r[SRD - 2];
+    const int nf = frames_of(kb);
+    const float *const rb = ring + (kb % 3) * F * RS;
+    double *const ab = arow + (size_t)(kb & 1) * F * SRD;
+    for (int f = 0; f < nf; ++f) {
+      const float *const rr = rb + f * RS;
+      double *const a = ab + f * SRD;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
+      if (KIND == 1) {  // the state BEFORE the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) a[lane * NS + j] = C[j];
+        if (lane == 0) a[SRD - 2] = cs;
+      }
+      wk_alpha_step<KIND, NL>(O, C, cs, e, fr, wild, allow);
+      if (KIND == 0) {  // the state AFTER the frame
+#pragma unroll
+        for (int j = 0; j < NL; ++j) *reinterpret_cast<double2 *>(a + lane * NS + 2 * j) = make_double2(O[j], C[j]);
+        if (lane == 0) a[SRD - 2] = cs;
+      }
+    }
+  };
+
+  // ---- beta wave: the posteriors of block kb's frames, last first, and beta back over each; wild_loss_kernel's MODE 3 split: the
+  // labels' shares and the blank's in two planes of the block's LDS posterior rows, nothing summed here ----
+  double bO[NL], bC[NL];  // beta: the mass of the frames still to come; behind the last frame only the end states have any
+#pragma unroll
+  for (int j = 0; j < NL; ++j) bO[j] = bC[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
+  double bcs = NINF;  // (L > 0)
+  auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
+  auto beta_block = [&](int kb) {
+    const int nf = frames_of(kb);
+    const float *const rb = ring + (kb % 3) * F * RS;
+    const double *const ab = arow + (size_t)(kb & 1) * F * SRD;
+    float *const pb = pst + (size_t)(kb & 1) * F * PR;
+    double An[NS], Acsn;
+    auto load_row = [&](int f) {
+      const double *const a = ab + f * SRD;
+#pragma unroll
+      for (int q = 0; q < NS; ++q) An[q] = a[lane * NS + q];
+      Acsn = a[SRD - 2];
+    };
+    load_row(nf - 1);
+    for (int f = nf - 1; f >= 0; --f) {
+      const float *const rr = rb + f * RS;
+      float *const o = pb + f * PR;
+      float e[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
+      const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
+      const double eb = fr.eb;
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      double A[NS];
+#pragma unroll
+      for (int q = 0; q < NS; ++q) A[q] = An[q];
+      const double Acs = Acsn;
+      if (f > 0) load_row(f - 1);  // the next frame's row, a frame ahead
+      float pl[NL], pk[NL];  // the labels' shares of the lane's positions and the blank's
+      if (KIND == 0) {  // the open states are the labels', the closed ones and the start state the blank's
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          pl[j] = post(A[2 * j] + bO[j]);
+          pk[j] = post(A[2 * j + 1] + bC[j]);
+        }
+        wk_put_run<NL>(o + lane * NL, pl);
+        wk_put_run<NL>(o + UP + lane * NL, pk);
+        if (lane == 0) o[2 * UP] = post(Acs + bcs);
+        double x = bO[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? bO[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+          const double cb = bC[j] + eb;
+          bO[j] = wk_lse(x, cb, al ? xn : NINF);
+          bC[j] = wk_lse(cb, xn);
+          x = xn;
+        }
+      } else {  // entering a position is its label's; a stay emits the wildcard behind a wildcard, the blank otherwise
+        const double ap0 = from_prev_lane(A[NL - 1], Acs);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          const bool wj = ((wild >> j) & 1u) != 0;
+          const float pe = post(ap + em(j) + bC[j]), ps = post(A[j] + (wj ? fr.ew : eb) + bC[j]);
+          pl[j] = wj ? pe + ps : pe;
+          pk[j] = wj ? 0.f : ps;
+        }
+        wk_put_run<NL>(o + lane * NL, pl);
+        wk_put_run<NL>(o + UP + lane * NL, pk);
+        if (lane == 0) o[2 * UP] = post(Acs + eb + bcs);
+        double x = bC[0] + em(0);
+        const double xl = from_next_lane(x, NINF);
+        bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          const double xn = j + 1 < NL ? bC[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+          bC[j] = wk_lse(bC[j] + (((wild >> j) & 1u) ? fr.ew : eb), xn);
+          x = xn;
+        }
+      }
+    }
+  };
+
+  // every wavefront derives the same K from T_b: K + 3 barriers each, by construction
+  for (int s = 0; s <= K + 2; ++s) {
+    if (wave == 0) {
+      const int kb = K + 1 - s;
+      if (kb >= 0 && kb < K) beta_block(kb);
+    } else if (wave == 1) {
+      const int kb = K - s;
+      if (kb >= 0 && kb < K) recompute(kb);
+    } else {
+      const int kg = K - 1 - s, kr = K + 2 - s;
+      if (kg >= 0) gather(kg);
+      if (kr >= 0 && kr < K) writer(kr);
+    }
+    fused::block_barrier();
+  }
+
+  if (!want) return;  // (the same in every thread)
+  // the four writers' sums meet in LDS and are added in the order of the wavefronts; the quotient in float64, rounded once
+  if (wave >= 2) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      acc[0][wave - 2][lane + 64 * q] = dsum[q];
+      acc[1][wave - 2][lane + 64 * q] = msum[q];
+    }
+  }
+  __syncthreads();
+  if (tid < U) {
+    double d = 0.0, m = 0.0;
+#pragma unroll
+    for (int pw = 0; pw < WK_PW; ++pw) { d += acc[0][pw][tid]; m += acc[1][pw][tid]; }
+    out.dur[(size_t)b * U + tid] = (float)d;
+    out.exf[(size_t)b * U + tid] = d > 0.0 ? (float)(m / d) : -1.f;  // (positions from L on summed zeros)
+  }
+}
+
+template <int KIND, int NL>
+hipError_t launch_wild_ckpt_post(const Problem &p, double w2, float *loss, const WkWs &ws, const WkPost &out, hipStream_t st) {
+  hipLaunchKernelGGL((wild_ckpt_fwd_kernel<KIND, NL>), dim3(p.B), dim3(WK_FWD_THREADS), 0, st, p, w2, loss, ws);
+  if (hipError_t e = hipGetLastError()) return e;
+  // (T == 0 or U == 0 too: the statistics of such a call are written by the same kernel)
+  hipLaunchKernelGGL((wild_ckpt_post_kernel<KIND, NL>), dim3(p.B), dim3(WK_BWD_THREADS), 0, st, p, w2, ws, out);
+  return hipGetLastError();
+}
+
 template <int KIND, int NL>
 hipError_t launch_wild_ckpt(const Problem &p, double w2, const float *d_loss, float *loss, void *grad, const WkWs &ws, hipStream_t st) {
   hipLaunchKernelGGL((wild_ckpt_fwd_kernel<KIND, NL>), dim3(p.B), dim3(WK_FWD_THREADS), 0, st, p, w2, loss, ws);
@@ -633,6 +959,21 @@ hipError_t run_wild_loss_ckpt(const Problem &p, float wildcard_log_weight, const
   const WkWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + ck),
                 reinterpret_cast<double *>(wsp + ck + wk_al((size_t)p.B * p.T * 16))};
   return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, d_loss, loss, grad, ws, st);
+}
+
+hipError_t run_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
+                                    float *duration, float *expected_frame, char *wsp, hipStream_t st) {
+  if (!wk_tier(p.U)) return run_label_posterior(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, wsp, st);
+  typedef hipError_t Launch(const Problem &, double, float *, const WkWs &, const WkPost &, hipStream_t);
+  static Launch *const table[2][3] = {{launch_wild_ckpt_post<0, 1>, launch_wild_ckpt_post<0, 2>, launch_wild_ckpt_post<0, 4>},
+                                      {launch_wild_ckpt_post<1, 1>, launch_wild_ckpt_post<1, 2>, launch_wild_ckpt_post<1, 4>}};
+  const int NL = nl_for(p.U);
+  if (p.kind < 0 || p.kind > 1 || NL > 4) return hipErrorInvalidValue;
+  const size_t ck = wk_al(wk_ck_bytes(p.kind, p.B, p.T, p.U));
+  const WkWs ws{reinterpret_cast<double *>(wsp), reinterpret_cast<float *>(wsp + ck),
+                reinterpret_cast<double *>(wsp + ck + wk_al((size_t)p.B * p.T * 16))};
+  const WkPost out{label_posterior, blank_posterior, duration, expected_frame};
+  return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, loss, ws, out, st);
 }
 
 }  // namespace ctc

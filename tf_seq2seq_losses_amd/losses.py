@@ -813,7 +813,7 @@ class CtcLabelPosterior(NamedTuple):
 
 def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
                      max_label_length=None, frame_window=None, optional_wildcards=False,
-                     exclude_next_label=False) -> CtcLabelPosterior:
+                     exclude_next_label=False, checkpoint=False) -> CtcLabelPosterior:
     _no_window_with_optional(frame_window, optional_wildcards)
     _no_window_with_exclusion(frame_window, exclude_next_label)
     x = _as_tensor(x)
@@ -832,6 +832,8 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
         window["optional_wildcards"] = True
     if exclude_next_label:
         window["exclude_next_label"] = True
+    if checkpoint:
+        window["checkpoint"] = True
     with torch.no_grad():  # forward only: the result is detached
         return CtcLabelPosterior(*ops.label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
                                                       _blank(blank_index), U, wildcard_log_weight=weight, **window))
@@ -840,7 +842,8 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
 def classic_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                 blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                                 max_label_length: Optional[int] = None, frame_window=None,
-                                optional_wildcards: bool = False, exclude_next_label: bool = False) -> CtcLabelPosterior:
+                                optional_wildcards: bool = False, exclude_next_label: bool = False,
+                                checkpoint: bool = False) -> CtcLabelPosterior:
     """The soft alignment of a transcript on the classic lattice: the occupancy matrix of a forward-backward pass, where
     classic_ctc_alignment returns the single best path.  label_posterior[b, t, i] is the probability that frame t emits label
     position i; a frame's remaining mass is blank_posterior[b, t].  Labels may contain WILDCARD (-2), with the lattice and
@@ -850,31 +853,35 @@ def classic_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_le
     label_posterior is exactly 0 outside a position's window and every frame still sums to 1.  optional_wildcards as in
     classic_ctc_wildcard_loss: the column of an OPTIONAL_WILDCARD (-3) may sum to less than one frame (duration >= 0, expected_frame
     -1 where it is 0); every frame still sums to 1.  exclude_next_label as in classic_ctc_wildcard_loss: the posteriors of that
-    lattice, `loss` with the bits of that call."""
+    lattice, `loss` with the bits of that call.  checkpoint=True computes the same outputs (the same bars) from block checkpoints, as
+    in classic_ctc_wildcard_loss: for up to 256 label positions the workspace holds one chain state per block of frames, not one
+    per frame (14 x smaller at 128 positions), and duration / expected_frame come from the same sweep; with frame_window,
+    optional_wildcards or exclude_next_label the keyword is accepted and the call is that of checkpoint=False."""
     return _label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
-                            max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                            max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 def simplified_ctc_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
                                    blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
                                    max_label_length: Optional[int] = None, frame_window=None,
-                                   optional_wildcards: bool = False, exclude_next_label: bool = False) -> CtcLabelPosterior:
+                                   optional_wildcards: bool = False, exclude_next_label: bool = False,
+                                   checkpoint: bool = False) -> CtcLabelPosterior:
     """The same on the simplified lattice: label_posterior[b, t, i] is the probability that label i is emitted at frame t (so an
     ordinary label's duration is 1 and expected_frame is its expected emission frame); a wildcard also owns the frames spent
     behind it.  Same arguments and return value as classic_ctc_label_posterior."""
     return _label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
                                       wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
                                       frame_window=None, optional_wildcards: bool = False,
-                                      exclude_next_label: bool = False) -> CtcLabelPosterior:
+                                      exclude_next_label: bool = False, checkpoint: bool = False) -> CtcLabelPosterior:
     """The same for log-probabilities used as they stand (a wildcard frame emits wildcard_log_weight + logsumexp(logprobas[t]));
     ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
-                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label)
+                            wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
 
 # --------------------------------------------------------------------------------------------------

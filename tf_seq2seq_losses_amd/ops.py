@@ -980,14 +980,18 @@ def _long_loss_grad(frame_window, kind, wrt, labels, x, label_length, logit_leng
 
 def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
                     blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, want_stats: bool = True,
-                    frame_window: Optional[torch.Tensor] = None, optional_wildcards: bool = False, exclude_next_label: bool = False):
+                    frame_window: Optional[torch.Tensor] = None, optional_wildcards: bool = False, exclude_next_label: bool = False,
+                    *, checkpoint: bool = False):
     """(loss[B], label_posterior[B, T, U], blank_posterior[B, T], duration[B, U], expected_frame[B, U]), all float32: with what
     probability every frame belongs to every label position (or to the blank) over all paths of the lattice, and per position the
     expected number of frames and the soft timestamp (ctc_amd_label_posterior).  Labels may be wildcards (_lib.WILDCARD); the loss
     is wildcard_loss_grad's forward-only one, bit for bit.  want_stats=False skips the statistics launch and returns None for the
     last two.  Arguments as wildcard_loss_grad (frame_window: ctc_amd_windowed_label_posterior; optional_wildcards:
     ctc_amd_optional_wildcard_label_posterior; exclude_next_label: ctc_amd_star_label_posterior); every element of every output is
-    written.  Does not synchronise."""
+    written.  checkpoint: the posteriors from block checkpoints (ctc_amd_label_posterior_ckpt: for U <= 256 a workspace of one
+    chain state per block of frames, 14 x smaller at U = 128 on the classic lattice, and the statistics from the same sweep; the
+    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (their
+    checkpointed kernels are owed).  Does not synchronise."""
     if optional_wildcards and frame_window is not None:
         raise ValueError("label_posterior: frame_window and optional_wildcards cannot be combined")
     if exclude_next_label and frame_window is not None:
@@ -999,10 +1003,12 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     lib = _lib.load()
     dev = x.device
     B, T, V = (int(s) for s in x.shape)
-    key = ("label_posterior", kind, B, T, V, U)
+    ckpt = bool(checkpoint) and frame_window is None and not optional_wildcards and not exclude_next_label
+    key = ("label_posterior_ckpt" if ckpt else "label_posterior", kind, B, T, V, U)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = _lib.label_posterior_workspace_bytes(kind, B, T, V, U)
+        size = _lib.label_posterior_ckpt_workspace_bytes if ckpt else _lib.label_posterior_workspace_bytes
+        n = _WS_BYTES[key] = size(kind, B, T, V, U)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     post = torch.empty((B, T, U), dtype=torch.float32, device=dev)
     blk = torch.empty((B, T), dtype=torch.float32, device=dev)
@@ -1036,11 +1042,12 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
                                                                _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
         _lib.check(rc, "ctc_amd_optional_wildcard_label_posterior")
         return loss, post, blk, dur, exf
+    call = lib.ctc_amd_label_posterior_ckpt if ckpt else lib.ctc_amd_label_posterior
     with _on_device(dev):
-        rc = lib.ctc_amd_label_posterior(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
-                                         _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
-                                         _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
-    _lib.check(rc, "ctc_amd_label_posterior")
+        rc = call(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                  _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
+                  _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_label_posterior_ckpt" if ckpt else "ctc_amd_label_posterior")
     return loss, post, blk, dur, exf
 
 
