@@ -1588,6 +1588,31 @@ int ctc_amd_star_best_path(int kind, int wrt,
                            float *label_score /* may be NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Star CTC loss and gradient from block checkpoints (added under ABI v6: two new entry points, nothing existing changed): the
+ * checkpointed route for star temporal classification.  ctc_amd_star_loss_grad's arguments plus `int exclude_next_label` behind
+ * optional_wildcards: 0 is ctc_amd_optional_wildcard_loss_grad's definition (optional_wildcards != 0) or ctc_amd_wildcard_loss_grad's,
+ * anything else ctc_amd_star_loss_grad's.  Results, rules and validation are that counterpart's, checked by the same code in the same
+ * order with the same messages; loss has the bits of its forward-only call; grad == NULL IS that call; an utterance whose d_loss is
+ * 0 gets +0 throughout.  optional_wildcards == 0 and exclude_next_label == 0: ctc_amd_wildcard_loss_grad_ckpt, bit for bit; so is an
+ * utterance without an optional wildcard and without an excluding one under any flags.
+ * U <= 256: the two launches, the workspace and the pipeline of ctc_amd_wildcard_loss_grad_ckpt, in kernels that carry the skip over
+ * an optional wildcard and the exclusion; the size is ctc_amd_wildcard_loss_ckpt_workspace_bytes.
+ * U > 256: the call IS the per-frame counterpart, bit for bit, and the size query returns ctc_amd_wildcard_loss_workspace_bytes.
+ * There is no frame-window variant and no label-posterior variant with either flag.
+ * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_star_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
+int ctc_amd_star_loss_grad_ckpt(int kind, int wrt,
+                                const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                const int32_t *labels, int label_stride,
+                                const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                int optional_wildcards, int exclude_next_label,
+                                float wildcard_log_weight, int B, int T, int V, int U,
+                                const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
+                                void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The exclusion above 1024 labels: the long-form loss, gradient and label posteriors (added under ABI v6: three new entry points
  * with their size queries, nothing existing changed).  The definition above, word for word, for label_length <=
  * CTC_AMD_LONG_MAX_U:

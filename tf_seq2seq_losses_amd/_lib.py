@@ -152,6 +152,9 @@ SIGNATURES = {
     "ctc_amd_star_loss_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
     "ctc_amd_star_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_star_loss_ckpt_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U, want_grad
+    "ctc_amd_star_loss_grad_ckpt": (_c_int, _COMMON_EX[:11] + [_c_int, _c_int, ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, optional_wildcards, exclude_next_label, weight
+                                    [_c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),
     "ctc_amd_star_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
     "ctc_amd_star_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                      [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
@@ -370,6 +373,13 @@ def wildcard_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U: int
     out = _c_size_t(0)
     check(load().ctc_amd_wildcard_loss_ckpt_workspace_bytes(kind, B, T, V, U, int(want_grad), ctypes.byref(out)),
           "ctc_amd_wildcard_loss_ckpt_workspace_bytes")
+    return int(out.value)
+
+
+def star_loss_ckpt_workspace_bytes(kind: int, B: int, T: int, V: int, U: int, want_grad: bool = True) -> int:
+    out = _c_size_t(0)
+    check(load().ctc_amd_star_loss_ckpt_workspace_bytes(kind, B, T, V, U, int(want_grad), ctypes.byref(out)),
+          "ctc_amd_star_loss_ckpt_workspace_bytes")
     return int(out.value)
 
 

@@ -1131,7 +1131,8 @@ int ctc_amd_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, 
 
 // The gradient's strides are looked at only when there is one; without one it needs no workspace today, so a null one passes.
 // One body for ctc_amd_windowed_loss_grad, ctc_amd_optional_wildcard_loss_grad and ctc_amd_star_loss_grad (which have no window), and
-// for ctc_amd_wildcard_loss_grad_ckpt (ckpt: no window, star or optional wildcards), which differs in the workspace and the launcher.
+// for ctc_amd_wildcard_loss_grad_ckpt (ckpt: no window, star or optional wildcards) and ctc_amd_star_loss_grad_ckpt (ckpt: no window),
+// which differ in the workspace and the launcher.
 static int wildcard_loss_grad_call(bool ckpt, bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                    int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                    const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
@@ -1147,7 +1148,11 @@ static int wildcard_loss_grad_call(bool ckpt, bool star, bool optional_wildcards
   const size_t need = ckpt ? ctc::wild_loss_ckpt_workspace_bytes(kind, B, T, U, grad != nullptr) : ctc::wild_loss_workspace_bytes(kind, B, T, U, grad != nullptr);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::TakenIfUnneeded)) return rc;
   if (ckpt) {
-    CTC_TRY(ctc::run_wild_loss_ckpt(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace), static_cast<hipStream_t>(stream)),
+    CTC_TRY((star || optional_wildcards)
+                ? ctc::run_star_loss_ckpt(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
+                                          static_cast<hipStream_t>(stream), optional_wildcards, star)
+                : ctc::run_wild_loss_ckpt(pre.p, wildcard_log_weight, d_loss, loss, grad, static_cast<char *>(workspace),
+                                          static_cast<hipStream_t>(stream)),
             "wildcard loss launch");
     return CTC_AMD_OK;
   }
@@ -1221,6 +1226,22 @@ int ctc_amd_wildcard_loss_grad_ckpt(int kind, int wrt, const void *logits, int l
   return wildcard_loss_grad_call(true, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                                  label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, d_loss, loss, grad,
                                  grad_dtype, grad_stride_b, grad_stride_t, workspace, workspace_bytes, stream);
+}
+
+// Star CTC from block checkpoints: optional wildcards, the exclusion of the following label, or both; neither is the call above.
+int ctc_amd_star_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes) {
+  return ctc_amd_wildcard_loss_ckpt_workspace_bytes(kind, B, T, V, U, want_grad, out_bytes);
+}
+
+int ctc_amd_star_loss_grad_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                const int32_t *labels, int label_stride, const int32_t *label_length, const int32_t *logit_length,
+                                int blank_index, int optional_wildcards, int exclude_next_label, float wildcard_log_weight, int B, int T,
+                                int V, int U, const float *d_loss, float *loss, void *grad, int grad_dtype, int64_t grad_stride_b,
+                                int64_t grad_stride_t, void *workspace, size_t workspace_bytes, void *stream) {
+  return wildcard_loss_grad_call(true, exclude_next_label != 0, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b,
+                                 logits_stride_t, labels, label_stride, label_length, logit_length, blank_index, nullptr, 0,
+                                 wildcard_log_weight, B, T, V, U, d_loss, loss, grad, grad_dtype, grad_stride_b, grad_stride_t, workspace,
+                                 workspace_bytes, stream);
 }
 
 int ctc_amd_long_wildcard_loss_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, int want_grad, size_t *out_bytes) {

@@ -18,6 +18,17 @@ size_t wild_loss_ckpt_workspace_bytes(int kind, int B, int T, int U, bool want_g
 // and log2 Z (the loss has the bits of the forward-only call), then the pipelined backward sweep (T == 0: the first alone)
 hipError_t run_wild_loss_ckpt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
                               hipStream_t st);
+// ctc_amd_star_loss_grad_ckpt: the call above with optional wildcards, with the exclusion of the following
+// label, or with both, on the same workspace.  grad == nullptr or U > 256: run_wild_loss / run_star_loss with the same flags.
+// Neither flag: run_wild_loss_ckpt's kernels.  Otherwise the two launches of the (OPT, XN) kernels, which live in units of their own
+// (ctc_wild_loss_ckpt.hip compiled with -DCTC_CKPT_OPT and with -DCTC_STAR) behind the two entry points below it
+hipError_t run_star_loss_ckpt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
+                              hipStream_t st, bool optional_wildcards, bool exclude_next_label);
+// (grad != nullptr, U <= 256, a workspace of wild_loss_ckpt_workspace_bytes(want_grad = true))
+hipError_t run_wild_loss_ckpt_opt(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
+                                  hipStream_t st);
+hipError_t run_wild_loss_ckpt_star(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *ws,
+                                   hipStream_t st, bool optional_wildcards);
 // ctc_amd_label_posterior_ckpt: `ws` is a workspace of wild_loss_ckpt_workspace_bytes(want_grad = true).  U > 256: run_label_posterior.
 // Otherwise two launches: the same alpha sweep, then the backward pipeline whose last stage writes label_posterior [B][T][U],
 // blank_posterior [B][T] and, when duration is given, duration / expected_frame [B][U]; no per-frame row and no second read of the matrix

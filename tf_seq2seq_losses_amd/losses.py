@@ -538,8 +538,9 @@ class _WildcardLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, labels, label_length, logit_length, kind, wrt, blank, U, weight, frame_window, optional_wildcards=False,
-                exclude_next_label=False, checkpoint=False):
+                exclude_next_label=False, checkpoint=False, star=False):
         ctx.save_for_backward(x, labels, label_length, logit_length)
+        ctx.fn = ops.star_loss_grad if star else ops.wildcard_loss_grad
         ctx.call = (kind, wrt, blank, U, weight)
         ctx.checkpoint = {"checkpoint": True} if checkpoint else {}  # (the backward call alone: forward keeps no workspace)
         ctx.window = {} if frame_window is None else {"frame_window": frame_window}  # (no window: the call as it always was)
@@ -547,17 +548,19 @@ class _WildcardLossFn(torch.autograd.Function):
             ctx.window["optional_wildcards"] = True
         if exclude_next_label:
             ctx.window["exclude_next_label"] = True
-        return ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
-                                      wildcard_log_weight=weight, want_grad=False, **ctx.window)[0]
+        if star:  # (ops.star_loss_grad: both keywords default to True there, so both are stated)
+            ctx.window = {"optional_wildcards": bool(optional_wildcards), "exclude_next_label": bool(exclude_next_label)}
+        return ctx.fn(kind, wrt, labels, x, label_length, logit_length, blank, None, U,
+                      wildcard_log_weight=weight, want_grad=False, **ctx.window)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_loss):
         x, labels, label_length, logit_length = ctx.saved_tensors
         kind, wrt, blank, U, weight = ctx.call
-        _, grad = ops.wildcard_loss_grad(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
-                                         wildcard_log_weight=weight, **ctx.window, **ctx.checkpoint)
-        return grad, None, None, None, None, None, None, None, None, None, None, None, None
+        _, grad = ctx.fn(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype=x.dtype,
+                         wildcard_log_weight=weight, **ctx.window, **ctx.checkpoint)
+        return grad, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _no_window_with_optional(frame_window, optional_wildcards):
@@ -572,7 +575,7 @@ def _no_window_with_exclusion(frame_window, exclude_next_label):
 
 def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
                    max_label_length=None, frame_window=None, optional_wildcards=False, exclude_next_label=False,
-                   checkpoint=False) -> torch.Tensor:
+                   checkpoint=False, star=False) -> torch.Tensor:
     _no_window_with_optional(frame_window, optional_wildcards)
     _no_window_with_exclusion(frame_window, exclude_next_label)
     x = _as_tensor(x)
@@ -594,8 +597,9 @@ def _wildcard_loss(kind_name: str, wrt: int, labels, x, label_length, logit_leng
         window["exclude_next_label"] = True
     if x.requires_grad and torch.is_grad_enabled():
         return _WildcardLossFn.apply(x, labels, label_length, logit_length, kind, wrt, _blank(blank_index), U, weight,
-                                     window.get("frame_window"), bool(optional_wildcards), bool(exclude_next_label), bool(checkpoint))
-    with torch.no_grad():  # forward only: the result is detached
+                                     window.get("frame_window"), bool(optional_wildcards), bool(exclude_next_label), bool(checkpoint),
+                                     bool(star))
+    with torch.no_grad():  # forward only: the result is detached (star: the same forward-only launch)
         return ops.wildcard_loss_grad(kind, wrt, labels, x.detach(), label_length, logit_length, _blank(blank_index), None, U,
                                       wildcard_log_weight=weight, want_grad=False, **window)[0]
 
@@ -631,7 +635,8 @@ def classic_ctc_wildcard_loss(labels: TensorLike, logits: TensorLike, label_leng
     1000 frames and 128 labels) and hands the rows and posteriors of a block from wavefront to wavefront on chip.  The loss has the
     same bits, the gradient meets the same bars (a zero incoming gradient gives +0 throughout).  Above 256 labels, and together with
     frame_window, optional_wildcards=True or exclude_next_label=True, the keyword is accepted and the call is that of
-    checkpoint=False, bit for bit: the checkpointed form of those kernels is owed."""
+    checkpoint=False, bit for bit: classic_ctc_star_loss is the checkpointed route with the latter two keywords; that of
+    frame_window is owed."""
     return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
                           max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
 
@@ -658,6 +663,43 @@ def ctc_wildcard_loss_from_logproba(labels, logprobas, label_length, logit_lengt
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
                           wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
+
+
+def classic_ctc_star_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                          blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                          optional_wildcards: bool = True, exclude_next_label: bool = True,
+                          max_label_length: Optional[int] = None) -> torch.Tensor:
+    """Star temporal classification on the classic lattice, the gradient from block checkpoints: the checkpointed route for STC.
+    classic_ctc_wildcard_loss(optional_wildcards=..., exclude_next_label=...) with the same labels (WILDCARD -2, OPTIONAL_WILDCARD
+    -3), the same loss bit for bit and a gradient to the same bars, but the backward call (ctc_amd_star_loss_grad_ckpt) keeps one
+    lattice row per block of 32 / 16 / 8 frames instead of one per frame and hands a block's rows and posteriors from wavefront
+    to wavefront on chip, for max_label_length <= 256; above that it is the per-frame call, bit for bit.  A zero incoming gradient
+    gives +0 throughout; a second derivative raises.  There is no frame_window; the checkpointed label posteriors with these
+    keywords are owed.  With exclude_next_label the route currently buys workspace, not time: at B = 256, T = 1000, V = 256 and
+    129 positions 7.8x less workspace at 1.03-1.13x the time of classic_ctc_wildcard_loss with the same keywords (cause not
+    found); with optional_wildcards alone it takes 0.87-0.88x the time."""
+    return _wildcard_loss("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                          max_label_length, None, optional_wildcards, exclude_next_label, star=True)
+
+
+def simplified_ctc_star_loss(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                             blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                             optional_wildcards: bool = True, exclude_next_label: bool = True,
+                             max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same on the simplified lattice: the checkpointed route for STC there.  Same arguments and return value as
+    classic_ctc_star_loss."""
+    return _wildcard_loss("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                          max_label_length, None, optional_wildcards, exclude_next_label, star=True)
+
+
+def ctc_star_loss_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                wildcard_log_weight: float = 0.0, optional_wildcards: bool = True,
+                                exclude_next_label: bool = True, max_label_length: Optional[int] = None) -> torch.Tensor:
+    """The same for log-probabilities used as they stand (the checkpointed route for STC of ctc_wildcard_loss_from_logproba);
+    ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData).  The gradient is with respect to logprobas."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _wildcard_loss(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                          wildcard_log_weight, max_label_length, None, optional_wildcards, exclude_next_label, star=True)
 
 
 # --------------------------------------------------------------------------------------------------

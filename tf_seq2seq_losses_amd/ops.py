@@ -773,8 +773,15 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
     exclude_next_label: a wildcard of either kind emits every token but the ordinary label that follows it (ctc_amd_star_loss_grad;
     not with a window).  checkpoint: the gradient from block checkpoints (ctc_amd_wildcard_loss_grad_ckpt: for U <= 256 a
     workspace of one lattice row per block of 32 / 16 / 8 frames instead of one per frame, the same loss bits, a gradient to the
-    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (their
-    checkpointed kernels are owed).  Does not synchronise."""
+    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (star_loss_grad
+    is the checkpointed route with the latter two; that of frame windows is owed).  Does not synchronise."""
+    return _wildcard_loss_grad_impl(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                                    want_grad, frame_window, optional_wildcards, exclude_next_label, checkpoint, False)
+
+
+def _wildcard_loss_grad_impl(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                             want_grad, frame_window, optional_wildcards, exclude_next_label, checkpoint, _star_ckpt):
+    """The argument handling and the launch behind wildcard_loss_grad and star_loss_grad (_star_ckpt: ctc_amd_star_loss_grad_ckpt)."""
     if optional_wildcards and frame_window is not None:
         raise ValueError("wildcard_loss_grad: frame_window and optional_wildcards cannot be combined")
     if exclude_next_label and frame_window is not None:
@@ -797,16 +804,26 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
         raise ValueError(f"wildcard_loss_grad: grad_dtype must be float32, bfloat16 or float16, got {grad_dtype}")
     with_grad = bool(want_grad) and T > 0  # (T == 0: no row to write and no gradient pointer to pass)
     ckpt = bool(checkpoint) and frame_window is None and not optional_wildcards and not exclude_next_label
-    key = ("wildcard_loss_grad_ckpt" if ckpt else "wildcard_loss_grad", kind, B, T, V, U, with_grad)
+    key = ("star_loss_grad_ckpt" if _star_ckpt else "wildcard_loss_grad_ckpt" if ckpt else "wildcard_loss_grad", kind, B, T, V, U, with_grad)
     n = _WS_BYTES.get(key)
     if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
-        n = _WS_BYTES[key] = (_lib.wildcard_loss_ckpt_workspace_bytes if ckpt else _lib.wildcard_loss_workspace_bytes)(kind, B, T, V, U, with_grad)
+        n = _WS_BYTES[key] = (_lib.star_loss_ckpt_workspace_bytes if _star_ckpt else _lib.wildcard_loss_ckpt_workspace_bytes if ckpt
+                              else _lib.wildcard_loss_workspace_bytes)(kind, B, T, V, U, with_grad)
     loss = torch.empty(B, dtype=torch.float32, device=dev)
     grad = torch.empty_like(x, dtype=grad_dtype) if want_grad else None  # (a dense permuted layout is kept, anything else is contiguous)
     if B == 0:
         return loss, grad
     ws = torch.empty(n, dtype=torch.uint8, device=dev) if n else None
     gsb, gst = (grad.stride(0), grad.stride(1)) if with_grad else (T * V, V)
+    if _star_ckpt:
+        with _on_device(dev):
+            rc = lib.ctc_amd_star_loss_grad_ckpt(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                 _ptr(label_length), _ptr(logit_length), int(blank), int(bool(optional_wildcards)),
+                                                 int(bool(exclude_next_label)), float(wildcard_log_weight), B, T, V, U, _ptr(d_loss),
+                                                 _ptr(loss), _ptr(grad) if with_grad else None, _DTYPES[grad_dtype], gsb, gst, _ptr(ws), n,
+                                                 _stream(dev))
+        _lib.check(rc, "ctc_amd_star_loss_grad_ckpt")
+        return loss, grad
     if frame_window is not None:
         fw, fws = _frame_window("wildcard_loss_grad", frame_window, B, U, dev)
         with _on_device(dev):
@@ -847,6 +864,21 @@ def wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tenso
                                             _ptr(ws), n, _stream(dev))
     _lib.check(rc, "ctc_amd_wildcard_loss_grad")
     return loss, grad
+
+
+def star_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor, logit_length: torch.Tensor,
+                   blank: int, d_loss: Optional[torch.Tensor] = None, U: Optional[int] = None, grad_dtype: Optional[torch.dtype] = None,
+                   wildcard_log_weight: float = 0.0, want_grad: bool = True, optional_wildcards: bool = True,
+                   exclude_next_label: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """wildcard_loss_grad(optional_wildcards=..., exclude_next_label=...) from block checkpoints (ctc_amd_star_loss_grad_ckpt): the
+    checkpointed route for star temporal classification.  The same arguments and results, the loss bit for bit, the gradient to
+    the same bars; for U <= 256 two launches and wildcard_loss_ckpt_workspace_bytes (one lattice row per block of 32 / 16 / 8
+    frames), for U > 256 that call itself.  With neither keyword it is wildcard_loss_grad(checkpoint=True).  No frame_window.
+    What the route buys today with exclude_next_label is workspace, not time: 7.8x less at B = 256, T = 1000, V = 256 and 129
+    positions, but 1.03-1.13x the per-frame call's time (cause not found); with optional_wildcards alone
+    it takes 0.87-0.88x."""
+    return _wildcard_loss_grad_impl(kind, wrt, labels, x, label_length, logit_length, blank, d_loss, U, grad_dtype, wildcard_log_weight,
+                                    want_grad, None, optional_wildcards, exclude_next_label, False, True)
 
 
 def long_wildcard_loss_grad(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
