@@ -1598,7 +1598,7 @@ int ctc_amd_star_best_path(int kind, int wrt,
  * U <= 256: the two launches, the workspace and the pipeline of ctc_amd_wildcard_loss_grad_ckpt, in kernels that carry the skip over
  * an optional wildcard and the exclusion; the size is ctc_amd_wildcard_loss_ckpt_workspace_bytes.
  * U > 256: the call IS the per-frame counterpart, bit for bit, and the size query returns ctc_amd_wildcard_loss_workspace_bytes.
- * There is no frame-window variant and no label-posterior variant with either flag.
+ * There is no frame-window variant; the label posteriors are ctc_amd_star_label_posterior_ckpt below.
  * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
  */
 int ctc_amd_star_loss_ckpt_workspace_bytes(int kind, int B, int T, int V, int U, int want_grad, size_t *out_bytes /*host*/);
@@ -1611,6 +1611,29 @@ int ctc_amd_star_loss_grad_ckpt(int kind, int wrt,
                                 const float *d_loss /* [B], NULL = ones */, float *loss /* [B] */,
                                 void *grad /* NULL = forward only */, int grad_dtype, int64_t grad_stride_b, int64_t grad_stride_t,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Star label posteriors from block checkpoints (added under ABI v6: one new entry point, nothing existing changed): the soft
+ * alignment of a star temporal classification transcript without a lattice row per frame.  ctc_amd_star_label_posterior's arguments
+ * plus `int exclude_next_label` behind optional_wildcards: 0 is ctc_amd_optional_wildcard_label_posterior's definition
+ * (optional_wildcards != 0) or ctc_amd_label_posterior's, anything else ctc_amd_star_label_posterior's.  Outputs, rules and validation
+ * are ctc_amd_label_posterior_ckpt's, checked by the same code in the same order with the same messages; loss has the bits of the
+ * counterpart's forward-only call; a star that every path skips has duration 0 and expected_frame -1.  Neither flag:
+ * ctc_amd_label_posterior_ckpt, bit for bit; so is an utterance without an optional wildcard and without an excluding one.
+ * U <= 256: the two launches and the pipeline of ctc_amd_label_posterior_ckpt in kernels that carry the skip over an optional
+ * wildcard and the exclusion.  U > 256: the call IS the per-frame counterpart, bit for bit.
+ * There is no size query of its own: the workspace is ctc_amd_label_posterior_ckpt_workspace_bytes for either range of U.
+ * No allocation, copy or synchronisation; asynchronous on `stream`, capturable.
+ */
+int ctc_amd_star_label_posterior_ckpt(int kind, int wrt,
+                                      const void *logits, int logits_dtype, int64_t logits_stride_b, int64_t logits_stride_t,
+                                      const int32_t *labels, int label_stride,
+                                      const int32_t *label_length, const int32_t *logit_length, int blank_index,
+                                      int optional_wildcards, int exclude_next_label,
+                                      float wildcard_log_weight, int B, int T, int V, int U,
+                                      float *loss, float *label_posterior, float *blank_posterior,
+                                      float *duration /* may be NULL */, float *expected_frame /* with duration */,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The exclusion above 1024 labels: the long-form loss, gradient and label posteriors (added under ABI v6: three new entry points

@@ -158,6 +158,8 @@ SIGNATURES = {
     "ctc_amd_star_label_posterior_workspace_bytes": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_size_t)]),  # kind, B, T, V, U
     "ctc_amd_star_label_posterior": (_c_int, _COMMON_EX[:11] + [_c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                      [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "ctc_amd_star_label_posterior_ckpt": (_c_int, _COMMON_EX[:11] + [_c_int, _c_int, ctypes.c_float] + _COMMON_EX[11:] +  # .. blank_index, optional_wildcards, exclude_next_label, weight
+                                          [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     # ... and the three long-form ones of the summed lattice, in the same manner
     "ctc_amd_long_windowed_loss_grad": (_c_int, _COMMON_EX[:11] + [_c_void_p, _c_int, ctypes.c_float] + _COMMON_EX[11:] +
                                         [_c_int, _c_void_p] + _OUT_EX + [_c_void_p, _c_size_t, _c_void_p]),

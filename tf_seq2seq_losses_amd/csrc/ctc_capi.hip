@@ -1389,8 +1389,8 @@ int ctc_amd_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U
 }
 
 // One body for ctc_amd_windowed_label_posterior, ctc_amd_optional_wildcard_label_posterior and ctc_amd_star_label_posterior (which
-// have no window), and for ctc_amd_label_posterior_ckpt (ckpt: no window, star or optional wildcards), which differs in the workspace
-// and the launcher.
+// have no window), and for ctc_amd_label_posterior_ckpt (ckpt: no window, star or optional wildcards) and
+// ctc_amd_star_label_posterior_ckpt (ckpt: no window), which differ in the workspace and the launcher.
 static int label_posterior_call(bool ckpt, bool star, bool optional_wildcards, int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
                                 int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
                                 const int32_t *logit_length, int blank_index, const int32_t *frame_window, int window_stride,
@@ -1410,8 +1410,9 @@ static int label_posterior_call(bool ckpt, bool star, bool optional_wildcards, i
   const size_t need = ckpt ? ctc::wild_loss_ckpt_workspace_bytes(kind, B, T, U, true) : ctc::wild_loss_workspace_bytes(kind, B, T, U, true);
   if (int rc = check_workspace(workspace, workspace_bytes, need, NullWs::Refused)) return rc;
   if (ckpt) {
-    CTC_TRY(ctc::run_label_posterior_ckpt(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
-                                          static_cast<char *>(workspace), static_cast<hipStream_t>(stream)), "label posterior launch");
+    CTC_TRY(ctc::run_star_label_posterior_ckpt(pre.p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame,
+                                               static_cast<char *>(workspace), static_cast<hipStream_t>(stream), optional_wildcards, star),
+            "label posterior launch");
     return CTC_AMD_OK;
   }
   CTC_TRY((star ? ctc::run_star_label_posterior : ctc::run_label_posterior)(pre.p, wildcard_log_weight, loss, label_posterior,
@@ -1485,6 +1486,20 @@ int ctc_amd_label_posterior_ckpt(int kind, int wrt, const void *logits, int logi
   return label_posterior_call(true, false, false, kind, wrt, logits, logits_dtype, logits_stride_b, logits_stride_t, labels, label_stride,
                               label_length, logit_length, blank_index, nullptr, 0, wildcard_log_weight, B, T, V, U, loss, label_posterior,
                               blank_posterior, duration, expected_frame, workspace, workspace_bytes, stream);
+}
+
+// Star label posteriors from block checkpoints: optional wildcards, the exclusion of the following label, or both; neither is the
+// call above.  The workspace is ctc_amd_label_posterior_ckpt_workspace_bytes.
+int ctc_amd_star_label_posterior_ckpt(int kind, int wrt, const void *logits, int logits_dtype, int64_t logits_stride_b,
+                                      int64_t logits_stride_t, const int32_t *labels, int label_stride, const int32_t *label_length,
+                                      const int32_t *logit_length, int blank_index, int optional_wildcards, int exclude_next_label,
+                                      float wildcard_log_weight, int B, int T, int V, int U, float *loss, float *label_posterior,
+                                      float *blank_posterior, float *duration, float *expected_frame, void *workspace,
+                                      size_t workspace_bytes, void *stream) {
+  return label_posterior_call(true, exclude_next_label != 0, optional_wildcards != 0, kind, wrt, logits, logits_dtype, logits_stride_b,
+                              logits_stride_t, labels, label_stride, label_length, logit_length, blank_index, nullptr, 0,
+                              wildcard_log_weight, B, T, V, U, loss, label_posterior, blank_posterior, duration, expected_frame, workspace,
+                              workspace_bytes, stream);
 }
 
 int ctc_amd_long_label_posterior_workspace_bytes(int kind, int B, int T, int V, int U, int frames_per_tile, size_t *out_bytes) {

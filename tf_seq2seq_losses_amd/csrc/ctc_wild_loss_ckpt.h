@@ -34,5 +34,17 @@ hipError_t run_wild_loss_ckpt_star(const Problem &p, float wildcard_log_weight, 
 // blank_posterior [B][T] and, when duration is given, duration / expected_frame [B][U]; no per-frame row and no second read of the matrix
 hipError_t run_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
                                     float *duration, float *expected_frame, char *ws, hipStream_t st);
+// ctc_amd_star_label_posterior_ckpt: the call above with optional wildcards, with the exclusion of the
+// following label, or with both, on the same workspace.  U > 256: run_label_posterior / run_star_label_posterior with the same
+// flags.  Neither flag: run_label_posterior_ckpt.  Otherwise the two launches of the (OPT, XN) kernels, in the two star units
+hipError_t run_star_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                         float *blank_posterior, float *duration, float *expected_frame, char *ws, hipStream_t st,
+                                         bool optional_wildcards, bool exclude_next_label);
+// (U <= 256, a workspace of wild_loss_ckpt_workspace_bytes(want_grad = true))
+hipError_t run_label_posterior_ckpt_opt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                        float *blank_posterior, float *duration, float *expected_frame, char *ws, hipStream_t st);
+hipError_t run_label_posterior_ckpt_star(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                         float *blank_posterior, float *duration, float *expected_frame, char *ws, hipStream_t st,
+                                         bool optional_wildcards);
 
 }  // namespace ctc

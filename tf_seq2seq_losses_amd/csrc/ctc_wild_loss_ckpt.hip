@@ -49,6 +49,11 @@
 //        position and the chains add it to e_w.  The beta wave leaves c_i = Gamma_{t,i} 2^-slot in Gamma's place and the frame's
 //        largest c in the posterior row's second spare float; the row stage splits its wavefront's bins into gamma's and D's, 512
 //        columns a pass, and sums C through the row's last two spare floats as one 64-bit integer: the same LDS, byte for byte.
+//
+// Star label posteriors from the same checkpoints: ctc_amd_star_label_posterior_ckpt, DESIGN.md section 5.35.  wild_ckpt_post_kernel
+// carries OPT and XN too, in the same two units: the gather, recompute and beta recursion of the star backward kernel with the
+// output stage and the writer of the posterior kernel.  The shares are MODE 3's: a skipped star owns no frame, a frame entered over
+// one belongs to the position entered; under XN the label plane holds Gamma itself (no c, no bins): the posterior kernel's LDS.
 #include "ctc_wild_loss_ckpt.h"
 
 #include "ctc_lane_ops.h"
@@ -962,12 +967,6 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_bwd_kernel(const Pro
   }
 }
 
-// The units of the star variants (-DCTC_CKPT_OPT, -DCTC_STAR) hold their instantiations of the two kernels above and nothing else
-#if defined(CTC_CKPT_OPT) || defined(CTC_STAR)
-#define CTC_CKPT_VARIANT 1
-#endif
-
-#ifndef CTC_CKPT_VARIANT
 // ---- label posteriors from the same checkpoints: the backward pipeline with a posterior writer as its last stage ----
 struct WkPost {
   float *post;  // [B][T][U] label_posterior
@@ -985,8 +984,9 @@ __device__ __forceinline__ void wk_put_run(float *o, const float (&v)[NL]) {
 }
 
 // The gather, recompute and beta roles are wild_ckpt_bwd_kernel's, statement for statement (that kernel keeps its code, so they are
-// repeated and not shared); what differs is what the beta wave leaves in LDS and who takes it from there.
-template <int KIND, int NL>
+// repeated and not shared); what differs is what the beta wave leaves in LDS and who takes it from there.  OPT and XN as in that
+// kernel (section 5.35); under XN the label plane holds Gamma itself, and the four spare floats of a posterior row keep their use.
+template <int KIND, int NL, bool OPT, bool XN>
 __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Problem p, const double w2, const WkWs ws, const WkPost out) {
   constexpr int UP = 64 * NL;
   constexpr int NS = (KIND == 0 ? 2 : 1) * NL;
@@ -1036,22 +1036,33 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
     return;
   }
 
-  wk_labels<UP, WK_BWD_THREADS>(p, b, L, tid, lab_s);
+  wk_labels<UP, WK_BWD_THREADS, OPT>(p, b, L, tid, lab_s);
   __syncthreads();
 
+  // (the kernels without OPT and XN set their masks in the statements they always had and keep their code)
+  [[maybe_unused]] WkLane<NL> ln = {};
   int lab[NL];
   unsigned wild = 0, allow = 0;
+  if constexpr (OPT || XN) {
+    ln = wk_lane_of<KIND, NL, OPT, XN>(lab_s, lane, L);
+    wild = ln.wild;
+    allow = ln.allow;
+  }
 #pragma unroll
   for (int j = 0; j < NL; ++j) {
     const int i = lane * NL + j;
     lab[j] = lab_s[i];
-    if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
-    if (KIND == 0 && i > 0) {
-      const int q = lab_s[i - 1];
-      if (lab[j] != q || lab[j] == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD) allow |= 1u << j;
+    if constexpr (!(OPT || XN)) {
+      if (lab[j] == WILD_LOSS_WILDCARD) wild |= 1u << j;
+      if (KIND == 0 && i > 0) {
+        const int q = lab_s[i - 1];
+        if (lab[j] != q || lab[j] == WILD_LOSS_WILDCARD || q == WILD_LOSS_WILDCARD) allow |= 1u << j;
+      }
     }
   }
   const int allow_nx = KIND == 0 ? fused::from_next_lane_i((int)(allow & 1u), 0) : 0;
+  [[maybe_unused]] const unsigned skip = ln.skip, skipo = ln.skipo;
+  const bool excl = XN && ln.excl;
 
   const int K = (Tb + F - 1) / F;       // blocks of the utterance
   const int nck = (p.T + F - 1) / F;    // checkpoint rows per utterance
@@ -1071,8 +1082,9 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
         const char *const row = xb + (size_t)((long)t * p.xst) * esz;
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          const float v = row_load1(row, lab[j] >= 0 ? lab[j] : blank, dt);
-          e[g][j] = lab[j] >= 0 ? v : -__builtin_inff();
+          const int tk = XN && lab[j] < 0 ? ln.nx[j] : lab[j];  // XN: a wildcard position gathers the token it excludes
+          const float v = row_load1(row, tk >= 0 ? tk : blank, dt);
+          e[g][j] = tk >= 0 ? v : -__builtin_inff();
         }
         sv[g] = *reinterpret_cast<const float4 *>(ws.stat + ((size_t)b * p.T + t) * 4);
       }
@@ -1081,7 +1093,13 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
         if (t0 + f0 + g < Tb) {
           float *const r = rb + (f0 + g) * RS;
 #pragma unroll
-          for (int j = 0; j < NL; ++j) r[lane * NL + j] = e[g][j];
+          for (int j = 0; j < NL; ++j) {
+            float v = e[g][j];
+            if constexpr (XN) {  // the alpha sweep's slot from its statistics: (max, log2(rest + 1), rest) in .y, .z, .w
+              if (excl && ((wild >> j) & 1u)) v = ln.nx[j] >= 0 ? wk_log2_rest(v, sv[g].y, sv[g].w, sv[g].z) : 0.f;
+            }
+            r[lane * NL + j] = v;
+          }
           if (lane == 0) *reinterpret_cast<float4 *>(r + UP) = sv[g];
         }
       }
@@ -1146,7 +1164,8 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
         for (int j = 0; j < NL; ++j) a[lane * NS + j] = C[j];
         if (lane == 0) a[SRD - 2] = cs;
       }
-      wk_alpha_step<KIND, NL>(O, C, cs, e, fr, wild, allow);
+      if constexpr (OPT || XN) wk_star_step<KIND, NL, OPT, XN>(O, C, cs, e, fr, wild, allow, ln.skip, ln.skipo, excl);
+      else wk_alpha_step<KIND, NL>(O, C, cs, e, fr, wild, allow);
       if (KIND == 0) {  // the state AFTER the frame
 #pragma unroll
         for (int j = 0; j < NL; ++j) *reinterpret_cast<double2 *>(a + lane * NS + 2 * j) = make_double2(O[j], C[j]);
@@ -1159,8 +1178,8 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
   // labels' shares and the blank's in two planes of the block's LDS posterior rows, nothing summed here ----
   double bO[NL], bC[NL];  // beta: the mass of the frames still to come; behind the last frame only the end states have any
 #pragma unroll
-  for (int j = 0; j < NL; ++j) bO[j] = bC[j] = (lane * NL + j == L - 1) ? 0.0 : NINF;
-  double bcs = NINF;  // (L > 0)
+  for (int j = 0; j < NL; ++j) bO[j] = bC[j] = (lane * NL + j == L - 1 || (OPT && ln.last_opt && lane * NL + j == L - 2)) ? 0.0 : NINF;
+  double bcs = (OPT && ln.last_opt && L == 1) ? 0.0 : NINF;  // (L > 0; OPT: a lone optional position makes the start state an end state)
   auto post = [&](double l2) { return fexp2((float)(l2 - lP)); };
   auto beta_block = [&](int kb) {
     const int nf = frames_of(kb);
@@ -1183,7 +1202,9 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
       for (int j = 0; j < NL; ++j) e[j] = rr[lane * NL + j];
       const WkFrame fr = wk_frame_of(*reinterpret_cast<const float4 *>(rr + UP), lpin, w2);
       const double eb = fr.eb;
-      auto em = [&](int j) { return ((wild >> j) & 1u) ? fr.ew : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
+      // (XN, in an utterance that excludes: the ring slot of a wildcard position is log2(1 - p_t(y)))
+      auto ewj = [&](int j) { return excl ? fr.ew + (double)e[j] : fr.ew; };
+      auto em = [&](int j) { return ((wild >> j) & 1u) ? ewj(j) : fma((double)e[j] - fr.Md, LOG2E_D, fr.nl2s); };
       double A[NS];
 #pragma unroll
       for (int q = 0; q < NS; ++q) A[q] = An[q];
@@ -1201,23 +1222,45 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
         if (lane == 0) o[2 * UP] = post(Acs + bcs);
         double x = bO[0] + em(0);
         const double xl = from_next_lane(x, NINF);
-        bcs = wk_lse(bcs + eb, x);
+        if constexpr (OPT) {  // the mirror image of wk_star_step, as in wild_ckpt_bwd_kernel: one and two positions ahead
+          double x1 = NL > 1 ? bO[NL > 1 ? 1 : 0] + em(NL > 1 ? 1 : 0) : xl;
+          const double xl2 = from_next_lane(x1, NINF);
+          bcs = wk_lse(bcs + eb, x, ((skip >> 1) & 1u) ? x1 : NINF);
 #pragma unroll
-        for (int j = 0; j < NL; ++j) {
-          const double xn = j + 1 < NL ? bO[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
-          const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
-          const double cb = bC[j] + eb;
-          bO[j] = wk_lse(x, cb, al ? xn : NINF);
-          bC[j] = wk_lse(cb, xn);
-          x = xn;
+          for (int j = 0; j < NL; ++j) {
+            const double x2 = j + 2 < NL ? bO[j + 2 < NL ? j + 2 : 0] + em(j + 2 < NL ? j + 2 : 0) : j + 2 == NL ? xl : xl2;
+            const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+            const double cb = bC[j] + eb;
+            bO[j] = wk_lse(x, cb, al ? x1 : NINF, ((skipo >> (j + 2)) & 1u) ? x2 : NINF);
+            bC[j] = wk_lse(cb, x1, ((skip >> (j + 2)) & 1u) ? x2 : NINF);
+            x = x1;
+            x1 = x2;
+          }
+        } else {
+          bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? bO[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            const bool al = j + 1 < NL ? ((allow >> (j + 1)) & 1u) != 0 : allow_nx != 0;
+            const double cb = bC[j] + eb;
+            bO[j] = wk_lse(x, cb, al ? xn : NINF);
+            bC[j] = wk_lse(cb, xn);
+            x = xn;
+          }
         }
       } else {  // entering a position is its label's; a stay emits the wildcard behind a wildcard, the blank otherwise
         const double ap0 = from_prev_lane(A[NL - 1], Acs);
+        [[maybe_unused]] double ap00 = NINF;  // OPT: alpha two positions before the lane's first
+        if constexpr (OPT) ap00 = from_prev_lane(NL == 1 ? ap0 : A[NL > 1 ? NL - 2 : 0], NINF);
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
-          const double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          double ap = j > 0 ? A[j > 0 ? j - 1 : 0] : ap0;
+          if constexpr (OPT) {  // entered from one position back or, over a skipped star, from two: the frame is the position's
+            const double ap2 = j > 1 ? A[j > 1 ? j - 2 : 0] : j == 1 ? ap0 : ap00;
+            ap = wk_lse(ap, ((skip >> j) & 1u) ? ap2 : NINF);
+          }
           const bool wj = ((wild >> j) & 1u) != 0;
-          const float pe = post(ap + em(j) + bC[j]), ps = post(A[j] + (wj ? fr.ew : eb) + bC[j]);
+          const float pe = post(ap + em(j) + bC[j]), ps = post(A[j] + (wj ? ewj(j) : eb) + bC[j]);
           pl[j] = wj ? pe + ps : pe;
           pk[j] = wj ? 0.f : ps;
         }
@@ -1226,12 +1269,24 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
         if (lane == 0) o[2 * UP] = post(Acs + eb + bcs);
         double x = bC[0] + em(0);
         const double xl = from_next_lane(x, NINF);
-        bcs = wk_lse(bcs + eb, x);
+        if constexpr (OPT) {
+          double x1 = NL > 1 ? bC[NL > 1 ? 1 : 0] + em(NL > 1 ? 1 : 0) : xl;
+          const double xl2 = from_next_lane(x1, NINF);
+          bcs = wk_lse(bcs + eb, x, ((skip >> 1) & 1u) ? x1 : NINF);
 #pragma unroll
-        for (int j = 0; j < NL; ++j) {
-          const double xn = j + 1 < NL ? bC[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
-          bC[j] = wk_lse(bC[j] + (((wild >> j) & 1u) ? fr.ew : eb), xn);
-          x = xn;
+          for (int j = 0; j < NL; ++j) {
+            const double x2 = j + 2 < NL ? bC[j + 2 < NL ? j + 2 : 0] + em(j + 2 < NL ? j + 2 : 0) : j + 2 == NL ? xl : xl2;
+            bC[j] = wk_lse(bC[j] + (((wild >> j) & 1u) ? ewj(j) : eb), x1, ((skip >> (j + 2)) & 1u) ? x2 : NINF);
+            x1 = x2;
+          }
+        } else {
+          bcs = wk_lse(bcs + eb, x);
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const double xn = j + 1 < NL ? bC[j + 1 < NL ? j + 1 : 0] + em(j + 1 < NL ? j + 1 : 0) : xl;
+            bC[j] = wk_lse(bC[j] + (((wild >> j) & 1u) ? ewj(j) : eb), xn);
+            x = xn;
+          }
         }
       }
     }
@@ -1272,15 +1327,14 @@ __global__ __launch_bounds__(WK_BWD_THREADS) void wild_ckpt_post_kernel(const Pr
   }
 }
 
-template <int KIND, int NL>
+template <int KIND, int NL, bool OPT, bool XN>
 hipError_t launch_wild_ckpt_post(const Problem &p, double w2, float *loss, const WkWs &ws, const WkPost &out, hipStream_t st) {
-  hipLaunchKernelGGL((wild_ckpt_fwd_kernel<KIND, NL, false, false>), dim3(p.B), dim3(WK_FWD_THREADS), 0, st, p, w2, loss, ws);
+  hipLaunchKernelGGL((wild_ckpt_fwd_kernel<KIND, NL, OPT, XN>), dim3(p.B), dim3(WK_FWD_THREADS), 0, st, p, w2, loss, ws);
   if (hipError_t e = hipGetLastError()) return e;
   // (T == 0 or U == 0 too: the statistics of such a call are written by the same kernel)
-  hipLaunchKernelGGL((wild_ckpt_post_kernel<KIND, NL>), dim3(p.B), dim3(WK_BWD_THREADS), 0, st, p, w2, ws, out);
+  hipLaunchKernelGGL((wild_ckpt_post_kernel<KIND, NL, OPT, XN>), dim3(p.B), dim3(WK_BWD_THREADS), 0, st, p, w2, ws, out);
   return hipGetLastError();
 }
-#endif  // !CTC_CKPT_VARIANT
 
 template <int KIND, int NL, bool OPT, bool XN>
 hipError_t launch_wild_ckpt(const Problem &p, double w2, const float *d_loss, float *loss, void *grad, const WkWs &ws, hipStream_t st) {
@@ -1314,6 +1368,18 @@ hipError_t wk_run(const Problem &p, float wildcard_log_weight, const float *d_lo
   return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, d_loss, loss, grad, wk_regions(p, wsp), st);
 }
 
+// ... and of the label posteriors on the same workspace: U <= 256
+template <bool OPT, bool XN>
+hipError_t wk_post_run(const Problem &p, float wildcard_log_weight, float *loss, const WkPost &out, char *wsp, hipStream_t st) {
+  typedef hipError_t Launch(const Problem &, double, float *, const WkWs &, const WkPost &, hipStream_t);
+  static Launch *const table[2][3] = {
+      {launch_wild_ckpt_post<0, 1, OPT, XN>, launch_wild_ckpt_post<0, 2, OPT, XN>, launch_wild_ckpt_post<0, 4, OPT, XN>},
+      {launch_wild_ckpt_post<1, 1, OPT, XN>, launch_wild_ckpt_post<1, 2, OPT, XN>, launch_wild_ckpt_post<1, 4, OPT, XN>}};
+  const int NL = nl_for(p.U);
+  if (p.kind < 0 || p.kind > 1 || NL > 4) return hipErrorInvalidValue;
+  return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, loss, wk_regions(p, wsp), out, st);
+}
+
 }  // namespace
 
 #if defined(CTC_CKPT_OPT)
@@ -1321,11 +1387,22 @@ hipError_t run_wild_loss_ckpt_opt(const Problem &p, float wildcard_log_weight, c
                                   hipStream_t st) {
   return wk_run<true, false>(p, wildcard_log_weight, d_loss, loss, grad, wsp, st);
 }
+hipError_t run_label_posterior_ckpt_opt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                        float *blank_posterior, float *duration, float *expected_frame, char *wsp, hipStream_t st) {
+  return wk_post_run<true, false>(p, wildcard_log_weight, loss, WkPost{label_posterior, blank_posterior, duration, expected_frame}, wsp, st);
+}
 #elif defined(CTC_STAR)
 hipError_t run_wild_loss_ckpt_star(const Problem &p, float wildcard_log_weight, const float *d_loss, float *loss, void *grad, char *wsp,
                                    hipStream_t st, bool optional_wildcards) {
   return optional_wildcards ? wk_run<true, true>(p, wildcard_log_weight, d_loss, loss, grad, wsp, st)
                             : wk_run<false, true>(p, wildcard_log_weight, d_loss, loss, grad, wsp, st);
+}
+hipError_t run_label_posterior_ckpt_star(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                         float *blank_posterior, float *duration, float *expected_frame, char *wsp, hipStream_t st,
+                                         bool optional_wildcards) {
+  const WkPost out{label_posterior, blank_posterior, duration, expected_frame};
+  return optional_wildcards ? wk_post_run<true, true>(p, wildcard_log_weight, loss, out, wsp, st)
+                            : wk_post_run<false, true>(p, wildcard_log_weight, loss, out, wsp, st);
 }
 #else
 // checkpoints, then the row statistics, then log2 Z: each region rounded up to 256 bytes (include/ctc_amd.h has the formula)
@@ -1354,13 +1431,22 @@ hipError_t run_star_loss_ckpt(const Problem &p, float wildcard_log_weight, const
 hipError_t run_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior, float *blank_posterior,
                                     float *duration, float *expected_frame, char *wsp, hipStream_t st) {
   if (!wk_tier(p.U)) return run_label_posterior(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, wsp, st);
-  typedef hipError_t Launch(const Problem &, double, float *, const WkWs &, const WkPost &, hipStream_t);
-  static Launch *const table[2][3] = {{launch_wild_ckpt_post<0, 1>, launch_wild_ckpt_post<0, 2>, launch_wild_ckpt_post<0, 4>},
-                                      {launch_wild_ckpt_post<1, 1>, launch_wild_ckpt_post<1, 2>, launch_wild_ckpt_post<1, 4>}};
-  const int NL = nl_for(p.U);
-  if (p.kind < 0 || p.kind > 1 || NL > 4) return hipErrorInvalidValue;
-  const WkPost out{label_posterior, blank_posterior, duration, expected_frame};
-  return table[p.kind][NL == 1 ? 0 : NL == 2 ? 1 : 2](p, (double)wildcard_log_weight * LOG2E_D, loss, wk_regions(p, wsp), out, st);
+  return wk_post_run<false, false>(p, wildcard_log_weight, loss, WkPost{label_posterior, blank_posterior, duration, expected_frame}, wsp, st);
+}
+
+hipError_t run_star_label_posterior_ckpt(const Problem &p, float wildcard_log_weight, float *loss, float *label_posterior,
+                                         float *blank_posterior, float *duration, float *expected_frame, char *wsp, hipStream_t st,
+                                         bool optional_wildcards, bool exclude_next_label) {
+  if (!wk_tier(p.U))
+    return (exclude_next_label ? run_star_label_posterior : run_label_posterior)(p, wildcard_log_weight, loss, label_posterior, blank_posterior,
+                                                                                 duration, expected_frame, wsp, st, nullptr, 0,
+                                                                                 optional_wildcards);
+  if (exclude_next_label)
+    return run_label_posterior_ckpt_star(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, wsp, st,
+                                         optional_wildcards);
+  if (optional_wildcards)
+    return run_label_posterior_ckpt_opt(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, wsp, st);
+  return run_label_posterior_ckpt(p, wildcard_log_weight, loss, label_posterior, blank_posterior, duration, expected_frame, wsp, st);
 }
 #endif
 

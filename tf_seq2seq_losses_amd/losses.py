@@ -855,7 +855,7 @@ class CtcLabelPosterior(NamedTuple):
 
 def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_length, blank_index, wildcard_log_weight,
                      max_label_length=None, frame_window=None, optional_wildcards=False,
-                     exclude_next_label=False, checkpoint=False) -> CtcLabelPosterior:
+                     exclude_next_label=False, checkpoint=False, _star_ckpt=False) -> CtcLabelPosterior:
     _no_window_with_optional(frame_window, optional_wildcards)
     _no_window_with_exclusion(frame_window, exclude_next_label)
     x = _as_tensor(x)
@@ -869,6 +869,11 @@ def _label_posterior(kind_name: str, wrt: int, labels, x, label_length, logit_le
     if not (weight <= 0.0) or weight == float("-inf"):
         raise ValueError(f"wildcard_log_weight must be finite and <= 0, got {wildcard_log_weight}")
     U = None if max_label_length is None else max(0, min(int(labels.shape[1]), int(max_label_length)))
+    if _star_ckpt:  # the *_star_label_posterior functions: both keywords go to the checkpointed call as they are
+        with torch.no_grad():
+            return CtcLabelPosterior(*ops.star_label_posterior(ops.KINDS[kind_name], wrt, labels, x.detach(), label_length, logit_length,
+                                                               _blank(blank_index), U, weight, optional_wildcards=optional_wildcards,
+                                                               exclude_next_label=exclude_next_label))
     window = {} if frame_window is None else {"frame_window": _as_tensor(frame_window)}
     if optional_wildcards:
         window["optional_wildcards"] = True
@@ -924,6 +929,39 @@ def ctc_label_posterior_from_logproba(labels, logprobas, label_length, logit_len
     kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
     return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
                             wildcard_log_weight, max_label_length, frame_window, optional_wildcards, exclude_next_label, checkpoint)
+
+
+def classic_ctc_star_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                     blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                     max_label_length: Optional[int] = None, optional_wildcards: bool = True,
+                                     exclude_next_label: bool = True) -> CtcLabelPosterior:
+    """The soft alignment of a star temporal classification transcript from block checkpoints: which frames every label and every
+    star took, over all paths of the lattice of classic_ctc_star_loss.  It is classic_ctc_label_posterior with the same two
+    keywords (both default to True here, as in classic_ctc_star_loss): the same CtcLabelPosterior to the same bars, `loss` bit for
+    bit, a star that every path skips with duration 0 and expected_frame -1.  For up to 256 label positions the workspace holds one
+    chain state per block of 32 / 16 / 8 frames, not one per frame (7.8 x smaller at 129 positions), and duration /
+    expected_frame come from the same sweep; above 256 positions the call is classic_ctc_label_posterior's.  With neither keyword
+    it is classic_ctc_label_posterior(checkpoint=True).  No frame_window.  Detached, float32 on the logits' device."""
+    return _label_posterior("classic", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index, wildcard_log_weight,
+                            max_label_length, None, optional_wildcards, exclude_next_label, _star_ckpt=True)
+
+
+def simplified_ctc_star_label_posterior(labels: TensorLike, logits: TensorLike, label_length: TensorLike, logit_length: TensorLike,
+                                        blank_index: Union[int, torch.Tensor] = 0, *, wildcard_log_weight: float = 0.0,
+                                        max_label_length: Optional[int] = None, optional_wildcards: bool = True,
+                                        exclude_next_label: bool = True) -> CtcLabelPosterior:
+    """The same on the simplified lattice.  Same arguments and return value as classic_ctc_star_label_posterior."""
+    return _label_posterior("simplified", _lib.WRT_LOGITS, labels, logits, label_length, logit_length, blank_index,
+                            wildcard_log_weight, max_label_length, None, optional_wildcards, exclude_next_label, _star_ckpt=True)
+
+
+def ctc_star_label_posterior_from_logproba(labels, logprobas, label_length, logit_length, blank_index=0, ctc_loss_data_cls=None, *,
+                                           wildcard_log_weight: float = 0.0, max_label_length: Optional[int] = None,
+                                           optional_wildcards: bool = True, exclude_next_label: bool = True) -> CtcLabelPosterior:
+    """The same for log-probabilities used as they stand; ctc_loss_data_cls selects the lattice (default: ClassicCtcLossData)."""
+    kind_name = "classic" if ctc_loss_data_cls is None else ctc_loss_data_cls.kind_name
+    return _label_posterior(kind_name, _lib.WRT_LOGPROBS, labels, logprobas, label_length, logit_length, blank_index,
+                            wildcard_log_weight, max_label_length, None, optional_wildcards, exclude_next_label, _star_ckpt=True)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1022,8 +1022,8 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
     ctc_amd_optional_wildcard_label_posterior; exclude_next_label: ctc_amd_star_label_posterior); every element of every output is
     written.  checkpoint: the posteriors from block checkpoints (ctc_amd_label_posterior_ckpt: for U <= 256 a workspace of one
     chain state per block of frames, 14 x smaller at U = 128 on the classic lattice, and the statistics from the same sweep; the
-    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (their
-    checkpointed kernels are owed).  Does not synchronise."""
+    same bars); with frame_window, optional_wildcards or exclude_next_label the call is that of checkpoint=False (the
+    checkpointed route of the latter two is star_label_posterior; the windowed one is owed).  Does not synchronise."""
     if optional_wildcards and frame_window is not None:
         raise ValueError("label_posterior: frame_window and optional_wildcards cannot be combined")
     if exclude_next_label and frame_window is not None:
@@ -1080,6 +1080,42 @@ def label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, 
                   _ptr(label_length), _ptr(logit_length), int(blank), float(wildcard_log_weight), B, T, V, U,
                   _ptr(loss), _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
     _lib.check(rc, "ctc_amd_label_posterior_ckpt" if ckpt else "ctc_amd_label_posterior")
+    return loss, post, blk, dur, exf
+
+
+def star_label_posterior(kind: int, wrt: int, labels: torch.Tensor, x: torch.Tensor, label_length: torch.Tensor,
+                         logit_length: torch.Tensor, blank: int, U: Optional[int] = None, wildcard_log_weight: float = 0.0, *,
+                         want_stats: bool = True, optional_wildcards: bool = True, exclude_next_label: bool = True):
+    """label_posterior(optional_wildcards=..., exclude_next_label=...) from block checkpoints (ctc_amd_star_label_posterior_ckpt):
+    the soft alignment of a star temporal classification transcript.  The same arguments and the same five results to the same
+    bars, the loss bit for bit; for U <= 256 two launches on label_posterior_ckpt_workspace_bytes (one lattice row per block of
+    32 / 16 / 8 frames, not one per frame), for U > 256 that call itself.  With neither keyword it is
+    label_posterior(checkpoint=True).  No frame_window.  Does not synchronise."""
+    if labels.dim() != 2 or label_length.dim() != 1:
+        raise ValueError(f"star_label_posterior: labels must be [B, W] and label_length [B], got {tuple(labels.shape)} and {tuple(label_length.shape)}")
+    labels, x, label_length, logit_length, U, _, W = _nbest_args("star_label_posterior", labels.unsqueeze(1), x, label_length.unsqueeze(1),
+                                                                 logit_length, U)
+    lib = _lib.load()
+    dev = x.device
+    B, T, V = (int(s) for s in x.shape)
+    key = ("label_posterior_ckpt", kind, B, T, V, U)
+    n = _WS_BYTES.get(key)
+    if n is None:  # (also the check of V and U, which an empty batch would otherwise skip)
+        n = _WS_BYTES[key] = _lib.label_posterior_ckpt_workspace_bytes(kind, B, T, V, U)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    post = torch.empty((B, T, U), dtype=torch.float32, device=dev)
+    blk = torch.empty((B, T), dtype=torch.float32, device=dev)
+    dur = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    exf = torch.empty((B, U), dtype=torch.float32, device=dev) if want_stats else None
+    if B == 0:
+        return loss, post, blk, dur, exf
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = lib.ctc_amd_star_label_posterior_ckpt(kind, wrt, _ptr(x), _DTYPES[x.dtype], x.stride(0), x.stride(1), _ptr(labels), W,
+                                                   _ptr(label_length), _ptr(logit_length), int(blank), int(bool(optional_wildcards)),
+                                                   int(bool(exclude_next_label)), float(wildcard_log_weight), B, T, V, U, _ptr(loss),
+                                                   _ptr(post), _ptr(blk), _ptr(dur), _ptr(exf), _ptr(ws), n, _stream(dev))
+    _lib.check(rc, "ctc_amd_star_label_posterior_ckpt")
     return loss, post, blk, dur, exf
 
 
